@@ -8,12 +8,17 @@ already resident in HBM. Weak scaling: every rank runs its own 4 episodes, no da
 (episodes are independent).
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line (rank 0) with `roofline` (dominant kernel family = the fp32-MFMA implicit
-GEMM, timed live with HIP events on its launch stream) and, at N=1, `cpu_baseline` (the oracle
-port timed on the host cores on a bounded sample of the same workload).
+Prints ONE JSON line (rank 0). A plain run sets up, picks the launch mode (short trial), warms
+up, times the --steps steps and prints the headline. --dump-outputs DIR also writes what the
+last timed step returned as DIR/<name>.npy. --full adds every side measurement: `roofline`
+(dominant kernel family = the fp32-MFMA implicit GEMM, timed live with HIP events on its launch
+stream), `train_step`, the other configurations and, at N=1, `cpu_baseline` (the oracle port
+timed on the host cores on a bounded sample of the same workload).
 """
 import argparse
 import json
@@ -78,8 +83,21 @@ def parse():
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--single-stream", action="store_true",
                     help="collapse the model's streams to one (kernels run alone: for rocprof per-kernel averages)")
-    ap.add_argument("--dump-launches", default="", help="write the per-launch igemm table to this file")
-    return ap.parse_args()
+    ap.add_argument("--dump-launches", default="", help="write the per-launch igemm table to this file (needs --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements (rooflines and PMC passes, train_step, the other configurations, "
+                         "precisions and launch modes, cpu_baseline, host enqueue times); the --no-* switches thin them out")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the arrays the last timed step returned to DIR/<name>.npy (float32 / float64, at most 64 MB "
+                         "in all: a larger output is replaced by a fixed, seeded sample of its elements)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    if args.dump_launches and not args.full:
+        ap.error("--dump-launches comes from the roofline pass: add --full")
+    if not args.full:  # a plain run measures the headline only
+        args.no_train_step = args.no_roofline = args.no_secondary = args.no_cpu_baseline = True
+    return args
 
 
 def config_label(args):
@@ -203,6 +221,38 @@ def pmc_passes(args, kernel):
         res["mfma_busy"] = round(sums["SQ_VALU_MFMA_BUSY_CYCLES"][0] / (sums["GRBM_GUI_ACTIVE"][0] / 8.0 * 1024.0), 4)
         res["mfma_busy_is"] = "SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs) over the %s launches" % kernel
     return res
+
+
+OUTPUT_NAMES = ("rois", "cls_prob", "bbox_pred", "rpn_loss_cls", "rpn_loss_bbox", "RCNN_loss_cls", "RCNN_loss_bbox",
+                "rois_label")  # the model's 8-tuple (dana.py forward, Trainer.step, the replays)
+DUMP_BYTES = 63 * 10 ** 6  # array data; the .npy headers fit in the rest of the 64 MB
+
+
+def dump_outputs(path, named, limit=DUMP_BYTES):
+    """{name: tensor or number} -> path/<name>.npy. Floating point is written as float32 (float64 stays float64), integers
+    and booleans as float64. The arrays share `limit` bytes: smaller ones are written whole and the rest split what remains;
+    an array over its share is replaced by a sample of its flattened elements at fixed, seeded, sorted positions (the same
+    positions for the same shape, so two builds compare element for element)."""
+    arrays = {}
+    for name, v in named.items():
+        if v is None:
+            continue
+        if torch.is_tensor(v):
+            v = (v.detach().float() if v.dtype == torch.bfloat16 else v.detach()).cpu().numpy()
+        a = np.asarray(v)
+        floating = np.issubdtype(a.dtype, np.floating) and a.dtype != np.float64
+        arrays[name] = a.astype(np.float32 if floating else np.float64)
+    os.makedirs(path, exist_ok=True)
+    left, todo = limit, sorted(arrays, key=lambda n: arrays[n].nbytes)
+    for i, name in enumerate(todo):
+        a = arrays[name]
+        share = left // (len(todo) - i)
+        if a.nbytes > share:
+            k = share // a.itemsize
+            pick = np.sort(np.random.default_rng(1996).choice(a.size, size=k, replace=False))
+            a = a.reshape(-1)[pick]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes
 
 
 def self_launch(args):
@@ -480,16 +530,22 @@ def main():
         torch.cuda.synchronize()
 
     phase("launch trial done: %s" % chosen)
+    # the timed steps draw the training targets from the same host stream whatever the trial and the warm-up drew
+    np.random.seed(1996 + rank)
     barrier()
     marks_f = [torch.cuda.Event(enable_timing=True)]
     marks_f[0].record()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        step()
+        out = step()
         marks_f.append(torch.cuda.Event(enable_timing=True))
         marks_f[-1].record()
     barrier()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # (before anything else runs: a replayed step returns its static output tensors)
+        named = ({"detections_%d" % i: d for i, d in enumerate(out)} if args.mode == "infer" else dict(zip(OUTPUT_NAMES, out)))
+        dump_outputs(args.dump_outputs, named)
     per_rank_ms = None
     if world > 1:
         every = torch.zeros(world, device=dev, dtype=torch.float64)
@@ -498,7 +554,7 @@ def main():
         per_rank_ms = [round(1000.0 * float(x) / args.steps, 3) for x in every.tolist()]
         dt = float(every.max().item())
 
-    host_ms = {n: host_enqueue_ms(f, 10 if n == "eager" else 20) for n, f in cands.items()}
+    host_ms = {n: host_enqueue_ms(f, 10 if n == "eager" else 20) for n, f in cands.items()} if args.full else None
     what = {"step": "training step fwd+bwd+allreduce+SGD",
             "infer": "eval-mode forward + detection post-processing per image"}.get(args.mode, "%s-mode forward" % args.mode)
     result = {

@@ -229,3 +229,26 @@ def test_bench_rejects_a_launcher_whose_world_size_is_not_gpus():
     pr = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "4", "--steps", "1", "--warmup", "0"],
                         env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=120)
     assert pr.returncode != 0 and b"WORLD_SIZE=2" in pr.stderr and not pr.stdout.strip()
+
+
+def test_bench_dump_outputs_dtypes_and_byte_budget(tmp_path):
+    """bench.py --dump-outputs: floating point as float32 (float64 kept), integers and numbers as float64, None skipped;
+    arrays over the byte budget are replaced by a sample of their elements at fixed, sorted positions, the same on every
+    call (two builds compare element for element)"""
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("dana_bench", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    named = {"rois": torch.ones(2, 5), "rois_label": torch.tensor([1, 0, 2]), "loss": torch.tensor(0.5, dtype=torch.float64),
+             "half": torch.ones(3, dtype=torch.float16), "skipped": None, "zero": 0, "big": torch.arange(10000.0)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), named, limit=4096)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(n + ".npy" for n, v in named.items() if v is not None)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in files}
+    assert {n: a.dtype for n, a in got.items()} == {"rois": np.float32, "rois_label": np.float64, "loss": np.float64,
+                                                    "half": np.float32, "zero": np.float64, "big": np.float32}
+    assert np.array_equal(got["rois_label"], [1, 0, 2]) and np.array_equal(got["rois"], np.ones((2, 5)))
+    assert sum(a.nbytes for a in got.values()) <= 4096
+    assert 0 < got["big"].size < 10000 and np.all(np.diff(got["big"]) > 0)  # sorted positions of an arange
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))

@@ -29,8 +29,8 @@ def test_bench_two_ranks_prints_one_line(dev):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", "29733", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-pmc",
-           "--no-secondary"]
+           "--master-port", "29733", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full",
+           "--no-pmc", "--no-secondary"]
     pr = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert pr.returncode == 0, pr.stderr.decode()[-3000:]
     lines = [ln for ln in pr.stdout.decode().splitlines() if ln.startswith("{")]
