@@ -110,12 +110,21 @@ dets_assemble_kernel(const float4* __restrict__ boxes, const float* __restrict__
 // inference.py:106-125 for one image: de-normalise the deltas (x stds + means), bbox_transform_inv on the
 // rois, clip to the image, divide by the image scale; score = cls_prob[:, 1], masked to -inf when it does
 // not pass `thresh` so that the descending sort puts every discarded row after the kept ones.
+// blockIdx.y: the image of a batch of R-row images (im_info[b][3], count[b]); one image is grid.y = 1.
 __global__ void __launch_bounds__(256)
 detect_decode_kernel(const float* __restrict__ rois, const float* __restrict__ cls_prob,
                      const float* __restrict__ bbox_pred, const float* __restrict__ im_info, int R, float4 stds,
                      float4 means, int normalize, float thresh, float4* __restrict__ boxes, float* __restrict__ scores,
                      int* __restrict__ count) {
   const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  const long b = blockIdx.y;
+  rois += b * R * 5;
+  cls_prob += b * R * 2;
+  bbox_pred += b * R * 4;
+  im_info += b * 3;
+  boxes += b * R;
+  scores += b * R;
+  count += b;
   bool valid = false;
   if (r < R) {
     const float* q = rois + (long)r * 5;
@@ -140,6 +149,57 @@ detect_decode_kernel(const float* __restrict__ rois, const float* __restrict__ c
   }
   const unsigned long long m = __ballot(valid);
   if ((threadIdx.x & 63) == 0 && m) atomicAdd(count, __builtin_popcountll(m));
+}
+
+// Batched post-processing, last step: image b's detections are its kept sorted rows at positions < n_valid[b] (the kept
+// positions ascend and the rows below the threshold sort last, so they are a prefix of keep[b]), written packed in image
+// order at dets[offsets[b]..]. Workgroup b sums the counts of the images in front of it itself (a binary search per
+// image): no atomics, no second launch.
+__device__ __forceinline__ int kept_valid(const int* __restrict__ keep, const int* __restrict__ num_keep,
+                                          const int* __restrict__ n_valid, int i, int R) {
+  const int* k = keep + (long)i * R;
+  const int nv = n_valid[i];
+  int lo = 0, hi = num_keep[i];
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (k[mid] < nv)
+      lo = mid + 1;
+    else
+      hi = mid;
+  }
+  return lo;
+}
+
+__global__ void __launch_bounds__(256)
+dets_compact_kernel(const float4* __restrict__ sorted_boxes, const float* __restrict__ sorted_scores,
+                    const int* __restrict__ keep, const int* __restrict__ num_keep, const int* __restrict__ n_valid, int B,
+                    int R, float* __restrict__ dets, int* __restrict__ counts, int* __restrict__ offsets) {
+  __shared__ int s_off;
+  const int b = blockIdx.x;
+  if (threadIdx.x == 0) s_off = 0;
+  __syncthreads();
+  int part = 0;
+  for (int i = threadIdx.x; i < b; i += blockDim.x) part += kept_valid(keep, num_keep, n_valid, i, R);
+  if (part) atomicAdd(&s_off, part);  // (integer sum: the same total in any order)
+  __syncthreads();
+  const int off = s_off;
+  const int cnt = kept_valid(keep, num_keep, n_valid, b, R);
+  if (threadIdx.x == 0) {
+    counts[b] = cnt;
+    offsets[b] = off;
+    if (b == B - 1) offsets[B] = off + cnt;
+  }
+  const int* k = keep + (long)b * R;
+  for (int i = threadIdx.x; i < cnt; i += blockDim.x) {
+    const long src = (long)b * R + k[i];
+    const float4 bx = sorted_boxes[src];
+    float* o = dets + (long)(off + i) * 5;
+    o[0] = bx.x;
+    o[1] = bx.y;
+    o[2] = bx.z;
+    o[3] = bx.w;
+    o[4] = sorted_scores[src];
+  }
 }
 
 // ---- hand-written top-k + sort (round 4): proposal_layer.py:135-150 sorts every anchor's score and keeps the first
@@ -878,6 +938,94 @@ int dana_detect_postprocess(const float* rois, const float* cls_prob, const floa
   // dets in sorted order for every row; the caller indexes it with keep_pos
   dets_assemble_kernel<<<dana_ceil_div(R, 256), 256, 0, s>>>((const float4*)sorted_boxes, sorted_scores, R, dets);
   DANA_CHECK_LAUNCH("dana_detect_postprocess(assemble)");
+  return DANA_OK;
+}
+
+// ---- the same post-processing for B images of R rois each, in one call: decode / threshold over B*R rows, the batched
+// sort (B rows), box gather and NMS (B problems), then the kept rows of all images packed in image order
+struct DetectBatchedPlan {
+  size_t boxes, scores, order, sorted_scores, sorted_boxes, keep, num_keep, n_valid, sort_ws, nms_ws, total;
+};
+static DetectBatchedPlan detect_batched_plan(int B, int R) {
+  DetectBatchedPlan p;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    size_t at = o;
+    o += dana_align_up(bytes, 256);
+    return at;
+  };
+  const size_t n = (size_t)B * R;
+  p.boxes = take(n * 16);
+  p.scores = take(n * 4);
+  p.order = take(n * 4);
+  p.sorted_scores = take(n * 4);
+  p.sorted_boxes = take(n * 16);
+  p.keep = take(n * 4);
+  p.num_keep = take((size_t)B * 4);
+  p.n_valid = take((size_t)B * 4);
+  p.sort_ws = take(dana_sort_desc_workspace_bytes(B, R));
+  p.nms_ws = take(dana_nms_workspace_bytes(R, B));
+  p.total = o;
+  return p;
+}
+
+size_t dana_detect_postprocess_batched_workspace_bytes(int B, int R) {
+  return (B > 0 && R > 0) ? detect_batched_plan(B, R).total : 0;
+}
+
+int dana_detect_postprocess_batched(const float* rois, const float* cls_prob, const float* bbox_pred,
+                                    const float* im_info, int B, int R, const float* stds4, const float* means4,
+                                    int normalize, float score_thresh, float nms_thresh, int nms_inclusive, float* dets,
+                                    int* counts, int* offsets, void* workspace, size_t workspace_bytes,
+                                    dana_stream_t stream) {
+  DANA_CHECK_ARG(B >= 0 && R >= 0 && B <= 65535, "dana_detect_postprocess_batched: bad shape B=%d R=%d", B, R);
+  if (B == 0) return DANA_OK;
+  DANA_CHECK_ARG(counts && offsets, "dana_detect_postprocess_batched: null counts / offsets");
+  hipStream_t s = (hipStream_t)stream;
+  if (R == 0) {
+    if (hipMemsetAsync(counts, 0, (size_t)B * sizeof(int), s) != hipSuccess ||
+        hipMemsetAsync(offsets, 0, (size_t)(B + 1) * sizeof(int), s) != hipSuccess) {
+      dana_set_error("dana_detect_postprocess_batched: memset failed");
+      return DANA_ERR_HIP;
+    }
+    return DANA_OK;
+  }
+  DANA_CHECK_ARG(rois && cls_prob && bbox_pred && im_info && stds4 && means4 && dets,
+                 "dana_detect_postprocess_batched: null pointer");
+  const DetectBatchedPlan p = detect_batched_plan(B, R);
+  if (!workspace || workspace_bytes < p.total) {
+    dana_set_error("dana_detect_postprocess_batched: workspace %zu < %zu", workspace_bytes, p.total);
+    return DANA_ERR_WORKSPACE;
+  }
+  char* ws = (char*)workspace;
+  float* boxes = (float*)(ws + p.boxes);
+  float* scores = (float*)(ws + p.scores);
+  int* order = (int*)(ws + p.order);
+  float* sorted_scores = (float*)(ws + p.sorted_scores);
+  float* sorted_boxes = (float*)(ws + p.sorted_boxes);
+  int* keep = (int*)(ws + p.keep);
+  int* num_keep = (int*)(ws + p.num_keep);
+  int* n_valid = (int*)(ws + p.n_valid);
+  if (hipMemsetAsync(n_valid, 0, (size_t)B * sizeof(int), s) != hipSuccess) {
+    dana_set_error("dana_detect_postprocess_batched: memset failed");
+    return DANA_ERR_HIP;
+  }
+  const float4 sd = make_float4(stds4[0], stds4[1], stds4[2], stds4[3]);
+  const float4 mn = make_float4(means4[0], means4[1], means4[2], means4[3]);
+  detect_decode_kernel<<<dim3(dana_ceil_div(R, 256), B), 256, 0, s>>>(rois, cls_prob, bbox_pred, im_info, R, sd, mn,
+                                                                     normalize, score_thresh, (float4*)boxes, scores,
+                                                                     n_valid);
+  DANA_CHECK_LAUNCH("dana_detect_postprocess_batched(decode)");
+  int rc = dana_sort_desc(scores, B, R, order, sorted_scores, ws + p.sort_ws, p.nms_ws - p.sort_ws, stream);
+  if (rc) return rc;
+  rc = dana_gather_boxes(boxes, order, B, R, R, R, sorted_boxes, stream);
+  if (rc) return rc;
+  rc = dana_nms(sorted_boxes, R, B, nms_thresh, nms_inclusive, R, keep, R, num_keep, ws + p.nms_ws, p.total - p.nms_ws,
+                stream);
+  if (rc) return rc;
+  dets_compact_kernel<<<B, 256, 0, s>>>((const float4*)sorted_boxes, sorted_scores, keep, num_keep, n_valid, B, R, dets,
+                                        counts, offsets);
+  DANA_CHECK_LAUNCH("dana_detect_postprocess_batched(compact)");
   return DANA_OK;
 }
 

@@ -16,6 +16,7 @@ Data layout in HBM (all fp32):
   frozen BN     folded to per-channel scale/shift applied in the conv epilogue (dana.py:362-385).
 """
 import math
+import weakref
 
 import numpy as np
 import torch
@@ -742,6 +743,138 @@ class DAnARCNN(nn.Module):
         join()
         return corr, g0, sup, g1
 
+    # ---- the support side: query-independent, shared by the forward and encode_supports ------------------------
+    def _check_support_map(self, sh_, sw_):
+        if (sh_, sw_) != (20, 20):
+            # NOT a reference configuration (no oracle, no parity claim): the reference cannot run it at all. Opt-in
+            # generalisation for BASELINE.json's "224x224 supports": all L = sh*sw positions are attention keys and the
+            # 14/1 average pool becomes the (sh/7 x sw/7)-window pool that also ends in a 7x7 map.
+            if not self.generalised_support or sh_ % 7 or sw_ % 7:
+                raise RuntimeError("support images must be 320x320 (20x20 stride-16 map), as the reference hard-codes "
+                                   "(dana.py:105); got a %dx%d map%s" % (sh_, sw_, "" if self.generalised_support else
+                                   " (set model.generalised_support = True for maps whose sides are multiples of 7)"))
+
+    def _support_rpn_side(self, sup, B, shot, way, L, dev, stream, ctx=None, branch=True):
+        """RPN-level support side (dana.py:126-145) on `stream` (the current one): PE, BA block, K projection + column mean,
+        unary term + softmax, S^T of the positive supports of B images -> (s_pe, kp [B*shot*L][d], unary [B*shot][L],
+        s_t [B][1024][shot*L])"""
+        d = self.rpn_reduce_dim
+        K1 = shot * L
+        s_pe = torch.empty((B, shot * L, 1024), dtype=torch.float32, device=dev)
+        # positives = the first `shot` supports of each image (dana.py:103), way * shot maps apart: one launch
+        ops.add_pe_groups(sup, self._pe_table(L, dev), B, shot * L, L, 1024, way * shot * L * 1024, s_pe)
+        if self.semantic_enhance:  # BA block (dana.py:133-137)
+            wc, bc = self._w(self.rpn_channel_k_layer)
+            wgt = ops.rowdot(s_pe, wc, bc, B * shot * L, 1024)
+            ops.softmax_rows_(wgt, B * shot, L)
+            if ctx is not None:
+                ctx.update(s_pre=s_pe.clone(), ba_w=wgt)
+            ops.ba_apply_(s_pe, wgt, B * shot, L, 1024, gamma=self.channel_gamma, slope=0.01)
+        # three independent consumers of the (BA-enhanced) support rows: K projection, unary term, S^T. The chain behind
+        # the support trunk is latency-bound (small dependent launches, 0.24 ms of which the caller's stream WAITS 0.125:
+        # tools/phase_times.py), so the unary term and the transpose run beside the K projection on an idle role stream
+        br_role = getattr(self, "rpn_side_role", "wgrad")
+        br = self._stream(br_role, dev) if (branch and br_role and not getattr(self, "_single_stream", False)
+                                            and not torch.cuda.is_current_stream_capturing()) else None
+
+        def unary_and_transpose():
+            wu, bu = self._w(self.rpn_unary_layer)
+            u_ = ops.rowdot(s_pe, wu, bu, B * shot * L, 1024)
+            ops.softmax_rows_(u_, B * shot, L)
+            return u_, ops.transpose_batched(s_pe, B, K1, 1024)  # [B][1024][K1]
+
+        if br is not None:
+            s_pe_ready = ops.record_event()
+            br.wait_event(s_pe_ready)
+            s_pe.record_stream(br)
+            with ops.on_stream(br):
+                unary, s_t = unary_and_transpose()
+                branch_done = ops.record_event()
+        wk, bk = self._w(self.rpn_adapt_k_layer)
+        kb3, kld = self._lin_b(self.rpn_adapt_k_layer)
+        kp = ops.gemm_nt(s_pe, kb3, B * shot * L, d, 1024, ldb=kld, shift=bk)
+        ops.colmean_sub_(kp, B * shot, L, d)
+        if br is not None:
+            stream.wait_event(branch_done)
+        else:
+            unary, s_t = unary_and_transpose()
+        return s_pe, kp, unary, s_t
+
+    def _support_roi_side(self, sup, Ns, sh_, sw_, plan, dev, product, ctx=None):
+        """RoI-level support side (dana.py:105-108,258,271-277) of Ns support maps on the current stream: avg-pool, PE, K /
+        unary projections once per support (the reference recomputes them for every RoI), and the folded S.Wt^T table ->
+        (sp_pe [Ns*49][1024], k2 [Ns*49][dq], un2 [Ns][49], sw [Ns*49][64] or None, pool)"""
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        dq = self.rcnn_reduce_dim
+        if (sh_, sw_) == (20, 20):
+            pool = (14, 1)  # nn.AvgPool2d(14, stride=1) (dana.py:42): 20x20 -> 7x7
+        else:
+            if sh_ != sw_:
+                raise RuntimeError("generalised supports must be square")
+            pool = (sh_ // 7, sh_ // 7)
+        sp = ops.avgpool(sup, Ns, sh_, sw_, 1024, pool[0], pool[1])  # [Ns][49][1024]
+        sp_pe = ops.add_pe(sp, plan["pe49"], Ns * P2, P2, 1024)
+        wk2, bk2 = self._w(self.rcnn_adapt_k_layer)
+        k2b3, k2ld = self._lin_b(self.rcnn_adapt_k_layer)
+        k2 = ops.gemm_nt(sp_pe, k2b3, Ns * P2, dq, 1024, ldb=k2ld, shift=bk2)
+        ops.colmean_sub_(k2, Ns, P2, dq)
+        wu2, bu2 = self._w(self.rcnn_unary_layer)
+        un2 = ops.rowdot(sp_pe, wu2, bu2, Ns * P2, 1024)
+        ops.softmax_rows_(un2, Ns, P2)
+        sw = None
+        if getattr(self, "fold_roi_attn", True) and not product:  # (product needs the attended rows themselves)
+            # The head's two contractions re-associated (dana.py:279-286): the attended rows only feed the second half
+            # of rcnn_transform_layer, and (A . S) . Wt_a^T = A . (S . Wt_a^T) -- S . Wt_a^T is a [147][64] table per
+            # image computed ONCE here (under the proposal layer), the per-RoI work drops from K = 147 -> 1024 -> 64
+            # (10.8 GF per head at bs 4) to K = 147 -> 64 (0.5 GF) and the [n*49][1024] attended tensor (103 MB written
+            # and read back, per head) never exists -- nor do its adjoints in the backward, which differentiates the
+            # same re-associated form (backward.model_backward_gen).
+            wt_a_s, wt_a_s_ld = self._lin_b(self.rcnn_transform_layer, 1024, 1024)
+            sw = ops.gemm_nt(sp_pe, wt_a_s, Ns * P2, self.rcnn_dim, 1024, ldb=wt_a_s_ld)  # [Ns*49][64]
+            if ctx is not None:
+                ctx["sw"] = sw
+        return sp_pe, k2, un2, sw, pool
+
+    def _cache_state(self, dev):
+        """what a SupportCache's tensors depend on besides the support images"""
+        return (self._sig(), str(dev), self.attention_type, bool(self.semantic_enhance),
+                bool(getattr(self, "fold_roi_attn", True)), int(self.n_shot))
+
+    def encode_supports(self, support_ims):
+        """support_ims [C, shot, 3, S, S] (C support sets, e.g. one per class) -> SupportCache: the eval forward's
+        query-independent support work (support trunk, RPN-level and RoI-level support chains), done once per set with the
+        launches an uncached B = 1 forward issues for it. `model(im_data, im_info, gt_boxes, num_boxes, cache)` then runs
+        the query side only (inference.py:82-103 draws each class's shots once and reuses them for every query)."""
+        if self.training:
+            raise RuntimeError("encode_supports runs in eval mode (model.eval()): a SupportCache serves inference only")
+        if not torch.is_tensor(support_ims) or support_ims.dim() != 5 or support_ims.size(2) != 3:
+            raise ValueError("encode_supports: support_ims must be [C, shot, 3, S, S], got %s"
+                             % (tuple(support_ims.shape) if torch.is_tensor(support_ims) else type(support_ims)))
+        if not support_ims.is_cuda:
+            raise RuntimeError("support_ims must be a CUDA (HIP) tensor: this build has no CPU path")
+        C, shot = support_ims.size(0), support_ims.size(1)
+        if shot != self.n_shot:
+            raise ValueError("encode_supports: %d shots per set, the model was built for num_shot = %d" % (shot, self.n_shot))
+        if C < 1:
+            raise ValueError("encode_supports: no support set")
+        dev = support_ims.device
+        plan = self._get_plan()
+        product = self.attention_type == "product"
+        stream = ops.cur_stream()
+        per_set = []
+        with torch.no_grad():
+            for c in range(C):
+                sup_ims = support_ims[c].float().contiguous()
+                sup, sh_, sw_ = self._rcnn_base(sup_ims, plan)
+                self._check_support_map(sh_, sw_)
+                L = sh_ * sw_
+                _, kp, unary, s_t = self._support_rpn_side(sup, 1, shot, 1, L, dev, stream, branch=False)
+                sp_pe, k2, un2, sw, pool = self._support_roi_side(sup, shot, sh_, sw_, plan, dev, product)
+                per_set.append(dict(kp=kp, unary=unary, s_t=s_t, k2=k2, un2=un2, sw=sw, sp_pe=None if sw is not None else sp_pe))
+            tensors = {k: (None if per_set[0][k] is None else torch.stack([p_[k].reshape(-1) for p_ in per_set]))
+                       for k in SupportCache.FIELDS}
+        return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev)
+
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         """dana.py:87-220. The body is `_forward_gen`, a generator that pauses at the ONE host round trip of the
@@ -765,6 +898,12 @@ class DAnARCNN(nn.Module):
         plan = self._get_plan()
         dev = im_data.device
         training = self.training
+        cache = support_ims if isinstance(support_ims, SupportCache) else None
+        if cache is not None:
+            if training:
+                raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
+                                   "support side from support images")
+            cache._check(self, dev)
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
         B = im_data.size(0)
         im_info = im_info.data.float().contiguous()
@@ -852,19 +991,32 @@ class DAnARCNN(nn.Module):
         # -- feature extraction (dana.py:98-115): query and support batches share every trunk launch
         #    (twice the tiles -> half the tail on the 256 CUs); everything that depends only on the
         #    supports then runs on its own stream, concurrently with the query side. --
-        sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
-        Ns = sup_ims.size(0)
-        if Ns != B * way * shot:
-            raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, Ns))
-        # positions of a support map: 20 x 20 = 400 for the reference's 320 x 320 supports (dana.py:105 hard-codes it)
-        sh0, sw0 = self._feat_size(sup_ims.size(2), sup_ims.size(3))
+        if cache is not None:
+            # cached supports (encode_supports): the query-independent support side was computed once per support set;
+            # one launch gathers image b's set into this forward's B-batched buffers, the query side runs unchanged
+            Ns = B * shot
+            sh0, sw0 = cache.sup_map
+        else:
+            sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
+            Ns = sup_ims.size(0)
+            if Ns != B * way * shot:
+                raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, Ns))
+            # positions of a support map: 20 x 20 = 400 for the reference's 320 x 320 supports (dana.py:105 hard-codes it)
+            sh0, sw0 = self._feat_size(sup_ims.size(2), sup_ims.size(3))
         L = sh0 * sw0
         d = self.rpn_reduce_dim
         P = cfg.POOLING_SIZE
         P2 = P * P
         dq = self.rcnn_reduce_dim
         K1 = shot * L
-        if merge_trunk:
+        if cache is not None:
+            gathered = cache._gather(B)
+            kp, unary, s_t = gathered["kp"], gathered["unary"], gathered["s_t"]
+            fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
+            sh_, sw_ = sh0, sw0
+            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
+            self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
+        elif merge_trunk:
             sup_stream.wait_event(inputs_ready)
             corr, (fh, fw), sup, (sh_, sw_) = self._rcnn_base_dual(im_data, sup_ims, plan, dev,
                                                                    save_q=ctx["q_saved"] if ctx is not None else None,
@@ -901,61 +1053,20 @@ class DAnARCNN(nn.Module):
                 sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)
                 self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None)
         hw = fh * fw
-        if (sh_, sw_) != (20, 20):
-            # NOT a reference configuration (no oracle, no parity claim): the reference cannot run it at all. Opt-in
-            # generalisation for BASELINE.json's "224x224 supports": all L = sh*sw positions are attention keys and the
-            # 14/1 average pool becomes the (sh/7 x sw/7)-window pool that also ends in a 7x7 map.
-            if not self.generalised_support or sh_ % 7 or sw_ % 7:
-                raise RuntimeError("support images must be 320x320 (20x20 stride-16 map), as the reference hard-codes "
-                                   "(dana.py:105); got a %dx%d map%s" % (sh_, sw_, "" if self.generalised_support else
-                                   " (set model.generalised_support = True for maps whose sides are multiples of 7)"))
+        if cache is None:
+            self._check_support_map(sh_, sw_)
         mark("trunk (query + support)")
-        with ops.on_stream(sup_stream):
-            sup.record_stream(sup_stream)
-            # RPN-level support side (dana.py:126-145): PE, BA block, K projection, unary term, S^T
-            s_pe = torch.empty((B, shot * L, 1024), dtype=torch.float32, device=dev)
-            # positives = the first `shot` supports of each image (dana.py:103), way * shot maps apart: one launch
-            ops.add_pe_groups(sup, self._pe_table(L, dev), B, shot * L, L, 1024, way * shot * L * 1024, s_pe)
-            if self.semantic_enhance:  # BA block (dana.py:133-137)
-                wc, bc = self._w(self.rpn_channel_k_layer)
-                wgt = ops.rowdot(s_pe, wc, bc, B * shot * L, 1024)
-                ops.softmax_rows_(wgt, B * shot, L)
+        if cache is not None:
+            support_done = None
+        else:
+            with ops.on_stream(sup_stream):
+                sup.record_stream(sup_stream)
+                s_pe, kp, unary, s_t = self._support_rpn_side(sup, B, shot, way, L, dev, sup_stream, ctx)
+                for t_ in (kp, unary, s_t):
+                    t_.record_stream(main)
+                support_done = ops.record_event()
                 if ctx is not None:
-                    ctx.update(s_pre=s_pe.clone(), ba_w=wgt)
-                ops.ba_apply_(s_pe, wgt, B * shot, L, 1024, gamma=self.channel_gamma, slope=0.01)
-            # three independent consumers of the (BA-enhanced) support rows: K projection, unary term, S^T. The chain behind
-            # the support trunk is latency-bound (small dependent launches, 0.24 ms of which the caller's stream WAITS 0.125:
-            # tools/phase_times.py), so the unary term and the transpose run beside the K projection on an idle role stream
-            br_role = getattr(self, "rpn_side_role", "wgrad")
-            br = self._stream(br_role, dev) if (br_role and not getattr(self, "_single_stream", False)
-                                                and not torch.cuda.is_current_stream_capturing()) else None
-
-            def unary_and_transpose():
-                wu, bu = self._w(self.rpn_unary_layer)
-                u_ = ops.rowdot(s_pe, wu, bu, B * shot * L, 1024)
-                ops.softmax_rows_(u_, B * shot, L)
-                return u_, ops.transpose_batched(s_pe, B, K1, 1024)  # [B][1024][K1]
-
-            if br is not None:
-                s_pe_ready = ops.record_event()
-                br.wait_event(s_pe_ready)
-                s_pe.record_stream(br)
-                with ops.on_stream(br):
-                    unary, s_t = unary_and_transpose()
-                    branch_done = ops.record_event()
-            wk, bk = self._w(self.rpn_adapt_k_layer)
-            kb3, kld = self._lin_b(self.rpn_adapt_k_layer)
-            kp = ops.gemm_nt(s_pe, kb3, B * shot * L, d, 1024, ldb=kld, shift=bk)
-            ops.colmean_sub_(kp, B * shot, L, d)
-            if br is not None:
-                sup_stream.wait_event(branch_done)
-            else:
-                unary, s_t = unary_and_transpose()
-            for t_ in (kp, unary, s_t):
-                t_.record_stream(main)
-            support_done = ops.record_event()
-            if ctx is not None:
-                ctx.update(sup=sup, s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
+                    ctx.update(sup=sup, s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
 
         # -- RPN-level dual-awareness attention, query side (dana.py:118-154) --
         wq, bq = self._w(self.rpn_adapt_q_layer)
@@ -963,7 +1074,8 @@ class DAnARCNN(nn.Module):
         qp = ops.gemm_nt(corr, qb3, B * hw, d, 1024, lda=2048, ldb=qld, shift=bq)
         ops.colmean_sub_(qp, B, hw, d)
         mark("rpn-level Q projection")
-        main.wait_event(support_done)
+        if support_done is not None:
+            main.wait_event(support_done)
         mark("... wait for the support side (trunk + RPN-level K / unary / S^T chain)")
         scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
         ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
@@ -1006,42 +1118,21 @@ class DAnARCNN(nn.Module):
         #    reference recomputes them for every RoI). Only the RoI heads need them, so they are queued behind the RPN
         #    head: they run while the proposal layer (sort / NMS: a handful of workgroups) leaves the CUs idle,
         #    instead of competing with the query trunk. --
-        proposals_start = ops.record_event()
-        with ops.on_stream(sup_stream):
-            sup_stream.wait_event(proposals_start)
-            if (sh_, sw_) == (20, 20):
-                pool = (14, 1)  # nn.AvgPool2d(14, stride=1) (dana.py:42): 20x20 -> 7x7
-            else:
-                if sh_ != sw_:
-                    raise RuntimeError("generalised supports must be square")
-                pool = (sh_ // 7, sh_ // 7)
-            sp = ops.avgpool(sup, Ns, sh_, sw_, 1024, pool[0], pool[1])  # [Ns][49][1024]
-            sp_pe = ops.add_pe(sp, plan["pe49"], Ns * P2, P2, 1024)
-            wk2, bk2 = self._w(self.rcnn_adapt_k_layer)
-            k2b3, k2ld = self._lin_b(self.rcnn_adapt_k_layer)
-            k2 = ops.gemm_nt(sp_pe, k2b3, Ns * P2, dq, 1024, ldb=k2ld, shift=bk2)
-            ops.colmean_sub_(k2, Ns, P2, dq)
-            wu2, bu2 = self._w(self.rcnn_unary_layer)
-            un2 = ops.rowdot(sp_pe, wu2, bu2, Ns * P2, 1024)
-            ops.softmax_rows_(un2, Ns, P2)
-            sw = None
-            if getattr(self, "fold_roi_attn", True) and not product:  # (product needs the attended rows themselves)
-                # The head's two contractions re-associated (dana.py:279-286): the attended rows only feed the second half
-                # of rcnn_transform_layer, and (A . S) . Wt_a^T = A . (S . Wt_a^T) -- S . Wt_a^T is a [147][64] table per
-                # image computed ONCE here (under the proposal layer), the per-RoI work drops from K = 147 -> 1024 -> 64
-                # (10.8 GF per head at bs 4) to K = 147 -> 64 (0.5 GF) and the [n*49][1024] attended tensor (103 MB written
-                # and read back, per head) never exists -- nor do its adjoints in the backward, which differentiates the
-                # same re-associated form (backward.model_backward_gen).
-                wt_a_s, wt_a_s_ld = self._lin_b(self.rcnn_transform_layer, 1024, 1024)
-                sw = ops.gemm_nt(sp_pe, wt_a_s, Ns * P2, self.rcnn_dim, 1024, ldb=wt_a_s_ld)  # [Ns*49][64]
-                sw.record_stream(main)
+        if cache is not None:
+            sp_pe, k2, un2, sw = gathered["sp_pe"], gathered["k2"], gathered["un2"], gathered["sw"]
+            support_roi_done = None
+        else:
+            proposals_start = ops.record_event()
+            with ops.on_stream(sup_stream):
+                sup_stream.wait_event(proposals_start)
+                sp_pe, k2, un2, sw, pool = self._support_roi_side(sup, Ns, sh_, sw_, plan, dev, product, ctx)
+                if sw is not None:
+                    sw.record_stream(main)
+                for t_ in (sp_pe, k2, un2):
+                    t_.record_stream(main)
+                support_roi_done = ops.record_event()
                 if ctx is not None:
-                    ctx["sw"] = sw
-            for t_ in (sp_pe, k2, un2):
-                t_.record_stream(main)
-            support_roi_done = ops.record_event()
-            if ctx is not None:
-                ctx.update(sp_pe=sp_pe, k2=k2, un2=un2, sup_map=(sh_, sw_), sup_pool=pool)
+                    ctx.update(sp_pe=sp_pe, k2=k2, un2=un2, sup_map=(sh_, sw_), sup_pool=pool)
         if ctx is not None:
             # the backward's weight-only launches, on the (idle) weight-gradient stream: they run under the proposal layer and
             # the host round trip, where the chip has nothing else to do (backward.prefetch_dgrad_weights)
@@ -1215,7 +1306,6 @@ class DAnARCNN(nn.Module):
         def head(offset):  # offset 0: positive supports, `shot`: negatives (dana.py:189-190)
             kb = k2.view(-1)[offset * P2 * dq:]
             ub = un2.view(-1)[offset * P2:]
-            sb = sp_pe.view(-1)[offset * P2 * 1024:]
             sc2 = torch.empty((B, R * P2, K2p), dtype=torch.float32, device=dev)
             ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=B, batch_a=R * P2 * qld,
                         batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
@@ -1231,6 +1321,7 @@ class DAnARCNN(nn.Module):
                             batch_a=R * P2 * K2p, batch_b=rd_ * K2p, batch_c=R * P2 * rd_, k_true=K2)
                 ops.axpy_rows_(tr, tr_q, n_roi * P2, rd_, ld_y=rd_, ld_x=tr_q_ld)  # + q half (and the bias)
             else:
+                sb = sp_pe.view(-1)[offset * P2 * 1024:]
                 st2 = ops.transpose_batched(sb, B, K2, 1024, ldi=1024, ldo=K2p, in_batch=way * shot * P2 * 1024)
                 dense = torch.empty((n_roi * P2, 1024), dtype=torch.float32, device=dev)
                 ops.gemm_nt(sc2, st2, R * P2, 1024, K2p, lda=K2p, ldb=K2p, out=dense, ldc=1024, batch=B,
@@ -1293,3 +1384,120 @@ class DAnARCNN(nn.Module):
             rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = _LossBridge.apply(
                 self._grad_anchor, self, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox)
         return rois, cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label
+
+
+class SupportCache:
+    """The query-independent support tensors of C support sets (DAnARCNN.encode_supports), per set:
+    RPN level  kp [shot*L][d] (column mean subtracted), unary [shot][L] (softmaxed), s_t [1024][shot*L];
+    RoI level  k2 [shot*49][dq], un2 [shot][49], and sw [shot*49][64] (folded S.Wt^T) or sp_pe [shot*49][1024]
+               (product attention or fold_roi_attn off).
+    `model(im_data, im_info, gt_boxes, num_boxes, cache)`: query image b uses set index[b] -- `select(indices)`, else the
+    identity when C == B and a broadcast when C == 1. The forward gathers the selected sets into B-batched buffers the cache
+    owns (one launch, dana_gather_blocks, index read on the device: a recorded replay follows later `select` calls).
+    The cache records what it was built under; a forward after any of it changed raises ("re-encode")."""
+
+    FIELDS = ("kp", "unary", "s_t", "k2", "un2", "sw", "sp_pe")
+
+    def __init__(self, model, tensors, shot, sup_map, pool, state, dev):
+        self._model = weakref.ref(model)
+        self._t = {k: v for k, v in tensors.items() if v is not None}
+        self.shot, self.sup_map, self.pool, self.device = shot, tuple(sup_map), pool, torch.device(dev)
+        self._state = state
+        self._C = next(iter(self._t.values())).size(0)
+        L, P2 = sup_map[0] * sup_map[1], cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        d, dq, rd = model.rpn_reduce_dim, model.rcnn_reduce_dim, model.rcnn_dim
+        # the shapes the forward's consumers expect, per image (B of them stacked on the first axis)
+        self._shapes = dict(kp=(shot * L, d), unary=(shot, L), s_t=(1024, shot * L), k2=(shot * P2, dq), un2=(shot, P2),
+                            sw=(shot * P2, rd), sp_pe=(shot * P2, 1024))
+        self._sel = None        # host list of the last select(), or None
+        self._index = None      # device int32 [capacity]: what dana_gather_blocks reads
+        self._index_host = None  # what the device index holds
+        self._bufs = {}         # B -> (gathered tensors, device tables)
+
+    def __len__(self):
+        return self._C
+
+    @property
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in self._t.values())
+
+    def _check(self, model, dev):
+        if self._model() is not model:
+            raise RuntimeError("this SupportCache was encoded by another model: re-encode the supports with this one")
+        if torch.device(dev) != self.device:
+            raise RuntimeError("this SupportCache lives on %s, the query on %s: re-encode the supports there" % (self.device, dev))
+        if model._cache_state(dev) != self._state:
+            raise RuntimeError("the model changed since encode_supports (weights, MFMA mode, Winograd settings, "
+                               "attention_type, semantic_enhance, fold_roi_attn or num_shot): re-encode the supports")
+
+    @staticmethod
+    def _active_recording():
+        from . import _lib
+        return _lib.RECORDER is not None or torch.cuda.is_current_stream_capturing()
+
+    def select(self, indices):
+        """query image b of the next forwards uses support set indices[b] (a host sequence or a CPU tensor of length B).
+        Validated on the host, written into the device index the gather reads."""
+        if torch.is_tensor(indices):
+            if indices.is_cuda:
+                raise ValueError("SupportCache.select takes host indices (a sequence or a CPU tensor)")
+            indices = indices.reshape(-1).tolist()
+        idx = [int(i) for i in indices]
+        if not idx:
+            raise ValueError("SupportCache.select: empty selection")
+        bad = [i for i in idx if i < 0 or i >= self._C]
+        if bad:
+            raise IndexError("SupportCache.select: indices %s outside [0, %d)" % (bad, self._C))
+        self._sel = idx
+        self._write_index(idx)
+
+    def _resolve(self, B):
+        if self._sel is not None:
+            if len(self._sel) != B:
+                raise RuntimeError("SupportCache: %d selected sets for a batch of %d query images" % (len(self._sel), B))
+            return self._sel
+        if self._C == B:
+            return list(range(B))
+        if self._C == 1:
+            return [0] * B
+        raise RuntimeError("SupportCache of %d sets for a batch of %d query images: call cache.select(indices) "
+                           "(without it C == B means set b for image b, C == 1 one set for every image)" % (self._C, B))
+
+    def _write_index(self, idx):
+        if idx == self._index_host:
+            return
+        if self._active_recording():
+            raise RuntimeError("SupportCache: the selection changed inside a recording / capture: select before it")
+        if self._index is None or self._index.numel() < len(idx):
+            self._index = torch.zeros((max(len(idx), self._C, 16),), dtype=torch.int32, device=self.device)
+        self._index[:len(idx)].copy_(torch.tensor(idx, dtype=torch.int32))
+        self._index_host = list(idx)
+
+    def _prepare(self, B):
+        """host-side set-up of a B-image forward (selection written, gathered buffers + pointer tables allocated): what a
+        recording or capture must find done"""
+        self._write_index(self._resolve(B))
+        if (self._C == 1 and B == 1) or B in self._bufs:
+            return
+        if self._active_recording():
+            raise RuntimeError("SupportCache: first B = %d forward inside a recording / capture: run one eagerly first" % B)
+        names = [k for k in self.FIELDS if k in self._t]
+        dst = {k: torch.empty((B,) + self._shapes[k], dtype=torch.float32, device=self.device) for k in names}
+        for k in names:
+            if self._t[k][0].numel() != dst[k][0].numel():
+                raise RuntimeError("SupportCache: tensor %s has %d elements per set, expected %d"
+                                   % (k, self._t[k][0].numel(), dst[k][0].numel()))
+        tab = torch.tensor([[self._t[k].data_ptr() for k in names], [dst[k].data_ptr() for k in names],
+                            [self._t[k][0].numel() * 4 for k in names]], dtype=torch.int64).to(self.device)
+        self._bufs[B] = (dst, tab, len(names))
+
+    def _gather(self, B):
+        """-> {name: the B selected sets in the forward's layout}, gathered by one launch (none for one set, one image)"""
+        self._prepare(B)
+        if self._C == 1 and B == 1:
+            return {k: (self._t[k].view(self._shapes[k]) if k in self._t else None) for k in self.FIELDS}
+        dst, tab, n = self._bufs[B]
+        from ._lib import lib
+        lib().call("dana_gather_blocks", tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(), n, self._index.data_ptr(),
+                   self._C, B, ops._stream())
+        return {k: dst.get(k) for k in self.FIELDS}

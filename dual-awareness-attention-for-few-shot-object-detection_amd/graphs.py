@@ -44,6 +44,10 @@ class GraphedDAnA:
             raise RuntimeError("GraphedDAnA needs HIP tensors")
         if not hasattr(model, "_forward_gen"):
             raise RuntimeError("GraphedDAnA drives DAnARCNN (the siblings run eagerly)")
+        from .dana import SupportCache
+        if any(isinstance(t, SupportCache) for t in example_inputs):
+            raise NotImplementedError("GraphedDAnA does not capture the cached-support forward: replay it with "
+                                      "program.ProgramDAnA(model, ..., cache), or run it eagerly")
         self.model = model
         self.inputs = [_static_like(t) for t in example_inputs]
         self.stream = torch.cuda.Stream(device=dev)
@@ -93,6 +97,10 @@ class GraphedDAnA:
         cur.wait_stream(self.stream)
 
     def __call__(self, *inputs):
+        from .dana import SupportCache
+        if any(isinstance(t, SupportCache) for t in inputs):
+            raise NotImplementedError("GraphedDAnA replays the forward it captured (support images): a SupportCache "
+                                      "forward replays through program.ProgramDAnA")
         for s, t in zip(self.inputs, inputs):
             if torch.is_tensor(t) and t is not s:
                 s.copy_(t, non_blocking=True)

@@ -1,7 +1,8 @@
 """Inference post-processing on device: what inference.py:106-140 does between the
 model call and `all_boxes[j][i] = cls_dets` -- de-normalise the regression deltas, decode them on the rois,
 clip, rescale to the original image, threshold the fg score, sort, NMS (utils.py:312-317) -- as ONE C call
-(decode + device sort + on-device NMS) and one small D2H read for the variable-length result."""
+(decode + device sort + on-device NMS) and one small D2H read for the variable-length result.
+`detections_batched` does the same for B images in one C call and one D2H read of the per-image counts."""
 import ctypes
 
 import torch
@@ -35,3 +36,34 @@ def detections(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=Fa
     keep = host[:n_keep]
     keep = keep[keep < n_valid].long().to(dev)
     return dets[keep]
+
+
+def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False):
+    """rois [B,R,5], cls_prob [B*R,2], bbox_pred [B*R,4], im_info [B,3] (the eval forward's outputs for B images) ->
+    list of B cls_dets [K_b,5], each equal to `detections()` on its image. One C call (decode over B*R rows, B-row sort,
+    B NMS problems, packed compaction) and ONE D2H read of the per-image counts / offsets. with_layout=True also returns
+    the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]])."""
+    if rois.dim() != 3 or rois.size(2) != 5:
+        raise ValueError("detections_batched: rois must be [B, R, 5], got %s" % (tuple(rois.shape),))
+    B, R = rois.size(0), rois.size(1)
+    rois = ops._chk(rois.contiguous(), "rois")
+    cls_prob = ops._chk(cls_prob.reshape(-1, 2).contiguous(), "cls_prob")
+    bbox_pred = ops._chk(bbox_pred.reshape(-1, 4).contiguous(), "bbox_pred")
+    im_info = ops._chk(im_info.reshape(-1, im_info.size(-1))[:, :3].float().contiguous(), "im_info")
+    if cls_prob.size(0) != B * R or bbox_pred.size(0) != B * R or im_info.size(0) != B:
+        raise ValueError("detections_batched: cls_prob / bbox_pred need B*R = %d rows and im_info B = %d rows" % (B * R, B))
+    dev = rois.device
+    dets = torch.empty((max(B * R, 1), 5), dtype=torch.float32, device=dev)
+    layout = torch.empty((2 * B + 1,), dtype=torch.int32, device=dev)  # counts [B] | offsets [B+1]
+    ws = ops._ws(lib().query("dana_detect_postprocess_batched_workspace_bytes", B, R), dev)
+    f4 = ctypes.c_float * 4
+    lib().call("dana_detect_postprocess_batched", ops._p(rois), ops._p(cls_prob), ops._p(bbox_pred), ops._p(im_info), B,
+               R, ctypes.cast(f4(*cfg.TRAIN.BBOX_NORMALIZE_STDS), ctypes.c_void_p),
+               ctypes.cast(f4(*cfg.TRAIN.BBOX_NORMALIZE_MEANS), ctypes.c_void_p),
+               int(bool(cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED)), float(thresh), float(cfg.TEST.NMS),
+               int(bool(nms_inclusive)), ops._p(dets), layout.data_ptr(), layout.data_ptr() + 4 * B, ops._p(ws),
+               ws.numel(), ops._stream())
+    host = layout.cpu()
+    counts, offsets = host[:B], host[B:]
+    out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(B)]
+    return (out, counts, offsets) if with_layout else out

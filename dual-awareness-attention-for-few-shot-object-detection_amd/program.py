@@ -353,6 +353,11 @@ def _static_like(t):
     return t.detach().clone() if torch.is_tensor(t) else t
 
 
+def _support_cache(inputs):
+    from .dana import SupportCache
+    return next((t for t in inputs if isinstance(t, SupportCache)), None)
+
+
 class ProgramDAnA:
     """model(*inputs) as launch-program replays (train or eval mode, host or device RNG): the eager forward's launches on
     the eager forward's streams, minus its Python. Inputs are copied into static buffers (skipped when the caller passes
@@ -367,9 +372,15 @@ class ProgramDAnA:
             raise RuntimeError("ProgramDAnA drives DAnARCNN (the siblings run eagerly)")
         self.model = model
         self.inputs = [_static_like(t) for t in example_inputs]
+        # a SupportCache in place of support_ims (dana.encode_supports): the program keeps it (its tensors and the gathered
+        # buffers are what the recording points at) and refuses another cache or a stale one
+        self.cache = _support_cache(example_inputs)
         with torch.no_grad():
             for _ in range(warmup):  # eager: fills the plan / constant caches, creates the role streams
                 model(*self.inputs)
+        if self.cache is not None:
+            self.cache._prepare(self.inputs[0].size(0))  # selection written, gathered buffers allocated: outside the recording
+            self._cache_index = self.cache._index
         torch.cuda.synchronize(dev)
         self._device_rng = bool(getattr(model, "device_rng", False)) and model.training
         if self._device_rng:
@@ -412,6 +423,16 @@ class ProgramDAnA:
         torch.cuda.synchronize(dev)
 
     def __call__(self, *inputs):
+        cache = _support_cache(inputs)
+        if cache is not self.cache:
+            raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: record a new runner for it" % (
+                "support images" if self.cache is None else "another SupportCache",
+                "support images" if cache is None else "a different SupportCache"))
+        if cache is not None:
+            cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
+            cache._prepare(self.inputs[0].size(0))  # (the selection's length must still be the recorded batch)
+            if cache._index is not self._cache_index:
+                raise RuntimeError("the SupportCache's index buffer was reallocated after the recording: record a new runner")
         for s, t in zip(self.inputs, inputs):
             if torch.is_tensor(t) and t is not s:
                 s.copy_(t, non_blocking=True)

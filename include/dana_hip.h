@@ -150,6 +150,23 @@ int dana_detect_postprocess(const float* rois, const float* cls_prob, const floa
                             int R, const float* stds4, const float* means4, int normalize, float score_thresh,
                             float nms_thresh, int nms_inclusive, float* dets, int* keep_pos, int* meta,
                             void* workspace, size_t workspace_bytes, dana_stream_t stream);
+/* dana_detect_postprocess for B images of R rois each in one call: rois[B][R][5], cls_prob[B*R][2], bbox_pred[B*R][4],
+ * im_info[B][3]; the same decode, sort and NMS per image (B sort rows, B NMS problems). Output packed in image order:
+ * dets[sum K_b][5] (capacity B*R rows), image b's K_b = counts[b] detections at rows offsets[b].. (offsets[B] = sum K_b),
+ * each image's rows equal to what dana_detect_postprocess gives for it. */
+size_t dana_detect_postprocess_batched_workspace_bytes(int B, int R);
+int dana_detect_postprocess_batched(const float* rois, const float* cls_prob, const float* bbox_pred,
+                                    const float* im_info, int B, int R, const float* stds4, const float* means4,
+                                    int normalize, float score_thresh, float nms_thresh, int nms_inclusive, float* dets,
+                                    int* counts, int* offsets, void* workspace, size_t workspace_bytes,
+                                    dana_stream_t stream);
+
+/* Cached support sets (dana.SupportCache): for every tensor t < n_tensors and image b < B, copy block index[b] (block_bytes[t]
+ * bytes) of tensor t's sources into block b of its destination, all in ONE launch. src_ptrs / dst_ptrs are DEVICE arrays of
+ * n_tensors device pointers (const void* const* / void* const*), block_bytes a device array; index[B] is read on the device,
+ * so a recorded replay gathers the selection of the moment. Indices outside [0, n_sets) copy nothing. */
+int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* block_bytes, int n_tensors,
+                       const int* index, int n_sets, int B, dana_stream_t stream);
 
 /* ---- dense contractions on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) --------------------- */
 
