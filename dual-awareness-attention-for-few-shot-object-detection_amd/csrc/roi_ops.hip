@@ -123,7 +123,7 @@ __global__ void __launch_bounds__(256)
 roi_align_fwd_nhwc(const float* __restrict__ in, const float* __restrict__ rois, float* __restrict__ out,
                    float* __restrict__ out2, const float* __restrict__ add2,
                    int C, int H, int W, int PH, int PW, float scale, int sr, long in_pix_stride,
-                   long out_pix_stride, long out2_pix_stride) {
+                   long out_pix_stride, long out2_pix_stride, int group) {
   // XCD-aware order (block b runs on XCD b % 8): each XCD gets a contiguous run of (roi, bin) pairs, so the 49 bins of
   // a roi -- whose bilinear taps overlap -- and the rois of one image share ONE L2 instead of being dealt over all eight
   const int nwg = gridDim.x * gridDim.y, lin = blockIdx.y * gridDim.x + blockIdx.x;
@@ -134,7 +134,8 @@ roi_align_fwd_nhwc(const float* __restrict__ in, const float* __restrict__ rois,
   const int bin = v % bins;
   const int ph = bin / PW, pw = bin % PW;
   RoiGeom g = roi_geom(rois + (long)n * 5, scale, PH, PW, sr);
-  const float* img = in + (long)g.batch * H * W * in_pix_stride;
+  // (group > 1: roi column 0 is a class-sweep problem index, its image is problem / group)
+  const float* img = in + (long)(g.batch / group) * H * W * in_pix_stride;
   for (int c = threadIdx.x * 4; c < C; c += blockDim.x * 4) {
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int iy = 0; iy < g.grid_h; ++iy) {
@@ -182,7 +183,7 @@ __global__ void __launch_bounds__(256)
 roi_align_fwd_nhwc_sliced(const float* __restrict__ in, const float* __restrict__ rois, float* __restrict__ out,
                           float* __restrict__ out2, const float* __restrict__ add2,
                           int C, int H, int W, int PH, int PW, float scale, int sr, long in_pix_stride,
-                          long out_pix_stride, long out2_pix_stride, int total_bins, int xps) {
+                          long out_pix_stride, long out2_pix_stride, int total_bins, int xps, int group) {
   // workgroup b runs on XCD b % 8: XCDs slice * xps .. slice * xps + xps - 1 take that slice's (roi, bin) quadruples in turn
   const int lin = blockIdx.x, xcd = lin & 7, idx = lin >> 3;
   const int slice = xcd / xps, part = xcd - slice * xps;
@@ -196,7 +197,7 @@ roi_align_fwd_nhwc_sliced(const float* __restrict__ in, const float* __restrict_
   const RoiGeom g = roi_geom(rois + (long)n * 5, scale, PH, PW, sr);
   const int c = slice * 256 + lane * 4;
   const bool act = c < C;  // (the last slice of a C that is not a multiple of 256: idle lanes read channel 0)
-  const float* img = in + (long)g.batch * H * W * in_pix_stride + (act ? c : 0);
+  const float* img = in + (long)(g.batch / group) * H * W * in_pix_stride + (act ? c : 0);
   // (the second output's addend does not depend on the samples: in flight beside the first taps, not behind the last)
   float4 pe = make_float4(0.f, 0.f, 0.f, 0.f);
   if (out2) pe = *(const float4*)(add2 + (long)bin * C + (act ? c : 0));
@@ -504,11 +505,11 @@ int stream_grid(long total, int block) {
 
 extern "C" {
 
-int dana_roi_align_forward(const float* input, const float* rois, float* output, int batch, int channels,
-                           int height, int width, int num_rois, float spatial_scale, int pooled_h,
-                           int pooled_w, int sampling_ratio, int layout, long in_pix_stride,
-                           long out_pix_stride, float* output2, const float* add2, long out2_pix_stride,
-                           dana_stream_t stream) {
+static int roi_align_forward_impl(const float* input, const float* rois, float* output, int batch, int channels,
+                                  int height, int width, int num_rois, float spatial_scale, int pooled_h,
+                                  int pooled_w, int sampling_ratio, int layout, long in_pix_stride,
+                                  long out_pix_stride, float* output2, const float* add2, long out2_pix_stride, int group,
+                                  dana_stream_t stream) {
   DANA_CHECK_ARG(batch >= 0 && channels > 0 && height > 0 && width > 0 && num_rois >= 0 && pooled_h > 0 &&
                      pooled_w > 0,
                  "dana_roi_align_forward: bad shape B=%d C=%d H=%d W=%d R=%d P=%dx%d", batch, channels, height,
@@ -516,6 +517,8 @@ int dana_roi_align_forward(const float* input, const float* rois, float* output,
   if (num_rois == 0) return DANA_OK;  // ROIAlign_cuda.cu:278-281: empty -> no launch
   DANA_CHECK_ARG(input && rois && output, "dana_roi_align_forward: null pointer");
   hipStream_t s = (hipStream_t)stream;
+  DANA_CHECK_ARG(group > 0 && (group == 1 || layout == DANA_LAYOUT_NHWC), "dana_roi_align_forward: group %d (NHWC only)",
+                 group);
   if (layout == DANA_LAYOUT_NCHW) {
     DANA_CHECK_ARG(!output2, "dana_roi_align_forward: second output is NHWC-only");
     long total = (long)num_rois * channels * pooled_h * pooled_w;
@@ -536,18 +539,37 @@ int dana_roi_align_forward(const float* input, const float* rois, float* output,
       const long quads = (total_bins + 3) / 4;
       roi_align_fwd_nhwc_sliced<<<(unsigned)(8 * ((quads + xps - 1) / xps)), 256, 0, s>>>(
           input, rois, output, output2, add2, channels, height, width, pooled_h, pooled_w, spatial_scale, sampling_ratio,
-          in_pix_stride, out_pix_stride, out2_pix_stride, (int)total_bins, xps);
+          in_pix_stride, out_pix_stride, out2_pix_stride, (int)total_bins, xps, group);
     } else {  // (a slice count that does not divide the 8 XCDs: every workgroup sweeps all channels of its bin)
       dim3 grid(num_rois, pooled_h * pooled_w);
       roi_align_fwd_nhwc<<<grid, 256, 0, s>>>(input, rois, output, output2, add2, channels, height, width, pooled_h,
                                               pooled_w, spatial_scale, sampling_ratio, in_pix_stride,
-                                              out_pix_stride, out2_pix_stride);
+                                              out_pix_stride, out2_pix_stride, group);
     }
   } else {
     DANA_CHECK_ARG(false, "dana_roi_align_forward: unknown layout %d", layout);
   }
   DANA_CHECK_LAUNCH("dana_roi_align_forward");
   return DANA_OK;
+}
+
+int dana_roi_align_forward(const float* input, const float* rois, float* output, int batch, int channels,
+                           int height, int width, int num_rois, float spatial_scale, int pooled_h,
+                           int pooled_w, int sampling_ratio, int layout, long in_pix_stride,
+                           long out_pix_stride, float* output2, const float* add2, long out2_pix_stride,
+                           dana_stream_t stream) {
+  return roi_align_forward_impl(input, rois, output, batch, channels, height, width, num_rois, spatial_scale, pooled_h,
+                                pooled_w, sampling_ratio, layout, in_pix_stride, out_pix_stride, output2, add2,
+                                out2_pix_stride, 1, stream);
+}
+
+int dana_roi_align_forward_nhwc_grouped(const float* input, const float* rois, float* output, int batch, int channels,
+                                        int height, int width, int num_rois, float spatial_scale, int pooled,
+                                        int sampling_ratio, long in_pix_stride, long out_pix_stride, float* output2,
+                                        const float* add2, long out2_pix_stride, int group, dana_stream_t stream) {
+  return roi_align_forward_impl(input, rois, output, batch, channels, height, width, num_rois, spatial_scale, pooled,
+                                pooled, sampling_ratio, DANA_LAYOUT_NHWC, in_pix_stride, out_pix_stride, output2, add2,
+                                out2_pix_stride, group, stream);
 }
 
 int dana_roi_align_backward(const float* grad_out, const float* rois, float* grad_in, int batch, int channels,

@@ -103,7 +103,8 @@ wino_input_kernel(const float* __restrict__ in, float* __restrict__ V, int H, in
 __global__ void __launch_bounds__(256)
 wino_output_kernel(const float* __restrict__ M, float* __restrict__ out, const float* __restrict__ scale,
                    const float* __restrict__ shift, const float* __restrict__ mask, long ldm, int H, int W, int N4,
-                   int th, int tw, long tiles, long ldc, int relu) {
+                   int th, int tw, long tiles, long ldc, int relu, const float* __restrict__ res = nullptr, long ldr = 0,
+                   int rgroup = 1) {
   const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= tiles * N4) return;
   const int n4 = (int)(idx % N4);
@@ -138,6 +139,10 @@ wino_output_kernel(const float* __restrict__ M, float* __restrict__ out, const f
       const int x = 2 * j + c;
       if (x >= W) break;
       float4 v = make_float4(o[c].x * sc.x + sh.x, o[c].y * sc.y + sh.y, o[c].z * sc.z + sh.z, o[c].w * sc.w + sh.w);
+      if (res) {  // grouped residual (class sweep): output image img reads residual image img / rgroup
+        const float4 q = *(const float4*)(res + (((img / rgroup) * H + y) * W + x) * ldr + n4 * 4);
+        v = f4add(v, q);
+      }
       if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
       if (mask) {  // ReLU adjoint (data-gradient use): zero where the masking activation is <= 0
         const float4 k = *(const float4*)(mask + ((img * H + y) * W + x) * ldm + n4 * 4);
@@ -262,7 +267,8 @@ __device__ __forceinline__ void at6(const float4 (&m)[6], float4 (&o)[4]) {
 __global__ void __launch_bounds__(256)
 wino4_output_kernel(const float* __restrict__ M, float* __restrict__ out, const float* __restrict__ scale,
                     const float* __restrict__ shift, const float* __restrict__ mask, long ldm, int H, int W, int N4,
-                    int th, int tw, long tiles, long ldc, int relu, long plane_tiles = 0, long tile_off = 0) {
+                    int th, int tw, long tiles, long ldc, int relu, long plane_tiles = 0, long tile_off = 0,
+                    const float* __restrict__ res = nullptr, long ldr = 0, int rgroup = 1) {
   const unsigned idx = blockIdx.x * blockDim.x + threadIdx.x;  // (32-bit index math, see wino4_input_kernel)
   if (idx >= (unsigned)(tiles * N4)) return;
   if (plane_tiles == 0) plane_tiles = tiles;
@@ -297,6 +303,10 @@ wino4_output_kernel(const float* __restrict__ M, float* __restrict__ out, const 
       const int x = 4 * j + c;
       if (x >= W) break;
       float4 v = make_float4(o[c].x * sc.x + sh.x, o[c].y * sc.y + sh.y, o[c].z * sc.z + sh.z, o[c].w * sc.w + sh.w);
+      if (res) {  // grouped residual (class sweep): output image img reads residual image img / rgroup
+        const float4 q = *(const float4*)(res + (((img / rgroup) * H + y) * W + x) * ldr + n4 * 4);
+        v = f4add(v, q);
+      }
       if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
       if (mask) {
         const float4 k = *(const float4*)(mask + ((img * H + y) * W + x) * ldm + n4 * 4);
@@ -432,10 +442,10 @@ int dana_conv3x3_winograd_nhwc(const float* input, const float* u, float* output
                                            out_pix_stride, 0, flags, workspace, workspace_bytes, stream);
 }
 
-int dana_conv3x3_winograd_nhwc_masked(const float* input, const float* u, float* output, const float* scale,
-                                      const float* shift, const float* mask_act, int batch, int h, int w, int cin,
-                                      int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
-                                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+static int wino2_impl(const float* input, const float* u, float* output, const float* scale, const float* shift,
+                      const float* mask_act, const float* res, long res_pix_stride, int res_group, int batch, int h,
+                      int w, int cin, int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
+                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
   DANA_CHECK_ARG(batch >= 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && cin % 4 == 0 && cout % 4 == 0,
                  "dana_conv3x3_winograd_nhwc: bad shape");
   if (batch == 0) return DANA_OK;
@@ -443,6 +453,9 @@ int dana_conv3x3_winograd_nhwc_masked(const float* input, const float* u, float*
   const long lda = in_pix_stride > 0 ? in_pix_stride : cin;
   const long ldc = out_pix_stride > 0 ? out_pix_stride : cout;
   const long ldm = mask_pix_stride > 0 ? mask_pix_stride : cout;
+  const long ldr = res_pix_stride > 0 ? res_pix_stride : cout;
+  DANA_CHECK_ARG(!res || (ldr % 4 == 0 && ((uintptr_t)res & 15) == 0 && res_group > 0),
+                 "dana_conv3x3_winograd_nhwc: residual rows must be 16-byte aligned, group > 0");
   DANA_CHECK_ARG(!mask_act || (ldm % 4 == 0 && ((uintptr_t)mask_act & 15) == 0),
                  "dana_conv3x3_winograd_nhwc: mask rows must be 16-byte aligned");
   DANA_CHECK_ARG(lda % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)input & 15) == 0 && ((uintptr_t)output & 15) == 0,
@@ -466,9 +479,17 @@ int dana_conv3x3_winograd_nhwc_masked(const float* input, const float* u, float*
   if (rc) return rc;
   wino_output_kernel<<<dana_ceil_div(p.tiles * N4, 256), 256, 0, s>>>(M, output, scale, shift, mask_act, ldm, h, w, N4,
                                                                      p.th, p.tw, p.tiles, ldc,
-                                                                     (flags & DANA_EPI_RELU) ? 1 : 0);
+                                                                     (flags & DANA_EPI_RELU) ? 1 : 0, res, ldr, res_group);
   DANA_CHECK_LAUNCH("dana_conv3x3_winograd_nhwc(output transform)");
   return DANA_OK;
+}
+
+int dana_conv3x3_winograd_nhwc_masked(const float* input, const float* u, float* output, const float* scale,
+                                      const float* shift, const float* mask_act, int batch, int h, int w, int cin,
+                                      int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
+                                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+  return wino2_impl(input, u, output, scale, shift, mask_act, nullptr, 0, 1, batch, h, w, cin, cout, in_pix_stride,
+                    out_pix_stride, mask_pix_stride, flags, workspace, workspace_bytes, stream);
 }
 
 size_t dana_conv3x3_wgrad_winograd4_workspace_bytes(int batch, int h, int w, int cin, int cout) {
@@ -559,10 +580,10 @@ size_t dana_conv3x3_winograd4_workspace_bytes(int batch, int h, int w, int cin, 
   return wino_plan(batch, h, w, cin, cout, 4).total;
 }
 
-int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float* output, const float* scale,
-                                       const float* shift, const float* mask_act, int batch, int h, int w, int cin,
-                                       int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
-                                       int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+static int wino4_impl(const float* input, const float* u, float* output, const float* scale, const float* shift,
+                      const float* mask_act, const float* res, long res_pix_stride, int res_group, int batch, int h,
+                      int w, int cin, int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
+                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
   DANA_CHECK_ARG(batch >= 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && cin % 4 == 0 && cout % 4 == 0,
                  "dana_conv3x3_winograd4_nhwc: bad shape");
   if (batch == 0) return DANA_OK;
@@ -570,6 +591,9 @@ int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float
   const long lda = in_pix_stride > 0 ? in_pix_stride : cin;
   const long ldc = out_pix_stride > 0 ? out_pix_stride : cout;
   const long ldm = mask_pix_stride > 0 ? mask_pix_stride : cout;
+  const long ldr = res_pix_stride > 0 ? res_pix_stride : cout;
+  DANA_CHECK_ARG(!res || (ldr % 4 == 0 && ((uintptr_t)res & 15) == 0 && res_group > 0),
+                 "dana_conv3x3_winograd4_nhwc: residual rows must be 16-byte aligned, group > 0");
   DANA_CHECK_ARG(!mask_act || (ldm % 4 == 0 && ((uintptr_t)mask_act & 15) == 0),
                  "dana_conv3x3_winograd4_nhwc: mask rows must be 16-byte aligned");
   DANA_CHECK_ARG(lda % 4 == 0 && ldc % 4 == 0 && ((uintptr_t)input & 15) == 0 && ((uintptr_t)output & 15) == 0,
@@ -598,9 +622,17 @@ int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float
   if (rc) return rc;
   wino4_output_kernel<<<dana_ceil_div(p.tiles * N4, 256), 256, 0, s>>>(M, output, scale, shift, mask_act, ldm, h, w, N4,
                                                                       p.th, p.tw, p.tiles, ldc,
-                                                                      (flags & DANA_EPI_RELU) ? 1 : 0);
+                                                                      (flags & DANA_EPI_RELU) ? 1 : 0, 0, 0, res, ldr, res_group);
   DANA_CHECK_LAUNCH("dana_conv3x3_winograd4_nhwc(output transform)");
   return DANA_OK;
+}
+
+int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float* output, const float* scale,
+                                       const float* shift, const float* mask_act, int batch, int h, int w, int cin,
+                                       int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
+                                       int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+  return wino4_impl(input, u, output, scale, shift, mask_act, nullptr, 0, 1, batch, h, w, cin, cout, in_pix_stride,
+                    out_pix_stride, mask_pix_stride, flags, workspace, workspace_bytes, stream);
 }
 
 size_t dana_conv3x3_winograd4_dual_workspace_bytes(int n0, int h0, int w0, int n1, int h1, int w1, int cin, int cout) {
@@ -667,6 +699,20 @@ int dana_conv3x3_winograd4_nhwc_dual_masked(const float* input, const float* u, 
                                                                        p1.tw, p1.tiles, ldc1, relu, T, p0.tiles);
   DANA_CHECK_LAUNCH("dana_conv3x3_winograd4_nhwc_dual(output transforms)");
   return DANA_OK;
+}
+
+int dana_conv3x3_winograd_nhwc_grouped_res(const float* input, const float* u, float* output, const float* scale,
+                                           const float* shift, const float* residual, int batch, int h, int w, int cin,
+                                           int cout, long in_pix_stride, long out_pix_stride, long res_pix_stride,
+                                           int res_group, int tile, int flags, void* workspace, size_t workspace_bytes,
+                                           dana_stream_t stream) {
+  DANA_CHECK_ARG(residual && res_group > 0 && (tile == 2 || tile == 4),
+                 "dana_conv3x3_winograd_nhwc_grouped_res: needs a residual, res_group > 0, tile 2 or 4");
+  if (tile == 2)
+    return wino2_impl(input, u, output, scale, shift, nullptr, residual, res_pix_stride, res_group, batch, h, w, cin, cout,
+                      in_pix_stride, out_pix_stride, 0, flags, workspace, workspace_bytes, stream);
+  return wino4_impl(input, u, output, scale, shift, nullptr, residual, res_pix_stride, res_group, batch, h, w, cin, cout,
+                    in_pix_stride, out_pix_stride, 0, flags, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

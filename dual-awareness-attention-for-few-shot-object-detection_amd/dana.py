@@ -835,6 +835,55 @@ class DAnARCNN(nn.Module):
                 ctx["sw"] = sw
         return sp_pe, k2, un2, sw, pool
 
+    def _rpn_split_plan(self, plan):
+        """the RPN conv's filters split by input channels (W[:, :1024] on base_feat, W[:, 1024:] on the attended rows),
+        in the form the full conv uses (Winograd filters or packed weights, split planes when those are presplit), cached
+        by weight version like the plan"""
+        e = self._conv_cache.get("rpn_split")
+        if e is None or e[0] != plan["sig"]:
+            w = self.RCNN_rpn.RPN_Conv.weight.detach()
+            halves = {}
+            for k, c0 in (("base", 0), ("att", 1024)):
+                wp = ops.pack_conv_weight(w[:, c0:c0 + 1024].contiguous())
+                if plan["rpn_conv_u"] is not None:
+                    u = ops.winograd_filter_transform(wp, 512, 1024, self.winograd_tile)
+                    halves[k] = ops.split_weight(u, 512, 1024, batch=36) if plan["rpn_conv_b3"] is not None else u
+                else:
+                    halves[k] = ops.split_weight(wp, 512, 9 * 1024) if plan["rpn_conv_b3"] is not None else wp
+            e = self._conv_cache["rpn_split"] = (plan["sig"], halves)
+        return e[1]
+
+    def _rpn_conv_sweep(self, plan, corr, att, B, Cs, fh, fw, product):
+        """RPN_Conv + ReLU (rpn.py:63) of a class sweep's B*C problems -> [B*C*hw][512]. Concat attention is linear in the
+        two input halves: W * [base | att_p] = W[:, :1024] * base + W[:, 1024:] * att_p, and the first term depends on the
+        image only -- it runs once per image, and the per-problem conv adds it in its epilogue (grouped residual: problem
+        p reads image p / C). Product attention is not separable: the conv runs per problem on the product rows."""
+        rpn = self.RCNN_rpn
+        NP, hw = B * Cs, fh * fw
+        if product:
+            if plan["rpn_conv_u"] is not None:
+                x, _, _ = ops.conv3x3_winograd(att, NP, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512,
+                                               shift=plan["rpn_conv_b"], relu=True, in_stride=1024)
+            else:
+                x, _, _ = ops.conv2d_nhwc(att, NP, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1,
+                                          1, shift=plan["rpn_conv_b"], relu=True, in_stride=1024)
+            return x
+        if rpn.din != 2048:
+            raise RuntimeError("class sweep: the RPN conv expects [base_feat | attended] = 2048 input channels, got %d" % rpn.din)
+        half = self._rpn_split_plan(plan)
+        if plan["rpn_conv_u"] is not None:
+            part, _, _ = ops.conv3x3_winograd(corr, B, fh, fw, 1024, half["base"], 512, in_stride=2048)
+            x, _, _ = ops.conv3x3_winograd(att, NP, fh, fw, 1024, half["att"], 512, shift=plan["rpn_conv_b"], relu=True,
+                                           in_stride=1024, residual=part, res_stride=512, res_group=Cs)
+        else:
+            # (the implicit-GEMM conv's residual has no group divisor: the per-image partial is replicated per problem,
+            #  one launch of B*C*hw*512 floats)
+            part, _, _ = ops.conv2d_nhwc(corr, B, fh, fw, 1024, half["base"], 512, 3, 3, 1, 1, in_stride=2048)
+            rep_ = ops.repeat_rows_grouped(part, hw, 512, Cs, NP)
+            x, _, _ = ops.conv2d_nhwc(att, NP, fh, fw, 1024, half["att"], 512, 3, 3, 1, 1, shift=plan["rpn_conv_b"],
+                                      relu=True, in_stride=1024, residual=rep_, res_stride=512)
+        return x
+
     def _cache_state(self, dev):
         """what a SupportCache's tensors depend on besides the support images"""
         return (self._sig(), str(dev), self.attention_type, bool(self.semantic_enhance),
@@ -898,14 +947,21 @@ class DAnARCNN(nn.Module):
         plan = self._get_plan()
         dev = im_data.device
         training = self.training
-        cache = support_ims if isinstance(support_ims, SupportCache) else None
+        # a ClassSweep (cache.sweep(classes)): every query image against each of C cached sets, B*C problems p = b*C + c
+        sweep = support_ims if isinstance(support_ims, ClassSweep) else None
+        cache = sweep.cache if sweep is not None else (support_ims if isinstance(support_ims, SupportCache) else None)
         if cache is not None:
             if training:
                 raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
                                    "support side from support images")
             cache._check(self, dev)
+        if sweep is not None and cfg.POOLING_MODE != "align":
+            raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
+                                      "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
         B = im_data.size(0)
+        Cs = len(sweep) if sweep is not None else 1
+        NP = B * Cs  # problems: the RPN stage from the attention on and the RoI stage run over them
         im_info = im_info.data.float().contiguous()
         gt_boxes = gt_boxes.data
         shot = self.n_shot
@@ -1010,7 +1066,8 @@ class DAnARCNN(nn.Module):
         dq = self.rcnn_reduce_dim
         K1 = shot * L
         if cache is not None:
-            gathered = cache._gather(B)
+            # (a sweep gathers B*C sets, the selection repeated for every image: image b's C blocks are contiguous)
+            gathered = cache._gather(NP, sweep._index(B) if sweep is not None else None)
             kp, unary, s_t = gathered["kp"], gathered["unary"], gathered["s_t"]
             fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
             sh_, sw_ = sh0, sw0
@@ -1077,14 +1134,28 @@ class DAnARCNN(nn.Module):
         if support_done is not None:
             main.wait_event(support_done)
         mark("... wait for the support side (trunk + RPN-level K / unary / S^T chain)")
-        scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
-        ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
-                    alpha=1.0 / math.sqrt(d))
-        ops.attn_softmax_unary_(scores, unary, B * hw, hw, shot, L, K1, K1, self.unary_gamma, 1.0 / shot)
-        ops.gemm_nt(scores, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=corr.view(-1)[1024:], ldc=2048, batch=B,
-                    batch_a=hw * K1, batch_b=1024 * K1, batch_c=hw * 2048)
         product = self.attention_type == "product"
-        if product:
+        if sweep is not None:
+            # one GEMM per image over the C classes' keys side by side (N = C*K1: one read of qp[b]), then the softmax
+            # moves row (b, i, c) to problem b*C + c, so the attended GEMM is a uniform batch over the B*C problems
+            scores = torch.empty((B, hw, Cs * K1), dtype=torch.float32, device=dev)
+            ops.gemm_nt(qp, kp, hw, Cs * K1, d, out=scores, ldc=Cs * K1, batch=B, batch_a=hw * d, batch_b=Cs * K1 * d,
+                        batch_c=hw * Cs * K1, alpha=1.0 / math.sqrt(d))
+            a_p = torch.empty((NP, hw, K1), dtype=torch.float32, device=dev)
+            ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, shot, L, K1, K1, K1, self.unary_gamma, 1.0 / shot)
+            att = torch.empty((NP * hw, 1024), dtype=torch.float32, device=dev)  # problem p's attended rows
+            ops.gemm_nt(a_p, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=att, ldc=1024, batch=NP, batch_a=hw * K1,
+                        batch_b=1024 * K1, batch_c=hw * 1024)
+            if product:  # dana.py:155-156 with base_feat of image p / C
+                ops.mul_rows_grouped_(att, corr, hw, 1024, Cs, NP, ld_y=1024, ld_x=2048)
+        else:
+            scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
+            ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
+                        alpha=1.0 / math.sqrt(d))
+            ops.attn_softmax_unary_(scores, unary, B * hw, hw, shot, L, K1, K1, self.unary_gamma, 1.0 / shot)
+            ops.gemm_nt(scores, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=corr.view(-1)[1024:], ldc=2048, batch=B,
+                        batch_a=hw * K1, batch_b=1024 * K1, batch_c=hw * 2048)
+        if product and sweep is None:
             # dana.py:155-156: correlation_feat = base_feat * dense_support_feature -- in place in the attended half of the
             # buffer (nothing else reads the attended rows); the RPN conv then reads that half only (cin 1024, pixel stride
             # 2048), RoIAlign keeps reading base_feat from the first half
@@ -1102,7 +1173,9 @@ class DAnARCNN(nn.Module):
         # -- RPN head + proposals (rpn.py:58-78, proposal_layer.py:49-190) --
         rpn = self.RCNN_rpn
         rpn_in = corr.view(-1)[1024:] if product else corr  # (product: the attended half, pixel stride 2048)
-        if plan["rpn_conv_u"] is not None:
+        if sweep is not None:
+            x = self._rpn_conv_sweep(plan, corr, att, B, Cs, fh, fw, product)
+        elif plan["rpn_conv_u"] is not None:
             kv = [] if ctx is not None else None
             x, _, _ = ops.conv3x3_winograd(rpn_in, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512,
                                            shift=plan["rpn_conv_b"], relu=True, keep_v=kv, in_stride=2048)
@@ -1112,7 +1185,7 @@ class DAnARCNN(nn.Module):
             x, _, _ = ops.conv2d_nhwc(rpn_in, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1, 1,
                                       shift=plan["rpn_conv_b"], relu=True, in_stride=2048)
         nh = rpn.nc_score_out + rpn.nc_bbox_out
-        heads = ops.gemm_nt(x, plan["rpn_head_w3"] or plan["rpn_head_w"], B * hw, nh, 512, shift=plan["rpn_head_b"])  # [B*hw][2A | 4A]
+        heads = ops.gemm_nt(x, plan["rpn_head_w3"] or plan["rpn_head_w"], NP * hw, nh, 512, shift=plan["rpn_head_b"])  # [B*hw][2A | 4A]
         mark("rpn conv + heads")
         # -- RoI-level support side (dana.py:105-108,258,271-277): K / unary projections once per support (the
         #    reference recomputes them for every RoI). Only the RoI heads need them, so they are queued behind the RPN
@@ -1140,8 +1213,10 @@ class DAnARCNN(nn.Module):
             BW.prefetch_dgrad_weights(self, ctx, dev)
         A = plan["anchors"].size(0)
         key = "TRAIN" if training else "TEST"
+        # (a sweep's problem p clips and filters with the im_info row of image p / C: one launch)
+        im_info_p = im_info if sweep is None else ops.repeat_rows_grouped(im_info, 1, 3, Cs, NP, ld_src=im_info.size(1))
         rois = ops.proposal_layer(heads, (hw * nh, 1, nh), False, heads.view(-1)[rpn.nc_score_out:], (hw * nh, 1, nh),
-                                  im_info, plan["anchors"], B, A, fh, fw, rpn.feat_stride,
+                                  im_info_p, plan["anchors"], NP, A, fh, fw, rpn.feat_stride,
                                   cfg[key].RPN_PRE_NMS_TOP_N, cfg[key].RPN_POST_NMS_TOP_N, cfg[key].RPN_NMS_THRESH,
                                   self.nms_inclusive)
         mark("proposal layer (decode, sort, nms)")
@@ -1207,7 +1282,7 @@ class DAnARCNN(nn.Module):
             rois_outside_ws = rois_outside_ws.view(-1, 4)
         mark("rpn losses + proposal targets")
         R = rois.size(1)
-        n_roi = B * R
+        n_roi = NP * R
 
         # -- RoIAlign on base_feat (dana.py:181-186), emitting pooled and pooled+PE in one pass --
         # Forward-only runs (nothing saved for a backward) fold the positional encoding of dana.py:259 into the two
@@ -1216,11 +1291,13 @@ class DAnARCNN(nn.Module):
         # Q projection and the query half of rcnn_transform_layer are ONE N = 128 GEMM over pooled (one read of it).
         fold_pe = (ctx is None and cfg.POOLING_MODE == "align" and getattr(self, "fold_roi_pe", True)
                    and self.attention_type == "concat")  # (product multiplies by pooled + PE itself: dana.py:286)
+        # (a sweep's rois carry the problem index p in column 0: RoIAlign reads base_feat of image p / C)
         if cfg.POOLING_MODE == "align" and fold_pe:
-            pooled, q_pe = ops.roi_align_forward_nhwc(corr, B, fh, fw, 1024, 2048, rois.view(-1, 5), 1.0 / 16.0, P, 0)
+            pooled, q_pe = ops.roi_align_forward_nhwc(corr, B, fh, fw, 1024, 2048, rois.view(-1, 5), 1.0 / 16.0, P, 0,
+                                                      group=Cs)
         elif cfg.POOLING_MODE == "align":
             pooled, q_pe = ops.roi_align_forward_nhwc(corr, B, fh, fw, 1024, 2048, rois.view(-1, 5), 1.0 / 16.0, P, 0,
-                                                      pe=plan["pe49"])  # pooled [n,49,1024] and pooled + PE (dana.py:259)
+                                                      pe=plan["pe49"], group=Cs)  # pooled [n,49,1024] and pooled + PE (dana.py:259)
         elif cfg.POOLING_MODE == "pool":
             # dana.py:183-184 (a resumed checkpoint's cfg may ask for it, train.py:100-101): the RoIPool operator of the
             # `_C` boundary on base_feat (the first 1024 channels of the [.. | attended] buffer); the saving forward keeps
@@ -1306,25 +1383,25 @@ class DAnARCNN(nn.Module):
         def head(offset):  # offset 0: positive supports, `shot`: negatives (dana.py:189-190)
             kb = k2.view(-1)[offset * P2 * dq:]
             ub = un2.view(-1)[offset * P2:]
-            sc2 = torch.empty((B, R * P2, K2p), dtype=torch.float32, device=dev)
-            ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=B, batch_a=R * P2 * qld,
+            sc2 = torch.empty((NP, R * P2, K2p), dtype=torch.float32, device=dev)
+            ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=NP, batch_a=R * P2 * qld,
                         batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
             ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, 1.0 / shot,
                                     unary_batch_stride=way * shot * P2)
             rd_ = self.rcnn_dim
             if sw is not None:
-                swt = ops.transpose_batched(sw.view(-1)[offset * P2 * rd_:], B, K2, rd_, ldi=rd_, ldo=K2p,
+                swt = ops.transpose_batched(sw.view(-1)[offset * P2 * rd_:], NP, K2, rd_, ldi=rd_, ldo=K2p,
                                             in_batch=way * shot * P2 * rd_)  # [B][64][K2p], zero padded
                 dense = None
                 tr = torch.empty((n_roi * P2, rd_), dtype=torch.float32, device=dev)
-                ops.gemm_nt(sc2, swt, R * P2, rd_, K2p, lda=K2p, ldb=K2p, out=tr, ldc=rd_, batch=B,
+                ops.gemm_nt(sc2, swt, R * P2, rd_, K2p, lda=K2p, ldb=K2p, out=tr, ldc=rd_, batch=NP,
                             batch_a=R * P2 * K2p, batch_b=rd_ * K2p, batch_c=R * P2 * rd_, k_true=K2)
                 ops.axpy_rows_(tr, tr_q, n_roi * P2, rd_, ld_y=rd_, ld_x=tr_q_ld)  # + q half (and the bias)
             else:
                 sb = sp_pe.view(-1)[offset * P2 * 1024:]
-                st2 = ops.transpose_batched(sb, B, K2, 1024, ldi=1024, ldo=K2p, in_batch=way * shot * P2 * 1024)
+                st2 = ops.transpose_batched(sb, NP, K2, 1024, ldi=1024, ldo=K2p, in_batch=way * shot * P2 * 1024)
                 dense = torch.empty((n_roi * P2, 1024), dtype=torch.float32, device=dev)
-                ops.gemm_nt(sc2, st2, R * P2, 1024, K2p, lda=K2p, ldb=K2p, out=dense, ldc=1024, batch=B,
+                ops.gemm_nt(sc2, st2, R * P2, 1024, K2p, lda=K2p, ldb=K2p, out=dense, ldc=1024, batch=NP,
                             batch_a=R * P2 * K2p, batch_b=1024 * K2p, batch_c=R * P2 * 1024, k_true=K2)
                 if product:
                     ops.mul_rows_(dense, q_pe, n_roi * P2, 1024)  # query_mat * attended (dana.py:286)
@@ -1451,6 +1528,24 @@ class SupportCache:
         self._sel = idx
         self._write_index(idx)
 
+    def sweep(self, classes=None):
+        """-> ClassSweep: `model(im_data, im_info, gt_boxes, num_boxes, cache.sweep(classes))` runs every query image
+        against each listed set (default: all C, in order). classes: a host sequence or a CPU tensor of set indices."""
+        if classes is None:
+            idx = list(range(self._C))
+        else:
+            if torch.is_tensor(classes):
+                if classes.is_cuda:
+                    raise ValueError("SupportCache.sweep takes host indices (a sequence or a CPU tensor)")
+                classes = classes.reshape(-1).tolist()
+            idx = [int(i) for i in classes]
+        if not idx:
+            raise ValueError("SupportCache.sweep: empty class list")
+        bad = [i for i in idx if i < 0 or i >= self._C]
+        if bad:
+            raise IndexError("SupportCache.sweep: indices %s outside [0, %d)" % (bad, self._C))
+        return ClassSweep(self, idx)
+
     def _resolve(self, B):
         if self._sel is not None:
             if len(self._sel) != B:
@@ -1473,10 +1568,11 @@ class SupportCache:
         self._index[:len(idx)].copy_(torch.tensor(idx, dtype=torch.int32))
         self._index_host = list(idx)
 
-    def _prepare(self, B):
-        """host-side set-up of a B-image forward (selection written, gathered buffers + pointer tables allocated): what a
-        recording or capture must find done"""
-        self._write_index(self._resolve(B))
+    def _prepare(self, B, idx=None):
+        """host-side set-up of a forward that gathers B sets (selection written, gathered buffers + pointer tables
+        allocated): what a recording or capture must find done. idx: the B set indices (a class sweep's), else the
+        selection / default for B images"""
+        self._write_index(self._resolve(B) if idx is None else idx)
         if (self._C == 1 and B == 1) or B in self._bufs:
             return
         if self._active_recording():
@@ -1491,9 +1587,9 @@ class SupportCache:
                             [self._t[k][0].numel() * 4 for k in names]], dtype=torch.int64).to(self.device)
         self._bufs[B] = (dst, tab, len(names))
 
-    def _gather(self, B):
+    def _gather(self, B, idx=None):
         """-> {name: the B selected sets in the forward's layout}, gathered by one launch (none for one set, one image)"""
-        self._prepare(B)
+        self._prepare(B, idx)
         if self._C == 1 and B == 1:
             return {k: (self._t[k].view(self._shapes[k]) if k in self._t else None) for k in self.FIELDS}
         dst, tab, n = self._bufs[B]
@@ -1501,3 +1597,26 @@ class SupportCache:
         lib().call("dana_gather_blocks", tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(), n, self._index.data_ptr(),
                    self._C, B, ops._stream())
         return {k: dst.get(k) for k in self.FIELDS}
+
+
+class ClassSweep:
+    """SupportCache.sweep(classes): as the 5th argument of an eval-mode forward, each of the B query images runs against
+    each of the C listed sets -- B*C problems p = b*C + c, each the cached forward of image b with set classes[c]
+    (dana.py:87-220 per class, as inference.py:70-140 fills all_boxes[j][i]). The query trunk runs once per image; the
+    outputs are laid out as the replicated call `model(im.repeat_interleave(C, 0), ..., cache)` after
+    `cache.select(classes * B)` lays them out: rois [B*C, R, 5] (column 0 = p), cls_prob [B*C*R, 2], bbox_pred [B*C*R, 4]."""
+
+    __slots__ = ("cache", "classes")
+
+    def __init__(self, cache, classes):
+        self.cache, self.classes = cache, tuple(classes)
+
+    def __len__(self):
+        return len(self.classes)
+
+    def _index(self, B):
+        """the gather index of a B-image forward: the class list repeated for every image"""
+        return list(self.classes) * B
+
+    def __repr__(self):
+        return "ClassSweep(%d sets: %s)" % (len(self.classes), list(self.classes))

@@ -44,9 +44,9 @@ class GraphedDAnA:
             raise RuntimeError("GraphedDAnA needs HIP tensors")
         if not hasattr(model, "_forward_gen"):
             raise RuntimeError("GraphedDAnA drives DAnARCNN (the siblings run eagerly)")
-        from .dana import SupportCache
-        if any(isinstance(t, SupportCache) for t in example_inputs):
-            raise NotImplementedError("GraphedDAnA does not capture the cached-support forward: replay it with "
+        from .dana import SupportCache, ClassSweep
+        if any(isinstance(t, (SupportCache, ClassSweep)) for t in example_inputs):
+            raise NotImplementedError("GraphedDAnA does not capture the cached-support forward (nor a class sweep): replay it with "
                                       "program.ProgramDAnA(model, ..., cache), or run it eagerly")
         self.model = model
         self.inputs = [_static_like(t) for t in example_inputs]
@@ -97,8 +97,8 @@ class GraphedDAnA:
         cur.wait_stream(self.stream)
 
     def __call__(self, *inputs):
-        from .dana import SupportCache
-        if any(isinstance(t, SupportCache) for t in inputs):
+        from .dana import SupportCache, ClassSweep
+        if any(isinstance(t, (SupportCache, ClassSweep)) for t in inputs):
             raise NotImplementedError("GraphedDAnA replays the forward it captured (support images): a SupportCache "
                                       "forward replays through program.ProgramDAnA")
         for s, t in zip(self.inputs, inputs):

@@ -187,9 +187,10 @@ def roi_align_forward(input, rois, spatial_scale, pooled_h, pooled_w, sampling_r
 
 
 def roi_align_forward_nhwc(feat, B, H, W, C, pix_stride, rois, spatial_scale, pooled, sampling_ratio, pe=None,
-                           out=None, out_pe=None, out_stride=0, out_pe_stride=0):
+                           out=None, out_pe=None, out_stride=0, out_pe_stride=0, group=1):
     """NHWC fast path: feat is a flat buffer whose pixel (b,y,x) starts at ((b*H+y)*W+x)*pix_stride.
-    Returns pooled [R, P*P, C] (and pooled+pe written with row stride out_pe_stride when pe given)."""
+    Returns pooled [R, P*P, C] (and pooled+pe written with row stride out_pe_stride when pe given).
+    group > 1 (class sweep): rois' column 0 is a problem index p, the roi reads image p // group."""
     _chk(feat, "feat")
     rois = _chk(rois.contiguous(), "rois")
     R = rois.shape[0]
@@ -200,6 +201,11 @@ def roi_align_forward_nhwc(feat, B, H, W, C, pix_stride, rois, spatial_scale, po
     if pe is not None and out_pe is None:
         out_pe = torch.empty((R, P2, C), dtype=torch.float32, device=feat.device)
         out_pe_stride = C
+    if group != 1:
+        lib().call("dana_roi_align_forward_nhwc_grouped", _p(feat), _p(rois), _p(out), B, C, H, W, R, float(spatial_scale),
+                   pooled, sampling_ratio, pix_stride, out_stride, _p(out_pe) if pe is not None else None, _p(pe),
+                   out_pe_stride, int(group), _stream())
+        return out, out_pe
     lib().call("dana_roi_align_forward", _p(feat), _p(rois), _p(out), B, C, H, W, R, float(spatial_scale), pooled,
                pooled, sampling_ratio, NHWC, pix_stride, out_stride, _p(out_pe) if pe is not None else None,
                _p(pe), out_pe_stride, _stream())
@@ -864,10 +870,11 @@ def winograd_filter_transform(w_packed, cout, cin, tile=2):
 
 
 def conv3x3_winograd(x, batch, h, w, cin, u, cout, scale=None, shift=None, relu=False, in_stride=0, out=None,
-                     out_stride=0, mask=None, mask_stride=0, keep_v=None):
+                     out_stride=0, mask=None, mask_stride=0, keep_v=None, residual=None, res_stride=0, res_group=1):
     """stride-1 pad-1 3x3 conv through Winograd F(2x2,3x3) or F(4x4,3x3), chosen by u (winograd_filter_transform).
     keep_v: a list that receives the launch's workspace (F(4x4) only): its first 36*tiles*cin floats are the input's
-    transform V, which conv3x3_wgrad_winograd(v=...) takes instead of transforming the input again."""
+    transform V, which conv3x3_wgrad_winograd(v=...) takes instead of transforming the input again.
+    residual (class sweep): out = relu?(conv * scale + shift + residual[image // res_group]), row stride res_stride."""
     _chk(x, "x")
     up, wfl = _wf(u)
     m = 2 if (u.batch if isinstance(u, W3) else u.size(0)) == 16 else 4
@@ -879,9 +886,16 @@ def conv3x3_winograd(x, batch, h, w, cin, u, cout, scale=None, shift=None, relu=
     sfx = "" if m == 2 else "4"
     ws = _ws(lib().query("dana_conv3x3_winograd%s_workspace_bytes" % sfx, batch, h, w, cin, cout), x.device)
     e0 = _prof_begin()
-    lib().call("dana_conv3x3_winograd%s_nhwc_masked" % sfx, _p(x), up, _p(out), _p(scale), _p(shift), _p(mask), batch,
-               h, w, cin, cout, in_stride, out_stride, mask_stride, (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(),
-               _stream())
+    if residual is not None:
+        if mask is not None:
+            raise ValueError("conv3x3_winograd: a residual and a mask do not combine")
+        lib().call("dana_conv3x3_winograd_nhwc_grouped_res", _p(x), up, _p(out), _p(scale), _p(shift),
+                   _p(_chk(residual, "residual")), batch, h, w, cin, cout, in_stride, out_stride, res_stride,
+                   int(res_group), m, (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(), _stream())
+    else:
+        lib().call("dana_conv3x3_winograd%s_nhwc_masked" % sfx, _p(x), up, _p(out), _p(scale), _p(shift), _p(mask), batch,
+                   h, w, cin, cout, in_stride, out_stride, mask_stride, (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(),
+                   _stream())
     if keep_v is not None and m == 4:
         keep_v.append(ws)
     _prof_end(e0, ("wino3x3 M=%d N=%d K=%d s1", (batch * h * w, cout, 9 * cin)), 2.0 * batch * h * w * cout * 9 * cin,
@@ -1251,6 +1265,18 @@ def attn_softmax_unary_(scores, unary, rows, rows_per_batch, nseg, length, ld, k
     return scores
 
 
+def attn_softmax_unary_sweep(scores, out, unary, B, C, hw, nseg, length, ld_in, ld_out, kpad, unary_gamma, out_scale,
+                             unary_stride=0):
+    """class sweep: attn_softmax_unary_ over rows (b, i, c) of scores [B][hw][C][ld_in], written out of place to row
+    (b*C + c)*hw + i of out [B*C][hw][ld_out] with problem b*C + c's unary term"""
+    _chk(scores, "scores")
+    _chk(out, "out")
+    _chk(unary, "unary")
+    lib().call("dana_attn_softmax_unary_sweep", _p(scores), _p(out), _p(unary), B, C, hw, unary_stride, nseg, length,
+               ld_in, ld_out, kpad, float(unary_gamma), float(out_scale), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # backward building blocks (groundwork for the training step)
 # ------------------------------------------------------------------------------------------------
@@ -1384,6 +1410,23 @@ def mul_rows_(y, x, rows, channels, ld_y=0, ld_x=0):
     """y *= x over strided rows (attention_type 'product')"""
     lib().call("dana_mul_rows", _p(_chk(y, "y")), _p(_chk(x, "x")), rows, channels, ld_y, ld_x, _stream())
     return y
+
+
+def mul_rows_grouped_(y, x, rows, channels, group, n_blocks, ld_y=0, ld_x=0):
+    """y rows p*rows + i *= x rows (p // group)*rows + i for p < n_blocks (class sweep, attention_type 'product')"""
+    lib().call("dana_mul_rows_grouped", _p(_chk(y, "y")), _p(_chk(x, "x")), rows, channels, ld_y, ld_x, int(group),
+               n_blocks, _stream())
+    return y
+
+
+def repeat_rows_grouped(src, rows, cols, group, n_blocks, ld_src=0, out=None, ld_out=0):
+    """-> out [n_blocks*rows][cols]: row p*rows + i is src row (p // group)*rows + i (one launch)"""
+    if out is None:
+        out = torch.empty((n_blocks * rows, cols), dtype=torch.float32, device=src.device)
+        ld_out = cols
+    lib().call("dana_repeat_rows_grouped", _p(_chk(src, "src")), _p(_chk(out, "out")), rows, cols, ld_src, ld_out,
+               int(group), n_blocks, _stream())
+    return out
 
 
 def rowscale_(dw, scale, rows, cols):

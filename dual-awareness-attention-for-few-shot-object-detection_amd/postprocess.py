@@ -67,3 +67,20 @@ def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_incl
     counts, offsets = host[:B], host[B:]
     out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(B)]
     return (out, counts, offsets) if with_layout else out
+
+
+def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=0.05, nms_inclusive=False):
+    """A class sweep's outputs (model(..., cache.sweep(classes)): rois [B*C,R,5], cls_prob [B*C*R,2], bbox_pred [B*C*R,4])
+    with im_info [B,3] per IMAGE -> dets[b][c], a [K,5] tensor equal to `detections()` on problem b*C + c with image b's
+    im_info: the all_boxes[j][i] layout of inference.py:70-140 (j the class, i the image). One batched post-processing
+    call over the B*C problems, one D2H read; the im_info row of problem p (image p // C) is repeated on the device."""
+    if rois.dim() != 3 or rois.size(2) != 5:
+        raise ValueError("detections_by_class: rois must be [B*C, R, 5], got %s" % (tuple(rois.shape),))
+    C = int(num_classes)
+    im_info = ops._chk(im_info.reshape(-1, im_info.size(-1)).float().contiguous(), "im_info")
+    B = im_info.size(0)
+    if C < 1 or rois.size(0) != B * C:
+        raise ValueError("detections_by_class: %d problems for %d images x %d classes" % (rois.size(0), B, C))
+    info_p = ops.repeat_rows_grouped(im_info, 1, 3, C, B * C, ld_src=im_info.size(1))
+    flat = detections_batched(rois, cls_prob, bbox_pred, info_p, thresh=thresh, nms_inclusive=nms_inclusive)
+    return [flat[b * C:(b + 1) * C] for b in range(B)]

@@ -358,6 +358,11 @@ def _support_cache(inputs):
     return next((t for t in inputs if isinstance(t, SupportCache)), None)
 
 
+def _class_sweep(inputs):
+    from .dana import ClassSweep
+    return next((t for t in inputs if isinstance(t, ClassSweep)), None)
+
+
 class ProgramDAnA:
     """model(*inputs) as launch-program replays (train or eval mode, host or device RNG): the eager forward's launches on
     the eager forward's streams, minus its Python. Inputs are copied into static buffers (skipped when the caller passes
@@ -375,11 +380,22 @@ class ProgramDAnA:
         # a SupportCache in place of support_ims (dana.encode_supports): the program keeps it (its tensors and the gathered
         # buffers are what the recording points at) and refuses another cache or a stale one
         self.cache = _support_cache(example_inputs)
+        # ... or a ClassSweep of one (cache.sweep(classes)): a later sweep of the same cache with the same number of sets
+        # replays through the recorded gather, whose index is read on the device
+        sw = _class_sweep(example_inputs)
+        self.sweep_n = None
+        if sw is not None:
+            self.cache, self.sweep_n = sw.cache, len(sw)
         with torch.no_grad():
             for _ in range(warmup):  # eager: fills the plan / constant caches, creates the role streams
                 model(*self.inputs)
         if self.cache is not None:
-            self.cache._prepare(self.inputs[0].size(0))  # selection written, gathered buffers allocated: outside the recording
+            B = self.inputs[0].size(0)
+            # selection written, gathered buffers allocated: outside the recording
+            if sw is not None:
+                self.cache._prepare(B * len(sw), sw._index(B))
+            else:
+                self.cache._prepare(B)
             self._cache_index = self.cache._index
         torch.cuda.synchronize(dev)
         self._device_rng = bool(getattr(model, "device_rng", False)) and model.training
@@ -423,12 +439,24 @@ class ProgramDAnA:
         torch.cuda.synchronize(dev)
 
     def __call__(self, *inputs):
+        sw = _class_sweep(inputs)
+        if (sw is None) != (self.sweep_n is None) or (sw is not None and (sw.cache is not self.cache or len(sw) != self.sweep_n)):
+            raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: re-record a runner for it" % (
+                "a sweep of %s sets" % self.sweep_n if self.sweep_n is not None else "no class sweep",
+                "a sweep of %d sets%s" % (len(sw), "" if sw.cache is self.cache else " of another SupportCache")
+                if sw is not None else "no class sweep"))
+        if sw is not None:
+            B = self.inputs[0].size(0)
+            sw.cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
+            sw.cache._prepare(B * self.sweep_n, sw._index(B))  # the sweep's classes into the index the replay reads
+            if sw.cache._index is not self._cache_index:
+                raise RuntimeError("the SupportCache's index buffer was reallocated after the recording: record a new runner")
         cache = _support_cache(inputs)
-        if cache is not self.cache:
+        if sw is None and cache is not self.cache:
             raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: record a new runner for it" % (
                 "support images" if self.cache is None else "another SupportCache",
                 "support images" if cache is None else "a different SupportCache"))
-        if cache is not None:
+        if sw is None and cache is not None:
             cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
             cache._prepare(self.inputs[0].size(0))  # (the selection's length must still be the recorded batch)
             if cache._index is not self._cache_index:

@@ -168,6 +168,31 @@ int dana_detect_postprocess_batched(const float* rois, const float* cls_prob, co
 int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* block_bytes, int n_tensors,
                        const int* index, int n_sets, int B, dana_stream_t stream);
 
+/* ---- class sweep (dana.SupportCache.sweep): B query images x C cached support sets as B*C problems p = b*C + c, the
+ * per-class forward of dana.py:87-220 for every class of an image (inference.py:70-140 fills all_boxes[j][i] with it).
+ * A problem reads its image's query-side tensors through p / C ("group" = C below). */
+/* dana.py:143-146 over the class-interleaved scores of one GEMM per image (N = C*K1: the C classes' keys side by side):
+ * input row (b*hw + i)*C + c of scores [B][hw][C][ld_in] -> output row (b*C + c)*hw + i of out [B*C][hw][ld_out], per
+ * `length`-wide segment (one per shot) (softmax + unary_gamma * unary[p]) * out_scale, unary + p*unary_stride ->
+ * [nseg][length]; cols nseg*length..kpad-1 zeroed. The per-row arithmetic of dana_attn_softmax_unary (C = 1: same bits). */
+int dana_attn_softmax_unary_sweep(const float* scores, float* out, const float* unary, int B, int C, long hw,
+                                  long unary_stride, int nseg, int length, long ld_in, long ld_out, int kpad,
+                                  float unary_gamma, float out_scale, dana_stream_t stream);
+/* dst row p*rows + i <- src row (p / group)*rows + i (`cols` floats), p < n_blocks: a problem's copy of its image's rows
+ * (im_info of proposal_layer.py:49-190 / inference.py:106-140 per problem) */
+int dana_repeat_rows_grouped(const float* src, float* dst, long rows, int cols, long ld_src, long ld_dst, int group,
+                             long n_blocks, dana_stream_t stream);
+/* y row p*rows + i *= x row (p / group)*rows + i, p < n_blocks (dana.py:155-156 product attention: base_feat of image
+ * p / group times problem p's attended rows); channels % 4 == 0, 16-byte aligned rows */
+int dana_mul_rows_grouped(float* y, const float* x, long rows, int channels, long ld_y, long ld_x, int group,
+                          long n_blocks, dana_stream_t stream);
+/* RoIAlign (dana.py:181-186, ROIAlign_cuda.cu) in NHWC with rois' column 0 a problem index: roi n reads image
+ * (int)rois[n][0] / group. Arguments and outputs as dana_roi_align_forward(layout NHWC); group 1: the same bits. */
+int dana_roi_align_forward_nhwc_grouped(const float* input, const float* rois, float* output, int batch, int channels,
+                                        int height, int width, int num_rois, float spatial_scale, int pooled,
+                                        int sampling_ratio, long in_pix_stride, long out_pix_stride, float* output2,
+                                        const float* add2, long out2_pix_stride, int group, dana_stream_t stream);
+
 /* ---- dense contractions on the fp32 matrix cores (v_mfma_f32_32x32x2_f32) --------------------- */
 
 /* nn.Conv2d + frozen BatchNorm2d/bias + residual + ReLU (resnet.py:66-102 Bottleneck, :109-112 stem;
@@ -232,6 +257,16 @@ int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float
                                        const float* shift, const float* mask_act, int batch, int h, int w, int cin,
                                        int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
                                        int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream);
+/* The RPN 3x3 conv of a class sweep (rpn.py:63 RPN_Conv on cat([base_feat, attended]) of dana.py:157), split by input
+ * channels: W[:, :1024] * base_feat once per image (no shift, no ReLU) gives `residual`, then this launch runs
+ * W[:, 1024:] * attended per problem with out = relu?(conv*scale + shift + residual[image / res_group]): output image n
+ * reads residual image n / res_group (row stride res_pix_stride). tile 2: F(2x2,3x3) filters (dana_winograd_filter_transform),
+ * 4: F(4x4,3x3) (dana_winograd4_filter_transform, DANA_W_SPLIT3 split planes allowed); workspace as for that tile. */
+int dana_conv3x3_winograd_nhwc_grouped_res(const float* input, const float* u, float* output, const float* scale,
+                                           const float* shift, const float* residual, int batch, int h, int w, int cin,
+                                           int cout, long in_pix_stride, long out_pix_stride, long res_pix_stride,
+                                           int res_group, int tile, int flags, void* workspace, size_t workspace_bytes,
+                                           dana_stream_t stream);
 /* F(4x4,3x3) over TWO image groups (input: group 0's [n0][h0][w0] pixels, then group 1's [n1][h1][w1]): two input
  * transforms, ONE batched plane GEMM over all tiles, two output transforms (resnet.py:92-94 on the query and the support
  * batch of dana.py:98,100 with the same filters) */

@@ -11,6 +11,11 @@ uncached one), timed as bench.py's trial(): 3 warm steps, then the median GPU-si
   *_pp_loop / *_pp_batched   the last two plus post-processing: the per-image postprocess.detections() loop (one C call +
                          one D2H read per image) vs postprocess.detections_batched() (one call, one read)
 plus contraction launches per step (ops.PROFILE, single stream), the gather launch alone, and encode_supports per set.
+Class sweep (cache.sweep: every image against C sets, the query trunk once per image), C = 5 sets, each against the
+replicated B*C cached forward (cache.select(classes * B), every image repeated C times) in the same rounds, alternated:
+  sweep_b1_c5 / repl_b1_c5   one image x 5 sets       sweep_b4_c5 / repl_b4_c5   four images x 5 sets
+reported as ms per (image, class), with their contraction launches and the RPN conv's launches (the split conv's two
+against the single cin-2048 conv). --only-sweep skips the other cases.
 The last line is the JSON record."""
 import argparse
 import json
@@ -54,11 +59,61 @@ def best_of(cands, k):
     return {n: round(v, 4) for n, v in ms.items()}, min(ms, key=ms.get)
 
 
+def sweep_cases(m, in1, in4, sets5, k):
+    from dana_amd import ops
+    from dana_amd.program import ProgramDAnA
+    C = sets5.size(0)
+    cache = m.encode_supports(sets5)
+    classes = list(range(C))
+    out = {}
+    for B, inp in ((1, in1), (4, in4)):
+        q = inp[:4]
+        rq = [t.repeat_interleave(C, 0) for t in q]
+        sw = cache.sweep(classes)
+        cache.select(classes * B)
+
+        def repl(rq=rq):
+            return m(*rq, cache)
+
+        def swp(q=q, sw=sw):
+            return m(*q, sw)
+
+        # contraction launches and the RPN conv's launches (single stream, ops.PROFILE)
+        m._single_stream = True
+        prof = {}
+        for name, call in (("sweep", swp), ("repl", repl)):
+            call()
+            ops.PROFILE = []
+            call()
+            torch.cuda.synchronize()
+            rpn = [(e[0], round(e[2].elapsed_time(e[3]) * 1e3, 1)) for e in ops.PROFILE
+                   if e[0].startswith(("wino3x3", "conv3x3")) and " N=512 " in e[0]
+                   and (" K=%d " % (9 * 1024) in e[0] or " K=%d " % (9 * 2048) in e[0])]
+            prof[name] = dict(contraction_launches=len(ops.PROFILE), rpn_conv_launches_us=rpn)
+            ops.PROFILE = None
+        m._single_stream = False
+        p_sw = ProgramDAnA(m, *q, sw)
+        p_re = ProgramDAnA(m, *rq, cache)
+        ms, _ = best_of({"sweep_eager": swp, "sweep_program": lambda: p_sw(*p_sw.inputs),
+                         "repl_eager": repl, "repl_program": lambda: p_re(*p_re.inputs)}, k)
+        for name in ("sweep", "repl"):
+            best = min(("eager", "program"), key=lambda mode: ms["%s_%s" % (name, mode)])
+            tag = "%s_b%d_c%d" % (name, B, C)
+            out[tag] = dict(ms_per_image_class=round(ms["%s_%s" % (name, best)] / (B * C), 4), mode=best,
+                            ms_per_step={mode: ms["%s_%s" % (name, mode)] for mode in ("eager", "program")}, **prof[name])
+            print("%-14s %8.3f ms per (image, class)  (best: %s; ms/step %s; %d contraction launches)"
+                  % (tag, out[tag]["ms_per_image_class"], best, out[tag]["ms_per_step"], prof[name]["contraction_launches"]),
+                  flush=True)
+        del p_sw, p_re
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=1000)
+    ap.add_argument("--only-sweep", action="store_true")
     args = ap.parse_args()
     import dana_amd
     from dana_amd import ops, postprocess as PP, synthetic as S
@@ -75,6 +130,11 @@ def main():
     sets4 = in4[4].reshape(4, shot, 3, 320, 320)
     rec = {"shape": "query %dx%d, shot %d, supports 320x320, BA on" % (H, W, shot), "steps": k}
     torch.backends.cudnn.benchmark = False
+    with torch.no_grad():
+        rec["sweep"] = sweep_cases(m, in1, in4, torch.cat([sets4, sets1], 0), k)
+    if args.only_sweep:
+        print(json.dumps(rec))
+        return
     with torch.no_grad():
         cache1 = m.encode_supports(sets1)
         cache4 = m.encode_supports(sets4)
