@@ -16,7 +16,9 @@ Data layout in HBM (all fp32):
   frozen BN     folded to per-channel scale/shift applied in the conv epilogue (dana.py:362-385).
 """
 import math
+import time
 import weakref
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -790,7 +792,7 @@ class DAnARCNN(nn.Module):
             with ops.on_stream(br):
                 unary, s_t = unary_and_transpose()
                 branch_done = ops.record_event()
-        wk, bk = self._w(self.rpn_adapt_k_layer)
+        _, bk = self._w(self.rpn_adapt_k_layer)
         kb3, kld = self._lin_b(self.rpn_adapt_k_layer)
         kp = ops.gemm_nt(s_pe, kb3, B * shot * L, d, 1024, ldb=kld, shift=bk)
         ops.colmean_sub_(kp, B * shot, L, d)
@@ -814,7 +816,7 @@ class DAnARCNN(nn.Module):
             pool = (sh_ // 7, sh_ // 7)
         sp = ops.avgpool(sup, Ns, sh_, sw_, 1024, pool[0], pool[1])  # [Ns][49][1024]
         sp_pe = ops.add_pe(sp, plan["pe49"], Ns * P2, P2, 1024)
-        wk2, bk2 = self._w(self.rcnn_adapt_k_layer)
+        _, bk2 = self._w(self.rcnn_adapt_k_layer)
         k2b3, k2ld = self._lin_b(self.rcnn_adapt_k_layer)
         k2 = ops.gemm_nt(sp_pe, k2b3, Ns * P2, dq, 1024, ldb=k2ld, shift=bk2)
         ops.colmean_sub_(k2, Ns, P2, dq)
@@ -861,13 +863,7 @@ class DAnARCNN(nn.Module):
         rpn = self.RCNN_rpn
         NP, hw = B * Cs, fh * fw
         if product:
-            if plan["rpn_conv_u"] is not None:
-                x, _, _ = ops.conv3x3_winograd(att, NP, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512,
-                                               shift=plan["rpn_conv_b"], relu=True, in_stride=1024)
-            else:
-                x, _, _ = ops.conv2d_nhwc(att, NP, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1,
-                                          1, shift=plan["rpn_conv_b"], relu=True, in_stride=1024)
-            return x
+            return self._rpn_conv(plan, att, NP, fh, fw, in_stride=1024)
         if rpn.din != 2048:
             raise RuntimeError("class sweep: the RPN conv expects [base_feat | attended] = 2048 input channels, got %d" % rpn.din)
         half = self._rpn_split_plan(plan)
@@ -924,6 +920,85 @@ class DAnARCNN(nn.Module):
                        for k in SupportCache.FIELDS}
         return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev)
 
+    # ---- stages shared with the sibling detectors (frcnn.py, fgn.py, fsod.py) ------------------------------------
+    def _saving_ctx(self, lists, align_only_for=None):
+        """-> (bridge: loss.backward() will follow, ctx: a list per name in `lists` when the forward saves, else None)"""
+        # bridge: a training forward whose losses loss.backward() (train.py:141-143) differentiates; a forward saves for
+        # the HIP backward then, or when model.save_for_backward asks for it. align_only_for: the model's name when its
+        # backward covers POOLING_MODE 'align' only
+        bridge = self.training and torch.is_grad_enabled()
+        if not (self.training and (bridge or getattr(self, "save_for_backward", False))):
+            return bridge, None
+        if align_only_for is not None and cfg.POOLING_MODE != "align":
+            raise NotImplementedError("the HIP backward of %s covers POOLING_MODE 'align'" % align_only_for)
+        return bridge, {k: [] for k in lists}
+
+    def _loss_bridge(self, dev, losses):
+        """hand the four losses to autograd: loss.backward() runs the model's HIP backward (backward.model_backward)"""
+        if self._grad_anchor is None or self._grad_anchor.device != dev:
+            self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
+        return _LossBridge.apply(self._grad_anchor, self, *losses)
+
+    @staticmethod
+    def _support_batch(support_ims, B, way, shot):
+        """support_ims [B, way*shot, 3, S, S] (or any shape with those images) -> [B*way*shot, 3, S, S]"""
+        sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
+        if sup_ims.size(0) != B * way * shot:
+            raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, sup_ims.size(0)))
+        return sup_ims
+
+    def _rpn_conv(self, plan, x, n, fh, fw, in_stride=0, keep_v=None):
+        """RPN_Conv + ReLU (rpn.py:63) on n maps of NHWC rows in_stride apart -> [n*fh*fw][512]. keep_v: Winograd only"""
+        rpn = self.RCNN_rpn
+        if plan["rpn_conv_u"] is not None:
+            return ops.conv3x3_winograd(x, n, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512,
+                                        shift=plan["rpn_conv_b"], relu=True, keep_v=keep_v, in_stride=in_stride)[0]
+        return ops.conv2d_nhwc(x, n, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1, 1,
+                               shift=plan["rpn_conv_b"], relu=True, in_stride=in_stride)[0]
+
+    def _rpn_head(self, plan, x, rows):
+        """RPN_cls_score | RPN_bbox_pred (rpn.py:66-78) as one GEMM -> (heads [rows][2A | 4A], 6A)"""
+        rpn = self.RCNN_rpn
+        nh = rpn.nc_score_out + rpn.nc_bbox_out
+        return ops.gemm_nt(x, plan["rpn_head_w3"] or plan["rpn_head_w"], rows, nh, 512, shift=plan["rpn_head_b"]), nh
+
+    def _proposals(self, plan, heads, nh, im_info, n, fh, fw):
+        """the proposal layer (proposal_layer.py:49-190) on the head buffer of n maps -> rois [n, post_nms_topn, 5]"""
+        rpn = self.RCNN_rpn
+        hw = fh * fw
+        c = cfg.TRAIN if self.training else cfg.TEST
+        return ops.proposal_layer(heads, (hw * nh, 1, nh), False, heads.view(-1)[rpn.nc_score_out:], (hw * nh, 1, nh),
+                                  im_info, plan["anchors"], n, plan["anchors"].size(0), fh, fw, rpn.feat_stride,
+                                  c.RPN_PRE_NMS_TOP_N, c.RPN_POST_NMS_TOP_N, c.RPN_NMS_THRESH, self.nms_inclusive)
+
+    def _roi_pool(self, plan, feat, B, fh, fw, ld, rois, pe=False, group=1, ctx=None):
+        """RoI pooling (faster_rcnn.py:70-73, dana.py:181-186) -> (pooled [n_roi][49][1024], pooled + PE or None)"""
+        # base_feat: the first 1024 channels of NHWC rows `ld` apart. pe: also pooled + PE (dana.py:259). group: a class
+        # sweep's problems per image (RoIAlign: rois' column 0 is the problem). POOLING_MODE 'pool' (a resumed checkpoint's
+        # cfg may ask for it, train.py:100-101): the RoIPool operator of the `_C` boundary; a saving forward keeps its
+        # argmax indices in ctx for the backward's scatter (ROIPool_cuda.cu:79-108, dana_roi_pool_backward)
+        P = cfg.POOLING_SIZE
+        if cfg.POOLING_MODE == "align":
+            return ops.roi_align_forward_nhwc(feat, B, fh, fw, 1024, ld, rois.view(-1, 5), 1.0 / 16.0, P, 0,
+                                              pe=plan["pe49"] if pe else None, group=group)
+        if cfg.POOLING_MODE != "pool":
+            raise NotImplementedError("POOLING_MODE '%s'" % cfg.POOLING_MODE)
+        pooled_nchw, roi_argmax = ops.roi_pool_forward(ops.nhwc_to_nchw(feat, B, 1024, fh, fw, in_stride=ld),
+                                                       rois.view(-1, 5).contiguous(), 1.0 / 16.0, P, P)
+        if ctx is not None:
+            ctx["roi_argmax"] = roi_argmax
+        n_roi = pooled_nchw.size(0)
+        pooled = ops.nchw_to_nhwc(pooled_nchw).view(n_roi, P * P, 1024)
+        if not pe:
+            return pooled, None
+        return pooled, ops.add_pe(pooled, plan["pe49"], n_roi * P * P, P * P, 1024).view(n_roi, P * P, 1024)
+
+    def _head_to_tail(self, x, n, h, w, plan, save=None):
+        """layer4 + spatial mean (faster_rcnn.py:183-185, dana.py:387-389) on an NHWC batch of n maps -> [n][2048]"""
+        for bi, bp in enumerate(plan["layer4"]):
+            x, h, w = self._bottleneck(x, n, h, w, bp, save=save, key="RCNN_top.0.%d" % bi)
+        return ops.spatial_mean(x, n, h * w, 2048)
+
     # ---- forward -----------------------------------------------------------------------------------
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         """dana.py:87-220. The body is `_forward_gen`, a generator that pauses at the ONE host round trip of the
@@ -944,6 +1019,58 @@ class DAnARCNN(nn.Module):
         raise RuntimeError("DAnARCNN._forward_gen paused twice")
 
     def _forward_gen(self, im_data, im_info, gt_boxes, num_boxes, support_ims):
+        # f: the forward's constants (_forward_setup); sup: the support tensors the query side reads, from this forward's
+        # support trunk or gathered from a SupportCache
+        f = self._forward_setup(im_data, im_info, gt_boxes, support_ims)
+        tg = (yield from self._anchor_targets(f, im_data)) if f.training else None
+        corr, (fh, fw), sup = self._trunks(f, im_data, support_ims)
+        att = self._rpn_attention(f, corr, fh, fw, sup)
+        x = self._rpn_conv_stage(f, corr, att, fh, fw)
+        heads, nh = self._rpn_head(f.plan, x, f.NP * fh * fw)  # [NP*hw][2A | 4A]
+        f.mark("rpn conv + heads")
+        self._roi_support(f, sup)
+        rois = self._proposal_stage(f, heads, nh, fh, fw)
+        targets = rpn_draws = None
+        if f.training:
+            rois, targets, rpn_draws = yield from self._proposal_targets(f, tg, rois, sup)
+        f.mark("rpn losses + proposal targets")
+        R = rois.size(1)
+        n_roi = f.NP * R
+        # Forward-only runs (nothing saved for a backward) fold the positional encoding of dana.py:259 into the two
+        # projections that consume it: (pooled + PE) W^T = pooled W^T + (PE W^T), a [49][N] table per weight version --
+        # RoIAlign then writes ONE [n,49,1024] output instead of two (it is bound by its own writes, DESIGN 3), and the
+        # Q projection and the query half of rcnn_transform_layer are ONE N = 128 GEMM over pooled (one read of it).
+        fold_pe = (f.ctx is None and cfg.POOLING_MODE == "align" and getattr(self, "fold_roi_pe", True)
+                   and not f.product)  # (product multiplies by pooled + PE itself: dana.py:286)
+        pooled, q_pe = self._roi_pool(f.plan, corr, f.B, fh, fw, 2048, rois, pe=not fold_pe, group=f.Cs, ctx=f.ctx)
+        if f.inter is not None:
+            f.inter["pooled"] = pooled
+        pooled_ready = ops.record_event()
+        f.mark("roi align")
+        rpn_losses = self._rpn_loss_stage(f, tg, rpn_draws, x, heads, nh) if f.training else (0, 0)
+        bbox_pred, l4_done = self._box_branch(f, pooled, pooled_ready, n_roi)
+        prob_all, cls_prob, cls_score, neg_score = self._roi_heads(f, pooled, q_pe, fold_pe, sup, rois, R, l4_done)
+        rcnn_losses, rois_label = (0, 0), None
+        if f.training:
+            cls_prob = prob_all  # (both heads wrote their halves)
+            labels_f, rois_target, rois_inside_ws, rois_outside_ws = targets
+            rois_label = ops.labels_posneg(labels_f)
+            # box smooth-L1 + 2-way cross-entropy with the 1:2:1 hard-negative mining (dana.py:203-217): one fused
+            # pass on the device, no host sync (the nonzero / sort / index chain of the reference has three)
+            rl, seeds = ops.rcnn_losses(cls_score, neg_score, labels_f, bbox_pred, rois_target.contiguous(),
+                                        rois_inside_ws.contiguous(), rois_outside_ws.contiguous(), with_grad=f.ctx is not None)
+            rcnn_losses = rl[0], rl[1]
+            if f.ctx is not None:
+                f.ctx.update(loss_seeds=seeds)
+        f.mark("rcnn losses")
+        f.tick("rcnn losses")
+        losses = rpn_losses + rcnn_losses
+        if f.ctx is not None and f.bridge:
+            losses = self._loss_bridge(f.dev, losses)
+        return (rois, cls_prob, bbox_pred) + tuple(losses) + (rois_label,)
+
+    def _forward_setup(self, im_data, im_info, gt_boxes, support_ims):
+        """checks the inputs, opens the saving-forward ctx and the support stream -> the forward's constants"""
         plan = self._get_plan()
         dev = im_data.device
         training = self.training
@@ -961,17 +1088,15 @@ class DAnARCNN(nn.Module):
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
         B = im_data.size(0)
         Cs = len(sweep) if sweep is not None else 1
-        NP = B * Cs  # problems: the RPN stage from the attention on and the RoI stage run over them
-        im_info = im_info.data.float().contiguous()
-        gt_boxes = gt_boxes.data
-        shot = self.n_shot
-        way = self.n_way if training else 1  # eval reshapes supports as [*, n_shot] (dana.py:111)
-        inter = getattr(self, "_capture", None)
+        f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, B=B, Cs=Cs,
+                            NP=B * Cs,  # problems: the RPN stage from the attention on and the RoI stage run over them
+                            im_info=im_info.data.float().contiguous(), gt_boxes=gt_boxes.data, shot=self.n_shot,
+                            way=self.n_way if training else 1,  # eval reshapes supports as [*, n_shot] (dana.py:111)
+                            product=self.attention_type == "product", inter=getattr(self, "_capture", None))
         tl = getattr(self, "_timeline", None)  # optional host-side phase clock (debug)
-        if tl is not None:
-            import time as _time
-            tl.append(("begin", _time.perf_counter()))
-        main = ops.cur_stream()
+        f.tick = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None else (lambda label: None)
+        f.tick("begin")
+        f.main = ops.cur_stream()
         gev = getattr(self, "_gpu_events", None)
 
         def mark(name):
@@ -980,118 +1105,110 @@ class DAnARCNN(nn.Module):
                 e.record()
                 gev.append((name, e))
 
-        ctx = None
-        self._bridge = training and torch.is_grad_enabled()  # train.py:141-143 will call loss.backward()
-        merge_trunk, merge_from = bool(self.merge_trunk), int(self.merge_from)
-        if training and (self._bridge or getattr(self, "save_for_backward", False)):
+        f.mark = mark
+        f.bridge, ctx = self._saving_ctx(("q_saved", "s_saved", "m_saved", "l4_saved", "heads"))
+        f.merge = (bool(self.merge_trunk), int(self.merge_from))
+        if ctx is not None:
             if getattr(self, "_train_merge", None) is not None:
                 # a Trainer's preference for forwards that SAVE for its backward only (shared [query | support] buffers,
                 # trainer.py); every other forward of this model keeps the configured path
-                merge_trunk, merge_from = self._train_merge
+                f.merge = self._train_merge
             # everything backward.model_backward needs. The side streams of this forward are all joined into the
             # caller's stream before it returns, and each of them starts by waiting for an event of the NEXT
             # forward's caller stream, so the saved tensors are safe for a backward that runs on that stream.
-            ctx = self._ctx = dict(plan=plan, B=B, shot=shot, way=way, q_saved=[], s_saved=[], m_saved=[], l4_saved=[], heads=[])
-        else:
-            self._ctx = None
+            ctx.update(plan=plan, B=B, shot=f.shot, way=f.way)
+        f.ctx = self._ctx = ctx
+        if f.product and ctx is not None:
+            raise NotImplementedError("attention_type='product' runs the forward (train and eval mode) on the HIP "
+                                      "kernels; its backward is not implemented -- train 'concat', what utils.get_model "
+                                      "builds (utils.py:120-123)")
         mark("begin")
-        inputs_ready = ops.record_event()
-        sup_stream = self._stream("support", dev)
-        at = rng = ctr = side = None
-        if training:
-            # Anchor targets, first half (anchor_target_layer.py:48-136: everything up to the fg / bg counts). They depend
-            # on the inputs only, so they go FIRST, on a side stream: the counts are on the host long before the trunk
-            # is done and the reference's np.random.permutation draws over ~10^5 anchors (about a millisecond of host
-            # time) run while the GPU is busy with the trunk.
-            capturing = torch.cuda.is_current_stream_capturing()
-            if self.device_rng:  # counter-based device RNG (opt-in): (seed, 2 * forward counter [+ 1])
-                rng = (int(self.rng_seed), 2 * self._rng_calls)
-                self._rng_calls += 1
-                if capturing or getattr(self, "_rng_counter_as_data", False):  # (a launch-program recording: program.py)
-                    # inside a hipGraph / a launch program the call counter must be DATA: a uint64 in device memory,
-                    # advanced by the replay itself
-                    ctr = self._consts.get(("rng_counter", str(dev)))
-                    if ctr is None:
-                        raise RuntimeError("capture with device_rng needs model._rng_counter(device) created BEFORE the "
-                                           "capture (inside it the zero fill would be replayed with the graph)")
-                    rng = (int(self.rng_seed), 0)
-            tr_ = cfg.TRAIN
-            num_fg = int(tr_.RPN_FG_FRACTION * tr_.RPN_BATCHSIZE)
-            afh, afw = self._feat_size(im_data.size(2), im_data.size(3))
-            # host-RNG capture: this block is its own little graph, replayed on the side stream (graphs.py)
-            side = main if (capturing and rng is None) else self._stream("targets", dev)
-            gt_f = gt_boxes.float().contiguous()
-            if side is not main:
-                side.wait_event(inputs_ready)
-                if gt_f is not gt_boxes:  # converted on the caller's stream: the side stream must see the result
-                    conv_done = ops.record_event()
-                    side.wait_event(conv_done)
-                gt_f.record_stream(side)
-            with ops.on_stream(side):
-                # allocated in the SIDE stream's pool: a block recycled from the caller's stream could still be
-                # written by kernels queued there after this stream has already filled it
-                at = ops.anchor_target_prepare(gt_f, im_info, plan["anchors"], afh, afw, self.RCNN_rpn.feat_stride,
-                                               tr_.RPN_NEGATIVE_OVERLAP, tr_.RPN_POSITIVE_OVERLAP)
-                if rng is not None:
-                    ops.anchor_target_subsample_device(at, tr_.RPN_BATCHSIZE, num_fg, rng[0], rng[1], counter=ctr)
-            if side is not main:
-                for k_ in ("ibuf", "labels", "max_ov", "counts"):
-                    at[k_].record_stream(main)
-                if rng is not None:
-                    at["inv_ne_dev"].record_stream(main)
-            if rng is None:
-                yield dict(stage="anchor", counts=at["counts"], stream=side)  # (a graph driver ends its first capture here)
-                inputs_ready = torch.cuda.Event()  # an event of a finished capture cannot fork streams into the next one
-                inputs_ready.record()
+        f.inputs_ready = ops.record_event()
+        f.sup_stream = self._stream("support", dev)
+        return f
 
-        # -- feature extraction (dana.py:98-115): query and support batches share every trunk launch
-        #    (twice the tiles -> half the tail on the 256 CUs); everything that depends only on the
-        #    supports then runs on its own stream, concurrently with the query side. --
-        if cache is not None:
+    def _anchor_targets(self, f, im_data):
+        """anchor targets, first half (anchor_target_layer.py:48-136); pauses with stage="anchor" under the host RNG"""
+        # Everything up to the fg / bg counts. They depend on the inputs only, so they go FIRST, on a side stream: the
+        # counts are on the host long before the trunk is done and the reference's np.random.permutation draws over ~10^5
+        # anchors (about a millisecond of host time) run while the GPU is busy with the trunk.
+        dev, main = f.dev, f.main
+        capturing = torch.cuda.is_current_stream_capturing()
+        rng = ctr = None
+        if self.device_rng:  # counter-based device RNG (opt-in): (seed, 2 * forward counter [+ 1])
+            rng = (int(self.rng_seed), 2 * self._rng_calls)
+            self._rng_calls += 1
+            if capturing or getattr(self, "_rng_counter_as_data", False):  # (a launch-program recording: program.py)
+                # inside a hipGraph / a launch program the call counter must be DATA: a uint64 in device memory,
+                # advanced by the replay itself
+                ctr = self._consts.get(("rng_counter", str(dev)))
+                if ctr is None:
+                    raise RuntimeError("capture with device_rng needs model._rng_counter(device) created BEFORE the "
+                                       "capture (inside it the zero fill would be replayed with the graph)")
+                rng = (int(self.rng_seed), 0)
+        tr_ = cfg.TRAIN
+        num_fg = int(tr_.RPN_FG_FRACTION * tr_.RPN_BATCHSIZE)
+        afh, afw = self._feat_size(im_data.size(2), im_data.size(3))
+        # host-RNG capture: this block is its own little graph, replayed on the side stream (graphs.py)
+        side = main if (capturing and rng is None) else self._stream("targets", dev)
+        gt_f = f.gt_boxes.float().contiguous()
+        if side is not main:
+            side.wait_event(f.inputs_ready)
+            if gt_f is not f.gt_boxes:  # converted on the caller's stream: the side stream must see the result
+                conv_done = ops.record_event()
+                side.wait_event(conv_done)
+            gt_f.record_stream(side)
+        with ops.on_stream(side):
+            # allocated in the SIDE stream's pool: a block recycled from the caller's stream could still be
+            # written by kernels queued there after this stream has already filled it
+            at = ops.anchor_target_prepare(gt_f, f.im_info, f.plan["anchors"], afh, afw, self.RCNN_rpn.feat_stride,
+                                           tr_.RPN_NEGATIVE_OVERLAP, tr_.RPN_POSITIVE_OVERLAP)
+            if rng is not None:
+                ops.anchor_target_subsample_device(at, tr_.RPN_BATCHSIZE, num_fg, rng[0], rng[1], counter=ctr)
+        if side is not main:
+            for k_ in ("ibuf", "labels", "max_ov", "counts"):
+                at[k_].record_stream(main)
+            if rng is not None:
+                at["inv_ne_dev"].record_stream(main)
+        if rng is None:
+            yield dict(stage="anchor", counts=at["counts"], stream=side)  # (a graph driver ends its first capture here)
+            f.inputs_ready = torch.cuda.Event()  # an event of a finished capture cannot fork streams into the next one
+            f.inputs_ready.record()
+        return SimpleNamespace(at=at, rng=rng, ctr=ctr, side=side, gt_f=gt_f, capturing=capturing, num_fg=num_fg)
+
+    def _trunks(self, f, im_data, support_ims):
+        """feature extraction (dana.py:98-115) + RPN-level support side -> (corr [B*h*w][base_feat | attended], (h, w), sup)"""
+        # The query trunk runs on the caller's stream; the support trunk (cached / merged into the query's launches /
+        # alternating block by block on its own stream / single-stream) and everything that depends only on the supports
+        # run on the support stream, concurrently with the query side.
+        plan, dev, B, shot, ctx, main, sup_stream = f.plan, f.dev, f.B, f.shot, f.ctx, f.main, f.sup_stream
+        fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
+        if f.cache is not None:
             # cached supports (encode_supports): the query-independent support side was computed once per support set;
-            # one launch gathers image b's set into this forward's B-batched buffers, the query side runs unchanged
-            Ns = B * shot
-            sh0, sw0 = cache.sup_map
-        else:
-            sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
-            Ns = sup_ims.size(0)
-            if Ns != B * way * shot:
-                raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, Ns))
-            # positions of a support map: 20 x 20 = 400 for the reference's 320 x 320 supports (dana.py:105 hard-codes it)
-            sh0, sw0 = self._feat_size(sup_ims.size(2), sup_ims.size(3))
-        L = sh0 * sw0
-        d = self.rpn_reduce_dim
-        P = cfg.POOLING_SIZE
-        P2 = P * P
-        dq = self.rcnn_reduce_dim
-        K1 = shot * L
-        if cache is not None:
-            # (a sweep gathers B*C sets, the selection repeated for every image: image b's C blocks are contiguous)
-            gathered = cache._gather(NP, sweep._index(B) if sweep is not None else None)
-            kp, unary, s_t = gathered["kp"], gathered["unary"], gathered["s_t"]
-            fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
-            sh_, sw_ = sh0, sw0
+            # one launch gathers image b's set into this forward's B-batched buffers (a sweep gathers B*C sets, the
+            # selection repeated for every image: image b's C blocks are contiguous), the query side runs unchanged
+            sup = dict(f.cache._gather(f.NP, f.sweep._index(B) if f.sweep is not None else None), map=f.cache.sup_map,
+                       rpn_done=None, roi_done=None)
             corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
             self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
-        elif merge_trunk:
-            sup_stream.wait_event(inputs_ready)
-            corr, (fh, fw), sup, (sh_, sw_) = self._rcnn_base_dual(im_data, sup_ims, plan, dev,
-                                                                   save_q=ctx["q_saved"] if ctx is not None else None,
-                                                                   save_s=ctx["s_saved"] if ctx is not None else None,
-                                                                   sup_stream=sup_stream, merge_from=merge_from,
-                                                                   save_m=ctx["m_saved"] if ctx is not None else None)
+            f.mark("trunk (query + support)")
+            return corr, (fh, fw), sup
+        sup_ims = self._support_batch(support_ims, B, f.way, shot)
+        save_q, save_s = (ctx["q_saved"], ctx["s_saved"]) if ctx is not None else (None, None)
+        sup_stream.wait_event(f.inputs_ready)
+        if f.merge[0]:
+            corr, (fh, fw), sfeat, (sh_, sw_) = self._rcnn_base_dual(
+                im_data, sup_ims, plan, dev, save_q=save_q, save_s=save_s, sup_stream=sup_stream, merge_from=f.merge[1],
+                save_m=ctx["m_saved"] if ctx is not None else None)
             trunk_done = ops.record_event()
             sup_stream.wait_event(trunk_done)
         else:
-            sup_stream.wait_event(inputs_ready)
-            fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
             corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
             if sup_stream != main:
                 # alternate issue, block by block: support trunk on its stream, query trunk on the caller's -- both streams
                 # have work from the step's first launch on, however slow the host is (8 ranks share one)
-                g_s = self._rcnn_base_gen(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)
-                g_q = self._rcnn_base_gen(im_data, plan, out_stride=2048, out_buf=corr,
-                                          save=ctx["q_saved"] if ctx is not None else None)
+                g_s = self._rcnn_base_gen(sup_ims, plan, save=save_s)
+                g_q = self._rcnn_base_gen(im_data, plan, out_stride=2048, out_buf=corr, save=save_q)
                 r_s = r_q = None
                 while r_s is None or r_q is None:
                     if r_q is None:
@@ -1105,250 +1222,215 @@ class DAnARCNN(nn.Module):
                                 next(g_s)
                             except StopIteration as done_:
                                 r_s = done_.value
-                sup, sh_, sw_ = r_s
+                sfeat, sh_, sw_ = r_s
             else:  # (single-stream passes: bench.py's per-launch timing)
-                sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)
-                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None)
-        hw = fh * fw
-        if cache is None:
-            self._check_support_map(sh_, sw_)
-        mark("trunk (query + support)")
-        if cache is not None:
-            support_done = None
-        else:
-            with ops.on_stream(sup_stream):
-                sup.record_stream(sup_stream)
-                s_pe, kp, unary, s_t = self._support_rpn_side(sup, B, shot, way, L, dev, sup_stream, ctx)
-                for t_ in (kp, unary, s_t):
-                    t_.record_stream(main)
-                support_done = ops.record_event()
-                if ctx is not None:
-                    ctx.update(sup=sup, s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
+                sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s)
+                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=save_q)
+        self._check_support_map(sh_, sw_)
+        f.mark("trunk (query + support)")
+        with ops.on_stream(sup_stream):
+            sfeat.record_stream(sup_stream)
+            s_pe, kp, unary, s_t = self._support_rpn_side(sfeat, B, shot, f.way, sh_ * sw_, dev, sup_stream, ctx)
+            for t_ in (kp, unary, s_t):
+                t_.record_stream(main)
+            rpn_done = ops.record_event()
+            if ctx is not None:
+                ctx.update(sup=sfeat, s_pe=s_pe, kp=kp, unary=unary, Ns=sup_ims.size(0))
+        return corr, (fh, fw), dict(feat=sfeat, map=(sh_, sw_), kp=kp, unary=unary, s_t=s_t, rpn_done=rpn_done)
 
-        # -- RPN-level dual-awareness attention, query side (dana.py:118-154) --
-        wq, bq = self._w(self.rpn_adapt_q_layer)
+    def _rpn_attention(self, f, corr, fh, fw, sup):
+        """RPN-level dual-awareness attention (dana.py:118-156) -> a class sweep's attended rows [B*C*hw][1024], else None"""
+        # without a sweep the attended rows go into the second half of corr (times base_feat in place for product attention)
+        B, Cs, NP, dev, main = f.B, f.Cs, f.NP, f.dev, f.main
+        d = self.rpn_reduce_dim
+        hw = fh * fw
+        L = sup["map"][0] * sup["map"][1]  # 20 x 20 = 400 for the reference's 320 x 320 supports (dana.py:105)
+        K1 = f.shot * L
+        kp, unary, s_t = sup["kp"], sup["unary"], sup["s_t"]
+        _, bq = self._w(self.rpn_adapt_q_layer)
         qb3, qld = self._lin_b(self.rpn_adapt_q_layer)
         qp = ops.gemm_nt(corr, qb3, B * hw, d, 1024, lda=2048, ldb=qld, shift=bq)
         ops.colmean_sub_(qp, B, hw, d)
-        mark("rpn-level Q projection")
-        if support_done is not None:
-            main.wait_event(support_done)
-        mark("... wait for the support side (trunk + RPN-level K / unary / S^T chain)")
-        product = self.attention_type == "product"
-        if sweep is not None:
+        f.mark("rpn-level Q projection")
+        if sup["rpn_done"] is not None:
+            main.wait_event(sup["rpn_done"])
+        f.mark("... wait for the support side (trunk + RPN-level K / unary / S^T chain)")
+        att = None
+        if f.sweep is not None:
             # one GEMM per image over the C classes' keys side by side (N = C*K1: one read of qp[b]), then the softmax
             # moves row (b, i, c) to problem b*C + c, so the attended GEMM is a uniform batch over the B*C problems
             scores = torch.empty((B, hw, Cs * K1), dtype=torch.float32, device=dev)
             ops.gemm_nt(qp, kp, hw, Cs * K1, d, out=scores, ldc=Cs * K1, batch=B, batch_a=hw * d, batch_b=Cs * K1 * d,
                         batch_c=hw * Cs * K1, alpha=1.0 / math.sqrt(d))
             a_p = torch.empty((NP, hw, K1), dtype=torch.float32, device=dev)
-            ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, shot, L, K1, K1, K1, self.unary_gamma, 1.0 / shot)
+            ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, 1.0 / f.shot)
             att = torch.empty((NP * hw, 1024), dtype=torch.float32, device=dev)  # problem p's attended rows
             ops.gemm_nt(a_p, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=att, ldc=1024, batch=NP, batch_a=hw * K1,
                         batch_b=1024 * K1, batch_c=hw * 1024)
-            if product:  # dana.py:155-156 with base_feat of image p / C
+            if f.product:  # dana.py:155-156 with base_feat of image p / C
                 ops.mul_rows_grouped_(att, corr, hw, 1024, Cs, NP, ld_y=1024, ld_x=2048)
         else:
             scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
             ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
                         alpha=1.0 / math.sqrt(d))
-            ops.attn_softmax_unary_(scores, unary, B * hw, hw, shot, L, K1, K1, self.unary_gamma, 1.0 / shot)
+            ops.attn_softmax_unary_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, 1.0 / f.shot)
             ops.gemm_nt(scores, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=corr.view(-1)[1024:], ldc=2048, batch=B,
                         batch_a=hw * K1, batch_b=1024 * K1, batch_c=hw * 2048)
-        if product and sweep is None:
-            # dana.py:155-156: correlation_feat = base_feat * dense_support_feature -- in place in the attended half of the
-            # buffer (nothing else reads the attended rows); the RPN conv then reads that half only (cin 1024, pixel stride
-            # 2048), RoIAlign keeps reading base_feat from the first half
-            if ctx is not None:
-                raise NotImplementedError("attention_type='product' runs the forward (train and eval mode) on the HIP "
-                                          "kernels; its backward is not implemented -- train 'concat', what utils.get_model "
-                                          "builds (utils.py:120-123)")
-            ops.mul_rows_(corr.view(-1)[1024:], corr, B * hw, 1024, ld_y=2048, ld_x=2048)
-        if inter is not None:
-            inter["corr"] = (corr, B, fh, fw)
-        if ctx is not None:
-            ctx.update(corr=corr, fh=fh, fw=fw, qp=qp, scores=scores)
+            if f.product:
+                # dana.py:155-156: correlation_feat = base_feat * dense_support_feature -- in place in the attended half
+                # of the buffer (nothing else reads the attended rows); the RPN conv then reads that half only (cin 1024,
+                # pixel stride 2048), RoIAlign keeps reading base_feat from the first half
+                ops.mul_rows_(corr.view(-1)[1024:], corr, B * hw, 1024, ld_y=2048, ld_x=2048)
+        if f.inter is not None:
+            f.inter["corr"] = (corr, B, fh, fw)
+        if f.ctx is not None:
+            f.ctx.update(corr=corr, fh=fh, fw=fw, qp=qp, scores=scores)
+        f.mark("rpn-level attention (incl. wait for support stream)")
+        return att
 
-        mark("rpn-level attention (incl. wait for support stream)")
-        # -- RPN head + proposals (rpn.py:58-78, proposal_layer.py:49-190) --
-        rpn = self.RCNN_rpn
-        rpn_in = corr.view(-1)[1024:] if product else corr  # (product: the attended half, pixel stride 2048)
-        if sweep is not None:
-            x = self._rpn_conv_sweep(plan, corr, att, B, Cs, fh, fw, product)
-        elif plan["rpn_conv_u"] is not None:
-            kv = [] if ctx is not None else None
-            x, _, _ = ops.conv3x3_winograd(rpn_in, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512,
-                                           shift=plan["rpn_conv_b"], relu=True, keep_v=kv, in_stride=2048)
-            if kv:
-                ctx["rpn_v"] = kv[0]  # the input's Winograd transform: the weight gradient does not repeat it
-        else:
-            x, _, _ = ops.conv2d_nhwc(rpn_in, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1, 1,
-                                      shift=plan["rpn_conv_b"], relu=True, in_stride=2048)
-        nh = rpn.nc_score_out + rpn.nc_bbox_out
-        heads = ops.gemm_nt(x, plan["rpn_head_w3"] or plan["rpn_head_w"], NP * hw, nh, 512, shift=plan["rpn_head_b"])  # [B*hw][2A | 4A]
-        mark("rpn conv + heads")
-        # -- RoI-level support side (dana.py:105-108,258,271-277): K / unary projections once per support (the
-        #    reference recomputes them for every RoI). Only the RoI heads need them, so they are queued behind the RPN
-        #    head: they run while the proposal layer (sort / NMS: a handful of workgroups) leaves the CUs idle,
-        #    instead of competing with the query trunk. --
-        if cache is not None:
-            sp_pe, k2, un2, sw = gathered["sp_pe"], gathered["k2"], gathered["un2"], gathered["sw"]
-            support_roi_done = None
-        else:
+    def _rpn_conv_stage(self, f, corr, att, fh, fw):
+        """RPN_Conv + ReLU (rpn.py:58-63) of the NP problems -> [NP*hw][512]"""
+        if f.sweep is not None:
+            return self._rpn_conv_sweep(f.plan, corr, att, f.B, f.Cs, fh, fw, f.product)
+        kv = [] if f.ctx is not None else None
+        # (product: the attended half, pixel stride 2048)
+        x = self._rpn_conv(f.plan, corr.view(-1)[1024:] if f.product else corr, f.B, fh, fw, in_stride=2048, keep_v=kv)
+        if kv:
+            f.ctx["rpn_v"] = kv[0]  # the input's Winograd transform: the weight gradient does not repeat it
+        return x
+
+    def _roi_support(self, f, sup):
+        """RoI-level support side (dana.py:105-108,258,271-277) into sup: sp_pe, k2, un2, sw, roi_done"""
+        # K / unary projections once per support (the reference recomputes them for every RoI; a cache gathered them
+        # already). Only the RoI heads need them, so they are queued behind the RPN head: they run while the proposal layer
+        # (sort / NMS: a handful of workgroups) leaves the CUs idle, instead of competing with the query trunk.
+        ctx = f.ctx
+        if f.cache is None:
             proposals_start = ops.record_event()
-            with ops.on_stream(sup_stream):
-                sup_stream.wait_event(proposals_start)
-                sp_pe, k2, un2, sw, pool = self._support_roi_side(sup, Ns, sh_, sw_, plan, dev, product, ctx)
+            with ops.on_stream(f.sup_stream):
+                f.sup_stream.wait_event(proposals_start)
+                sh_, sw_ = sup["map"]
+                Ns = f.B * f.way * f.shot
+                sp_pe, k2, un2, sw, pool = self._support_roi_side(sup["feat"], Ns, sh_, sw_, f.plan, f.dev, f.product, ctx)
                 if sw is not None:
-                    sw.record_stream(main)
+                    sw.record_stream(f.main)
                 for t_ in (sp_pe, k2, un2):
-                    t_.record_stream(main)
-                support_roi_done = ops.record_event()
+                    t_.record_stream(f.main)
+                sup.update(sp_pe=sp_pe, k2=k2, un2=un2, sw=sw, roi_done=ops.record_event())
                 if ctx is not None:
                     ctx.update(sp_pe=sp_pe, k2=k2, un2=un2, sup_map=(sh_, sw_), sup_pool=pool)
         if ctx is not None:
             # the backward's weight-only launches, on the (idle) weight-gradient stream: they run under the proposal layer and
             # the host round trip, where the chip has nothing else to do (backward.prefetch_dgrad_weights)
             from . import backward as BW
-            BW.prefetch_dgrad_weights(self, ctx, dev)
-        A = plan["anchors"].size(0)
-        key = "TRAIN" if training else "TEST"
+            BW.prefetch_dgrad_weights(self, ctx, f.dev)
+
+    def _proposal_stage(self, f, heads, nh, fh, fw):
+        """proposals of the NP problems (proposal_layer.py:49-190) -> rois [NP, post_nms_topn, 5]"""
         # (a sweep's problem p clips and filters with the im_info row of image p / C: one launch)
-        im_info_p = im_info if sweep is None else ops.repeat_rows_grouped(im_info, 1, 3, Cs, NP, ld_src=im_info.size(1))
-        rois = ops.proposal_layer(heads, (hw * nh, 1, nh), False, heads.view(-1)[rpn.nc_score_out:], (hw * nh, 1, nh),
-                                  im_info_p, plan["anchors"], NP, A, fh, fw, rpn.feat_stride,
-                                  cfg[key].RPN_PRE_NMS_TOP_N, cfg[key].RPN_POST_NMS_TOP_N, cfg[key].RPN_NMS_THRESH,
-                                  self.nms_inclusive)
-        mark("proposal layer (decode, sort, nms)")
-        if inter is not None:
-            inter["rpn_heads"] = heads
-            inter["rpn_rois"] = rois
+        im_info_p = f.im_info if f.sweep is None else ops.repeat_rows_grouped(f.im_info, 1, 3, f.Cs, f.NP,
+                                                                              ld_src=f.im_info.size(1))
+        rois = self._proposals(f.plan, heads, nh, im_info_p, f.NP, fh, fw)
+        f.mark("proposal layer (decode, sort, nms)")
+        if f.inter is not None:
+            f.inter["rpn_heads"] = heads
+            f.inter["rpn_rois"] = rois
         inj_rois = getattr(self, "_inject_rpn_rois", None)
         if inj_rois is not None:
             # stage-wise parity hook (tests only): an EXTERNAL proposal list (the oracle's) replaces this forward's, so that
             # this build's own proposal-target sampling runs on an identical candidate list and its picks can be compared
             # position by position at the full size (one near-tie among 12 000 sorted scores otherwise shifts every slot)
-            rois = inj_rois.to(dev).float().contiguous()
+            rois = inj_rois.to(f.dev).float().contiguous()
+        f.tick("enqueued trunk..proposals")
+        return rois
 
-        if tl is not None:
-            tl.append(("enqueued trunk..proposals", _time.perf_counter()))
-        rpn_loss_cls = rpn_loss_bbox = 0
-        rois_label = rpn_draws = None
-        if training:
-            # Proposal targets, first half (proposal_target_layer_cascade.py:113-141), behind the proposal layer
-            if side is not main:
-                main.wait_stream(side)
-            fg_per = int(np.round(tr_.FG_FRACTION * tr_.BATCH_SIZE)) or 1
-            R_t = int(tr_.BATCH_SIZE)
-            pt = ops.proposal_target_prepare(rois, gt_f, tr_.FG_THRESH, tr_.BG_THRESH_HI, tr_.BG_THRESH_LO)
-            if tl is not None:
-                tl.append(("target layers enqueued (first halves)", _time.perf_counter()))
-            if rng is None:
-                # -- the one host round trip: counts -> np.random draws (the reference's stream) -> one upload --
-                if capturing:  # a captured graph must end with every side stream joined
-                    main.wait_event(support_roi_done)
-                    support_roi_done = None
-                lay = ops.draw_layout(B, R_t, at["total"])
-                drawn = yield dict(stage="draw", anchor_counts=at["counts"], anchor_stream=side,
-                                   proposal_counts=pt["counts"], B=B, R=R_t, fg_per=fg_per,
-                                   rpn_batchsize=int(tr_.RPN_BATCHSIZE), num_fg=num_fg, total=at["total"], layout=lay)
-                rpn_draws = (drawn, lay)
-                picks_ptr, taken_ptr = drawn.data_ptr() + 4 * lay["picks"], drawn.data_ptr() + 4 * lay["taken"]
-            else:
-                host = ops.proposal_target_sample_device(pt, R_t, fg_per, rng[0], rng[1] + 1, counter=ctr)
-                if ctr is not None:
-                    ops.counter_add_(ctr, 2)
-                picks_ptr, taken_ptr = host.data_ptr(), host.data_ptr() + 4 * B * R_t
-            if tl is not None:
-                tl.append(("draws (host sync)", _time.perf_counter()))
-            # (the RPN losses are issued BEHIND RoIAlign, below: right behind the host round trip the host has no lead over the
-            #  GPU, so what is issued first starts first -- the sampled batch and RoIAlign are what the RoI stage waits for)
-            rois, rois_label, rois_target, rois_inside_ws, rois_outside_ws = ops.proposal_target_finish(
-                pt, picks_ptr, taken_ptr, R_t, tr_.BBOX_NORMALIZE_MEANS, tr_.BBOX_NORMALIZE_STDS,
-                tr_.BBOX_INSIDE_WEIGHTS, tr_.BBOX_NORMALIZE_TARGETS_PRECOMPUTED)
-            inj = getattr(self, "_inject_sampled", None)
-            if inj is not None:
-                # stage-wise parity hook (SURVEY.md 7 "feed reference intermediates"): the 5-tuple an EXTERNAL
-                # _ProposalTargetLayer produced (the oracle's / the reference's own sampled batch) replaces this
-                # forward's draw, so everything downstream is compared on identical rois. Tests only.
-                rois, rois_label, rois_target, rois_inside_ws, rois_outside_ws = [
-                    t_.to(dev).float().contiguous() for t_ in inj]
-            if tl is not None:
-                tl.append(("rpn losses + proposal targets (waits for rois)", _time.perf_counter()))
-            labels_f = rois_label.reshape(-1).contiguous()
-            rois_label = None  # (int64 [2n], built with the negative head's zeros at the end: ops.labels_posneg)
-            rois_target = rois_target.view(-1, 4)
-            rois_inside_ws = rois_inside_ws.view(-1, 4)
-            rois_outside_ws = rois_outside_ws.view(-1, 4)
-        mark("rpn losses + proposal targets")
-        R = rois.size(1)
-        n_roi = NP * R
-
-        # -- RoIAlign on base_feat (dana.py:181-186), emitting pooled and pooled+PE in one pass --
-        # Forward-only runs (nothing saved for a backward) fold the positional encoding of dana.py:259 into the two
-        # projections that consume it: (pooled + PE) W^T = pooled W^T + (PE W^T), a [49][N] table per weight version --
-        # RoIAlign then writes ONE [n,49,1024] output instead of two (it is bound by its own writes, DESIGN 3), and the
-        # Q projection and the query half of rcnn_transform_layer are ONE N = 128 GEMM over pooled (one read of it).
-        fold_pe = (ctx is None and cfg.POOLING_MODE == "align" and getattr(self, "fold_roi_pe", True)
-                   and self.attention_type == "concat")  # (product multiplies by pooled + PE itself: dana.py:286)
-        # (a sweep's rois carry the problem index p in column 0: RoIAlign reads base_feat of image p / C)
-        if cfg.POOLING_MODE == "align" and fold_pe:
-            pooled, q_pe = ops.roi_align_forward_nhwc(corr, B, fh, fw, 1024, 2048, rois.view(-1, 5), 1.0 / 16.0, P, 0,
-                                                      group=Cs)
-        elif cfg.POOLING_MODE == "align":
-            pooled, q_pe = ops.roi_align_forward_nhwc(corr, B, fh, fw, 1024, 2048, rois.view(-1, 5), 1.0 / 16.0, P, 0,
-                                                      pe=plan["pe49"], group=Cs)  # pooled [n,49,1024] and pooled + PE (dana.py:259)
-        elif cfg.POOLING_MODE == "pool":
-            # dana.py:183-184 (a resumed checkpoint's cfg may ask for it, train.py:100-101): the RoIPool operator of the
-            # `_C` boundary on base_feat (the first 1024 channels of the [.. | attended] buffer); the saving forward keeps
-            # the argmax indices for the backward's scatter (ROIPool_cuda.cu:79-108, dana_roi_pool_backward)
-            pooled_nchw, roi_argmax = ops.roi_pool_forward(ops.nhwc_to_nchw(corr, B, 1024, fh, fw, in_stride=2048),
-                                                           rois.view(-1, 5).contiguous(), 1.0 / 16.0, P, P)
-            if ctx is not None:
-                ctx["roi_argmax"] = roi_argmax
-            pooled = ops.nchw_to_nhwc(pooled_nchw).view(n_roi, P * P, 1024)
-            q_pe = ops.add_pe(pooled, plan["pe49"], n_roi * P * P, P * P, 1024).view(n_roi, P * P, 1024)
+    def _proposal_targets(self, f, tg, rois, sup):
+        """proposal targets (proposal_target_layer_cascade.py:113-141); pauses with stage="draw" under the host RNG"""
+        # -> (rois, (labels_f, rois_target, rois_inside_ws, rois_outside_ws), the anchor draws of the host RNG or None)
+        tr_, main, B = cfg.TRAIN, f.main, f.B
+        if tg.side is not main:
+            main.wait_stream(tg.side)
+        fg_per = int(np.round(tr_.FG_FRACTION * tr_.BATCH_SIZE)) or 1
+        R_t = int(tr_.BATCH_SIZE)
+        pt = ops.proposal_target_prepare(rois, tg.gt_f, tr_.FG_THRESH, tr_.BG_THRESH_HI, tr_.BG_THRESH_LO)
+        f.tick("target layers enqueued (first halves)")
+        rpn_draws = None
+        if tg.rng is None:
+            # -- the one host round trip: counts -> np.random draws (the reference's stream) -> one upload --
+            if tg.capturing:  # a captured graph must end with every side stream joined
+                main.wait_event(sup["roi_done"])
+                sup["roi_done"] = None
+            at = tg.at
+            lay = ops.draw_layout(B, R_t, at["total"])
+            drawn = yield dict(stage="draw", anchor_counts=at["counts"], anchor_stream=tg.side,
+                               proposal_counts=pt["counts"], B=B, R=R_t, fg_per=fg_per,
+                               rpn_batchsize=int(tr_.RPN_BATCHSIZE), num_fg=tg.num_fg, total=at["total"], layout=lay)
+            rpn_draws = (drawn, lay)
+            picks_ptr, taken_ptr = drawn.data_ptr() + 4 * lay["picks"], drawn.data_ptr() + 4 * lay["taken"]
         else:
-            raise NotImplementedError("POOLING_MODE '%s'" % cfg.POOLING_MODE)
-        if inter is not None:
-            inter["pooled"] = pooled
-        pooled_ready = ops.record_event()
-        mark("roi align")
-        if training:
-            # the anchor labels' drawn pairs, then the fused RPN losses (rpn.py:97-115) straight from the head buffer
-            # [B*hw][2A | 4A]: on the caller's stream, which has slack against layer4's chain on its own stream
-            if rpn_draws is not None:
-                ops.anchor_target_apply_draws(at, *rpn_draws)
-            rpn_l = ops.rpn_losses(heads, nh, at, sigma=3.0, inside_weight=tr_.RPN_BBOX_INSIDE_WEIGHTS[0])
-            rpn_loss_cls, rpn_loss_bbox = rpn_l[0], rpn_l[1]
-            if ctx is not None:
-                ctx.update(rpn_x=x, rpn_heads=heads, nh=nh, at=at, rpn_l=rpn_l)
+            host = ops.proposal_target_sample_device(pt, R_t, fg_per, tg.rng[0], tg.rng[1] + 1, counter=tg.ctr)
+            if tg.ctr is not None:
+                ops.counter_add_(tg.ctr, 2)
+            picks_ptr, taken_ptr = host.data_ptr(), host.data_ptr() + 4 * B * R_t
+        f.tick("draws (host sync)")
+        # (the RPN losses are issued BEHIND RoIAlign: right behind the host round trip the host has no lead over the GPU,
+        #  so what is issued first starts first -- the sampled batch and RoIAlign are what the RoI stage waits for)
+        rois, rois_label, rois_target, rois_inside_ws, rois_outside_ws = ops.proposal_target_finish(
+            pt, picks_ptr, taken_ptr, R_t, tr_.BBOX_NORMALIZE_MEANS, tr_.BBOX_NORMALIZE_STDS,
+            tr_.BBOX_INSIDE_WEIGHTS, tr_.BBOX_NORMALIZE_TARGETS_PRECOMPUTED)
+        inj = getattr(self, "_inject_sampled", None)
+        if inj is not None:
+            # stage-wise parity hook (SURVEY.md 7 "feed reference intermediates"): the 5-tuple an EXTERNAL
+            # _ProposalTargetLayer produced (the oracle's / the reference's own sampled batch) replaces this
+            # forward's draw, so everything downstream is compared on identical rois. Tests only.
+            rois, rois_label, rois_target, rois_inside_ws, rois_outside_ws = [t_.to(f.dev).float().contiguous() for t_ in inj]
+        f.tick("rpn losses + proposal targets (waits for rois)")
+        # (the int64 rois_label [2n] is built with the negative head's zeros at the end: ops.labels_posneg)
+        return rois, (rois_label.reshape(-1).contiguous(), rois_target.view(-1, 4), rois_inside_ws.view(-1, 4),
+                      rois_outside_ws.view(-1, 4)), rpn_draws
 
-        # -- box regression branch: layer4 + mean + Linear (dana.py:246,387-389), shared by the pos/neg heads.
-        #    It is independent of the attention head below, so it runs on its own stream (tails overlap). --
-        l4_stream = self._stream("layer4", dev)
+    def _rpn_loss_stage(self, f, tg, rpn_draws, x, heads, nh):
+        """the anchor labels' drawn pairs, then the fused RPN losses (rpn.py:97-115) from the head buffer"""
+        # on the caller's stream, which has slack against layer4's chain on its own stream
+        if rpn_draws is not None:
+            ops.anchor_target_apply_draws(tg.at, *rpn_draws)
+        rpn_l = ops.rpn_losses(heads, nh, tg.at, sigma=3.0, inside_weight=cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS[0])
+        if f.ctx is not None:
+            f.ctx.update(rpn_x=x, rpn_heads=heads, nh=nh, at=tg.at, rpn_l=rpn_l)
+        return rpn_l[0], rpn_l[1]
+
+    def _box_branch(self, f, pooled, pooled_ready, n_roi):
+        """box regression branch: layer4 + mean + Linear (dana.py:246,387-389) -> (bbox_pred, its event)"""
+        # shared by the pos/neg heads and independent of the attention head: on its own stream (tails overlap)
+        l4_stream = self._stream("layer4", f.dev)
         l4_stream.wait_event(pooled_ready)
         with ops.on_stream(l4_stream):
-            y, h4, w4 = pooled, P, P
-            for bi, bp in enumerate(plan["layer4"]):
-                y, h4, w4 = self._bottleneck(y, n_roi, h4, w4, bp, save=ctx["l4_saved"] if ctx is not None else None,
-                                             key="RCNN_top.0.%d" % bi)
-            fc7 = ops.spatial_mean(y, n_roi, h4 * w4, 2048)
+            P = cfg.POOLING_SIZE
+            fc7 = self._head_to_tail(pooled, n_roi, P, P, f.plan, save=f.ctx["l4_saved"] if f.ctx is not None else None)
             wb, bb = self._w(self.RCNN_bbox_pred)
             bbox_pred = ops.gemm_nt(fc7, wb, n_roi, 4, 2048, shift=bb)
-            bbox_pred.record_stream(main)
+            bbox_pred.record_stream(f.main)
             pooled.record_stream(l4_stream)
             l4_done = ops.record_event()
+        if f.ctx is not None:
+            f.ctx["fc7"] = fc7
+        return bbox_pred, l4_done
 
-        # -- RoI-level CISA (dana.py:248-292). Query side once: Q projection and the q half of
-        #    rcnn_transform_layer (cat([q, attended]) @ Wt^T = q @ Wt[:, :1024]^T + attended @ Wt[:, 1024:]^T,
-        #    so the [n*49][2048] concat of dana.py:284 is never materialised). --
-        if support_roi_done is not None:
-            main.wait_event(support_roi_done)
-        wq2, bq2 = self._w(self.rcnn_adapt_q_layer)
+    def _roi_heads(self, f, pooled, q_pe, fold_pe, sup, rois, R, l4_done):
+        """RoI-level CISA (dana.py:248-292) -> (prob_all, cls_prob, positive scores, negative scores or None)"""
+        # Positive head on the caller's stream, negative head (training) on its own, joined with layer4's branch. Query
+        # side once: Q projection and the q half of rcnn_transform_layer (cat([q, attended]) @ Wt^T = q @ Wt[:, :1024]^T +
+        # attended @ Wt[:, 1024:]^T, so the [n*49][2048] concat of dana.py:284 is never materialised).
+        plan, dev, main, ctx, NP, shot, way, training = f.plan, f.dev, f.main, f.ctx, f.NP, f.shot, f.way, f.training
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        n_roi = NP * R
+        dq, rd_ = self.rcnn_reduce_dim, self.rcnn_dim
+        if sup["roi_done"] is not None:
+            main.wait_event(sup["roi_done"])
+        _, bq2 = self._w(self.rcnn_adapt_q_layer)
         if fold_pe:
             wcat, wcat_ld, tfull = self._roi_query_fold(plan, n_roi, dev)
-            qld = dq + self.rcnn_dim
+            qld = dq + rd_
             qt = ops.gemm_nt(pooled, wcat, n_roi * P2, qld, 1024, ldb=wcat_ld, residual=tfull, ldr=qld)  # [n*49][dq | 64]
             q2 = qt.view(-1)
             ops.colmean_sub_(q2, n_roi, P2, dq, ld=qld)
@@ -1359,12 +1441,11 @@ class DAnARCNN(nn.Module):
             ops.colmean_sub_(q2, n_roi, P2, dq)
         K2 = shot * P2
         K2p = (K2 + 31) // 32 * 32
-        wt, bt_ = self._w(self.rcnn_transform_layer)
+        _, bt_ = self._w(self.rcnn_transform_layer)
         w1, b1 = self._w(self.output_score_layer.linear1)
         w2, b2 = self._w(self.output_score_layer.linear2)
-        product = self.attention_type == "product"
         w1b3, w1ld = self._lin_b(self.output_score_layer.linear1)
-        if product:  # dana.py:285-288: transform(query_mat * attended), Wt [64][1024]
+        if f.product:  # dana.py:285-288: transform(query_mat * attended), Wt [64][1024]
             wt_a, wt_a_ld = self._lin_b(self.rcnn_transform_layer)
             tr_q, tr_q_ld = None, 0
         else:
@@ -1373,9 +1454,10 @@ class DAnARCNN(nn.Module):
             if fold_pe:
                 tr_q, tr_q_ld = qt.view(-1)[dq:], qld  # the second column block of the fused projection
             else:
-                tr_q = ops.gemm_nt(q_pe, wt_q, n_roi * P2, self.rcnn_dim, 1024, ldb=wt_q_ld, shift=bt_)  # [n*49][64]
-                tr_q_ld = self.rcnn_dim
+                tr_q = ops.gemm_nt(q_pe, wt_q, n_roi * P2, rd_, 1024, ldb=wt_q_ld, shift=bt_)  # [n*49][64]
+                tr_q_ld = rd_
         q_ready = ops.record_event()
+        sp_pe, k2, un2, sw = sup["sp_pe"], sup["k2"], sup["un2"], sup["sw"]
 
         # cls_prob of both heads in one buffer (positive rows, then negative rows: the torch.cat of dana.py:193)
         prob_all = torch.empty((2 * n_roi if training else n_roi, 2), dtype=torch.float32, device=dev)
@@ -1388,7 +1470,6 @@ class DAnARCNN(nn.Module):
                         batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
             ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, 1.0 / shot,
                                     unary_batch_stride=way * shot * P2)
-            rd_ = self.rcnn_dim
             if sw is not None:
                 swt = ops.transpose_batched(sw.view(-1)[offset * P2 * rd_:], NP, K2, rd_, ldi=rd_, ldo=K2p,
                                             in_batch=way * shot * P2 * rd_)  # [B][64][K2p], zero padded
@@ -1403,13 +1484,13 @@ class DAnARCNN(nn.Module):
                 dense = torch.empty((n_roi * P2, 1024), dtype=torch.float32, device=dev)
                 ops.gemm_nt(sc2, st2, R * P2, 1024, K2p, lda=K2p, ldb=K2p, out=dense, ldc=1024, batch=NP,
                             batch_a=R * P2 * K2p, batch_b=1024 * K2p, batch_c=R * P2 * 1024, k_true=K2)
-                if product:
+                if f.product:
                     ops.mul_rows_(dense, q_pe, n_roi * P2, 1024)  # query_mat * attended (dana.py:286)
                     tr = ops.gemm_nt(dense, wt_a, n_roi * P2, rd_, 1024, ldb=wt_a_ld, shift=bt_)
                 else:
                     tr = ops.gemm_nt(dense, wt_a, n_roi * P2, rd_, 1024, ldb=wt_a_ld,
                                      residual=tr_q, ldr=tr_q_ld)  # [n*49][64] == [n][3136]
-            hid = ops.gemm_nt(tr, w1b3, n_roi, w1.size(0), P2 * self.rcnn_dim, ldb=w1ld, shift=b1, relu=True)
+            hid = ops.gemm_nt(tr, w1b3, n_roi, w1.size(0), P2 * rd_, ldb=w1ld, shift=b1, relu=True)
             score = ops.gemm_nt(hid, w2, n_roi, 2, w1.size(0), shift=b2)
             prob = ops.softmax_rows_to(score, prob_all[(n_roi if offset else 0):], n_roi, 2)[:n_roi]
             if ctx is not None:
@@ -1418,6 +1499,7 @@ class DAnARCNN(nn.Module):
 
         if ctx is not None:
             ctx.update(rois=rois, R=R, q_pe=q_pe, q2=q2, K2=K2, K2p=K2p)
+        neg_score = None
         if training:  # the negative-support head (dana.py:190) on its own stream, concurrent with the positive one
             neg_stream = self._stream("neg_head", dev)
             neg_stream.wait_event(q_ready)
@@ -1429,38 +1511,14 @@ class DAnARCNN(nn.Module):
                     if t_ is not None:  # (q_pe: None when the positional encoding is folded into the projections)
                         t_.record_stream(neg_stream)
                 neg_done = ops.record_event()
-        cls_prob, cls_score_all = head(0)
-        mark("pos head")
+        cls_prob, cls_score = head(0)
+        f.mark("pos head")
         main.wait_event(l4_done)
         if training:
             main.wait_event(neg_done)
-        if ctx is not None:
-            ctx["fc7"] = fc7
-        mark("join layer4 / neg head")
-        if tl is not None:
-            tl.append(("enqueued roialign..head", _time.perf_counter()))
-        RCNN_loss_cls = RCNN_loss_bbox = 0
-        if training:
-            cls_prob = prob_all  # (both heads wrote their halves)
-            rois_label = ops.labels_posneg(labels_f)
-            # box smooth-L1 + 2-way cross-entropy with the 1:2:1 hard-negative mining (dana.py:203-217): one fused
-            # pass on the device, no host sync (the nonzero / sort / index chain of the reference has three)
-            rl, seeds = ops.rcnn_losses(cls_score_all, neg_score, labels_f, bbox_pred,
-                                        rois_target.contiguous(), rois_inside_ws.contiguous(),
-                                        rois_outside_ws.contiguous(), with_grad=ctx is not None)
-            RCNN_loss_cls, RCNN_loss_bbox = rl[0], rl[1]
-            if ctx is not None:
-                ctx.update(loss_seeds=seeds)
-        mark("rcnn losses")
-        if tl is not None:
-            tl.append(("rcnn losses", _time.perf_counter()))
-        if ctx is not None and self._bridge:
-            # hand the four losses to autograd: loss.backward() runs backward.model_backward on the HIP kernels
-            if self._grad_anchor is None or self._grad_anchor.device != dev:
-                self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
-            rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = _LossBridge.apply(
-                self._grad_anchor, self, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox)
-        return rois, cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label
+        f.mark("join layer4 / neg head")
+        f.tick("enqueued roialign..head")
+        return prob_all, cls_prob, cls_score, neg_score
 
 
 class SupportCache:

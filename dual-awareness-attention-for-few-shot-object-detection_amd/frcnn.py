@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from . import ops
 from .config import cfg
-from .dana import DAnARCNN, _LossBridge, _RPNParams
+from .dana import DAnARCNN, _RPNParams
 
 
 class FasterRCNN(DAnARCNN):
@@ -66,28 +66,16 @@ class FasterRCNN(DAnARCNN):
         rfeat, rh, rw = (base, fh, fw) if rpn_input is None else rpn_input(base, B, fh, fw, plan)
         base_hw = (fh, fw)
         fh, fw = rh, rw  # the RPN / anchor / proposal geometry below is the RPN input's
-        hw = fh * fw
-        rpn = self.RCNN_rpn
-        if plan["rpn_conv_u"] is not None:
-            x, _, _ = ops.conv3x3_winograd(rfeat, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_u"], 512, shift=plan["rpn_conv_b"],
-                                           relu=True)
-        else:
-            x, _, _ = ops.conv2d_nhwc(rfeat, B, fh, fw, rpn.din, plan["rpn_conv_b3"] or plan["rpn_conv_w"], 512, 3, 3, 1, 1,
-                                      shift=plan["rpn_conv_b"], relu=True)
-        nh = rpn.nc_score_out + rpn.nc_bbox_out
-        heads = ops.gemm_nt(x, plan["rpn_head_w3"] or plan["rpn_head_w"], B * hw, nh, 512, shift=plan["rpn_head_b"])
-        A = plan["anchors"].size(0)
-        key = "TRAIN" if training else "TEST"
-        rois = ops.proposal_layer(heads, (hw * nh, 1, nh), False, heads.view(-1)[rpn.nc_score_out:], (hw * nh, 1, nh),
-                                  im_info, plan["anchors"], B, A, fh, fw, rpn.feat_stride, cfg[key].RPN_PRE_NMS_TOP_N,
-                                  cfg[key].RPN_POST_NMS_TOP_N, cfg[key].RPN_NMS_THRESH, self.nms_inclusive)
+        x = self._rpn_conv(plan, rfeat, B, fh, fw)
+        heads, nh = self._rpn_head(plan, x, B * fh * fw)
+        rois = self._proposals(plan, heads, nh, im_info, B, fh, fw)
         st = dict(B=B, rpn_loss_cls=0, rpn_loss_bbox=0, rois_label=None, labels_f=None)
         if training:
             tr_ = cfg.TRAIN
             side = self._stream("targets", dev)
             side.wait_event(inputs_ready)
             with ops.on_stream(side):
-                at = ops.anchor_target_assign(anchor_gt.float(), im_info, plan["anchors"], fh, fw, rpn.feat_stride,
+                at = ops.anchor_target_assign(anchor_gt.float(), im_info, plan["anchors"], fh, fw, self.RCNN_rpn.feat_stride,
                                               tr_.RPN_NEGATIVE_OVERLAP, tr_.RPN_POSITIVE_OVERLAP, tr_.RPN_BATCHSIZE,
                                               tr_.RPN_FG_FRACTION)
             at["ibuf"].record_stream(main)
@@ -111,34 +99,15 @@ class FasterRCNN(DAnARCNN):
         n_roi = B * R
         P = cfg.POOLING_SIZE
         fh, fw = base_hw
-        # -- RoI pooling (faster_rcnn.py:70-73) on base_feat: both modes of the reference --
-        if cfg.POOLING_MODE == "align":
-            pooled, _ = ops.roi_align_forward_nhwc(base, B, fh, fw, 1024, 1024, rois.view(-1, 5), 1.0 / 16.0, P, 0)
-        elif cfg.POOLING_MODE == "pool":
-            nchw = ops.nhwc_to_nchw(base, B, 1024, fh, fw)
-            pooled_nchw, _ = ops.roi_pool_forward(nchw, rois.view(-1, 5).contiguous(), 1.0 / 16.0, P, P)
-            pooled = ops.nchw_to_nhwc(pooled_nchw)
-        else:
-            raise NotImplementedError("POOLING_MODE '%s'" % cfg.POOLING_MODE)
+        pooled, _ = self._roi_pool(plan, base, B, fh, fw, 1024, rois)  # (faster_rcnn.py:70-73) on base_feat
         st.update(rois=rois, R=R, n_roi=n_roi, pooled=pooled, plan=plan,
                   fc7=self._head_to_tail(pooled, n_roi, P, P, plan, save=ctx["l4_saved"] if ctx is not None else None))
         if ctx is not None:
             ctx.update(plan=plan, B=B, R=R, rois=rois, fh=fh, fw=fw, fc7=st["fc7"])
         return st
 
-    def _head_to_tail(self, x, n, h, w, plan, save=None):
-        """layer4 + spatial mean (faster_rcnn.py:183-185) on an NHWC batch of n maps -> [n][2048]"""
-        for bi, bp in enumerate(plan["layer4"]):
-            x, h, w = self._bottleneck(x, n, h, w, bp, save=save, key="RCNN_top.0.%d" % bi)
-        return ops.spatial_mean(x, n, h * w, 2048)
-
     def forward(self, im_data, im_info, gt_boxes, num_boxes):
-        ctx = None
-        bridge = self.training and torch.is_grad_enabled() and type(self) is FasterRCNN
-        if self.training and type(self) is FasterRCNN and (bridge or getattr(self, "save_for_backward", False)):
-            if cfg.POOLING_MODE != "align":
-                raise NotImplementedError("the HIP backward of frcnn covers POOLING_MODE 'align'")
-            ctx = dict(q_saved=[], l4_saved=[])
+        bridge, ctx = self._saving_ctx(("q_saved", "l4_saved"), align_only_for="frcnn")
         self._ctx = None
         st = self._stages(im_data, im_info, gt_boxes, ctx=ctx)
         B, R, n_roi, fc7 = st["B"], st["R"], st["n_roi"], st["fc7"]
@@ -162,11 +131,8 @@ class FasterRCNN(DAnARCNN):
                 ctx.update(loss_seeds=(d_cls, d_bbox))
                 self._ctx = ctx
                 if bridge:  # loss.backward() (train.py:141-143) runs backward.frcnn_backward on the HIP kernels
-                    dev = im_data.device
-                    if self._grad_anchor is None or self._grad_anchor.device != dev:
-                        self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
-                    rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = _LossBridge.apply(
-                        self._grad_anchor, self, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox)
+                    rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
+                        im_data.device, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob.view(B, R, -1), bbox_pred.view(B, R, -1), rpn_loss_cls, rpn_loss_bbox,
                 RCNN_loss_cls, RCNN_loss_bbox, st["rois_label"])
 
@@ -195,20 +161,13 @@ class MetaRCNN(FasterRCNN):
         training = self.training
         shot = self.n_shot
         way = self.n_way if training else 1
-        ctx = None
-        bridge = training and torch.is_grad_enabled()
-        if training and (bridge or getattr(self, "save_for_backward", False)):
-            if cfg.POOLING_MODE != "align":
-                raise NotImplementedError("the HIP backward of meta covers POOLING_MODE 'align'")
-            ctx = dict(q_saved=[], l4_saved=[], s_saved=[], sl4_saved=[], heads=[])
+        bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "sl4_saved", "heads"), align_only_for="meta")
         self._ctx = None
         st = self._stages(im_data, im_info, gt_boxes, anchor_gt_boxes=all_cls_gt_boxes, ctx=ctx)
         B, R, n_roi, fc7, plan = st["B"], st["R"], st["n_roi"], st["fc7"], st["plan"]
         # PRN (meta.py:241-251) on every support image
-        sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
+        sup_ims = self._support_batch(support_ims, B, way, shot)
         Ns = sup_ims.size(0)
-        if Ns != B * way * shot:
-            raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, Ns))
         sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)
         mp, mh, mw = ops.maxpool2x2s2(sup, Ns, sh_, sw_, 1024)
         att = ops.sigmoid_(self._head_to_tail(mp, Ns, mh, mw, plan, save=ctx["sl4_saved"] if ctx is not None else None))
@@ -242,9 +201,6 @@ class MetaRCNN(FasterRCNN):
                 ctx.update(loss_seeds=seeds, att=att, sup=sup, sup_hw=(sh_, sw_), mp_hw=(mh, mw), Ns=Ns, shot=shot, way=way)
                 self._ctx = ctx
                 if bridge:  # loss.backward() (train.py:141-143) runs backward.meta_backward on the HIP kernels
-                    dev = im_data.device
-                    if self._grad_anchor is None or self._grad_anchor.device != dev:
-                        self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
-                    rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = _LossBridge.apply(
-                        self._grad_anchor, self, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox)
+                    rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
+                        im_data.device, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label)

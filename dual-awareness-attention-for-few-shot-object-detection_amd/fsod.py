@@ -14,8 +14,6 @@ import torch
 import torch.nn as nn
 
 from . import ops
-from .config import cfg
-from .dana import _LossBridge
 from .frcnn import FasterRCNN
 
 
@@ -59,16 +57,9 @@ class FSOD(FasterRCNN):
         B = im_data.size(0)
         dev = im_data.device
         plan = self._get_plan()
-        sup_ims = support_ims.reshape(-1, support_ims.size(2), support_ims.size(3), support_ims.size(4))
+        sup_ims = self._support_batch(support_ims, B, way, shot)
         Ns = sup_ims.size(0)
-        if Ns != B * way * shot:
-            raise RuntimeError("support_ims must hold batch*way*shot = %d images, got %d" % (B * way * shot, Ns))
-        ctx = None
-        bridge = training and torch.is_grad_enabled()
-        if training and (bridge or getattr(self, "save_for_backward", False)):
-            if cfg.POOLING_MODE != "align":
-                raise NotImplementedError("the HIP backward of fsod covers POOLING_MODE 'align'")
-            ctx = dict(q_saved=[], l4_saved=[], s_saved=[], heads=[])
+        bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "heads"), align_only_for="fsod")
         self._ctx = None
         sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
         if (sh_, sw_) != (20, 20):
@@ -150,8 +141,6 @@ class FSOD(FasterRCNN):
                        corr_roi=corr_roi, wp2=wp2)
             self._ctx = ctx
             if bridge:  # loss.backward() (train.py:141-143) runs backward.frcnn_backward (fsod branch) on the HIP kernels
-                if self._grad_anchor is None or self._grad_anchor.device != dev:
-                    self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
-                rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = _LossBridge.apply(
-                    self._grad_anchor, self, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox)
+                rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
+                    dev, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label)

@@ -49,7 +49,14 @@ def test_roi_align_matches_reference_cpu_op(G):
 def test_decode_clip_and_overlaps_match_reference(G):
     anchors = O.anchor_grid(G["anchors_a4"], 5, 7, 16).unsqueeze(0).expand(2, -1, 4)
     p = O.clip_boxes(O.bbox_transform_inv(anchors, torch.from_numpy(G["dec_deltas"])), torch.from_numpy(G["dec_im_info"]))
-    assert np.array_equal(p.numpy(), G["dec_out"])
+    # the decode's exp is CPU torch.exp, whose float32 kernel MKL picks per CPU (hosts differ by an ulp of exp, and the
+    # golden holds one host's): the clipped coordinates are bit-exact on every host, the others within that ulp
+    # carried through the width / height product (3.1e-5 px at most with MKL held to AVX2)
+    out, ref = p.numpy(), G["dec_out"]
+    xb, yb = G["dec_im_info"][:, 1] - 1, G["dec_im_info"][:, 0] - 1
+    clipped = (ref == 0) | (ref == np.stack([xb, yb, xb, yb], -1)[:, None, :])
+    assert clipped.any() and np.array_equal(out[clipped], ref[clipped])
+    assert np.abs(out - ref).max() <= 1e-4
     for b in range(2):
         pc = ON.decode_clip(G["anchors_a4"], G["dec_deltas"][b], 5, 7, 16, G["dec_im_info"][b, 0], G["dec_im_info"][b, 1])
         assert np.abs(pc - G["dec_out"][b]).max() < 1e-3
