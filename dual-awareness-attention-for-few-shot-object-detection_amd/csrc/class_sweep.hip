@@ -119,6 +119,67 @@ mul_rows_grouped_kernel(float4* __restrict__ y, const float4* __restrict__ x, lo
   }
 }
 
+// Meta R-CNN's class head over a sweep (meta.py:129-142 per class): one wave per RoI row b*R + r of fc7 [B*R][K], held
+// in registers (16-byte loads, K <= 64 * 4 * MH_V); for each of the C classes of its image, problem p = b*C + c:
+//   z = (fc7[b*R + r] * vec[p]) . W^T + bias  (the product rounded to fp32 first, as scale_rows_by_group writes it),
+//   cls_prob[p*R + r] = softmax_2(z), and the row's rois (column 0 = p) / bbox_pred copied to problem p's block.
+constexpr int MH_V = 8;
+
+__global__ void __launch_bounds__(256)
+meta_class_head_kernel(const float4* __restrict__ fc7, const float4* __restrict__ vec, const float4* __restrict__ w,
+                       const float* __restrict__ bias, const float* __restrict__ rois, const float* __restrict__ bbox,
+                       float* __restrict__ cls_prob, float* __restrict__ rois_out, float* __restrict__ bbox_out, int C,
+                       int R, int K4, long rows) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long b = row / R, r = row - b * R;
+  float4 f[MH_V];
+#pragma unroll
+  for (int t = 0; t < MH_V; ++t) {
+    const int j = lane + 64 * t;
+    f[t] = j < K4 ? fc7[row * K4 + j] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  const float b0 = bias[0], b1 = bias[1];
+  for (int c = 0; c < C; ++c) {
+    const long p = b * C + c;
+    const float4* v = vec + p * K4;
+    float s0 = 0.f, s1 = 0.f;
+#pragma unroll
+    for (int t = 0; t < MH_V; ++t) {
+      const int j = lane + 64 * t;
+      if (j < K4) {
+        const float4 a = v[j], w0 = w[j], w1 = w[K4 + j];
+        const float x0 = f[t].x * a.x, x1 = f[t].y * a.y, x2 = f[t].z * a.z, x3 = f[t].w * a.w;
+        s0 += x0 * w0.x;
+        s0 += x1 * w0.y;
+        s0 += x2 * w0.z;
+        s0 += x3 * w0.w;
+        s1 += x0 * w1.x;
+        s1 += x1 * w1.y;
+        s1 += x2 * w1.z;
+        s1 += x3 * w1.w;
+      }
+    }
+    s0 = wave_sum(s0) + b0;
+    s1 = wave_sum(s1) + b1;
+    const long o = p * R + r;
+    if (lane == 0) {
+      const float m = fmaxf(s0, s1);
+      const float e0 = expf(s0 - m), e1 = expf(s1 - m);
+      const float s = e0 + e1;
+      cls_prob[o * 2] = e0 / s;
+      cls_prob[o * 2 + 1] = e1 / s;
+    } else if (lane < 5) {
+      rois_out[o * 5 + lane] = rois[row * 5 + lane];
+    } else if (lane == 5) {
+      rois_out[o * 5] = (float)p;
+    } else if (lane < 10) {
+      bbox_out[o * 4 + (lane - 6)] = bbox[row * 4 + (lane - 6)];
+    }
+  }
+}
+
 unsigned grid_for(long total) {
   const long g = (total + 255) / 256;
   return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));  // 256 CUs x 32 resident blocks, grid-stride the rest
@@ -174,6 +235,24 @@ int dana_mul_rows_grouped(float* y, const float* x, long rows, int channels, lon
   mul_rows_grouped_kernel<<<grid_for(total), 256, 0, (hipStream_t)stream>>>((float4*)y, (const float4*)x, rows,
                                                                             channels / 4, ld_y / 4, ld_x / 4, group, total);
   DANA_CHECK_LAUNCH("dana_mul_rows_grouped");
+  return DANA_OK;
+}
+
+int dana_meta_class_head(const float* fc7, const float* vec, const float* weight, const float* bias, const float* rois,
+                         const float* bbox_pred, float* cls_prob, float* rois_out, float* bbox_out, int B, int C, int R,
+                         int K, dana_stream_t stream) {
+  DANA_CHECK_ARG(B >= 0 && C > 0 && R > 0 && K > 0 && K % 4 == 0 && K <= 256 * MH_V,
+                 "dana_meta_class_head: bad shape B=%d C=%d R=%d K=%d (K %% 4 == 0, K <= %d)", B, C, R, K, 256 * MH_V);
+  if (B == 0) return DANA_OK;
+  DANA_CHECK_ARG(fc7 && vec && weight && bias && rois && bbox_pred && cls_prob && rois_out && bbox_out,
+                 "dana_meta_class_head: null pointer");
+  DANA_CHECK_ARG((((uintptr_t)fc7 | (uintptr_t)vec | (uintptr_t)weight) & 15) == 0,
+                 "dana_meta_class_head: fc7 / vec / weight not 16-byte aligned");
+  const long rows = (long)B * R;
+  meta_class_head_kernel<<<dana_ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(
+      (const float4*)fc7, (const float4*)vec, (const float4*)weight, bias, rois, bbox_pred, cls_prob, rois_out, bbox_out,
+      C, R, K / 4, rows);
+  DANA_CHECK_LAUNCH("dana_meta_class_head");
   return DANA_OK;
 }
 

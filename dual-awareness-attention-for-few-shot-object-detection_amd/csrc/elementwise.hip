@@ -142,6 +142,21 @@ scale_rows_by_group_kernel(const float4* __restrict__ x, const float4* __restric
   }
 }
 
+// class sweep of the fgn attention RPN (fgn.py:71-73 per problem): out row p*rows + i = x row (p / group)*rows + i (row
+// stride ldx4) times vec[p], channel-wise -- scale_rows_by_group_kernel's product on the image's rows, which are never
+// replicated
+__global__ void __launch_bounds__(256)
+scale_rows_grouped_kernel(const float4* __restrict__ x, const float4* __restrict__ vec, float4* __restrict__ out,
+                          long rows, int C4, long ldx4, int group, long total) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)blockDim.x * gridDim.x) {
+    const int c = (int)(i % C4);
+    const long r = i / C4;
+    const long p = r / rows, ri = r - p * rows;
+    const float4 a = x[((p / group) * rows + ri) * ldx4 + c], v = vec[p * C4 + c];
+    out[i] = make_float4(a.x * v.x, a.y * v.y, a.z * v.z, a.w * v.w);
+  }
+}
+
 // depth-wise "valid" cross-correlation (fsod.py:109-116,207-214: F.conv2d(feat, kernel.view(C,1,kh,kw), groups=C)):
 // out[n][oh][ow][c] = sum_{i,j} feat[n][oh+i][ow+j][c] * kern[n / per_kernel][i][j][c]
 __global__ void __launch_bounds__(256)
@@ -154,6 +169,32 @@ depthwise_corr_kernel(const float4* __restrict__ feat, const float4* __restrict_
     const long n = i / C4 / OW / OH;
     const float4* kp = kern + (n / per_kernel) * KH * KW * C4 + c;
     const float4* fp = feat + ((n * H + oh) * W + ow) * lda4 + c;
+    float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int a = 0; a < KH; ++a)
+      for (int b = 0; b < KW; ++b) {
+        const float4 f = fp[((long)a * W + b) * lda4], k = kp[(a * KW + b) * C4];
+        acc.x += f.x * k.x;
+        acc.y += f.y * k.y;
+        acc.z += f.z * k.z;
+        acc.w += f.w * k.w;
+      }
+    out[i] = acc;
+  }
+}
+
+// class sweep of the fsod attention RPN (fsod.py:109-116 per problem): out map n = the correlation of feat map n / group
+// with kernel n. The per-element arithmetic and summation order of depthwise_corr_kernel (maps_per_kernel 1): a feat
+// map replicated `group` times gives the same bits
+__global__ void __launch_bounds__(256)
+depthwise_corr_grouped_kernel(const float4* __restrict__ feat, const float4* __restrict__ kern, float4* __restrict__ out,
+                              int H, int W, int KH, int KW, int OH, int OW, int C4, long lda4, int group, long total) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)blockDim.x * gridDim.x) {
+    const int c = (int)(i % C4);
+    const int ow = (int)((i / C4) % OW);
+    const int oh = (int)((i / C4 / OW) % OH);
+    const long n = i / C4 / OW / OH;
+    const float4* kp = kern + n * KH * KW * C4 + c;
+    const float4* fp = feat + (((n / group) * H + oh) * W + ow) * lda4 + c;
     float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
     for (int a = 0; a < KH; ++a)
       for (int b = 0; b < KW; ++b) {
@@ -654,6 +695,27 @@ int dana_depthwise_corr_nhwc(const float* feat, const float* kernels, float* out
   return DANA_OK;
 }
 
+int dana_depthwise_corr_nhwc_grouped(const float* feat, const float* kernels, float* out, long n_maps, int height,
+                                     int width, int channels, int kh, int kw, int group, long feat_pix_stride,
+                                     dana_stream_t stream) {
+  DANA_CHECK_ARG(n_maps >= 0 && height >= kh && width >= kw && kh > 0 && kw > 0 && channels > 0 && channels % 4 == 0 &&
+                     group > 0,
+                 "dana_depthwise_corr_nhwc_grouped: bad shape");
+  if (n_maps == 0) return DANA_OK;
+  DANA_CHECK_ARG(feat && kernels && out, "dana_depthwise_corr_nhwc_grouped: null pointer");
+  if (feat_pix_stride <= 0) feat_pix_stride = channels;
+  DANA_CHECK_ARG(feat_pix_stride % 4 == 0 && feat_pix_stride >= channels &&
+                     (((uintptr_t)feat | (uintptr_t)kernels | (uintptr_t)out) & 15) == 0,
+                 "dana_depthwise_corr_nhwc_grouped: stride %% 4 != 0, below channels, or unaligned pointers");
+  const int oh = height - kh + 1, ow = width - kw + 1;
+  const long total = n_maps * oh * ow * (channels / 4);
+  depthwise_corr_grouped_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+      (const float4*)feat, (const float4*)kernels, (float4*)out, height, width, kh, kw, oh, ow, channels / 4,
+      feat_pix_stride / 4, group, total);
+  DANA_CHECK_LAUNCH("dana_depthwise_corr_nhwc_grouped");
+  return DANA_OK;
+}
+
 int dana_depthwise_corr_backward_nhwc(const float* grad_out, const float* feat, const float* kernels, float* grad_feat,
                                       float* grad_kernels, long n_maps, int height, int width, int channels, int kh,
                                       int kw, long maps_per_kernel, long feat_pix_stride, int accumulate_kernels,
@@ -730,6 +792,22 @@ int dana_scale_rows_by_group(const float* x, const float* group_vec, float* out,
   scale_rows_by_group_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
       (const float4*)x, (const float4*)group_vec, (float4*)out, rows_per_group, channels / 4, total);
   DANA_CHECK_LAUNCH("dana_scale_rows_by_group");
+  return DANA_OK;
+}
+
+int dana_scale_rows_grouped(const float* x, const float* vec, float* out, long rows, int channels, long ld_x, int group,
+                            long n_blocks, dana_stream_t stream) {
+  DANA_CHECK_ARG(rows > 0 && channels > 0 && channels % 4 == 0 && group > 0 && n_blocks >= 0,
+                 "dana_scale_rows_grouped: bad shape");
+  if (n_blocks == 0) return DANA_OK;
+  DANA_CHECK_ARG(x && vec && out, "dana_scale_rows_grouped: null pointer");
+  if (ld_x <= 0) ld_x = channels;
+  DANA_CHECK_ARG(ld_x % 4 == 0 && ld_x >= channels && (((uintptr_t)x | (uintptr_t)vec | (uintptr_t)out) & 15) == 0,
+                 "dana_scale_rows_grouped: stride %% 4 != 0, below channels, or unaligned pointers");
+  const long total = n_blocks * rows * (channels / 4);
+  scale_rows_grouped_kernel<<<grid_for(total, 256), 256, 0, (hipStream_t)stream>>>(
+      (const float4*)x, (const float4*)vec, (float4*)out, rows, channels / 4, ld_x / 4, group, total);
+  DANA_CHECK_LAUNCH("dana_scale_rows_grouped");
   return DANA_OK;
 }
 

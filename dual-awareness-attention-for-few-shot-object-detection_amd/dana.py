@@ -885,11 +885,16 @@ class DAnARCNN(nn.Module):
         return (self._sig(), str(dev), self.attention_type, bool(self.semantic_enhance),
                 bool(getattr(self, "fold_roi_attn", True)), int(self.n_shot))
 
-    def encode_supports(self, support_ims):
-        """support_ims [C, shot, 3, S, S] (C support sets, e.g. one per class) -> SupportCache: the eval forward's
-        query-independent support work (support trunk, RPN-level and RoI-level support chains), done once per set with the
-        launches an uncached B = 1 forward issues for it. `model(im_data, im_info, gt_boxes, num_boxes, cache)` then runs
-        the query side only (inference.py:82-103 draws each class's shots once and reuses them for every query)."""
+    def _cache_layout(self, shot, sup_map):
+        """name -> per-set shape of a SupportCache's tensors, in the order the forward's consumers expect them (B sets
+        stacked on a first axis). RPN level: kp, unary, s_t; RoI level: k2, un2 and sw (folded S.Wt^T) or sp_pe"""
+        L, P2 = sup_map[0] * sup_map[1], cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        d, dq, rd = self.rpn_reduce_dim, self.rcnn_reduce_dim, self.rcnn_dim
+        return dict(kp=(shot * L, d), unary=(shot, L), s_t=(1024, shot * L), k2=(shot * P2, dq), un2=(shot, P2),
+                    sw=(shot * P2, rd), sp_pe=(shot * P2, 1024))
+
+    def _check_support_sets(self, support_ims):
+        """encode_supports' input checks -> (C, shot, device)"""
         if self.training:
             raise RuntimeError("encode_supports runs in eval mode (model.eval()): a SupportCache serves inference only")
         if not torch.is_tensor(support_ims) or support_ims.dim() != 5 or support_ims.size(2) != 3:
@@ -902,7 +907,14 @@ class DAnARCNN(nn.Module):
             raise ValueError("encode_supports: %d shots per set, the model was built for num_shot = %d" % (shot, self.n_shot))
         if C < 1:
             raise ValueError("encode_supports: no support set")
-        dev = support_ims.device
+        return C, shot, support_ims.device
+
+    def encode_supports(self, support_ims):
+        """support_ims [C, shot, 3, S, S] (C support sets, e.g. one per class) -> SupportCache: the eval forward's
+        query-independent support work (support trunk, RPN-level and RoI-level support chains), done once per set with the
+        launches an uncached B = 1 forward issues for it. `model(im_data, im_info, gt_boxes, num_boxes, cache)` then runs
+        the query side only (inference.py:82-103 draws each class's shots once and reuses them for every query)."""
+        C, shot, dev = self._check_support_sets(support_ims)
         plan = self._get_plan()
         product = self.attention_type == "product"
         stream = ops.cur_stream()
@@ -917,7 +929,7 @@ class DAnARCNN(nn.Module):
                 sp_pe, k2, un2, sw, pool = self._support_roi_side(sup, shot, sh_, sw_, plan, dev, product)
                 per_set.append(dict(kp=kp, unary=unary, s_t=s_t, k2=k2, un2=un2, sw=sw, sp_pe=None if sw is not None else sp_pe))
             tensors = {k: (None if per_set[0][k] is None else torch.stack([p_[k].reshape(-1) for p_ in per_set]))
-                       for k in SupportCache.FIELDS}
+                       for k in self._cache_layout(shot, (sh_, sw_))}
         return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev)
 
     # ---- stages shared with the sibling detectors (frcnn.py, fgn.py, fsod.py) ------------------------------------
@@ -1522,16 +1534,16 @@ class DAnARCNN(nn.Module):
 
 
 class SupportCache:
-    """The query-independent support tensors of C support sets (DAnARCNN.encode_supports), per set:
+    """The query-independent support tensors of C support sets (encode_supports), per set as the model's
+    `_cache_layout` names them. DAnA:
     RPN level  kp [shot*L][d] (column mean subtracted), unary [shot][L] (softmaxed), s_t [1024][shot*L];
     RoI level  k2 [shot*49][dq], un2 [shot][49], and sw [shot*49][64] (folded S.Wt^T) or sp_pe [shot*49][1024]
                (product attention or fold_roi_attn off).
+    The sibling detectors' layouts are in frcnn.py (meta), fsod.py and fgn.py.
     `model(im_data, im_info, gt_boxes, num_boxes, cache)`: query image b uses set index[b] -- `select(indices)`, else the
     identity when C == B and a broadcast when C == 1. The forward gathers the selected sets into B-batched buffers the cache
     owns (one launch, dana_gather_blocks, index read on the device: a recorded replay follows later `select` calls).
     The cache records what it was built under; a forward after any of it changed raises ("re-encode")."""
-
-    FIELDS = ("kp", "unary", "s_t", "k2", "un2", "sw", "sp_pe")
 
     def __init__(self, model, tensors, shot, sup_map, pool, state, dev):
         self._model = weakref.ref(model)
@@ -1539,11 +1551,9 @@ class SupportCache:
         self.shot, self.sup_map, self.pool, self.device = shot, tuple(sup_map), pool, torch.device(dev)
         self._state = state
         self._C = next(iter(self._t.values())).size(0)
-        L, P2 = sup_map[0] * sup_map[1], cfg.POOLING_SIZE * cfg.POOLING_SIZE
-        d, dq, rd = model.rpn_reduce_dim, model.rcnn_reduce_dim, model.rcnn_dim
         # the shapes the forward's consumers expect, per image (B of them stacked on the first axis)
-        self._shapes = dict(kp=(shot * L, d), unary=(shot, L), s_t=(1024, shot * L), k2=(shot * P2, dq), un2=(shot, P2),
-                            sw=(shot * P2, rd), sp_pe=(shot * P2, 1024))
+        self._shapes = model._cache_layout(shot, sup_map)
+        self.FIELDS = tuple(self._shapes)
         self._sel = None        # host list of the last select(), or None
         self._index = None      # device int32 [capacity]: what dana_gather_blocks reads
         self._index_host = None  # what the device index holds

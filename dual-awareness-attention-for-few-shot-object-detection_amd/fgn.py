@@ -13,6 +13,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .dana import ClassSweep
 from .frcnn import FasterRCNN
 
 
@@ -54,6 +55,24 @@ class FGN(FasterRCNN):
         scale, shift = ops.bn_fold(bn.weight, bn.bias, mean, var, bn.eps)
         return ops.scale_shift_relu_(x, scale, shift, rows, C, relu=True)
 
+    # ---- cached support sets (encode_supports) ---------------------------------------------------------------------
+    def _cache_layout(self, shot, sup_map):
+        """pos_rpn: AvgPool2d(20) of the shots' mean map (fgn.py:71-73); s_half: the support half of cls_conv1 (3x3 valid)
+        on its AvgPool2d(14, 1) (fgn.py:148-152)"""
+        return dict(pos_rpn=(1024,), s_half=(25, 512))
+
+    def _support_set(self, sup_ims, plan, dev):
+        """one support set's cache tensors, with the launches of the uncached eval forward at B = 1"""
+        shot = sup_ims.size(0)
+        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan)
+        L = sh_ * sw_
+        pos_map = ops.spatial_mean(sup, 1, shot, L * 1024)
+        pos_rpn = ops.spatial_mean(pos_map, 1, L, 1024)
+        pos_rcnn = ops.avgpool(pos_map, 1, sh_, sw_, 1024, 14, 1)
+        w1_sup = ops.pack_conv_weight(self.cls_conv1.weight.detach()[:, :1024].contiguous())
+        s_half, _, _ = ops.conv2d_nhwc(pos_rcnn, 1, 7, 7, 1024, w1_sup, 512, 3, 3, 1, 0)
+        return dict(pos_rpn=pos_rpn, s_half=s_half)
+
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         training = self.training
         shot = self.n_shot
@@ -61,14 +80,20 @@ class FGN(FasterRCNN):
         B = im_data.size(0)
         dev = im_data.device
         plan = self._get_plan()
-        sup_ims = self._support_batch(support_ims, B, way, shot)
-        Ns = sup_ims.size(0)
+        # cached: the support sets' tensors gathered per problem (a class sweep: B*Cs problems p = b*Cs + c)
+        cached, Cs = self._cached_supports(support_ims, B, dev)
+        sweep = isinstance(support_ims, ClassSweep)
+        NP = B * Cs
+        if cached is None:
+            sup_ims = self._support_batch(support_ims, B, way, shot)
+            Ns = sup_ims.size(0)
         bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "heads"), align_only_for="fgn")
         self._ctx = None
-        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
-        if (sh_, sw_) != (20, 20):
-            raise RuntimeError("support images must be 320x320 (fgn.py:34-35: AvgPool2d(20) / AvgPool2d(14, 1) of a 20x20 map)")
-        L = sh_ * sw_
+        if cached is None:
+            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
+            if (sh_, sw_) != (20, 20):
+                raise RuntimeError("support images must be 320x320 (fgn.py:34-35: AvgPool2d(20) / AvgPool2d(14, 1) of a 20x20 map)")
+            L = sh_ * sw_
 
         def mean_map(offset):  # mean over the shots [offset, offset + shot): [B][400*1024]
             m = torch.empty((B, L * 1024), dtype=torch.float32, device=dev)
@@ -76,21 +101,27 @@ class FGN(FasterRCNN):
                 m[b:b + 1] = ops.spatial_mean(sup.view(-1)[(b * way * shot + offset) * L * 1024:], 1, shot, L * 1024)
             return m
 
-        pos_map = mean_map(0)
-        pos_rpn = ops.spatial_mean(pos_map, B, L, 1024)            # AvgPool2d(20): [B][1024]
-        pos_rcnn = ops.avgpool(pos_map, B, sh_, sw_, 1024, 14, 1)  # AvgPool2d(14, 1): [B][49][1024]
+        if cached is None:
+            pos_map = mean_map(0)
+            pos_rpn = ops.spatial_mean(pos_map, B, L, 1024)            # AvgPool2d(20): [B][1024]
+            pos_rcnn = ops.avgpool(pos_map, B, sh_, sw_, 1024, 14, 1)  # AvgPool2d(14, 1): [B][49][1024]
+        else:
+            pos_rpn, pos_rcnn = cached["pos_rpn"], None
 
         def attention_rpn_input(base, B_, fh, fw, plan_):
             if ctx is not None:
                 ctx["base"] = base
+            if sweep:  # problem p: image p / Cs's map times set p's vector (the map is never replicated)
+                return ops.scale_rows_grouped(base, pos_rpn, fh * fw, 1024, Cs, NP), fh, fw
             return ops.scale_rows_by_group(base, pos_rpn, B_ * fh * fw, fh * fw, 1024), fh, fw
 
-        st = self._stages(im_data, im_info, gt_boxes, rpn_input=attention_rpn_input, ctx=ctx)
+        st = self._stages(im_data, im_info, gt_boxes, rpn_input=attention_rpn_input, ctx=ctx, group=Cs)
         R, n_roi, pooled, fc7 = st["R"], st["n_roi"], st["pooled"], st["fc7"]
         wb, bb = self._w(self.RCNN_bbox_pred)
         bbox_pred = ops.gemm_nt(fc7, wb, n_roi, 4, 2048, shift=bb)
         w1 = self.cls_conv1.weight.detach()
-        w1_sup = ops.pack_conv_weight(w1[:, :1024].contiguous())   # torch.cat([support, roi], 1): support channels first
+        # torch.cat([support, roi], 1): support channels first (a cache holds the support half's output)
+        w1_sup = ops.pack_conv_weight(w1[:, :1024].contiguous()) if cached is None else None
         w1_roi = ops.pack_conv_weight(w1[:, 1024:].contiguous())
         w2 = ops.pack_conv_weight(self.cls_conv2.weight)
         # Linear(1152, 2) reads the NCHW flatten (c, h, w); the activations here are (h, w, c)
@@ -98,10 +129,13 @@ class FGN(FasterRCNN):
         bl = self.RCNN_cls_score.bias.detach().contiguous()
         roi_half, _, _ = ops.conv2d_nhwc(pooled, n_roi, 7, 7, 1024, w1_roi, 512, 3, 3, 1, 0)  # [n*25][512], shared
 
-        def head(support, offset):  # support [B][49][1024]
+        def head(support, offset):  # support [B][49][1024]; cached: s_half [NP*25][512] from the cache
             saved = [] if ctx is not None else None
-            s_half, _, _ = ops.conv2d_nhwc(support, B, 7, 7, 1024, w1_sup, 512, 3, 3, 1, 0)  # [B*25][512]
-            x = ops.broadcast_rows(s_half, B, R, 25 * 512)                                      # [n*25][512]
+            if cached is None:
+                s_half, _, _ = ops.conv2d_nhwc(support, B, 7, 7, 1024, w1_sup, 512, 3, 3, 1, 0)  # [B*25][512]
+            else:
+                s_half = cached["s_half"]
+            x = ops.broadcast_rows(s_half, NP, R, 25 * 512)                                     # [n*25][512]
             ops.axpy_rows_(x, roi_half, n_roi * 25, 512)
             x1 = self._bn(x, n_roi * 25, self.bn1, save=saved)
             x, _, _ = ops.conv2d_nhwc(x1, n_roi, 5, 5, 512, w2, 128, 3, 3, 1, 0)                # [n*9][128]

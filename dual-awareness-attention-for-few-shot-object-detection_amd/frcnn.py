@@ -10,7 +10,7 @@ import torch.nn as nn
 
 from . import ops
 from .config import cfg
-from .dana import DAnARCNN, _RPNParams
+from .dana import ClassSweep, DAnARCNN, SupportCache, _RPNParams
 
 
 class FasterRCNN(DAnARCNN):
@@ -45,16 +45,63 @@ class FasterRCNN(DAnARCNN):
         self.RCNN_cls_score.weight.data.normal_(0, 0.01)
         self.RCNN_cls_score.bias.data.zero_()
 
+    # ---- cached support sets of the support-conditioned siblings (meta, fsod, fgn) ---------------------------------
+    _support_set = None  # (model, sup_ims [shot, 3, 320, 320], plan, dev) -> {name: tensor} of _cache_layout; None: frcnn
+
+    def _cache_state(self, dev):
+        """what a sibling's SupportCache depends on besides the support images (every state_dict tensor is in _sig)"""
+        return (self._sig(), str(dev), type(self).__name__, int(self.n_shot))
+
+    def encode_supports(self, support_ims):
+        """support_ims [C, shot, 3, 320, 320] -> SupportCache of the model's per-set support tensors (`_cache_layout`),
+        each set built by `_support_set` with the launches an uncached B = 1 eval forward issues for it. The forward takes
+        the cache (or cache.select / cache.sweep) in place of support images, as DAnARCNN's does."""
+        if self._support_set is None:
+            raise TypeError("%s is the plain Faster R-CNN (faster_rcnn.py): it has no support branch, so there are no "
+                            "support sets to encode" % type(self).__name__)
+        C, shot, dev = self._check_support_sets(support_ims)
+        if tuple(support_ims.shape[-2:]) != (320, 320):
+            raise RuntimeError("support images must be 320x320 (a 20x20 stride-16 map) for a cached support set, got %dx%d"
+                               % tuple(support_ims.shape[-2:]))
+        plan = self._get_plan()
+        with torch.no_grad():
+            per_set = [self._support_set(support_ims[c].float().contiguous(), plan, dev) for c in range(C)]
+            tensors = {k: torch.stack([p_[k].reshape(-1) for p_ in per_set]) for k in self._cache_layout(shot, (20, 20))}
+        return SupportCache(self, tensors, shot, (20, 20), None, self._cache_state(dev), dev)
+
+    def _cached_supports(self, support_ims, B, dev):
+        """-> (the gathered per-problem support tensors, problems per image) when support_ims is a SupportCache or a
+        ClassSweep (problems p = b*C + c), else (None, 1). One dana_gather_blocks launch, none for one set and one image"""
+        sweep = support_ims if isinstance(support_ims, ClassSweep) else None
+        cache = sweep.cache if sweep is not None else (support_ims if isinstance(support_ims, SupportCache) else None)
+        if cache is None:
+            return None, 1
+        if self.training:
+            raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
+                               "support side from support images")
+        cache._check(self, dev)
+        if sweep is None:
+            return cache._gather(B), 1
+        if cfg.POOLING_MODE != "align":
+            raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
+                                      "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
+        return cache._gather(B * len(sweep), sweep._index(B)), len(sweep)
+
     # ---- shared stages of the sibling detectors (frcnn, meta): trunk -> RPN -> targets -> RoI features -> layer4 ----
-    def _stages(self, im_data, im_info, gt_boxes, anchor_gt_boxes=None, rpn_input=None, ctx=None):
-        """-> dict(B, R, n_roi, rois, rpn losses, rois_label / targets (train), pooled, fc7 [n_roi][2048]).
+    def _stages(self, im_data, im_info, gt_boxes, anchor_gt_boxes=None, rpn_input=None, ctx=None, group=1):
+        """-> dict(B, NP, R, n_roi, rois, rpn losses, rois_label / targets (train), pooled, fc7 [n_roi][2048]).
         anchor_gt_boxes: boxes the anchor-target layer sees (meta.py:65 passes ALL classes' boxes); default gt_boxes.
-        rpn_input(base, B, fh, fw, plan) -> (feature [B*h*w][1024], h, w): what the RPN runs on instead of base_feat
-        (fsod.py:109-119: the attention RPN's correlation map, which is smaller than base_feat)"""
+        rpn_input(base, B, fh, fw, plan) -> (feature [B*group*h*w][1024], h, w): what the RPN runs on instead of base_feat
+        (fsod.py:109-119: the attention RPN's correlation map, which is smaller than base_feat).
+        group: a class sweep's problems per image (eval): the RPN, the proposals (im_info of image p / group), RoI pooling
+        (rois' column 0 = p, base_feat of image p / group) and layer4 run over NP = B*group problems p = b*group + c"""
         plan = self._get_plan()
         dev = im_data.device
         training = self.training
         B = im_data.size(0)
+        NP = B * group
+        if group > 1 and training:
+            raise RuntimeError("a class sweep runs in eval mode")
         im_info = im_info.data.float().contiguous()
         gt_boxes = gt_boxes.data
         anchor_gt = gt_boxes if anchor_gt_boxes is None else anchor_gt_boxes.data
@@ -66,10 +113,12 @@ class FasterRCNN(DAnARCNN):
         rfeat, rh, rw = (base, fh, fw) if rpn_input is None else rpn_input(base, B, fh, fw, plan)
         base_hw = (fh, fw)
         fh, fw = rh, rw  # the RPN / anchor / proposal geometry below is the RPN input's
-        x = self._rpn_conv(plan, rfeat, B, fh, fw)
-        heads, nh = self._rpn_head(plan, x, B * fh * fw)
-        rois = self._proposals(plan, heads, nh, im_info, B, fh, fw)
-        st = dict(B=B, rpn_loss_cls=0, rpn_loss_bbox=0, rois_label=None, labels_f=None)
+        x = self._rpn_conv(plan, rfeat, NP, fh, fw)
+        heads, nh = self._rpn_head(plan, x, NP * fh * fw)
+        if group > 1:  # problem p clips and filters with the im_info row of image p / group (one launch)
+            im_info = ops.repeat_rows_grouped(im_info, 1, 3, group, NP, ld_src=im_info.size(1))
+        rois = self._proposals(plan, heads, nh, im_info, NP, fh, fw)
+        st = dict(B=B, NP=NP, rpn_loss_cls=0, rpn_loss_bbox=0, rois_label=None, labels_f=None)
         if training:
             tr_ = cfg.TRAIN
             side = self._stream("targets", dev)
@@ -96,10 +145,10 @@ class FasterRCNN(DAnARCNN):
             st["rois_inside_ws"] = rois_inside_ws.view(-1, 4)
             st["rois_outside_ws"] = rois_outside_ws.view(-1, 4)
         R = rois.size(1)
-        n_roi = B * R
+        n_roi = NP * R
         P = cfg.POOLING_SIZE
         fh, fw = base_hw
-        pooled, _ = self._roi_pool(plan, base, B, fh, fw, 1024, rois)  # (faster_rcnn.py:70-73) on base_feat
+        pooled, _ = self._roi_pool(plan, base, B, fh, fw, 1024, rois, group=group)  # (faster_rcnn.py:70-73) on base_feat
         st.update(rois=rois, R=R, n_roi=n_roi, pooled=pooled, plan=plan,
                   fc7=self._head_to_tail(pooled, n_roi, P, P, plan, save=ctx["l4_saved"] if ctx is not None else None))
         if ctx is not None:
@@ -155,9 +204,41 @@ class MetaRCNN(FasterRCNN):
         from .dana import DAnARCNN
         DAnARCNN._init_weights(self)
 
+    def _cache_layout(self, shot, sup_map):
+        """a set's class-attentive vector: the mean over its shots of sigmoid(mean(layer4(maxpool2(trunk))))"""
+        return dict(vec=(2048,))
+
+    def _support_set(self, sup_ims, plan, dev):
+        """the PRN (meta.py:58-62,241-251) of one support set, as the uncached eval forward runs it for one image"""
+        shot = sup_ims.size(0)
+        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan)
+        mp, mh, mw = ops.maxpool2x2s2(sup, shot, sh_, sw_, 1024)
+        att = ops.sigmoid_(self._head_to_tail(mp, shot, mh, mw, plan))
+        return dict(vec=ops.spatial_mean(att, 1, shot, 2048))
+
+    def _cached_forward(self, im_data, im_info, gt_boxes, all_cls_gt_boxes, vec, Cs, sweep):
+        """the eval forward on cached class-attentive vectors vec [B*Cs][2048]. The RPN runs on base_feat alone
+        (meta.py:65), so proposals, RoIAlign and layer4 run once per image; a sweep's 2-way heads of all Cs classes are one
+        launch (dana_meta_class_head) that writes the problems' rois / cls_prob / bbox_pred in ClassSweep's layout"""
+        st = self._stages(im_data, im_info, gt_boxes, anchor_gt_boxes=all_cls_gt_boxes)
+        B, R, n_roi, fc7 = st["B"], st["R"], st["n_roi"], st["fc7"]
+        wb, bb = self._w(self.RCNN_bbox_pred)
+        wc, bc = self._w(self.RCNN_cls_score[0])
+        bbox_pred = ops.gemm_nt(fc7, wb, n_roi, 4, 2048, shift=bb)
+        if sweep:
+            rois, cls_prob, bbox_pred = ops.meta_class_head(fc7, vec, wc, bc, st["rois"], bbox_pred, B, Cs, R)
+            return (rois, cls_prob, bbox_pred, 0, 0, 0, 0, None)
+        comb = ops.scale_rows_by_group(fc7, vec, n_roi, R, 2048)
+        score = ops.gemm_nt(comb, wc, n_roi, 2, 2048, shift=bc)
+        return (st["rois"], ops.softmax_rows_(score.clone(), n_roi, 2), bbox_pred, 0, 0, 0, 0, None)
+
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         if all_cls_gt_boxes is None:
             raise RuntimeError("meta: all_cls_gt_boxes is required (meta.py:48,65)")
+        cached, Cs = self._cached_supports(support_ims, im_data.size(0), im_data.device)
+        if cached is not None:
+            return self._cached_forward(im_data, im_info, gt_boxes, all_cls_gt_boxes, cached["vec"], Cs,
+                                        isinstance(support_ims, ClassSweep))
         training = self.training
         shot = self.n_shot
         way = self.n_way if training else 1

@@ -14,6 +14,7 @@ import torch
 import torch.nn as nn
 
 from . import ops
+from .dana import ClassSweep
 from .frcnn import FasterRCNN
 
 
@@ -50,6 +51,39 @@ class FSOD(FasterRCNN):
         from .dana import DAnARCNN
         DAnARCNN._init_weights(self)
 
+    # ---- cached support sets (encode_supports): per set, the pooled positive map and the support halves of the heads ----
+    def _cache_layout(self, shot, sup_map):
+        """pos: AvgPool2d(14, 1) of the shots' mean map (fsod.py:103-104); g_sup / corr_sup / p_sup: the support halves of
+        the global, local-correlation and patch relation heads (fsod.py:185-234)"""
+        return dict(pos=(49, 1024), g_sup=(1024,), corr_sup=(49, 1024), p_sup=(49, 256))
+
+    def _sup_global(self, support, n):
+        """global relation's support half (fsod.py:185-199): mean_49(support) . W1[:, 1024:]^T -> (m_sup, g_sup [n][1024])"""
+        d = 1024
+        w1, _ = self._w(self.global_fc_1)
+        m_sup = ops.spatial_mean(support, n, 49, d)
+        return m_sup, ops.gemm_nt(m_sup, w1.view(-1)[d:], n, d, d, ldb=2 * d)
+
+    def _sup_corr(self, support, n):
+        """local correlation's support half (fsod.py:201-216): corr_conv(support) -> [n*49][1024]"""
+        d = 1024
+        return ops.gemm_nt(support, self.corr_conv.weight.detach().view(d, d).contiguous(), n * 49, d, d)
+
+    def _sup_patch(self, support, n):
+        """patch relation's support half (fsod.py:218-234): support . W_p1[:, 1024:]^T -> [n][49*256]"""
+        d = 1024
+        wp1 = self.patch_conv_1.weight.detach().view(d // 4, 2 * d).contiguous()
+        return ops.gemm_nt(support, wp1.view(-1)[d:], n * 49, d // 4, d, ldb=2 * d)
+
+    def _support_set(self, sup_ims, plan, dev):
+        """one support set's cache tensors, with the launches of the uncached eval forward at B = 1"""
+        shot = sup_ims.size(0)
+        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan)
+        L = sh_ * sw_
+        pos = ops.avgpool(ops.spatial_mean(sup, 1, shot, L * 1024), 1, sh_, sw_, 1024, 14, 1)
+        return dict(pos=pos, g_sup=self._sup_global(pos, 1)[1], corr_sup=self._sup_corr(pos, 1),
+                    p_sup=self._sup_patch(pos, 1))
+
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         training = self.training
         shot = self.n_shot
@@ -57,14 +91,20 @@ class FSOD(FasterRCNN):
         B = im_data.size(0)
         dev = im_data.device
         plan = self._get_plan()
-        sup_ims = self._support_batch(support_ims, B, way, shot)
-        Ns = sup_ims.size(0)
+        # cached: the support sets' tensors gathered per problem (a class sweep: B*Cs problems p = b*Cs + c)
+        cached, Cs = self._cached_supports(support_ims, B, dev)
+        sweep = isinstance(support_ims, ClassSweep)
+        NP = B * Cs
+        if cached is None:
+            sup_ims = self._support_batch(support_ims, B, way, shot)
+            Ns = sup_ims.size(0)
         bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "heads"), align_only_for="fsod")
         self._ctx = None
-        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
-        if (sh_, sw_) != (20, 20):
-            raise RuntimeError("support images must be 320x320 (fsod.py:44: AvgPool2d(14) of a 20x20 map -> 7x7)")
-        L = sh_ * sw_
+        if cached is None:
+            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
+            if (sh_, sw_) != (20, 20):
+                raise RuntimeError("support images must be 320x320 (fsod.py:44: AvgPool2d(14) of a 20x20 map -> 7x7)")
+            L = sh_ * sw_
 
         def pooled_support(offset):  # mean over the shots [offset, offset+shot), then AvgPool2d(14, 1): [B][49][1024]
             m = torch.empty((B, L * 1024), dtype=torch.float32, device=dev)
@@ -72,14 +112,16 @@ class FSOD(FasterRCNN):
                 m[b:b + 1] = ops.spatial_mean(sup.view(-1)[(b * way * shot + offset) * L * 1024:], 1, shot, L * 1024)
             return ops.avgpool(m, B, sh_, sw_, 1024, 14, 1)
 
-        pos = pooled_support(0)
+        pos = pooled_support(0) if cached is None else cached["pos"]
 
         def attention_rpn_input(base, B_, fh, fw, plan_):
             if ctx is not None:
                 ctx["base"] = base
+            if sweep:  # problem p: image p / Cs's map against set p's kernel
+                return ops.depthwise_corr_grouped(base, pos, NP, fh, fw, 1024, 7, 7, Cs)
             return ops.depthwise_corr(base, pos, B_, fh, fw, 1024, 7, 7)
 
-        st = self._stages(im_data, im_info, gt_boxes, rpn_input=attention_rpn_input, ctx=ctx)
+        st = self._stages(im_data, im_info, gt_boxes, rpn_input=attention_rpn_input, ctx=ctx, group=Cs)
         R, n_roi, pooled, fc7 = st["R"], st["n_roi"], st["pooled"], st["fc7"]
         wb, bb = self._w(self.RCNN_bbox_pred)
         bbox_pred = ops.gemm_nt(fc7, wb, n_roi, 4, 2048, shift=bb)
@@ -97,22 +139,21 @@ class FSOD(FasterRCNN):
         g_roi = ops.spatial_mean(pooled, n_roi, P2, d)                       # avgpool_fc of the roi half [n][1024]
         corr_roi = ops.gemm_nt(pooled, wcc, n_roi * P2, d, d)                # corr_conv(rois) [n*49][1024]
 
-        def head(support, offset=0):  # support [B][49][1024]
+        def head(support, offset=0):  # support [NP][49][1024]; cached: the support halves come from the cache
             # global relation (fsod.py:185-199): fc1([mean(roi) | mean(support)]) = roi half + support half
-            m_sup = ops.spatial_mean(support, B, P2, d)
-            g_sup = ops.gemm_nt(m_sup, w1.view(-1)[d:], B, d, d, ldb=2 * d)
-            h1 = ops.gemm_nt(g_roi, w1, n_roi, d, d, ldb=2 * d, shift=b1, residual=ops.broadcast_rows(g_sup, B, R, d),
+            m_sup, g_sup = self._sup_global(support, NP) if cached is None else (None, cached["g_sup"])
+            h1 = ops.gemm_nt(g_roi, w1, n_roi, d, d, ldb=2 * d, shift=b1, residual=ops.broadcast_rows(g_sup, NP, R, d),
                              ldr=d, relu=True)
             h2 = ops.gemm_nt(h1, w2, n_roi, d, d, shift=b2, relu=True)
             s_g = ops.gemm_nt(h2, wg, n_roi, 2, d, shift=bg)
             # local correlation (fsod.py:201-216)
-            corr_sup = ops.gemm_nt(support, wcc, B * P2, d, d)
+            corr_sup = self._sup_corr(support, NP) if cached is None else cached["corr_sup"]
             oc, _, _ = ops.depthwise_corr(corr_roi, corr_sup, n_roi, 7, 7, d, 7, 7, maps_per_kernel=R)
             s_c = ops.gemm_nt(oc, wcs, n_roi, 2, d, shift=bcs)
             # patch relation (fsod.py:218-234)
-            p_sup = ops.gemm_nt(support, wp1.view(-1)[d:], B * P2, d // 4, d, ldb=2 * d)  # [B][49*256]
+            p_sup = self._sup_patch(support, NP) if cached is None else cached["p_sup"]  # [NP][49*256]
             x0 = ops.gemm_nt(pooled, wp1, n_roi * P2, d // 4, d, ldb=2 * d,
-                             residual=ops.broadcast_rows(p_sup, B, R, P2 * (d // 4)), ldr=d // 4, relu=True)
+                             residual=ops.broadcast_rows(p_sup, NP, R, P2 * (d // 4)), ldr=d // 4, relu=True)
             x1 = ops.avgpool(x0, n_roi, 7, 7, d // 4, 3, 1)                                    # 7x7 -> 5x5
             x2, _, _ = ops.conv2d_nhwc(x1, n_roi, 5, 5, d // 4, wp2, d // 4, 3, 3, 1, 0, relu=True)  # -> 3x3
             x3 = ops.gemm_nt(x2, wp3, n_roi * 9, d, d // 4, relu=True)

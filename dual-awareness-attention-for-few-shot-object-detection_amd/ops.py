@@ -1064,6 +1064,16 @@ def depthwise_corr(feat, kernels, n_maps, H, W, C, kh, kw, maps_per_kernel=1, fe
     return out, oh, ow
 
 
+def depthwise_corr_grouped(feat, kernels, n_maps, H, W, C, kh, kw, group, feat_stride=0):
+    """class sweep: out map p = depthwise_corr of feat map p // group with kernel p, p < n_maps (one launch)
+    -> ([n_maps*(H-kh+1)*(W-kw+1)][C], oh, ow)"""
+    oh, ow = H - kh + 1, W - kw + 1
+    out = torch.empty((n_maps * oh * ow, C), dtype=torch.float32, device=feat.device)
+    lib().call("dana_depthwise_corr_nhwc_grouped", _p(_chk(feat, "feat")), _p(_chk(kernels, "kernels")), _p(out), n_maps,
+               H, W, C, kh, kw, int(group), feat_stride, _stream())
+    return out, oh, ow
+
+
 def depthwise_corr_backward(grad_out, feat, kernels, n_maps, H, W, C, kh, kw, maps_per_kernel=1, feat_stride=0,
                             need_feat=True, grad_kernels=None):
     """adjoints of depthwise_corr: -> (grad_feat [n_maps*H*W][C] or None, grad_kernels [kernels][kh*kw][C], accumulated
@@ -1129,6 +1139,14 @@ def scale_rows_by_group(x, vec, rows, rows_per_group, channels):
     out = torch.empty((rows, channels), dtype=torch.float32, device=x.device)
     lib().call("dana_scale_rows_by_group", _p(_chk(x, "x")), _p(_chk(vec, "vec")), _p(out), rows, rows_per_group,
                channels, _stream())
+    return out
+
+
+def scale_rows_grouped(x, vec, rows, channels, group, n_blocks, ld_x=0):
+    """-> out [n_blocks*rows][channels]: row p*rows + i = x row (p // group)*rows + i (row stride ld_x) * vec[p]"""
+    out = torch.empty((n_blocks * rows, channels), dtype=torch.float32, device=x.device)
+    lib().call("dana_scale_rows_grouped", _p(_chk(x, "x")), _p(_chk(vec, "vec")), _p(out), rows, channels, ld_x,
+               int(group), n_blocks, _stream())
     return out
 
 
@@ -1427,6 +1445,19 @@ def repeat_rows_grouped(src, rows, cols, group, n_blocks, ld_src=0, out=None, ld
     lib().call("dana_repeat_rows_grouped", _p(_chk(src, "src")), _p(_chk(out, "out")), rows, cols, ld_src, ld_out,
                int(group), n_blocks, _stream())
     return out
+
+
+def meta_class_head(fc7, vec, weight, bias, rois, bbox_pred, B, C, R, K=2048):
+    """Meta R-CNN's 2-way head for each of C classes per image (one launch): fc7 [B*R][K], vec [B*C][K] ->
+    (rois [B*C, R, 5] with column 0 = p, cls_prob [B*C*R][2], bbox_pred [B*C*R][4]) for problems p = b*C + c"""
+    dev = fc7.device
+    cls_prob = torch.empty((B * C * R, 2), dtype=torch.float32, device=dev)
+    rois_out = torch.empty((B * C, R, 5), dtype=torch.float32, device=dev)
+    bbox_out = torch.empty((B * C * R, 4), dtype=torch.float32, device=dev)
+    lib().call("dana_meta_class_head", _p(_chk(fc7, "fc7")), _p(_chk(vec, "vec")), _p(_chk(weight, "weight")),
+               _p(_chk(bias, "bias")), _p(_chk(rois, "rois")), _p(_chk(bbox_pred, "bbox_pred")), _p(cls_prob), _p(rois_out),
+               _p(bbox_out), B, C, R, K, _stream())
+    return rois_out, cls_prob, bbox_out
 
 
 def rowscale_(dw, scale, rows, cols):

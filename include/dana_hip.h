@@ -186,6 +186,13 @@ int dana_repeat_rows_grouped(const float* src, float* dst, long rows, int cols, 
  * p / group times problem p's attended rows); channels % 4 == 0, 16-byte aligned rows */
 int dana_mul_rows_grouped(float* y, const float* x, long rows, int channels, long ld_y, long ld_x, int group,
                           long n_blocks, dana_stream_t stream);
+/* Meta R-CNN's class head over a class sweep (framework/meta.py:129-142 for each of C classes): for RoI row b*R + r of
+ * fc7 [B*R][K] and problem p = b*C + c, cls_prob[p*R + r] = softmax_2((fc7 row * vec[p]) . weight^T + bias) with the
+ * product rounded to fp32 (weight [2][K], vec [B*C][K]); rois [B][R][5] / bbox_pred [B*R][4] rows copied to problem p's
+ * block of rois_out [B*C][R][5] (column 0 = p) / bbox_out [B*C*R][4]. K % 4 == 0, K <= 2048 */
+int dana_meta_class_head(const float* fc7, const float* vec, const float* weight, const float* bias, const float* rois,
+                         const float* bbox_pred, float* cls_prob, float* rois_out, float* bbox_out, int B, int C, int R,
+                         int K, dana_stream_t stream);
 /* RoIAlign (dana.py:181-186, ROIAlign_cuda.cu) in NHWC with rois' column 0 a problem index: roi n reads image
  * (int)rois[n][0] / group. Arguments and outputs as dana_roi_align_forward(layout NHWC); group 1: the same bits. */
 int dana_roi_align_forward_nhwc_grouped(const float* input, const float* rois, float* output, int batch, int channels,
@@ -342,6 +349,12 @@ int dana_bn_train_backward(const float* grad_out, const float* x, const float* m
 int dana_depthwise_corr_nhwc(const float* feat, const float* kernels, float* out, long n_maps, int height, int width,
                              int channels, int kh, int kw, long maps_per_kernel, long feat_pix_stride,
                              dana_stream_t stream);
+/* class sweep of the fsod attention RPN (framework/fsod.py:109-116 per problem): out map n = the depth-wise
+ * correlation of feat map n / group with kernels[n], n < n_maps; feat [ceil(n_maps / group)][height][width][feat_pix_stride].
+ * Per-element arithmetic and order of dana_depthwise_corr_nhwc (a replicated feat map gives the same bits) */
+int dana_depthwise_corr_nhwc_grouped(const float* feat, const float* kernels, float* out, long n_maps, int height,
+                                     int width, int channels, int kh, int kw, int group, long feat_pix_stride,
+                                     dana_stream_t stream);
 /* adjoints of dana_depthwise_corr_nhwc: grad_feat [n_maps][height][width][channels] (dense; null to skip) and
  * grad_kernels [ceil(n_maps / maps_per_kernel)][kh][kw][channels] (null to skip; accumulated when accumulate_kernels) */
 int dana_depthwise_corr_backward_nhwc(const float* grad_out, const float* feat, const float* kernels, float* grad_feat,
@@ -358,6 +371,11 @@ int dana_maxpool2x2s2_backward_nhwc(const float* in, const float* grad_out, floa
 int dana_sigmoid(float* x, long n, dana_stream_t stream);
 int dana_scale_rows_by_group(const float* x, const float* group_vec, float* out, long rows, long rows_per_group,
                              int channels, dana_stream_t stream);
+/* class sweep of the fgn attention RPN (framework/fgn.py:71-73 per problem): out row p*rows + i = x row
+ * (p / group)*rows + i (row stride ld_x; 0 = channels) times vec[p], channel-wise, p < n_blocks; out dense. The product of
+ * dana_scale_rows_by_group on replicated rows (same bits); channels % 4 == 0, 16-byte aligned pointers */
+int dana_scale_rows_grouped(const float* x, const float* vec, float* out, long rows, int channels, long ld_x, int group,
+                            long n_blocks, dana_stream_t stream);
 /* PositionalEncoding.forward: dana.py:322-324; out[r] = in[r] + pe[r % length] */
 int dana_add_pe(const float* in, const float* pe, float* out, long rows, int length, int channels,
                 long in_stride, long out_stride, dana_stream_t stream);

@@ -16,6 +16,13 @@ replicated B*C cached forward (cache.select(classes * B), every image repeated C
   sweep_b1_c5 / repl_b1_c5   one image x 5 sets       sweep_b4_c5 / repl_b4_c5   four images x 5 sets
 reported as ms per (image, class), with their contraction launches and the RPN conv's launches (the split conv's two
 against the single cin-2048 conv). --only-sweep skips the other cases.
+--model meta | fsod | fgn: the sibling detector instead (eager only: launch programs and hipGraphs replay DAnA), C = 5
+sets, B = 1 and 4, in ms per (image, class), all four in the same rounds, alternated:
+  uncached   the eval forward of B images, image b against set b % C's support images (one class per image)
+  cached     the cached forward of the same B images and sets (cache.select)
+  repl       the replicated cached forward: B*C images, every image against every set
+  sweep      cache.sweep(all C sets): B images x C sets
+with their contraction launches per step (ops.PROFILE).
 The last line is the JSON record."""
 import argparse
 import json
@@ -108,12 +115,52 @@ def sweep_cases(m, in1, in4, sets5, k):
     return out
 
 
+def sibling_cases(m, name, in1, in4, sets5, k):
+    """the four cases of a sibling detector (module docstring) at B = 1 and 4 -> {case_bB_cC: record}"""
+    from dana_amd import ops
+    C = sets5.size(0)
+    classes = list(range(C))
+    cache_sel = m.encode_supports(sets5)  # (one cache per selection: select() between steps would copy the index)
+    cache_rep = m.encode_supports(sets5)
+    extra = (lambda q: [q[2]]) if name == "meta" else (lambda q: [])  # meta: all_cls_gt_boxes (meta.py:48,65)
+    out = {}
+    for B, inp in ((1, in1), (4, in4)):
+        q = inp[:4]
+        rq = [t.repeat_interleave(C, 0) for t in q]
+        sel = [b % C for b in range(B)]
+        sup = sets5[sel].contiguous()
+        cache_sel.select(sel)
+        cache_rep.select(classes * B)
+        sw = cache_sel.sweep(classes)
+        cases = {"uncached": (B, lambda q=q, sup=sup: m(*q, sup, *extra(q))),
+                 "cached": (B, lambda q=q: m(*q, cache_sel, *extra(q))),
+                 "repl": (B * C, lambda rq=rq: m(*rq, cache_rep, *extra(rq))),
+                 "sweep": (B * C, lambda q=q, sw=sw: m(*q, sw, *extra(q)))}
+        launches = {}
+        for case, (_, fn) in cases.items():
+            fn()
+            ops.PROFILE = []
+            fn()
+            torch.cuda.synchronize()
+            launches[case] = len(ops.PROFILE)
+            ops.PROFILE = None
+        ms, _ = best_of({case: fn for case, (_, fn) in cases.items()}, k)
+        for case, (n, _) in cases.items():
+            tag = "%s_b%d_c%d" % (case, B, C)
+            out[tag] = dict(ms_per_image_class=round(ms[case] / n, 4), ms_per_step=ms[case], problems=n,
+                            contraction_launches=launches[case])
+            print("%-16s %8.3f ms per (image, class)  (%.3f ms/step over %d problems; %d contraction launches)"
+                  % (tag, ms[case] / n, ms[case], n, launches[case]), flush=True)
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--height", type=int, default=600)
     ap.add_argument("--width", type=int, default=1000)
     ap.add_argument("--only-sweep", action="store_true")
+    ap.add_argument("--model", choices=["DAnA", "meta", "fsod", "fgn"], default="DAnA")
     args = ap.parse_args()
     import dana_amd
     from dana_amd import ops, postprocess as PP, synthetic as S
@@ -121,6 +168,19 @@ def main():
     from dana_amd.program import ProgramDAnA
     dev = torch.device("cuda:0")
     shot, H, W, k = 3, args.height, args.width, args.steps
+    if args.model != "DAnA":
+        m = dana_amd.get_model(args.model, pretrained=False, way=1, shot=shot, classes=["fg", "bg"])
+        tame = {"fsod": S.tame_fsod_weights, "fgn": S.tame_fgn_weights}.get(args.model, lambda sd_: sd_)
+        m.load_state_dict(tame(S.fill_state_dict(m.state_dict(), seed=5, profile="test")))
+        m.to(dev).eval()
+        in1 = [t.to(dev) for t in S.episode_inputs(1, 1, shot, H, W, seed=9)]
+        in4 = [t.to(dev) for t in S.episode_inputs(4, 1, shot, H, W, seed=10)]
+        sets5 = torch.cat([in4[4].reshape(4, shot, 3, 320, 320), in1[4].reshape(1, shot, 3, 320, 320)], 0)
+        rec = {"model": args.model, "shape": "query %dx%d, shot %d, supports 320x320" % (H, W, shot), "steps": k}
+        with torch.no_grad():
+            rec["cases"] = sibling_cases(m, args.model, in1, in4, sets5, k)
+        print(json.dumps(rec))
+        return
     m = dana_amd.get_model("DAnA", pretrained=False, use_BA_block=True, way=1, shot=shot, classes=["fg", "bg"])
     m.load_state_dict(S.fill_state_dict(m.state_dict(), seed=5, profile="test"))
     m.to(dev).eval()
