@@ -684,7 +684,11 @@ int dana_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_
   DANA_CHECK_ARG(n >= 0 && n % 4 == 0 && step >= 1, "dana_adam: n must be a multiple of 4 and step >= 1");
   if (n == 0) return DANA_OK;
   DANA_CHECK_ARG(params && grads && exp_avg && exp_avg_sq, "dana_adam: null pointer");
-  const float bc1 = 1.f - powf(beta1, (float)step), bc2 = 1.f - powf(beta2, (float)step);
+  DANA_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0,
+                 "dana_adam: buffers must be 16-byte aligned");
+  // the bias corrections in double, as torch.optim.Adam forms them: 1 - beta^step cancels, and in float 1 - 0.999^2 keeps
+  // five digits (a relative 1.5e-5, which reaches the update through sqrt(bc2))
+  const float bc1 = (float)(1.0 - pow((double)beta1, (double)step)), bc2 = (float)(1.0 - pow((double)beta2, (double)step));
   adam_kernel<<<grid_for(n / 4, 256), 256, 0, (hipStream_t)stream>>>((float4*)params, (const float4*)grads,
                                                                     (float4*)exp_avg, (float4*)exp_avg_sq, n / 4, lr, beta1,
                                                                     beta2, eps, weight_decay, grad_scale, bc1, bc2);

@@ -629,3 +629,232 @@ def test_large_lds_kernels_launch_on_every_visible_device():
             for o in outs:
                 _close(o.cpu(), ref.float())
             _close(dw.cpu(), (outs[0].cpu().double().t() @ a0.double()).float(), 2e-4)
+
+
+# ---- the options of the data-gradient and Winograd-gradient paths that only the training step reached -----------------
+def _nhwc(t):
+    """NCHW (CPU) -> [N*H*W][C] rows"""
+    return t.permute(0, 2, 3, 1).reshape(-1, t.size(1)).contiguous()
+
+
+@pytest.mark.parametrize("case", [(2, 19, 23, 64, 96, 3, 1), (3, 7, 7, 1024, 512, 3, 0), (2, 12, 16, 128, 512, 1, 0), (1, 9, 11, 64, 64, 3, 1)],
+                         ids=["3x3", "3x3-pad0-fgn-head", "1x1", "3x3-small"])
+def test_conv2d_dgrad_options_vs_fp64_autograd(dev, case):
+    """conv2d_dgrad beyond the default call, against float64 autograd through the forward statement
+    y = F.conv2d(F.relu(a), w, padding=pad) * scale (resnet.py:83-100 with a frozen BatchNorm; pad 0 on 7x7 maps is the
+    fsod / fgn head, backward.py): scale=, wd= handed in (the bits of the call that builds it), residual= (the shortcut's
+    gradient, added), mask= / mask_stride= (the ReLU adjoint of the activation in front: exactly 0 where mask <= 0, the
+    bits of the unmasked launch elsewhere), out="""
+    ops = _ops()
+    N, H, W, Cin, Cout, k, pad = case
+    g = torch.Generator().manual_seed(sum(case))
+    a = torch.randn(N, Cin, H, W, generator=g, dtype=torch.float32).double().requires_grad_(True)
+    w = (torch.randn(Cout, Cin, k, k, generator=g) / np.sqrt(Cin * k * k)).double()
+    scale = (torch.rand(Cout, generator=g) + 0.5).double()
+    xin = F.relu(a)
+    y = F.conv2d(xin, w, padding=pad) * scale.view(1, -1, 1, 1)
+    gy = torch.randn(y.shape, generator=g).double()
+    r = torch.randn(a.shape, generator=g).double()
+    xin.retain_grad()
+    y.backward(gy, retain_graph=True)
+    ref_plain = _nhwc(xin.grad)                                   # dgrad(gy) with the BN scale
+    a.grad = None
+    ((y * gy).sum() + (xin * r).sum()).backward()
+    ref_full = _nhwc(a.grad)                                      # (dgrad + residual), ReLU adjoint applied
+    M = N * H * W
+    gyd, wp, sc = _nhwc(gy).float().to(dev), ops.pack_conv_weight(w.float().to(dev)), scale.float().to(dev)
+    rd, act = _nhwc(r).float().to(dev), _nhwc(xin.detach()).float().to(dev)
+    plain = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, k, k, 1, pad, scale=sc)
+    _close(plain.cpu(), ref_plain, 2e-5)
+    wd = ops.conv2d_dgrad_weight(wp, Cout, Cin, k, k, sc)
+    assert torch.equal(ops.conv2d_dgrad(gyd, None, N, H, W, Cin, Cout, k, k, 1, pad, wd=wd), plain)
+    res = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, k, k, 1, pad, wd=wd, residual=rd)
+    _close(res.cpu(), ref_plain + _nhwc(r), 2e-5)
+    full = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, k, k, 1, pad, wd=wd, residual=rd, mask=act)
+    _close(full.cpu(), ref_full, 2e-5)
+    assert torch.equal(full, torch.where(act > 0, res, torch.zeros_like(res)))
+    masked = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, k, k, 1, pad, wd=wd, mask=act)
+    assert torch.equal(masked, torch.where(act > 0, plain, torch.zeros_like(plain)))
+    wide = torch.full((M, Cin + 32), -1.0, device=dev)            # the mask inside a wider buffer; out= given
+    wide[:, :Cin] = act
+    buf = torch.full((M + 2, Cin), -7.0, device=dev)
+    got = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, k, k, 1, pad, wd=wd, residual=rd, mask=wide, mask_stride=Cin + 32,
+                           out=buf[:M])
+    assert got.data_ptr() == buf.data_ptr() and torch.equal(buf[:M], full) and (buf[M:] == -7.0).all()
+
+
+@pytest.mark.parametrize("case", [(3, 7, 7, 1024, 512, 2), (2, 37, 25, 256, 128, 2), (2, 8, 6, 64, 64, 2)],
+                         ids=["layer4-entry-7x7", "odd-37x25", "even-8x6"])
+def test_strided_1x1_dgrad_compact_and_scatter_vs_fp64_autograd(dev, case):
+    """the strided 1x1 convs of the Caffe bottleneck (resnet.py:71 and the downsample): conv1's data gradient takes the
+    downsample branch's COMPACT gradient as residual, is scattered to the strided positions (zero elsewhere; even sizes
+    leave a last row / column that no output reads) and masked by the block input. compact_out=True followed by the
+    scatter equals the scattered call."""
+    ops = _ops()
+    N, H, W, Cin, Cout, s = case
+    g = torch.Generator().manual_seed(sum(case))
+    a = torch.randn(N, Cin, H, W, generator=g).double().requires_grad_(True)
+    w1 = (torch.randn(Cout, Cin, 1, 1, generator=g) / np.sqrt(Cin)).double()
+    wds = (torch.randn(2 * Cout, Cin, 1, 1, generator=g) / np.sqrt(Cin)).double()
+    xin = F.relu(a)
+    y1, yd = F.conv2d(xin, w1, stride=s), F.conv2d(xin, wds, stride=s)
+    g1, gd = torch.randn(y1.shape, generator=g).double(), torch.randn(yd.shape, generator=g).double()
+    ((y1 * g1).sum() + (yd * gd).sum()).backward()
+    oh, ow = y1.shape[2:]
+    g1d, gdd = _nhwc(g1).float().to(dev), _nhwc(gd).float().to(dev)
+    wp1, wpd = ops.pack_conv_weight(w1.float().to(dev)), ops.pack_conv_weight(wds.float().to(dev))
+    act = _nhwc(xin.detach()).float().to(dev)
+    cr = ops.conv2d_dgrad(gdd, wpd, N, H, W, Cin, 2 * Cout, 1, 1, s, 0, compact_out=True)
+    assert cr.shape == (N * oh * ow, Cin)
+    _close(cr.cpu(), _nhwc(F.conv_transpose2d(gd, wds)), 2e-5)    # (stride-1 adjoint of the 1x1 conv on the compact grid)
+    dx = ops.conv2d_dgrad(g1d, wp1, N, H, W, Cin, Cout, 1, 1, s, 0, residual=cr, mask=act)
+    _close(dx.cpu(), _nhwc(a.grad), 2e-5)
+    comp = ops.conv2d_dgrad(g1d, wp1, N, H, W, Cin, Cout, 1, 1, s, 0, residual=cr, compact_out=True)
+    scat = torch.full((N * H * W + 1, Cin), -7.0, device=dev)
+    ops.lib().call("dana_upsample_scatter_nhwc", comp.data_ptr(), scat.data_ptr(), act.data_ptr(), N, oh, ow, H, W, Cin, s,
+                   ops._stream())
+    assert torch.equal(scat[:N * H * W], dx) and (scat[N * H * W:] == -7.0).all()
+    unmasked = ops.conv2d_dgrad(g1d, wp1, N, H, W, Cin, Cout, 1, 1, s, 0, residual=cr)
+    assert torch.equal(dx, torch.where(act > 0, unmasked, torch.zeros_like(unmasked)))
+    v = unmasked.view(N, H, W, Cin)
+    assert torch.equal(v[:, ::s, ::s].reshape(-1, Cin), comp)
+    keep = torch.zeros(H, W, dtype=torch.bool, device=dev)
+    keep[::s, ::s] = True
+    assert (v[:, ~keep] == 0).all()
+
+
+@pytest.mark.parametrize("tile", [2, 4])
+@pytest.mark.parametrize("case", [(2, 19, 23, 256, 64), (3, 7, 9, 64, 128), (1, 12, 16, 512, 1024), (2, 5, 6, 64, 64)])
+def test_winograd_data_gradient_vs_fp64_autograd(dev, case, tile):
+    """the data gradient the model runs for its Winograd convs (backward.py _dgrad_weights): ud =
+    winograd_filter_transform(conv2d_dgrad_weight(w, scale), cin, cout, tile) fed to conv2d_dgrad(ud=...) -- the Winograd
+    FORWARD kernel on the flipped / transposed filters -- on sizes that are not tile multiples, with mask / mask_stride and
+    out=; and conv3x3_winograd(mask=...) itself: exactly 0 where mask <= 0, the unmasked launch's bits elsewhere"""
+    ops = _ops()
+    N, H, W, Cin, Cout = case
+    g = torch.Generator().manual_seed(sum(case) + tile)
+    a = torch.randn(N, Cin, H, W, generator=g).double().requires_grad_(True)
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(Cin * 9)).double()
+    scale = (torch.rand(Cout, generator=g) + 0.5).double()
+    xin = F.relu(a)
+    xin.retain_grad()
+    y = F.conv2d(xin, w, padding=1) * scale.view(1, -1, 1, 1)
+    gy = torch.randn(y.shape, generator=g).double()
+    y.backward(gy)
+    M = N * H * W
+    gyd, wp, sc = _nhwc(gy).float().to(dev), ops.pack_conv_weight(w.float().to(dev)), scale.float().to(dev)
+    act = _nhwc(xin.detach()).float().to(dev)
+    wd = ops.conv2d_dgrad_weight(wp, Cout, Cin, 3, 3, sc)
+    ud = ops.winograd_filter_transform(wd, Cin, Cout, tile)
+    assert ud.shape == ((tile + 2) ** 2, Cin, Cout)
+    plain = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, 3, 3, 1, 1, wd=wd, ud=ud)
+    _close(plain.cpu(), _nhwc(xin.grad), 1e-4)
+    direct, _, _ = ops.conv3x3_winograd(gyd, N, H, W, Cout, ud, Cin)  # ud= is the forward kernel on the gradient rows
+    assert torch.equal(plain, direct)
+    masked = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, 3, 3, 1, 1, wd=wd, ud=ud, mask=act)
+    _close(masked.cpu(), _nhwc(a.grad), 1e-4)
+    assert torch.equal(masked, torch.where(act > 0, plain, torch.zeros_like(plain)))
+    wide = torch.full((M, Cin + 16), -1.0, device=dev)
+    wide[:, :Cin] = act
+    buf = torch.full((M + 2, Cin), -7.0, device=dev)
+    got = ops.conv2d_dgrad(gyd, wp, N, H, W, Cin, Cout, 3, 3, 1, 1, wd=wd, ud=ud, mask=wide, mask_stride=Cin + 16, out=buf[:M])
+    assert got.data_ptr() == buf.data_ptr() and torch.equal(buf[:M], masked) and (buf[M:] == -7.0).all()
+    # the forward conv with a mask (scale, shift and ReLU in the same epilogue)
+    u = ops.winograd_filter_transform(wp, Cout, Cin, tile)
+    xd, shift = _nhwc(a.detach()).float().to(dev), torch.randn(Cout, generator=g).to(dev)
+    mk = torch.randn(M, Cout + 8, generator=g).to(dev)
+    for relu in (False, True):
+        free, _, _ = ops.conv3x3_winograd(xd, N, H, W, Cin, u, Cout, scale=sc, shift=shift, relu=relu)
+        msk, _, _ = ops.conv3x3_winograd(xd, N, H, W, Cin, u, Cout, scale=sc, shift=shift, relu=relu, mask=mk, mask_stride=Cout + 8)
+        assert torch.equal(msk, torch.where(mk[:, :Cout] > 0, free, torch.zeros_like(free)))
+
+
+@pytest.mark.parametrize("case", [(2, 19, 23, 3, 10, 10, 64, 64), (1, 12, 16, 4, 20, 20, 256, 256), (2, 5, 7, 1, 3, 2, 128, 64)])
+def test_winograd_dual_dgrad_is_two_single_launches(dev, case):
+    """conv3x3_winograd_dual_dgrad (the merged [query | support] 3x3 data gradient of an identity bottleneck: one batched
+    plane GEMM) gives the bits of the two single launches, masked and unmasked, and float64 autograd's gradient"""
+    ops = _ops()
+    n0, h0, w0, n1, h1, w1, Cin, Cout = case
+    g = torch.Generator().manual_seed(sum(case))
+    w = (torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(Cin * 9)).double()
+    wp = ops.pack_conv_weight(w.float().to(dev))
+    ud = ops.winograd_filter_transform(ops.conv2d_dgrad_weight(wp, Cout, Cin, 3, 3), Cin, Cout, 4)
+    gys, acts, refs = [], [], []
+    for n, h, w_ in ((n0, h0, w0), (n1, h1, w1)):
+        a = torch.randn(n, Cin, h, w_, generator=g).double().requires_grad_(True)
+        y = F.conv2d(F.relu(a), w, padding=1)
+        gy = torch.randn(y.shape, generator=g).double()
+        y.backward(gy)
+        gys.append(_nhwc(gy).float())
+        acts.append(_nhwc(F.relu(a.detach())).float())
+        refs.append(_nhwc(a.grad))
+    gyd, act = torch.cat(gys).to(dev), torch.cat(acts).to(dev)
+    m0 = n0 * h0 * w0
+    for mask in (None, act):
+        s0, _, _ = ops.conv3x3_winograd(gyd, n0, h0, w0, Cout, ud, Cin, mask=mask)
+        s1, _, _ = ops.conv3x3_winograd(gyd[m0:], n1, h1, w1, Cout, ud, Cin, mask=mask[m0:] if mask is not None else None)
+        buf = torch.full((gyd.size(0) + 2, Cin), -7.0, device=dev)
+        d = ops.conv3x3_winograd_dual_dgrad(gyd, n0, h0, w0, n1, h1, w1, Cout, ud, Cin, mask=mask, out=buf[:gyd.size(0)])
+        assert torch.equal(d[:m0], s0) and torch.equal(d[m0:], s1) and (buf[gyd.size(0):] == -7.0).all()
+    _close(d.cpu(), torch.cat(refs), 1e-4)
+
+
+@pytest.mark.parametrize("case", [(2, 38, 63, 256, 256), (16, 4, 4, 512, 128), (1, 12, 17, 128, 64), (2, 5, 3, 64, 72)])
+def test_winograd_weight_gradient_from_kept_v_planes(dev, case):
+    """conv3x3_wgrad_winograd(v=kept): the V planes a forward F(4x4,3x3) launch left in its workspace (keep_v) replace the
+    weight gradient's own input transform -- against float64 autograd and against the x path, with row scale + accumulate"""
+    ops = _ops()
+    N, H, W, Cin, Cout = case
+    g = torch.Generator().manual_seed(sum(case) + 1)
+    x = torch.randn(N, Cin, H, W, generator=g)
+    wz = (torch.randn(Cout, Cin, 3, 3, generator=g) / np.sqrt(Cin * 9)).double().requires_grad_(True)
+    gy = torch.randn(N, Cout, H, W, generator=g)
+    scale = torch.rand(Cout, generator=g) + 0.5
+    init = torch.randn(Cout, 9 * Cin, generator=g)
+    F.conv2d(x.double(), wz, padding=1).backward(gy.double())
+    ref = wz.grad.permute(0, 2, 3, 1).reshape(Cout, 9 * Cin)
+    xd, gd = _nhwc(x).to(dev), _nhwc(gy).to(dev)
+    u = ops.winograd_filter_transform(ops.pack_conv_weight(wz.detach().float().to(dev)), Cout, Cin, 4)
+    keep = []
+    ops.conv3x3_winograd(xd, N, H, W, Cin, u, Cout, relu=True, keep_v=keep)
+    assert len(keep) == 1
+    from_v = ops.conv3x3_wgrad_winograd(gd, xd, N, H, W, Cin, Cout, v=keep[0])
+    _close(from_v.cpu(), ref, 2e-4)
+    from_x = ops.conv3x3_wgrad_winograd(gd, xd, N, H, W, Cin, Cout)
+    _close(from_v.cpu(), from_x.cpu(), 2e-4)
+    acc = init.clone().to(dev)
+    ops.conv3x3_wgrad_winograd(gd, xd, N, H, W, Cin, Cout, out=acc, row_scale=scale.to(dev), v=keep[0])
+    _close(acc.cpu(), ref * scale.double().view(-1, 1) + init.double(), 2e-4)
+
+
+@pytest.mark.parametrize("m,n,k,ldx,ldg,half", [(384, 256, 1024, 2048, 256, False), (256, 1024, 1024, 1024, 1024, True),
+                                                (77, 64, 128, 192, 72, True), (1, 4, 64, 64, 4, False), (1000, 72, 512, 512, 80, False)])
+def test_linear_backward_options_vs_fp64_autograd(dev, m, n, k, ldx, ldg, half):
+    """linear_backward against float64 autograd through F.linear(x[:, :k], w, b): x and g rows inside wider buffers (ldx,
+    ldg), the weight a column half w1[:, d:] of a [d][2d] matrix (ldw; fsod.py:145), the data gradient ACCUMULATED into
+    dx_out with its own row stride, need_dx=False, need_dw=False"""
+    ops = _ops()
+    gen = torch.Generator().manual_seed(m + n + k)
+    x = torch.randn(m, ldx, generator=gen)
+    gbuf = torch.randn(m, ldg, generator=gen)
+    wfull = torch.randn(n, 2 * k if half else k, generator=gen) / np.sqrt(k)
+    ldw = wfull.size(1)
+    wv = wfull[:, k:] if half else wfull
+    xd = x[:, :k].double().requires_grad_(True)
+    wdd = wv.double().requires_grad_(True)
+    bd = torch.zeros(n, dtype=torch.float64, requires_grad=True)
+    F.linear(xd, wdd, bd).backward(gbuf[:, :n].double())
+    xdev, gdev, wdev = x.to(dev), gbuf.to(dev), wfull.to(dev)
+    wptr = wdev.view(-1)[k:] if half else wdev
+    dw, db, dx = ops.linear_backward(gdev, xdev, wptr, m, n, k, ldx=ldx, ldg=ldg, ldw=ldw)
+    _close(dw.cpu(), wdd.grad, 2e-5)
+    _close(db.cpu(), bd.grad, 2e-5)
+    _close(dx.cpu(), xd.grad, 2e-5)
+    dw2, db2, none = ops.linear_backward(gdev, xdev, wptr, m, n, k, ldx=ldx, ldg=ldg, ldw=ldw, need_dx=False)
+    assert none is None and torch.equal(dw2, dw) and torch.equal(db2, db)
+    init = torch.randn(m, k + 64, generator=gen)
+    acc = init.clone().to(dev)
+    nw, nb, dx3 = ops.linear_backward(gdev, xdev, wptr, m, n, k, ldx=ldx, ldg=ldg, ldw=ldw, need_dw=False, dx_out=acc, dx_ld=k + 64)
+    assert nw is None and nb is None and dx3.data_ptr() == acc.data_ptr()
+    _close(acc[:, :k].cpu(), init[:, :k].double() + xd.grad, 2e-5)
+    assert torch.equal(acc[:, k:].cpu(), init[:, k:])
