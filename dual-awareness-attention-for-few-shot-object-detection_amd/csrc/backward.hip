@@ -483,6 +483,99 @@ sgd_momentum_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4
   }
 }
 
+// ---- optimizer scalars in device memory (include/dana_hip.h: hyper[] from the host, state[] from dana_optim_prepare) ----
+constexpr int OPT_LR = 0, OPT_GRAD_SCALE = 4, OPT_CLIP = 5, OPT_BC1 = 6, OPT_BC2 = 7;  // hyper[]
+constexpr int OPT_SQNORM = 0, OPT_TOTAL = 1, OPT_COEF = 2, OPT_GS_EFF = 3;             // state[]
+constexpr int SQN_THREADS = 256, SQN_MAX_BLOCKS = 2048;
+
+// a wave's 64 values, then the block's 4 wave sums, in a fixed order -> the total in thread 0
+__device__ __forceinline__ double block_sum_f64(double s, double* wave_sums) {
+#pragma unroll
+  for (int off = 32; off > 0; off >>= 1) s += __shfl_down(s, off, 64);
+  if ((threadIdx.x & 63) == 0) wave_sums[threadIdx.x >> 6] = s;
+  __syncthreads();
+  return (wave_sums[0] + wave_sums[1]) + (wave_sums[2] + wave_sums[3]);
+}
+
+// sum of g^2, one double per block. Memory-bound (one float4 load per 4 FMAs); the fp32 chains are short by construction
+// (four per thread, n / (4 * 4 * 256 * grid) FMAs each), everything behind them is double.
+__global__ void __launch_bounds__(SQN_THREADS)
+grad_sqnorm_kernel(const float4* __restrict__ g, long n4, double* __restrict__ partial) {
+  __shared__ double wave_sums[SQN_THREADS / 64];
+  float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+#pragma unroll 4
+  for (long i = (long)blockIdx.x * SQN_THREADS + threadIdx.x; i < n4; i += (long)SQN_THREADS * gridDim.x) {
+    const float4 v = g[i];
+    a0 = fmaf(v.x, v.x, a0);
+    a1 = fmaf(v.y, v.y, a1);
+    a2 = fmaf(v.z, v.z, a2);
+    a3 = fmaf(v.w, v.w, a3);
+  }
+  const double s = block_sum_f64(((double)a0 + (double)a1) + ((double)a2 + (double)a3), wave_sums);
+  if (threadIdx.x == 0) partial[blockIdx.x] = s;
+}
+
+// one block: all partials -> state[] (the clipping coefficient of net_utils.py:37-48 without the host's .item())
+__global__ void __launch_bounds__(SQN_THREADS)
+optim_prepare_kernel(const double* __restrict__ partial, long count, const float* __restrict__ hyper,
+                     float* __restrict__ state) {
+  __shared__ double wave_sums[SQN_THREADS / 64];
+  double s = 0.0;
+  for (long i = threadIdx.x; i < count; i += SQN_THREADS) s += partial[i];
+  s = block_sum_f64(s, wave_sums);
+  if (threadIdx.x == 0) {
+    const float gs = hyper[OPT_GRAD_SCALE], clip = hyper[OPT_CLIP];
+    const double total = (double)gs * sqrt(s);
+    const float coef = (clip > 0.f && total > (double)clip) ? (float)((double)clip / total) : 1.f;
+    state[OPT_SQNORM] = (float)s;
+    state[OPT_TOTAL] = (float)total;
+    state[OPT_COEF] = coef;
+    state[OPT_GS_EFF] = gs * coef;
+  }
+}
+
+// adam_kernel with lr, grad_scale and the bias corrections read from the control block
+__global__ void __launch_bounds__(256)
+adam_ctl_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ m, float4* __restrict__ v, long n4,
+                const float* __restrict__ hyper, const float* __restrict__ state, int group, float b1, float b2, float eps,
+                float wd) {
+  const float lr = hyper[OPT_LR + group], gs = state[OPT_GS_EFF], bc1 = hyper[OPT_BC1], bc2 = hyper[OPT_BC2];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)blockDim.x * gridDim.x) {
+    float4 pv = p[i], mv = m[i], vv = v[i];
+    const float4 gv = g[i];
+    adam1(pv.x, gv.x, mv.x, vv.x, lr, b1, b2, eps, wd, gs, bc1, bc2);
+    adam1(pv.y, gv.y, mv.y, vv.y, lr, b1, b2, eps, wd, gs, bc1, bc2);
+    adam1(pv.z, gv.z, mv.z, vv.z, lr, b1, b2, eps, wd, gs, bc1, bc2);
+    adam1(pv.w, gv.w, mv.w, vv.w, lr, b1, b2, eps, wd, gs, bc1, bc2);
+    p[i] = pv;
+    m[i] = mv;
+    v[i] = vv;
+  }
+}
+
+// sgd_momentum_kernel with lr and grad_scale read from the control block
+__global__ void __launch_bounds__(256)
+sgd_momentum_ctl_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ buf, long n4,
+                        const float* __restrict__ hyper, const float* __restrict__ state, int group, float momentum,
+                        float wd, int first) {
+  const float lr = hyper[OPT_LR + group], grad_scale = state[OPT_GS_EFF];
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += (long)blockDim.x * gridDim.x) {
+    float4 pv = p[i];
+    const float4 gv = g[i];
+    float4 b = first ? make_float4(0.f, 0.f, 0.f, 0.f) : buf[i];
+    b.x = momentum * b.x + (gv.x * grad_scale + wd * pv.x);
+    b.y = momentum * b.y + (gv.y * grad_scale + wd * pv.y);
+    b.z = momentum * b.z + (gv.z * grad_scale + wd * pv.z);
+    b.w = momentum * b.w + (gv.w * grad_scale + wd * pv.w);
+    pv.x -= lr * b.x;
+    pv.y -= lr * b.y;
+    pv.z -= lr * b.z;
+    pv.w -= lr * b.w;
+    buf[i] = b;
+    p[i] = pv;
+  }
+}
+
 // adjoint of dana_rowdot (nn.Linear(dim, 1)): partial[chunk][c] = sum_r dl[r] * x[r][c]  (-> dw by colsum_final)
 // and, when dx is given, dx[r][c] += dl[r] * w[c].
 __global__ void __launch_bounds__(256)
@@ -707,6 +800,95 @@ int dana_sgd_momentum(float* params, const float* grads, float* momentum_buf, lo
                                                                             (float4*)momentum_buf, n / 4, lr, momentum,
                                                                             weight_decay, grad_scale, first_step);
   DANA_CHECK_LAUNCH("dana_sgd_momentum");
+  return DANA_OK;
+}
+
+int dana_optim_pack_hyper(float* hyper_host, const float* lrs, int groups, float grad_scale, float clip_norm, float beta1,
+                          float beta2, int step) {
+  DANA_CHECK_ARG(hyper_host && lrs, "dana_optim_pack_hyper: null pointer");
+  DANA_CHECK_ARG(groups >= 1 && groups <= DANA_OPTIM_MAX_GROUPS, "dana_optim_pack_hyper: %d parameter groups (1..%d)", groups,
+                 DANA_OPTIM_MAX_GROUPS);
+  DANA_CHECK_ARG(clip_norm >= 0.f, "dana_optim_pack_hyper: clip_norm must be >= 0 (0 = no clipping), got %g", (double)clip_norm);
+  DANA_CHECK_ARG(grad_scale > 0.f && step >= 1, "dana_optim_pack_hyper: grad_scale must be > 0 and step >= 1");
+  for (int k = 0; k < DANA_OPTIM_MAX_GROUPS; ++k) hyper_host[OPT_LR + k] = k < groups ? lrs[k] : 0.f;
+  hyper_host[OPT_GRAD_SCALE] = grad_scale;
+  hyper_host[OPT_CLIP] = clip_norm;
+  // (the expressions of dana_adam)
+  hyper_host[OPT_BC1] = (float)(1.0 - pow((double)beta1, (double)step));
+  hyper_host[OPT_BC2] = (float)(1.0 - pow((double)beta2, (double)step));
+  return DANA_OK;
+}
+
+static int sqnorm_grid(long n) {
+  const long g = (n / 4 + SQN_THREADS - 1) / SQN_THREADS;
+  return (int)(g > SQN_MAX_BLOCKS ? SQN_MAX_BLOCKS : g);
+}
+
+size_t dana_grad_sqnorm_workspace_bytes(long n) {
+  if (n <= 0) return 0;
+  return (size_t)sqnorm_grid((n + 3) / 4 * 4) * sizeof(double);
+}
+
+int dana_grad_sqnorm(const float* grads, long n, void* partials, size_t partials_bytes, dana_stream_t stream) {
+  DANA_CHECK_ARG(n >= 0 && n % 4 == 0, "dana_grad_sqnorm: n must be a multiple of 4 (pad the flat segment)");
+  if (n == 0) return DANA_OK;
+  DANA_CHECK_ARG(grads && partials, "dana_grad_sqnorm: null pointer");
+  DANA_CHECK_ARG(((uintptr_t)grads & 15) == 0 && ((uintptr_t)partials & 7) == 0,
+                 "dana_grad_sqnorm: grads must be 16-byte aligned, partials 8-byte aligned");
+  const size_t need = dana_grad_sqnorm_workspace_bytes(n);
+  if (partials_bytes < need) {
+    dana_set_error("dana_grad_sqnorm: workspace %zu < %zu", partials_bytes, need);
+    return DANA_ERR_WORKSPACE;
+  }
+  grad_sqnorm_kernel<<<sqnorm_grid(n), SQN_THREADS, 0, (hipStream_t)stream>>>((const float4*)grads, n / 4,
+                                                                             (double*)partials);
+  DANA_CHECK_LAUNCH("dana_grad_sqnorm");
+  return DANA_OK;
+}
+
+int dana_optim_prepare(const void* partials, long count, const float* hyper, float* state, dana_stream_t stream) {
+  DANA_CHECK_ARG(count >= 0 && (count == 0 || partials), "dana_optim_prepare: null partials or count < 0");
+  DANA_CHECK_ARG(hyper && state, "dana_optim_prepare: null pointer");
+  DANA_CHECK_ARG(((uintptr_t)partials & 7) == 0 && (((uintptr_t)hyper | (uintptr_t)state) & 3) == 0,
+                 "dana_optim_prepare: partials must be 8-byte aligned, hyper / state 4-byte aligned");
+  optim_prepare_kernel<<<1, SQN_THREADS, 0, (hipStream_t)stream>>>((const double*)partials, count, hyper, state);
+  DANA_CHECK_LAUNCH("dana_optim_prepare");
+  return DANA_OK;
+}
+
+int dana_sgd_momentum_ctl(float* params, const float* grads, float* momentum_buf, long n, const float* hyper,
+                          const float* state, int group, float momentum, float weight_decay, int first_step,
+                          dana_stream_t stream) {
+  DANA_CHECK_ARG(n >= 0 && n % 4 == 0, "dana_sgd_momentum_ctl: n must be a multiple of 4 (pad the flat segment)");
+  DANA_CHECK_ARG(group >= 0 && group < DANA_OPTIM_MAX_GROUPS, "dana_sgd_momentum_ctl: group %d out of range (0..%d)", group,
+                 DANA_OPTIM_MAX_GROUPS - 1);
+  if (n == 0) return DANA_OK;
+  DANA_CHECK_ARG(params && grads && momentum_buf && hyper && state, "dana_sgd_momentum_ctl: null pointer");
+  DANA_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)momentum_buf) & 15) == 0 &&
+                     (((uintptr_t)hyper | (uintptr_t)state) & 3) == 0,
+                 "dana_sgd_momentum_ctl: buffers must be 16-byte aligned (hyper / state: 4-byte)");
+  sgd_momentum_ctl_kernel<<<grid_for(n / 4, 256), 256, 0, (hipStream_t)stream>>>(
+      (float4*)params, (const float4*)grads, (float4*)momentum_buf, n / 4, hyper, state, group, momentum, weight_decay,
+      first_step);
+  DANA_CHECK_LAUNCH("dana_sgd_momentum_ctl");
+  return DANA_OK;
+}
+
+int dana_adam_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, const float* hyper,
+                  const float* state, int group, float beta1, float beta2, float eps, float weight_decay,
+                  dana_stream_t stream) {
+  DANA_CHECK_ARG(n >= 0 && n % 4 == 0, "dana_adam_ctl: n must be a multiple of 4 (pad the flat segment)");
+  DANA_CHECK_ARG(group >= 0 && group < DANA_OPTIM_MAX_GROUPS, "dana_adam_ctl: group %d out of range (0..%d)", group,
+                 DANA_OPTIM_MAX_GROUPS - 1);
+  if (n == 0) return DANA_OK;
+  DANA_CHECK_ARG(params && grads && exp_avg && exp_avg_sq && hyper && state, "dana_adam_ctl: null pointer");
+  DANA_CHECK_ARG((((uintptr_t)params | (uintptr_t)grads | (uintptr_t)exp_avg | (uintptr_t)exp_avg_sq) & 15) == 0 &&
+                     (((uintptr_t)hyper | (uintptr_t)state) & 3) == 0,
+                 "dana_adam_ctl: buffers must be 16-byte aligned (hyper / state: 4-byte)");
+  adam_ctl_kernel<<<grid_for(n / 4, 256), 256, 0, (hipStream_t)stream>>>((float4*)params, (const float4*)grads,
+                                                                        (float4*)exp_avg, (float4*)exp_avg_sq, n / 4, hyper,
+                                                                        state, group, beta1, beta2, eps, weight_decay);
+  DANA_CHECK_LAUNCH("dana_adam_ctl");
   return DANA_OK;
 }
 

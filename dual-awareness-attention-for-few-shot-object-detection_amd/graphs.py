@@ -129,14 +129,16 @@ class GraphedTrainer:
         gt = GraphedTrainer(trainer, *example_inputs)
         out = gt.step(*inputs)          # the model's 8-tuple (static tensors)
 
-    SGD only (train.py's default; Adam's bias correction is a per-step launch parameter). The learning rate is baked
-    in: call `recapture()` after `trainer.adjust_learning_rate`. The graphs re-derive every weight-dependent tensor
-    (Winograd-domain filters, data-gradient weights, the merged RPN head) from the live flat parameter buffer on every
-    replay, so the optimizer's in-place updates are picked up without re-capturing."""
+    SGD or Adam, with or without `Trainer(clip_norm=...)`: the graphs hold the `*_ctl` optimizer kernels, which read the
+    learning rate, 1 / world size, Adam's bias corrections and the clipping coefficient from the trainer's control block in
+    device memory; `step()` refreshes it (`trainer.upload_hyper()`) in front of the first replay, outside any capture. So
+    `trainer.adjust_learning_rate`, or a schedule assigned to `trainer.lr`, takes effect on the next `step()` with the same
+    graphs; `recapture()` is only needed after what a capture really bakes in (shapes, cfg, mode, momentum / weight decay /
+    clip on-off). The graphs re-derive every weight-dependent tensor (Winograd-domain filters, data-gradient weights, the
+    merged RPN head) from the live flat parameter buffer on every replay, so the optimizer's in-place updates are picked up
+    without re-capturing."""
 
     def __init__(self, trainer, *example_inputs, warmup=2):
-        if trainer.optimizer != "sgd":
-            raise RuntimeError("GraphedTrainer: SGD only (Adam's step count is a launch parameter)")
         self.trainer = trainer
         self.model = trainer.model
         if not hasattr(self.model, "_forward_gen"):
@@ -153,7 +155,8 @@ class GraphedTrainer:
         snap = None
         if warmup > 0:
             import numpy as _np
-            snap = ([fb.params.clone() for fb, _, _ in trainer.groups], [b.clone() for b in trainer.bufs], trainer.steps,
+            snap = ([fb.params.clone() for fb, _, _ in trainer.groups],
+                    [b.clone() for b in trainer.bufs + (trainer.bufs2 or [])], trainer.steps,
                     self.model._rng_calls, _np.random.get_state())  # (host-RNG mode draws np.random in the warm-up too)
         with ops.on_stream(self.stream):
             for _ in range(warmup):
@@ -162,7 +165,7 @@ class GraphedTrainer:
         if snap is not None:
             for (fb, _, _), p0 in zip(trainer.groups, snap[0]):
                 fb.params.copy_(p0)
-            for b, b0 in zip(trainer.bufs, snap[1]):
+            for b, b0 in zip(trainer.bufs + (trainer.bufs2 or []), snap[1]):
                 b.copy_(b0)
             trainer.steps, self.model._rng_calls = snap[2], snap[3]
             _np.random.set_state(snap[4])
@@ -266,11 +269,10 @@ class GraphedTrainer:
         ops.cur_stream().wait_stream(self.stream)
 
     def _sgd(self):
-        tr = self.trainer
-        for (fb, lr_mult, wd), buf in zip(tr.groups, tr.bufs):
-            # first_step=False: with a zero momentum buffer  buf = m * 0 + g  IS torch.optim.SGD's first step
-            ops.sgd_momentum_(fb.params, fb.grads, buf, tr.lr * lr_mult, tr.momentum, wd, grad_scale=1.0 / fb.world,
-                              first_step=False)
+        # (norm pass + clipping coefficient,) one update per group, scalars from the control block; multi-rank this is the
+        # last graph, behind every bucket's sum. first_step=False: with a zero momentum buffer  buf = m * 0 + g  IS
+        # torch.optim.SGD's first step
+        self.trainer._ctl_update(first_step=False)
 
     def _backward_until_cut(self, ctx, collective):
         """single rank: the whole backward + SGD into the current capture (returns None). Multi-rank: the backward up to
@@ -291,6 +293,7 @@ class GraphedTrainer:
         works = []
         last = len(self.graphs) - 1
         cur = ops.cur_stream()
+        tr.upload_hyper()  # this iteration's learning rate / step count: data the captured optimizer reads
         if self.g_anchor is not None:
             self.side.wait_stream(cur)
             with ops.on_stream(self.side):

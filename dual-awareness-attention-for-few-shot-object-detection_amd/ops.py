@@ -4,6 +4,7 @@ PyTorch is used here only for device memory and streams: every function hands ra
 and the current HIP stream to a hand-written gfx950 kernel. Non-CUDA tensors are rejected -- there
 is no CPU fallback on the product path.
 """
+import ctypes
 import time as _time
 
 import torch
@@ -1622,4 +1623,57 @@ def adam_(params, grads, exp_avg, exp_avg_sq, lr, step, beta1=0.9, beta2=0.999, 
     lib().call("dana_adam", _p(_chk(params, "params")), _p(_chk(grads, "grads")), _p(_chk(exp_avg, "exp_avg")),
                _p(_chk(exp_avg_sq, "exp_avg_sq")), params.numel(), float(lr), float(beta1), float(beta2), float(eps),
                float(weight_decay), float(grad_scale), int(step), _stream())
+    return params
+
+
+# ---- optimizer scalars in device memory (include/dana_hip.h: the control block of the *_ctl updates) --------------------
+OPTIM_MAX_GROUPS, OPTIM_HYPER_FLOATS, OPTIM_STATE_FLOATS = 4, 8, 4
+OPTIM_TOTAL_NORM = 1  # state[1]: grad_scale * sqrt(sum g^2), the norm before clipping
+
+
+def optim_pack_hyper(hyper_host, lrs, grad_scale, clip_norm=0.0, betas=(0.0, 0.0), step=1):
+    """fill the HOST tensor hyper_host (OPTIM_HYPER_FLOATS fp32, pinned or not) with the host-written half of the control
+    block; betas (0, 0) = SGD. Host only: no launch, nothing for a program to record."""
+    if hyper_host.is_cuda or hyper_host.dtype != torch.float32 or hyper_host.numel() < OPTIM_HYPER_FLOATS:
+        raise RuntimeError("hyper_host must be a host float32 tensor of %d elements" % OPTIM_HYPER_FLOATS)
+    arr = (ctypes.c_float * len(lrs))(*[float(x) for x in lrs])
+    rc = lib().fn["dana_optim_pack_hyper"](hyper_host.data_ptr(), ctypes.cast(arr, ctypes.c_void_p), len(lrs),
+                                           float(grad_scale), float(clip_norm), float(betas[0]), float(betas[1]), int(step))
+    if rc != 0:
+        raise DanaError("dana_optim_pack_hyper failed (%d): %s" % (rc, lib().cdll.dana_last_error().decode()))
+    return hyper_host
+
+
+def grad_sqnorm_workspace(n):
+    """number of double partials dana_grad_sqnorm writes for a segment of n floats"""
+    return lib().query("dana_grad_sqnorm_workspace_bytes", int(n)) // 8
+
+
+def grad_sqnorm_(grads, partials):
+    """sum of g^2 over one flat fp32 segment (numel % 4 == 0) -> grad_sqnorm_workspace(numel) float64 partials"""
+    lib().call("dana_grad_sqnorm", _p(_chk(grads, "grads")), grads.numel(), _p(_chk(partials, "partials", torch.float64)),
+               partials.numel() * 8, _stream())
+    return partials
+
+
+def optim_prepare_(partials, hyper, state):
+    """all groups' partials (float64, one group behind the other) + hyper -> state: sqnorm, total_norm, coef, gs_eff"""
+    lib().call("dana_optim_prepare", _p(_chk(partials, "partials", torch.float64)), partials.numel(), _p(_chk(hyper, "hyper")),
+               _p(_chk(state, "state")), _stream())
+    return state
+
+
+def sgd_momentum_ctl_(params, grads, buf, hyper, state, group, momentum, weight_decay, first_step=False):
+    """sgd_momentum_ with lr = hyper[group] and grad_scale = state's gs_eff read on the device"""
+    lib().call("dana_sgd_momentum_ctl", _p(_chk(params, "params")), _p(_chk(grads, "grads")), _p(_chk(buf, "buf")),
+               params.numel(), _p(_chk(hyper, "hyper")), _p(_chk(state, "state")), int(group), float(momentum),
+               float(weight_decay), int(bool(first_step)), _stream())
+    return params
+
+
+def adam_ctl_(params, grads, exp_avg, exp_avg_sq, hyper, state, group, beta1=0.9, beta2=0.999, eps=1e-8, weight_decay=0.0):
+    """adam_ with lr = hyper[group], grad_scale = state's gs_eff and the bias corrections of hyper read on the device"""
+    lib().call("dana_adam_ctl", _p(_chk(params, "params")), _p(_chk(grads, "grads")), _p(_chk(exp_avg, "exp_avg")),
+               _p(_chk(exp_avg_sq, "exp_avg_sq")), params.numel(), _p(_chk(hyper, "hyper")), _p(_chk(state, "state")),
+               int(group), float(beta1), float(beta2), float(eps), float(weight_decay), _stream())
     return params

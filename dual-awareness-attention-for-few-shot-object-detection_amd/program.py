@@ -474,17 +474,21 @@ class ProgramDAnA:
 
 
 class ProgramTrainer:
-    """Trainer.step (train.py:125-143: zero_grad, forward, summed loss, backward, SGD) as two launch programs around the one
-    host round trip. Multi-rank: the bucket all-reduces are host callbacks INSIDE the second program, issued where the eager
-    backward issues them (no cut of the backward is needed, unlike the hipGraph form). SGD only; the learning rate is baked
-    in: `rerecord()` after `trainer.adjust_learning_rate`.
+    """Trainer.step (train.py:125-143: zero_grad, forward, summed loss, backward, optimizer) as two launch programs around
+    the one host round trip. Multi-rank: the bucket all-reduces are host callbacks INSIDE the second program, issued where
+    the eager backward issues them (no cut of the backward is needed, unlike the hipGraph form).
+
+    SGD or Adam, with or without `Trainer(clip_norm=...)`: the programs hold the `*_ctl` optimizer kernels, which read the
+    learning rate, 1 / world size, Adam's bias corrections and the clipping coefficient from the trainer's control block in
+    device memory; `step()` refreshes it (`trainer.upload_hyper()`) in front of the first program. So
+    `trainer.adjust_learning_rate` -- or any per-iteration schedule assigned to `trainer.lr` -- takes effect on the next
+    `step()` with the same programs; `rerecord()` is only needed after what a recording really bakes in (shapes, cfg, mode,
+    momentum / weight decay / clip on-off).
 
         pt = ProgramTrainer(trainer, *example_inputs)
         out = pt.step(*inputs)          # the model's 8-tuple (static tensors)"""
 
     def __init__(self, trainer, *example_inputs, warmup=2):
-        if trainer.optimizer != "sgd":
-            raise RuntimeError("ProgramTrainer: SGD only (Adam's step count is a launch parameter)")
         self.trainer, self.model = trainer, trainer.model
         if not hasattr(self.model, "_forward_gen"):
             raise RuntimeError("ProgramTrainer drives DAnARCNN (the siblings train eagerly)")
@@ -493,14 +497,14 @@ class ProgramTrainer:
         snap = None
         if warmup > 0:  # eager warm-up iterations must not move the training trajectory (as in GraphedTrainer)
             import numpy as _np
-            snap = ([fb.params.clone() for fb, _, _ in trainer.groups], [b.clone() for b in trainer.bufs], trainer.steps,
-                    _np.random.get_state())
+            snap = ([fb.params.clone() for fb, _, _ in trainer.groups],
+                    [b.clone() for b in trainer.bufs + (trainer.bufs2 or [])], trainer.steps, _np.random.get_state())
             for _ in range(warmup):
                 trainer.step(*self.inputs)
             torch.cuda.synchronize(dev)
             for (fb, _, _), p0 in zip(trainer.groups, snap[0]):
                 fb.params.copy_(p0)
-            for b, b0 in zip(trainer.bufs, snap[1]):
+            for b, b0 in zip(trainer.bufs + (trainer.bufs2 or []), snap[1]):
                 b.copy_(b0)
             trainer.steps = snap[2]
             _np.random.set_state(snap[3])
@@ -515,10 +519,12 @@ class ProgramTrainer:
         tr, model = self.trainer, self.model
         dev = self.inputs[0].device
         import numpy as _np
-        # the recording IS an eager iteration (its launches really run): parameters, momentum, the step count and the host
+        # the recording IS an eager iteration (its launches really run): parameters, momentum / both Adam moments and the host
         # RNG are put back behind it, so that constructing the runner does not move the training trajectory
         torch.cuda.synchronize(dev)
-        snap = ([fb.params.clone() for fb, _, _ in tr.groups], [b.clone() for b in tr.bufs], _np.random.get_state())
+        snap = ([fb.params.clone() for fb, _, _ in tr.groups], [b.clone() for b in tr.bufs + (tr.bufs2 or [])],
+                _np.random.get_state())
+        tr.upload_hyper()      # the recorded iteration's optimizer reads the control block as every replay will
         model._get_plan()      # frozen-weight packs / BN folds are made ONCE, outside the program ...
         model._epoch += 1      # ... every trainable conv's derived tensors are re-derived INSIDE it, from the live weights
         prev_save = getattr(model, "save_for_backward", False)
@@ -542,10 +548,9 @@ class ProgramTrainer:
                 fb.recorder = prog
             BW.model_backward(model, (1.0, 1.0, 1.0, 1.0))
             prog.host_callback(self._wait_buckets)
-            for (fb, lr_mult, wd), buf in zip(tr.groups, tr.bufs):
-                # first_step=False: with a zero momentum buffer  buf = m * 0 + g  IS torch.optim.SGD's first step
-                ops.sgd_momentum_(fb.params, fb.grads, buf, tr.lr * lr_mult, tr.momentum, wd, grad_scale=1.0 / fb.world,
-                                  first_step=False)
+            # behind every bucket's sum: (norm pass + clipping coefficient,) one update per group, scalars from the control
+            # block. first_step=False: with a zero momentum buffer  buf = m * 0 + g  IS torch.optim.SGD's first step
+            tr._ctl_update(first_step=False)
 
         try:
             gen = model._forward_gen(*self.inputs)
@@ -582,7 +587,7 @@ class ProgramTrainer:
         torch.cuda.synchronize(dev)
         for (fb, _, _), p0 in zip(tr.groups, snap[0]):
             fb.params.copy_(p0)
-        for b_, b0 in zip(tr.bufs, snap[1]):
+        for b_, b0 in zip(tr.bufs + (tr.bufs2 or []), snap[1]):
             b_.copy_(b0)
         _np.random.set_state(snap[2])
         model._rng_calls = calls0
@@ -607,6 +612,7 @@ class ProgramTrainer:
                 s.copy_(t, non_blocking=True)
         for fb, _, _ in self.trainer.groups:
             fb.zero_grad_bookkeeping()
+        self.trainer.upload_hyper()  # this iteration's learning rate / step count: data the recorded optimizer reads
         self.p1.run()
         if self.p2 is not None:
             ops.draw_and_upload(self.req, self.drawn.device, static=self.drawn)

@@ -9,6 +9,10 @@
   path (replaces nn.DataParallel's reduce-add onto GPU 0, train.py:104-105).
 * `Trainer`: torch.optim.SGD(momentum) semantics of train.py:76-87 (2x learning rate and no weight decay for biases)
   as one fused HIP launch per flat segment; the 1/world_size of the gradient mean is folded into that launch.
+  The optimizer's scalars (per-group learning rate, 1/world_size, Adam's bias corrections, the clipping threshold) also
+  live in a control block in device memory (include/dana_hip.h), refreshed by `upload_hyper()` once per iteration: the
+  `*_ctl` kernels read them there, so a replayed iteration (program.py, graphs.py) follows a learning-rate schedule, runs
+  Adam, and clips by the global gradient norm (net_utils.clip_gradient, net_utils.py:37-48) without being re-recorded.
 """
 import torch
 import torch.distributed as dist
@@ -154,11 +158,18 @@ class FlatBuckets:
             dist.broadcast(self.params, src, group=self.group)
 
 
+_ADAM_BETAS = (0.9, 0.999)  # torch.optim.Adam's defaults (train.py:84-85), as ops.adam_
+
+
 class Trainer:
     def __init__(self, model, lr, momentum=None, weight_decay=None, double_bias=None, bias_decay=None,
-                 process_group=None, bucket_bytes=32 << 20, optimizer="sgd", always_reduce=False):
+                 process_group=None, bucket_bytes=32 << 20, optimizer="sgd", always_reduce=False, clip_norm=None):
         if optimizer not in ("sgd", "adam"):  # train.py:84-87
             raise ValueError("optimizer must be 'sgd' or 'adam'")
+        # net_utils.clip_gradient(model, clip_norm) between backward and step; None / 0: off. Configuration, not state.
+        self.clip_norm = 0.0 if clip_norm is None else float(clip_norm)
+        if not self.clip_norm >= 0.0:
+            raise ValueError("clip_norm must be >= 0 (None or 0 switches clipping off), got %r" % (clip_norm,))
         self.optimizer = optimizer
         self.model = model
         self.lr = float(lr)
@@ -183,6 +194,16 @@ class Trainer:
         self.bufs = [torch.zeros_like(fb.params) for fb, _, _ in self.groups]  # SGD momentum / Adam exp_avg
         self.bufs2 = [torch.zeros_like(fb.params) for fb, _, _ in self.groups] if optimizer == "adam" else None
         self.steps = 0
+        # the control block: `_hyper` is uploaded from the host mirror (upload_hyper), `_state` belongs to the device
+        # (dana_optim_prepare); without clipping it keeps these initial values: coef = 1, gs_eff = 1 / world
+        dev = self.weights.params.device
+        self._hyper_host = torch.zeros(ops.OPTIM_HYPER_FLOATS, dtype=torch.float32)
+        self._hyper = torch.zeros(ops.OPTIM_HYPER_FLOATS, dtype=torch.float32, device=dev)
+        self._state = torch.tensor([0.0, 0.0, 1.0, 1.0 / self.weights.world], dtype=torch.float32, device=dev)
+        self._sq_counts = self._sq_ws = None
+        if self.clip_norm > 0:  # one double per workgroup of the norm pass, the groups' partials one behind the other
+            self._sq_counts = [ops.grad_sqnorm_workspace(fb.numel) for fb, _, _ in self.groups]
+            self._sq_ws = torch.zeros(sum(self._sq_counts), dtype=torch.float64, device=dev)
         if type(model).__name__ == "DAnARCNN" and not model.merge_trunk and getattr(model, "train_merged", True):
             # the training iteration keeps the query and the support batch in ONE set of activation buffers (the trunk's
             # launches stay two per conv on two streams: merge_from 3), so that the backward's 1x1 weight / data gradients
@@ -215,8 +236,50 @@ class Trainer:
         for fb, _, _ in self.groups:
             fb.zero_grad()
 
+    def upload_hyper(self):
+        """refresh the host-written half of the control block from self.lr, the groups' multipliers, 1 / world, clip_norm
+        and steps + 1: one non-blocking copy on the current stream. The pinned staging buffer comes from torch's host
+        allocator on every call, which does not hand a block out again before the copy that read it has finished."""
+        betas = _ADAM_BETAS if self.optimizer == "adam" else (0.0, 0.0)
+        ops.optim_pack_hyper(self._hyper_host, [self.lr * lr_mult for _, lr_mult, _ in self.groups], 1.0 / self.weights.world,
+                             self.clip_norm, betas, self.steps + 1)
+        staged = torch.empty(ops.OPTIM_HYPER_FLOATS, dtype=torch.float32, pin_memory=True)
+        staged.copy_(self._hyper_host)
+        self._hyper.copy_(staged, non_blocking=True)
+
+    def grad_norm(self):
+        """the last clipped iteration's gradient norm BEFORE clipping (of the mean gradients over all trainable parameters,
+        what net_utils.clip_gradient measures): a one-element device tensor, a view of the control block -- no host sync"""
+        return self._state[ops.OPTIM_TOTAL_NORM:ops.OPTIM_TOTAL_NORM + 1]
+
+    def _ctl_update(self, first_step=False):
+        """the optimizer launches that read their scalars from the control block: with clipping the norm pass over both
+        groups and the coefficient, then one update per group. Every bucket's sum must have arrived. C-ABI calls only, so
+        a launch program or a hipGraph capture records them as they are."""
+        if self.clip_norm > 0:
+            off = 0
+            for (fb, _, _), k in zip(self.groups, self._sq_counts):
+                ops.grad_sqnorm_(fb.grads, self._sq_ws[off:off + k])
+                off += k
+            ops.optim_prepare_(self._sq_ws, self._hyper, self._state)
+        for gi, ((fb, _, wd), buf) in enumerate(zip(self.groups, self.bufs)):
+            if self.optimizer == "adam":
+                ops.adam_ctl_(fb.params, fb.grads, buf, self.bufs2[gi], self._hyper, self._state, gi, _ADAM_BETAS[0],
+                              _ADAM_BETAS[1], weight_decay=wd)
+            else:
+                ops.sgd_momentum_ctl_(fb.params, fb.grads, buf, self._hyper, self._state, gi, self.momentum, wd,
+                                      first_step=first_step)
+
     def optimizer_step(self):
         from . import ops
+        if self.clip_norm > 0:
+            for fb, _, _ in self.groups:
+                fb.wait_all()
+            self.upload_hyper()
+            self._ctl_update(first_step=self.steps == 0)
+            self.steps += 1
+            self.model._epoch += 1
+            return
         for (fb, lr_mult, wd), buf in zip(self.groups, self.bufs):
             fb.wait_all()
             if self.optimizer == "adam":

@@ -554,6 +554,54 @@ int dana_sgd_momentum(float* params, const float* grads, float* momentum_buf, lo
 /* torch.optim.Adam over a flat fp32 segment (train.py:84-85; defaults betas (0.9, 0.999), eps 1e-8): step = 1, 2, ... */
 int dana_adam(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, float lr, float beta1,
               float beta2, float eps, float weight_decay, float grad_scale, int step, dana_stream_t stream);
+/* ---- optimizer scalars in device memory (train.py:76-87,118-120; net_utils.py:37-48) ---------------------------------
+ * dana_sgd_momentum / dana_adam take lr, grad_scale and Adam's step as launch parameters, which a recorded launch list
+ * (launch programs, hipGraph) freezes. The *_ctl forms below read them from a control block of two small fp32 arrays in
+ * device memory, so that a learning-rate schedule (train.py:118-120), Adam's step count (train.py:84-85) and the
+ * gradient-norm clipping of net_utils.clip_gradient (net_utils.py:37-48; imported by train.py:18) are DATA of a replay:
+ *
+ *   hyper[DANA_OPTIM_HYPER_FLOATS], written by the HOST (one stream-ordered upload per iteration, packed by
+ *   dana_optim_pack_hyper):  [0..3] effective learning rate of parameter group 0..3 (lr * the group's multiplier,
+ *   train.py:79-84), [4] grad_scale (1 / world size of the gradient mean), [5] clip_norm (0 = no clipping),
+ *   [6] bc1 = 1 - beta1^step, [7] bc2 = 1 - beta2^step (Adam's bias corrections; 1 for SGD)
+ *   state[DANA_OPTIM_STATE_FLOATS], written by the DEVICE (dana_optim_prepare; the upload never touches it):
+ *   [0] sqnorm = sum of g^2 over all groups, [1] total_norm = grad_scale * sqrt(sqnorm): the norm clip_gradient measures
+ *   on the mean gradients, before clipping, [2] coef = clip_norm / max(total_norm, clip_norm) (1 when clip_norm == 0),
+ *   [3] gs_eff = grad_scale * coef: what the *_ctl updates multiply the raw gradient sums by
+ *
+ * Without clipping nobody runs dana_optim_prepare: the caller initialises state once to (0, 0, 1, grad_scale). */
+#define DANA_OPTIM_MAX_GROUPS 4
+#define DANA_OPTIM_HYPER_FLOATS 8
+#define DANA_OPTIM_STATE_FLOATS 4
+/* Host only (no GPU, no stream): fills hyper_host[DANA_OPTIM_HYPER_FLOATS] (pinned or pageable host memory) in the layout
+ * above. lrs[groups] are the effective rates, 1 <= groups <= DANA_OPTIM_MAX_GROUPS (the other slots become 0);
+ * clip_norm >= 0; step >= 1 counts like dana_adam's and the bias corrections are formed exactly as dana_adam forms them
+ * (1.0 - pow((double)beta, step), rounded to float); beta1 = beta2 = 0 (SGD) gives bc1 = bc2 = 1. */
+int dana_optim_pack_hyper(float* hyper_host, const float* lrs, int groups, float grad_scale, float clip_norm, float beta1,
+                          float beta2, int step);
+/* Sum of g^2 over one flat fp32 segment (n % 4 == 0, 16-byte aligned; n == 0 writes nothing and contributes 0) as one
+ * DOUBLE partial per workgroup in partials[dana_grad_sqnorm_workspace_bytes(n) / 8] (8-byte aligned). Deterministic: the
+ * grid is a function of n alone (ceil(n / 1024) workgroups of 256 threads, at most 2048), every thread sums a fixed
+ * grid-strided set of float4s in four fp32 chains (18 FMAs each at the 37 M gradients of a DAnA trainer, 256 at 2^29
+ * elements), and the chains, the 64 lanes of a wave (cross-lane shuffles) and the four waves (LDS) are combined in double
+ * in a fixed order; one plain store per workgroup, no atomics -- two calls, on any stream, give the same bits. */
+size_t dana_grad_sqnorm_workspace_bytes(long n);
+int dana_grad_sqnorm(const float* grads, long n, void* partials, size_t partials_bytes, dana_stream_t stream);
+/* One workgroup: sums partials[count] (the partials of all groups, laid out one group behind the other; count >= 0) in
+ * double -- thread t takes elements t, t + 256, ... in index order, then the fixed lane / wave tree -- so that the sum
+ * depends on the concatenated sequence only, not on where one group ends; then writes state[0..3] as defined above from
+ * hyper[4] (grad_scale) and hyper[5] (clip_norm) with plain stores of one lane. coef is exactly 1.0f, and gs_eff the bits
+ * of grad_scale, when clip_norm == 0 or total_norm <= clip_norm. */
+int dana_optim_prepare(const void* partials, long count, const float* hyper, float* state, dana_stream_t stream);
+/* dana_sgd_momentum / dana_adam with the same arithmetic in the same order (the same bits when coef == 1), where
+ * lr = hyper[group], grad_scale = state[3] (gs_eff) and Adam's bc1 / bc2 = hyper[6] / hyper[7]; what never changes during
+ * a run (momentum, weight decay, betas, eps, first_step) stays a launch parameter. 0 <= group < DANA_OPTIM_MAX_GROUPS. */
+int dana_sgd_momentum_ctl(float* params, const float* grads, float* momentum_buf, long n, const float* hyper,
+                          const float* state, int group, float momentum, float weight_decay, int first_step,
+                          dana_stream_t stream);
+int dana_adam_ctl(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, long n, const float* hyper,
+                  const float* state, int group, float beta1, float beta2, float eps, float weight_decay,
+                  dana_stream_t stream);
 /* adjoint of dana_rowdot: grad_w[dim] (+)= sum_r grad_out[r] x[r]; grad_x[r] += grad_out[r] w (grad_x may be NULL);
  * workspace: dana_colsum_workspace_bytes(rows, dim) */
 int dana_rowdot_backward(const float* x, const float* grad_out, const float* w, float* grad_x, float* grad_w, long rows,
