@@ -1,0 +1,716 @@
+// VOC-protocol detection evaluation on the device (dana_amd/evaluate.py): per-class AP at up to 16 IoU thresholds in
+// one pass over the accumulated detections.
+//
+// Reference semantics replaced (lib/datasets/voc_eval.py, not code): the TP/FP marking of :165-199, the cumulative
+// precision / recall curves of :202-207 and both voc_ap metrics of :35-66 -- all in float64, IoU with the `+ 1.` pixel
+// convention and unfused operations (this file is compiled with -ffp-contract=off). It is NOT COCOeval: no crowd
+// regions, area ranges or maxDets.
+//
+// Pipeline of dana_eval_ap (every step is its own launch; no workgroup ever waits on another one):
+//   1. ground truth: radix sort by (class, image) segment -> gathered boxes / difficult flags, offsets table, npos
+//   2. detections: radix sort by (class, descending score), stable in arrival order -> `order`, cls_offsets
+//   3. a second stable sort of the ranks by (class, image) segment: each segment keeps its global-rank order
+//   4. match_kernel: one wavefront per segment walks its detections in rank order against 64-lane ground-truth chunks
+//   5. curves_ap_kernel: one workgroup per (class, threshold): forward scan of the TP/FP flags, reverse running max of
+//      the precision, the AP sum in a fixed order
+#include "common.h"
+#include "../../include/dana_hip.h"
+#include "../../include/dana_hip_debug.h"
+#include <float.h>
+#include <limits.h>
+#include <math.h>
+
+namespace {
+
+typedef unsigned long long u64;
+
+// ---- block-wide scans over 256 threads (4 waves) ----------------------------------------------------------------------
+// inclusive prefix sum of v in thread order; total = the block's sum. Two barriers: safe to call back to back.
+__device__ __forceinline__ u64 block_scan_add(u64 v, u64& total, u64* lds4) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const u64 up = __shfl_up(v, o);
+    if (lane >= o) v += up;
+  }
+  __syncthreads();
+  if (lane == 63) lds4[w] = v;
+  __syncthreads();
+  u64 base = 0, tot = 0;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const u64 x = lds4[k];
+    if (k < w) base += x;
+    tot += x;
+  }
+  total = tot;
+  return v + base;
+}
+
+// inclusive suffix max of v (max over threads >= this one)
+__device__ __forceinline__ double block_rscan_max(double v, double& total, double* lds4) {
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const double dn = __shfl_down(v, o);
+    if (lane + o < 64) v = fmax(v, dn);
+  }
+  __syncthreads();
+  if (lane == 0) lds4[w] = v;
+  __syncthreads();
+  double after = 0.0, tot = 0.0;  // every value scanned here is >= 0
+#pragma unroll
+  for (int k = 0; k < 4; ++k) {
+    const double x = lds4[k];
+    if (k > w) after = fmax(after, x);
+    tot = fmax(tot, x);
+  }
+  total = tot;
+  return fmax(v, after);
+}
+
+// ---- stable LSD radix sort of (64-bit key, 32-bit value) pairs, 8 bits per pass ---------------------------------------
+// Three launches per pass: per-tile digit histograms, one scan per digit over the tiles, the scatter. A tile is
+// RS_TILE consecutive pairs; inside a tile element j*256 + thread keeps that order, so equal digits keep their order.
+constexpr int RS_ITEMS = 16;
+constexpr int RS_TILE = 256 * RS_ITEMS;
+
+__global__ void __launch_bounds__(256)
+rs_hist_kernel(const u64* __restrict__ keys, long n, int shift, unsigned mask, int nb, unsigned* __restrict__ hist) {
+  __shared__ unsigned h[256];
+  h[threadIdx.x] = 0;
+  __syncthreads();
+  const long base = (long)blockIdx.x * RS_TILE;
+  for (int j = 0; j < RS_ITEMS; ++j) {
+    const long e = base + j * 256 + threadIdx.x;
+    if (e < n) atomicAdd(&h[(unsigned)(keys[e] >> shift) & mask], 1u);
+  }
+  __syncthreads();
+  hist[(long)threadIdx.x * nb + blockIdx.x] = h[threadIdx.x];  // digit-major: a digit's tiles are one row
+}
+
+// block d: hist[d][0..nb) -> its exclusive prefix over the tiles, totals[d] = the digit's count
+__global__ void __launch_bounds__(256)
+rs_scan_kernel(unsigned* __restrict__ hist, int nb, unsigned* __restrict__ totals) {
+  __shared__ u64 s4[4];
+  unsigned* row = hist + (long)blockIdx.x * nb;
+  u64 carry = 0;
+  for (int base = 0; base < nb; base += 256) {
+    const int i = base + threadIdx.x;
+    const u64 v = i < nb ? row[i] : 0;
+    u64 tot;
+    const u64 incl = block_scan_add(v, tot, s4);
+    if (i < nb) row[i] = (unsigned)(carry + incl - v);
+    carry += tot;
+  }
+  if (threadIdx.x == 0) totals[blockIdx.x] = (unsigned)carry;
+}
+
+__global__ void __launch_bounds__(256)
+rs_scatter_kernel(const u64* __restrict__ keys, const int* __restrict__ vals, u64* __restrict__ keys_out,
+                  int* __restrict__ vals_out, long n, int shift, unsigned mask, int nb,
+                  const unsigned* __restrict__ hist,
+                  const unsigned* __restrict__ totals) {
+  __shared__ u64 s4[4];
+  __shared__ unsigned run[256];     // next output position of each digit for this tile
+  __shared__ unsigned cnt[4][256];  // this round's count of each digit per wave
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  {
+    const u64 t = totals[tid];
+    u64 tot;
+    const u64 incl = block_scan_add(t, tot, s4);
+    run[tid] = (unsigned)(incl - t) + hist[(long)tid * nb + blockIdx.x];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cnt[k][tid] = 0;
+  }
+  __syncthreads();
+  const long base = (long)blockIdx.x * RS_TILE;
+  for (int j = 0; j < RS_ITEMS; ++j) {
+    const long e = base + j * 256 + tid;
+    const bool valid = e < n;
+    const u64 key = valid ? keys[e] : 0;
+    const unsigned d = (unsigned)(key >> shift) & mask;
+    u64 peers = __ballot(valid);  // lanes of this wave that hold the same digit
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+      const bool bit = (d >> b) & 1u;
+      const u64 bal = __ballot(valid && bit);
+      peers &= bit ? bal : ~bal;
+    }
+    const unsigned rank = __popcll(peers & ((1ull << lane) - 1ull));
+    if (valid && rank == 0) cnt[w][d] = (unsigned)__popcll(peers);
+    __syncthreads();
+    if (valid) {
+      unsigned pos = run[d] + rank;
+      for (int k = 0; k < w; ++k) pos += cnt[k][d];
+      keys_out[pos] = key;
+      vals_out[pos] = vals[e];
+    }
+    __syncthreads();
+    run[tid] += cnt[0][tid] + cnt[1][tid] + cnt[2][tid] + cnt[3][tid];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) cnt[k][tid] = 0;
+    __syncthreads();
+  }
+}
+
+inline int rs_tiles(long n) { return (int)((n + RS_TILE - 1) / RS_TILE); }
+inline size_t rs_hist_bytes(long n) { return dana_align_up(((size_t)rs_tiles(n) * 256 + 256) * sizeof(unsigned), 256); }
+
+// Sorts the n pairs in (ka, va) by the low `bits` key bits only (higher bits are ignored); kb / vb are the ping-pong buffers. Returns which pair of
+// buffers holds the result (0: a, 1: b), or a negative error.
+int radix_sort(u64* ka, int* va, u64* kb, int* vb, long n, int bits, unsigned* hist, hipStream_t st) {
+  if (n <= 1) return 0;
+  const int nb = rs_tiles(n);
+  unsigned* totals = hist + (size_t)nb * 256;
+  int where = 0;
+  for (int shift = 0; shift < bits; shift += 8) {
+    const unsigned mask = bits - shift >= 8 ? 255u : (1u << (bits - shift)) - 1u;  // the last pass may be narrower
+    rs_hist_kernel<<<nb, 256, 0, st>>>(ka, n, shift, mask, nb, hist);
+    rs_scan_kernel<<<256, 256, 0, st>>>(hist, nb, totals);
+    rs_scatter_kernel<<<nb, 256, 0, st>>>(ka, va, kb, vb, n, shift, mask, nb, hist, totals);
+    u64* tk = ka; ka = kb; kb = tk;
+    int* tv = va; va = vb; vb = tv;
+    where ^= 1;
+  }
+  return where;
+}
+
+inline int bits_for(u64 max_value) {  // bits needed to hold max_value
+  int b = 0;
+  while (b < 64 && (max_value >> b)) ++b;
+  return b;
+}
+
+unsigned grid_for(long total) {
+  const long g = (total + 255) / 256;
+  return (unsigned)(g < 1 ? 1 : (g > 8192 ? 8192 : g));
+}
+
+// ---- keys, offsets, gathers ---------------------------------------------------------------------------------------------
+// (class ascending, score descending); rows whose class or image id is out of range go to the trailing class n_cls
+__global__ void __launch_bounds__(256)
+det_keys_kernel(const float* __restrict__ det, const int* __restrict__ det_img, const int* __restrict__ det_cls, long n,
+                int n_img, int n_cls, u64* __restrict__ keys, int* __restrict__ vals) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long)blockDim.x * gridDim.x) {
+    const int c = det_cls[i], im = det_img[i];
+    const bool ok = c >= 0 && c < n_cls && im >= 0 && im < n_img;
+    float s = det[i * 5 + 4];
+    if (s == 0.f) s = 0.f;  // -0 and +0 are one score
+    const unsigned u = __float_as_uint(s);
+    const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // ascending in the float order
+    keys[i] = ((u64)(ok ? c : n_cls) << 32) | (u64)(0xffffffffu - ord);
+    vals[i] = (int)i;
+  }
+}
+
+// rank r (detection order[r], class keys[r] >> 32) -> its (class, image) segment; value = the rank
+__global__ void __launch_bounds__(256)
+det_seg_keys_kernel(const u64* __restrict__ skeys, const int* __restrict__ order, const int* __restrict__ det_img, long n,
+                    int n_img, int n_cls, u64* __restrict__ keys, int* __restrict__ vals) {
+  for (long r = (long)blockIdx.x * blockDim.x + threadIdx.x; r < n; r += (long)blockDim.x * gridDim.x) {
+    const int c = (int)(skeys[r] >> 32);
+    keys[r] = c >= n_cls ? (u64)n_cls * n_img : (u64)c * n_img + (u64)det_img[order[r]];
+    vals[r] = (int)r;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+gt_keys_kernel(const int* __restrict__ gt_img, const int* __restrict__ gt_cls, long g, int n_img, int n_cls,
+               u64* __restrict__ keys, int* __restrict__ vals) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < g; i += (long)blockDim.x * gridDim.x) {
+    const int c = gt_cls[i], im = gt_img[i];
+    const bool ok = c >= 0 && c < n_cls && im >= 0 && im < n_img;
+    keys[i] = ok ? (u64)c * n_img + (u64)im : (u64)n_cls * n_img;
+    vals[i] = (int)i;
+  }
+}
+
+// off[s] = first position whose id (keys >> shift) is >= s, for s in 0..max_id (off[max_id] closes the last real
+// segment; ids equal to max_id are the out-of-range rows). n == 0: all zero.
+__global__ void __launch_bounds__(256)
+seg_offsets_kernel(const u64* __restrict__ keys, long n, int shift, long max_id, int* __restrict__ off) {
+  const long stride = (long)blockDim.x * gridDim.x;
+  const long first = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (n == 0) {
+    for (long s = first; s <= max_id; s += stride) off[s] = 0;
+    return;
+  }
+  for (long r = first; r < n; r += stride) {
+    const long id = (long)(keys[r] >> shift);
+    const long prev = r ? (long)(keys[r - 1] >> shift) : -1;
+    for (long s = prev + 1; s <= id && s <= max_id; ++s) off[s] = (int)r;
+    if (r == n - 1)
+      for (long s = id + 1; s <= max_id; ++s) off[s] = (int)n;
+  }
+}
+
+__global__ void __launch_bounds__(256)
+gt_gather_kernel(const u64* __restrict__ skeys, const int* __restrict__ svals, const float* __restrict__ gt_box,
+                 const unsigned char* __restrict__ gt_difficult, long g, int n_img, long n_seg,
+                 float4* __restrict__ gsbox, unsigned char* __restrict__ gsdiff, int* __restrict__ npos) {
+  for (long p = (long)blockIdx.x * blockDim.x + threadIdx.x; p < g; p += (long)blockDim.x * gridDim.x) {
+    const long i = svals[p];
+    gsbox[p] = make_float4(gt_box[i * 4], gt_box[i * 4 + 1], gt_box[i * 4 + 2], gt_box[i * 4 + 3]);
+    const unsigned char d = gt_difficult[i] ? 1 : 0;
+    gsdiff[p] = d;
+    const long seg = (long)skeys[p];
+    if (seg < n_seg && !d) atomicAdd(&npos[seg / n_img], 1);  // integer adds: the same count in any order
+  }
+}
+
+// ---- matching (voc_eval.py:165-199) -------------------------------------------------------------------------------------
+// One wavefront per (class, image) segment. Lane l holds ground-truth box 64*k + l of chunk k (chunk 0 in registers);
+// lane t < T owns threshold t and its taken bitmap: one 64-bit word per chunk -- chunk 0 in a register, chunks
+// 1..EV_LDS_CH-1 in LDS, later chunks (more than 64 * EV_LDS_CH boxes in one segment) in the zeroed global array `ovf`,
+// where segment [g0, g1) uses words (g0 >> 6) + k for k >= EV_LDS_CH: above every word of the segments before it.
+constexpr int EV_LDS_CH = 32;
+constexpr int EV_MAX_THR = 16;
+
+__device__ __forceinline__ double iou_voc(double bx1, double by1, double bx2, double by2, double gx1, double gy1,
+                                          double gx2, double gy2) {
+  const double ixmin = fmax(gx1, bx1), iymin = fmax(gy1, by1);
+  const double ixmax = fmin(gx2, bx2), iymax = fmin(gy2, by2);
+  const double iw = fmax(ixmax - ixmin + 1., 0.), ih = fmax(iymax - iymin + 1., 0.);
+  const double inters = iw * ih;
+  const double uni = ((bx2 - bx1 + 1.) * (by2 - by1 + 1.) + (gx2 - gx1 + 1.) * (gy2 - gy1 + 1.) - inters);
+  return inters / uni;
+}
+
+__global__ void __launch_bounds__(256)
+match_kernel(const float* __restrict__ det, const int* __restrict__ order, const int* __restrict__ srank,
+             const int* __restrict__ doff, const int* __restrict__ goff, const float4* __restrict__ gsbox,
+             const unsigned char* __restrict__ gsdiff, const double* __restrict__ thr, int T, long n, long n_seg,
+             u64* __restrict__ ovf, long ovf_stride, unsigned char* __restrict__ tpfp) {
+  __shared__ u64 lds_taken[4][EV_MAX_THR][EV_LDS_CH - 1];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const long s = (long)blockIdx.x * 4 + w;
+  if (s >= n_seg) return;  // (no block-wide barrier below: a wave leaves on its own)
+  const int d0 = doff[s], d1 = doff[s + 1];
+  if (d0 == d1) return;
+  const int g0 = goff[s], ng = goff[s + 1] - g0;
+  const int nch = (ng + 63) >> 6;
+  if (lane < T)
+    for (int k = 1; k < nch && k < EV_LDS_CH; ++k) lds_taken[w][lane][k - 1] = 0;
+  u64 taken0 = 0;
+  const double th = lane < T ? thr[lane] : 0.;
+  double cx1 = 0., cy1 = 0., cx2 = 0., cy2 = 0.;  // chunk 0
+  if (lane < ng) {
+    const float4 b = gsbox[g0 + lane];
+    cx1 = b.x; cy1 = b.y; cx2 = b.z; cy2 = b.w;
+  }
+  u64* my_ovf = ovf + (long)(lane < T ? lane : 0) * ovf_stride + (g0 >> 6);
+  for (int p0 = d0; p0 < d1; p0 += 64) {
+    const int cnt = d1 - p0 < 64 ? d1 - p0 : 64;
+    int my_rank = 0;
+    float mx1 = 0.f, my1 = 0.f, mx2 = 0.f, my2 = 0.f;
+    if (lane < cnt) {
+      my_rank = srank[p0 + lane];
+      const float* b = det + (long)order[my_rank] * 5;
+      mx1 = b[0]; my1 = b[1]; mx2 = b[2]; my2 = b[3];
+    }
+    for (int q = 0; q < cnt; ++q) {
+      const int rank = __shfl(my_rank, q);
+      const double bx1 = (double)__shfl(mx1, q), by1 = (double)__shfl(my1, q);
+      const double bx2 = (double)__shfl(mx2, q), by2 = (double)__shfl(my2, q);
+      double best = -INFINITY;  // ovmax
+      int bj = 0;               // jmax
+      for (int k = 0; k < nch; ++k) {
+        const int j = k * 64 + lane;
+        double m = -INFINITY;
+        if (j < ng) {
+          if (k == 0) {
+            m = iou_voc(bx1, by1, bx2, by2, cx1, cy1, cx2, cy2);
+          } else {
+            const float4 b = gsbox[g0 + j];
+            m = iou_voc(bx1, by1, bx2, by2, (double)b.x, (double)b.y, (double)b.z, (double)b.w);
+          }
+        }
+        int mj = j;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {  // (max, lowest index): np.max / np.argmax
+          const double om = __shfl_xor(m, o);
+          const int oj = __shfl_xor(mj, o);
+          if (om > m || (om == m && oj < mj)) {
+            m = om;
+            mj = oj;
+          }
+        }
+        if (m > best) {
+          best = m;
+          bj = mj;
+        }
+      }
+      if (lane < T) {
+        unsigned char code = 2;  // FP
+        if (ng > 0 && best > th) {
+          if (gsdiff[g0 + bj]) {
+            code = 0;  // difficult: neither
+          } else {
+            const int k = bj >> 6;
+            const u64 bit = 1ull << (bj & 63);
+            const u64 cur = k == 0 ? taken0 : (k < EV_LDS_CH ? lds_taken[w][lane][k - 1] : my_ovf[k]);
+            if (!(cur & bit)) {
+              code = 1;  // TP
+              if (k == 0) taken0 = cur | bit;
+              else if (k < EV_LDS_CH) lds_taken[w][lane][k - 1] = cur | bit;
+              else my_ovf[k] = cur | bit;
+            }
+          }
+        }
+        tpfp[(long)lane * n + rank] = code;
+      }
+    }
+  }
+}
+
+// ---- curves and AP (voc_eval.py:202-207, :35-66) ----------------------------------------------------------------------
+// One workgroup per (class, threshold). Forward: inclusive counts of TP (low word) and FP (high word) from the class's
+// first rank, tile by tile with a carry. Reverse: precision's running max from the class's end, and the AP terms.
+constexpr int CV_ITEMS = 8;
+constexpr int CV_TILE = 256 * CV_ITEMS;
+
+__global__ void __launch_bounds__(256)
+curves_ap_kernel(const unsigned char* __restrict__ tpfp, const int* __restrict__ cls_off, const int* __restrict__ npos,
+                 long n, int n_thr, int use07, u64* __restrict__ cum, double* __restrict__ rec, double* __restrict__ prec,
+                 double* __restrict__ ap) {
+  __shared__ u64 s4[4];
+  __shared__ double d4[4];
+  __shared__ double red[256];
+  const int tid = threadIdx.x;
+  const int c = blockIdx.x, t = blockIdx.y;
+  const long r0 = cls_off[c], r1 = cls_off[c + 1];
+  const int np_i = npos[c];
+  const double np_d = (double)np_i;
+  const unsigned char* flags = tpfp + (long)t * n;
+  u64* cumt = cum + (long)t * n;
+  u64 carry = 0;
+  for (long base = r0; base < r1; base += CV_TILE) {
+    const long i0 = base + (long)tid * CV_ITEMS;
+    u64 loc[CV_ITEMS];
+    u64 sum = 0;
+#pragma unroll
+    for (int j = 0; j < CV_ITEMS; ++j) {
+      const long r = i0 + j;
+      const unsigned f = r < r1 ? flags[r] : 0u;
+      sum += (u64)(f == 1u) + ((u64)(f == 2u) << 32);
+      loc[j] = sum;
+    }
+    u64 tot;
+    const u64 excl = carry + block_scan_add(sum, tot, s4) - sum;
+#pragma unroll
+    for (int j = 0; j < CV_ITEMS; ++j) {
+      const long r = i0 + j;
+      if (r < r1) {
+        const u64 v = excl + loc[j];
+        cumt[r] = v;
+        if (rec != nullptr) {
+          const double tp = (double)(unsigned)v, fp = (double)(unsigned)(v >> 32);
+          rec[(long)t * n + r] = tp / np_d;
+          prec[(long)t * n + r] = tp / fmax(tp + fp, DBL_EPSILON);
+        }
+      }
+    }
+    carry += tot;
+  }
+  __syncthreads();  // the reverse pass reads counts other threads of this workgroup wrote
+  double env_carry = 0.;  // mpre's trailing sentinel
+  double acc = 0.;
+  double p11[11];
+#pragma unroll
+  for (int k = 0; k < 11; ++k) p11[k] = 0.;
+  const long ntile = (r1 - r0 + CV_TILE - 1) / CV_TILE;
+  for (long ti = ntile - 1; ti >= 0; --ti) {
+    const long i0 = r0 + ti * CV_TILE + (long)tid * CV_ITEMS;
+    double pr[CV_ITEMS], rc[CV_ITEMS], sfx[CV_ITEMS];
+    unsigned tpc[CV_ITEMS + 1];
+    tpc[0] = (i0 > r0 && i0 <= r1) ? (unsigned)cumt[i0 - 1] : 0u;  // TP count in front of this thread's first rank
+#pragma unroll
+    for (int j = 0; j < CV_ITEMS; ++j) {
+      const long r = i0 + j;
+      pr[j] = 0.;
+      rc[j] = 0.;
+      tpc[j + 1] = tpc[j];
+      if (r < r1) {
+        const u64 v = cumt[r];
+        const double tp = (double)(unsigned)v, fp = (double)(unsigned)(v >> 32);
+        tpc[j + 1] = (unsigned)v;
+        rc[j] = tp / np_d;
+        pr[j] = tp / fmax(tp + fp, DBL_EPSILON);
+      }
+    }
+    double m = 0.;
+#pragma unroll
+    for (int j = CV_ITEMS - 1; j >= 0; --j) {
+      m = fmax(m, pr[j]);
+      sfx[j] = m;
+    }
+    double tile_max;
+    const double incl = block_rscan_max(m, tile_max, d4);
+    // max over the threads behind this one: the inclusive value of the next thread
+    double behind = __shfl_down(incl, 1);
+    if ((tid & 63) == 63) behind = 0.;
+    __syncthreads();
+    if ((tid & 63) == 0) d4[tid >> 6] = incl;
+    __syncthreads();
+    if ((tid & 63) == 63 && tid < 192) behind = d4[(tid >> 6) + 1];
+    behind = fmax(behind, env_carry);
+    if (use07) {
+#pragma unroll
+      for (int j = 0; j < CV_ITEMS; ++j)
+        if (i0 + j < r1) {
+#pragma unroll
+          for (int k = 0; k < 11; ++k)
+            if (rc[j] >= (double)k * 0.1) p11[k] = fmax(p11[k], pr[j]);
+        }
+    } else {
+#pragma unroll
+      for (int j = CV_ITEMS - 1; j >= 0; --j)
+        if (i0 + j < r1 && tpc[j + 1] != tpc[j]) {  // recall changes here
+          const double env = fmax(sfx[j], behind);
+          const double rprev = tpc[j] ? (double)tpc[j] / np_d : 0.;
+          acc += (rc[j] - rprev) * env;
+        }
+    }
+    env_carry = fmax(env_carry, tile_max);
+  }
+  double result;
+  if (use07) {
+    result = 0.;
+    for (int k = 0; k < 11; ++k) {
+      __syncthreads();
+      red[tid] = p11[k];
+      __syncthreads();
+      for (int o = 128; o > 0; o >>= 1) {
+        if (tid < o) red[tid] = fmax(red[tid], red[tid + o]);
+        __syncthreads();
+      }
+      result = result + red[0] / 11.;
+    }
+  } else {
+    __syncthreads();
+    red[tid] = acc;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {  // fixed tree: the same bits on every run
+      if (tid < o) red[tid] += red[tid + o];
+      __syncthreads();
+    }
+    result = red[0];
+  }
+  if (tid == 0) ap[(long)c * n_thr + t] = np_i > 0 ? result : (double)NAN;
+}
+
+// ---- append -------------------------------------------------------------------------------------------------------------
+// destination row dst_base + i, i in [dst_off[p], dst_off[p+1]), comes from source row src_off[p] + (i - dst_off[p])
+__global__ void __launch_bounds__(256)
+append_kernel(const float* __restrict__ src, const int* __restrict__ dst_off, const int* __restrict__ src_off,
+              const int* __restrict__ prob_img, const int* __restrict__ prob_cls, int P, long rows,
+              float* __restrict__ det, int* __restrict__ det_img, int* __restrict__ det_cls, long dst_base) {
+  for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < rows; i += (long)blockDim.x * gridDim.x) {
+    int lo = 0, hi = P - 1;  // the last p with dst_off[p] <= i
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (dst_off[mid] <= i) lo = mid; else hi = mid - 1;
+    }
+    const float* s = src + ((long)src_off[lo] + (i - dst_off[lo])) * 5;
+    float* d = det + (dst_base + i) * 5;
+#pragma unroll
+    for (int k = 0; k < 5; ++k) d[k] = s[k];
+    det_img[dst_base + i] = prob_img[lo];
+    det_cls[dst_base + i] = prob_cls[lo];
+  }
+}
+
+// ---- workspace layout of dana_eval_ap -----------------------------------------------------------------------------------
+struct EvalWs {
+  size_t keys_a, keys_b, vals_a, vals_b, hist, doff, goff, gsbox, gsdiff, ovf, cum, total;
+};
+
+EvalWs eval_layout(long n, long g, int n_img, int n_cls, int n_thr) {
+  EvalWs L;
+  const long big = n > g ? n : g;
+  const size_t n_seg = (size_t)n_img * n_cls;
+  size_t o = 0;
+  auto take = [&](size_t bytes) {
+    const size_t at = o;
+    o += dana_align_up(bytes ? bytes : 1, 256);
+    return at;
+  };
+  L.keys_a = take((size_t)big * 8);
+  L.keys_b = take((size_t)big * 8);
+  L.vals_a = take((size_t)big * 4);
+  L.vals_b = take((size_t)big * 4);
+  L.hist = take(rs_hist_bytes(big));
+  L.doff = take((n_seg + 1) * 4);
+  L.goff = take((n_seg + 1) * 4);
+  L.gsbox = take((size_t)g * 16);
+  L.gsdiff = take((size_t)g);
+  L.ovf = take((size_t)n_thr * ((size_t)(g >> 6) + 1) * 8);
+  L.cum = take((size_t)n_thr * (size_t)n * 8);
+  L.total = o;
+  return L;
+}
+
+constexpr long EV_MAX_ROWS = 1l << 30;
+
+bool eval_shape_ok(long n, long g, int n_img, int n_cls, int n_thr) {
+  return n >= 0 && g >= 0 && n <= EV_MAX_ROWS && g <= EV_MAX_ROWS && n_img >= 1 && n_cls >= 1 && n_thr >= 1 &&
+         n_thr <= EV_MAX_THR && (long)n_img * (long)n_cls < (long)INT_MAX;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dana_debug_radix_sort_workspace_bytes(long n) {
+  if (n < 0 || n > EV_MAX_ROWS) return 0;
+  return 2 * dana_align_up((size_t)n * 8 + 8, 256) + 2 * dana_align_up((size_t)n * 4 + 4, 256) + rs_hist_bytes(n);
+}
+
+int dana_debug_radix_sort_pairs(const unsigned long long* keys_in, const int* vals_in, unsigned long long* keys_out,
+                                int* vals_out, long n, int key_bits, void* workspace, size_t workspace_bytes,
+                                dana_stream_t stream) {
+  DANA_CHECK_ARG(n >= 0 && n <= EV_MAX_ROWS && key_bits >= 0 && key_bits <= 64,
+                 "dana_debug_radix_sort_pairs: bad shape n=%ld key_bits=%d", n, key_bits);
+  if (n == 0) return DANA_OK;
+  DANA_CHECK_ARG(keys_in && vals_in && keys_out && vals_out && workspace, "dana_debug_radix_sort_pairs: null pointer");
+  if (workspace_bytes < dana_debug_radix_sort_workspace_bytes(n)) {
+    dana_set_error("dana_debug_radix_sort_pairs: workspace too small (%zu < %zu)", workspace_bytes,
+                   dana_debug_radix_sort_workspace_bytes(n));
+    return DANA_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  const size_t kb = dana_align_up((size_t)n * 8 + 8, 256), vb = dana_align_up((size_t)n * 4 + 4, 256);
+  u64* k[2] = {(u64*)ws, (u64*)(ws + kb)};
+  int* v[2] = {(int*)(ws + 2 * kb), (int*)(ws + 2 * kb + vb)};
+  unsigned* hist = (unsigned*)(ws + 2 * kb + 2 * vb);
+  if (hipMemcpyAsync(k[0], keys_in, (size_t)n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(v[0], vals_in, (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    dana_set_error("dana_debug_radix_sort_pairs: copy in failed");
+    return DANA_ERR_HIP;
+  }
+  const int where = radix_sort(k[0], v[0], k[1], v[1], n, key_bits, hist, st);
+  DANA_CHECK_LAUNCH("dana_debug_radix_sort_pairs");
+  if (hipMemcpyAsync(keys_out, k[where], (size_t)n * 8, hipMemcpyDeviceToDevice, st) != hipSuccess ||
+      hipMemcpyAsync(vals_out, v[where], (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+    dana_set_error("dana_debug_radix_sort_pairs: copy out failed");
+    return DANA_ERR_HIP;
+  }
+  return DANA_OK;
+}
+
+int dana_eval_append(const float* src_dets, const int* dst_offsets, const int* src_offsets, const int* prob_img,
+                     const int* prob_cls, int n_problems, long rows, float* det, int* det_img, int* det_cls,
+                     long dst_base, long capacity, dana_stream_t stream) {
+  DANA_CHECK_ARG(n_problems >= 0 && rows >= 0 && dst_base >= 0 && capacity >= 0 && rows <= EV_MAX_ROWS &&
+                     dst_base <= EV_MAX_ROWS,
+                 "dana_eval_append: bad shape n_problems=%d rows=%ld dst_base=%ld", n_problems, rows, dst_base);
+  DANA_CHECK_ARG(dst_base + rows <= capacity, "dana_eval_append: %ld + %ld rows exceed the capacity %ld", dst_base, rows,
+                 capacity);
+  if (rows == 0) return DANA_OK;
+  DANA_CHECK_ARG(n_problems > 0, "dana_eval_append: bad shape: %ld rows of no problem", rows);
+  DANA_CHECK_ARG(src_dets && dst_offsets && src_offsets && prob_img && prob_cls && det && det_img && det_cls,
+                 "dana_eval_append: null pointer");
+  append_kernel<<<grid_for(rows), 256, 0, (hipStream_t)stream>>>(src_dets, dst_offsets, src_offsets, prob_img, prob_cls,
+                                                                 n_problems, rows, det, det_img, det_cls, dst_base);
+  DANA_CHECK_LAUNCH("dana_eval_append");
+  return DANA_OK;
+}
+
+size_t dana_eval_ap_workspace_bytes(long n, long g, int n_img, int n_cls, int n_thr) {
+  if (!eval_shape_ok(n, g, n_img, n_cls, n_thr)) return 0;
+  return eval_layout(n, g, n_img, n_cls, n_thr).total;
+}
+
+int dana_eval_ap(const float* det, const int* det_img, const int* det_cls, long n, const float* gt_box,
+                 const int* gt_img, const int* gt_cls, const unsigned char* gt_difficult, long g, int n_img, int n_cls,
+                 const void* iou_thr_, int n_thr, int use_07_metric, int* order, int* cls_offsets, void* tpfp_, void* rec_,
+                 void* prec_, void* ap_, int* npos, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+  const double* iou_thr = (const double*)iou_thr_;
+  unsigned char* tpfp = (unsigned char*)tpfp_;
+  double *rec = (double*)rec_, *prec = (double*)prec_, *ap = (double*)ap_;
+  DANA_CHECK_ARG(n_thr >= 1 && n_thr <= EV_MAX_THR, "dana_eval_ap: n_thr=%d outside 1..%d", n_thr, EV_MAX_THR);
+  DANA_CHECK_ARG(n >= 0 && g >= 0 && n <= EV_MAX_ROWS && g <= EV_MAX_ROWS && n_img >= 1 && n_cls >= 1,
+                 "dana_eval_ap: bad shape n=%ld g=%ld n_img=%d n_cls=%d", n, g, n_img, n_cls);
+  DANA_CHECK_ARG((long)n_img * (long)n_cls < (long)INT_MAX, "dana_eval_ap: n_cls * n_img = %d * %d overflows", n_cls,
+                 n_img);
+  DANA_CHECK_ARG(iou_thr && cls_offsets && ap && npos && workspace, "dana_eval_ap: null pointer");
+  DANA_CHECK_ARG(n == 0 || (det && det_img && det_cls && order && tpfp), "dana_eval_ap: null detection pointer");
+  DANA_CHECK_ARG(g == 0 || (gt_box && gt_img && gt_cls && gt_difficult), "dana_eval_ap: null ground-truth pointer");
+  DANA_CHECK_ARG((rec == nullptr) == (prec == nullptr), "dana_eval_ap: rec and prec are given together or not at all");
+  const EvalWs L = eval_layout(n, g, n_img, n_cls, n_thr);
+  if (workspace_bytes < L.total) {
+    dana_set_error("dana_eval_ap: workspace too small (%zu < %zu)", workspace_bytes, L.total);
+    return DANA_ERR_WORKSPACE;
+  }
+  hipStream_t st = (hipStream_t)stream;
+  char* ws = (char*)workspace;
+  u64* k[2] = {(u64*)(ws + L.keys_a), (u64*)(ws + L.keys_b)};
+  int* v[2] = {(int*)(ws + L.vals_a), (int*)(ws + L.vals_b)};
+  unsigned* hist = (unsigned*)(ws + L.hist);
+  int* doff = (int*)(ws + L.doff);
+  int* goff = (int*)(ws + L.goff);
+  float4* gsbox = (float4*)(ws + L.gsbox);
+  unsigned char* gsdiff = (unsigned char*)(ws + L.gsdiff);
+  u64* ovf = (u64*)(ws + L.ovf);
+  u64* cum = (u64*)(ws + L.cum);
+  const long n_seg = (long)n_img * n_cls;
+  const long ovf_stride = (g >> 6) + 1;
+  const int seg_bits = bits_for((u64)n_seg);
+
+  if (hipMemsetAsync(npos, 0, (size_t)n_cls * sizeof(int), st) != hipSuccess ||
+      hipMemsetAsync(ovf, 0, (size_t)n_thr * ovf_stride * 8, st) != hipSuccess ||
+      (n > 0 && hipMemsetAsync(tpfp, 0, (size_t)n_thr * n, st) != hipSuccess)) {
+    dana_set_error("dana_eval_ap: hipMemsetAsync failed");
+    return DANA_ERR_HIP;
+  }
+  // 1. ground truth into (class, image) segments
+  const u64* gkeys = k[0];
+  if (g > 0) {
+    gt_keys_kernel<<<grid_for(g), 256, 0, st>>>(gt_img, gt_cls, g, n_img, n_cls, k[0], v[0]);
+    const int where = radix_sort(k[0], v[0], k[1], v[1], g, seg_bits, hist, st);
+    gkeys = k[where];
+    gt_gather_kernel<<<grid_for(g), 256, 0, st>>>(k[where], v[where], gt_box, gt_difficult, g, n_img, n_seg, gsbox,
+                                                  gsdiff, npos);
+  }
+  seg_offsets_kernel<<<grid_for(g > n_seg ? g : n_seg), 256, 0, st>>>(gkeys, g, 0, n_seg, goff);
+  DANA_CHECK_LAUNCH("dana_eval_ap (ground truth)");
+  // 2. the global order: class ascending, score descending, arrival ascending
+  const u64* skeys = k[0];
+  const int* srank = v[0];
+  if (n > 0) {
+    det_keys_kernel<<<grid_for(n), 256, 0, st>>>(det, det_img, det_cls, n, n_img, n_cls, k[0], v[0]);
+    const int w1 = radix_sort(k[0], v[0], k[1], v[1], n, 32 + bits_for((u64)n_cls), hist, st);
+    skeys = k[w1];
+    if (hipMemcpyAsync(order, v[w1], (size_t)n * 4, hipMemcpyDeviceToDevice, st) != hipSuccess) {
+      dana_set_error("dana_eval_ap: copy of the order failed");
+      return DANA_ERR_HIP;
+    }
+  }
+  seg_offsets_kernel<<<grid_for(n > n_cls ? n : n_cls), 256, 0, st>>>(skeys, n, 32, n_cls, cls_offsets);
+  // 3. the ranks grouped by (class, image)
+  const u64* dkeys = k[0];
+  if (n > 0) {
+    const int w1 = skeys == k[0] ? 0 : 1;
+    det_seg_keys_kernel<<<grid_for(n), 256, 0, st>>>(skeys, order, det_img, n, n_img, n_cls, k[w1 ^ 1], v[w1 ^ 1]);
+    const int w2 = radix_sort(k[w1 ^ 1], v[w1 ^ 1], k[w1], v[w1], n, seg_bits, hist, st) ^ w1 ^ 1;
+    dkeys = k[w2];
+    srank = v[w2];
+  }
+  seg_offsets_kernel<<<grid_for(n > n_seg ? n : n_seg), 256, 0, st>>>(dkeys, n, 0, n_seg, doff);
+  DANA_CHECK_LAUNCH("dana_eval_ap (orderings)");
+  // 4. TP / FP marking
+  if (n > 0) {
+    match_kernel<<<dana_ceil_div(n_seg, 4), 256, 0, st>>>(det, order, srank, doff, goff, gsbox, gsdiff, iou_thr, n_thr, n,
+                                                          n_seg, ovf, ovf_stride, tpfp);
+    DANA_CHECK_LAUNCH("dana_eval_ap (matching)");
+  }
+  // 5. curves and AP
+  curves_ap_kernel<<<dim3((unsigned)n_cls, (unsigned)n_thr), 256, 0, st>>>(tpfp, cls_offsets, npos, n, n_thr,
+                                                                           use_07_metric ? 1 : 0, cum, rec, prec, ap);
+  DANA_CHECK_LAUNCH("dana_eval_ap (curves)");
+  return DANA_OK;
+}
+
+}  // extern "C"

@@ -38,11 +38,8 @@ def detections(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=Fa
     return dets[keep]
 
 
-def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False):
-    """rois [B,R,5], cls_prob [B*R,2], bbox_pred [B*R,4], im_info [B,3] (the eval forward's outputs for B images) ->
-    list of B cls_dets [K_b,5], each equal to `detections()` on its image. One C call (decode over B*R rows, B-row sort,
-    B NMS problems, packed compaction) and ONE D2H read of the per-image counts / offsets. with_layout=True also returns
-    the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]])."""
+def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive):
+    """the batched call itself -> (dets [max(B*R,1),5] packed device buffer, host int32 counts [B], offsets [B+1])"""
     if rois.dim() != 3 or rois.size(2) != 5:
         raise ValueError("detections_batched: rois must be [B, R, 5], got %s" % (tuple(rois.shape),))
     B, R = rois.size(0), rois.size(1)
@@ -64,16 +61,34 @@ def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_incl
                int(bool(nms_inclusive)), ops._p(dets), layout.data_ptr(), layout.data_ptr() + 4 * B, ops._p(ws),
                ws.numel(), ops._stream())
     host = layout.cpu()
-    counts, offsets = host[:B], host[B:]
-    out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(B)]
+    return dets, host[:B], host[B:]
+
+
+def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False):
+    """rois [B,R,5], cls_prob [B*R,2], bbox_pred [B*R,4], im_info [B,3] (the eval forward's outputs for B images) ->
+    list of B cls_dets [K_b,5], each equal to `detections()` on its image. One C call (decode over B*R rows, B-row sort,
+    B NMS problems, packed compaction) and ONE D2H read of the per-image counts / offsets. with_layout=True also returns
+    the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]])."""
+    dets, counts, offsets = _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive)
+    out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(counts.numel())]
     return (out, counts, offsets) if with_layout else out
 
 
-def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=0.05, nms_inclusive=False):
+class ClassDetections(list):
+    """`detections_by_class(with_layout=True)`: the nested list dets[b][c] itself, plus the one device buffer its entries
+    are views of -- `packed` [rows,5], host int32 `counts` [B*C] and `offsets` [B*C+1] of problem p = b*C + c -- which is
+    what `evaluate.DetectionEvaluator.add_by_class` appends in one launch instead of slicing B*C tensors apart."""
+    packed = counts = offsets = None
+    num_classes = 0
+
+
+def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=0.05, nms_inclusive=False,
+                        with_layout=False):
     """A class sweep's outputs (model(..., cache.sweep(classes)): rois [B*C,R,5], cls_prob [B*C*R,2], bbox_pred [B*C*R,4])
     with im_info [B,3] per IMAGE -> dets[b][c], a [K,5] tensor equal to `detections()` on problem b*C + c with image b's
     im_info: the all_boxes[j][i] layout of inference.py:70-140 (j the class, i the image). One batched post-processing
-    call over the B*C problems, one D2H read; the im_info row of problem p (image p // C) is repeated on the device."""
+    call over the B*C problems, one D2H read; the im_info row of problem p (image p // C) is repeated on the device.
+    with_layout=True returns the same nested list as a `ClassDetections`, which also carries the packed buffer."""
     if rois.dim() != 3 or rois.size(2) != 5:
         raise ValueError("detections_by_class: rois must be [B*C, R, 5], got %s" % (tuple(rois.shape),))
     C = int(num_classes)
@@ -82,5 +97,11 @@ def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=
     if C < 1 or rois.size(0) != B * C:
         raise ValueError("detections_by_class: %d problems for %d images x %d classes" % (rois.size(0), B, C))
     info_p = ops.repeat_rows_grouped(im_info, 1, 3, C, B * C, ld_src=im_info.size(1))
-    flat = detections_batched(rois, cls_prob, bbox_pred, info_p, thresh=thresh, nms_inclusive=nms_inclusive)
-    return [flat[b * C:(b + 1) * C] for b in range(B)]
+    packed, counts, offsets = _detections_packed(rois, cls_prob, bbox_pred, info_p, thresh, nms_inclusive)
+    flat = [packed[int(offsets[p]):int(offsets[p]) + int(counts[p])] for p in range(B * C)]
+    nested = [flat[b * C:(b + 1) * C] for b in range(B)]
+    if not with_layout:
+        return nested
+    out = ClassDetections(nested)
+    out.packed, out.counts, out.offsets, out.num_classes = packed, counts, offsets, C
+    return out

@@ -732,6 +732,39 @@ int dana_fill_zero(void* dst, size_t bytes, dana_stream_t stream);
 int dana_copy_d2d(void* dst, const void* src, size_t bytes, dana_stream_t stream);
 int dana_program_run(void* program, int begin, int end);
 
+/* ---- detection evaluation: lib/datasets/voc_eval.py (the last line of inference.py, :181) ---------------------------------
+ * The VOC protocol on the device, in float64: NOT COCOeval (no crowd regions, area ranges or maxDets). Evaluating at the
+ * thresholds 0.50:0.05:0.95 is voc_eval called with ten `ovthresh` values, done here in one pass. */
+
+/* Grows the evaluator's detection buffers (what pascal_voc.py:268-291 writes to per-class text files and voc_eval.py:143-151
+ * parses again): the packed rows of n_problems detection sets -> det[capacity][5] / det_img / det_cls from row dst_base on.
+ * Destination row dst_base + i with dst_offsets[p] <= i < dst_offsets[p+1] is source row src_offsets[p] + (i - dst_offsets[p])
+ * and gets the ids prob_img[p], prob_cls[p] (all four tables in device memory; `rows` = dst_offsets[n_problems] is the
+ * caller's host copy of the count). */
+int dana_eval_append(const float* src_dets, const int* dst_offsets, const int* src_offsets, const int* prob_img,
+                     const int* prob_cls, int n_problems, long rows, float* det, int* det_img, int* det_cls,
+                     long dst_base, long capacity, dana_stream_t stream);
+/* 0 for a shape dana_eval_ap refuses */
+size_t dana_eval_ap_workspace_bytes(long n, long g, int n_img, int n_cls, int n_thr);
+/* voc_eval.py:157-210 for every class and n_thr (1..16) IoU thresholds at once. det[n][5] = (x1, y1, x2, y2, score) with
+ * image / class ids det_img / det_cls; ground truth gt_box[g][4], gt_img, gt_cls, gt_difficult (bytes, non-zero =
+ * difficult). Rows whose ids are outside [0, n_img) x [0, n_cls) take no part.
+ *   order[n]: detection index by rank -- class ascending, score descending, equal scores in arrival order (:159-162; the
+ *     reference's argsort leaves the order of ties undefined); cls_offsets[n_cls + 1]: class c holds ranks
+ *     cls_offsets[c] .. cls_offsets[c+1];
+ *   tpfp[n_thr][n] by rank: 1 = TP, 2 = FP, 0 = matched a difficult box (:165-199; IoU with the `+ 1.` convention, the
+ *     lowest index among equal maxima, the taken state per class, image and threshold);
+ *   rec / prec [n_thr][n] by rank (:202-207), both null when not wanted; npos[n_cls]: non-difficult boxes per class;
+ *   ap[n_cls][n_thr]: voc_ap (:35-66), the 11-point metric when use_07_metric != 0. A class with npos == 0 has AP = NaN
+ *     under both metrics (the reference: 0 under the 11-point one, NaN under the other).
+ * iou_thr, rec, prec and ap are arrays of C `double` and tpfp one of bytes, passed as void* (this header keeps to the
+ * pointer types it already had). Sums run in a fixed order: two calls give the same bits. No synchronisation, no
+ * device-to-host copy. */
+int dana_eval_ap(const float* det, const int* det_img, const int* det_cls, long n, const float* gt_box,
+                 const int* gt_img, const int* gt_cls, const unsigned char* gt_difficult, long g, int n_img, int n_cls,
+                 const void* iou_thr, int n_thr, int use_07_metric, int* order, int* cls_offsets, void* tpfp, void* rec,
+                 void* prec, void* ap, int* npos, void* workspace, size_t workspace_bytes, dana_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

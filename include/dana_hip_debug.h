@@ -39,6 +39,14 @@ int dana_set_sort_mode(int mode);
 int dana_debug_stream_create_cumask(const unsigned int* mask, int mask_words, int n_xcd, dana_stream_t* stream_out);
 int dana_debug_stream_destroy(dana_stream_t stream);
 
+/* The evaluator's sort on its own (csrc/evaluate.hip): a stable LSD radix sort of n (64-bit key, 32-bit value) pairs,
+ * ascending in the low key_bits bits of the key (passes above them are skipped), eight bits per pass, three launches per
+ * pass. in / out may not overlap. (tests/test_gpu_evaluate.py) */
+size_t dana_debug_radix_sort_workspace_bytes(long n);
+int dana_debug_radix_sort_pairs(const unsigned long long* keys_in, const int* vals_in, unsigned long long* keys_out,
+                                int* vals_out, long n, int key_bits, void* workspace, size_t workspace_bytes,
+                                dana_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
