@@ -7,8 +7,8 @@ IoU threshold in one C call (csrc/evaluate.hip: two radix sorts, one wavefront p
 marking, one workgroup per (class, threshold) for the curves). All arithmetic is float64.
 
 This is the VOC protocol: the TP/FP marking of voc_eval.py:165-199, the curves of :202-207, both `voc_ap` metrics of
-:35-66. Thresholds 0.50:0.05:0.95 are ten `voc_eval` calls in one pass. It is NOT COCOeval: crowd regions, area ranges
-and maxDets are not modelled.
+:35-66. Thresholds 0.50:0.05:0.95 are ten `voc_eval` calls in one pass. That is NOT COCOeval: crowd regions, area ranges
+and maxDets are not modelled there. The COCO protocol is the second half of this module (`CocoEvaluator`, below).
 
 Defined where the reference is not, or differs:
   * equal scores within a class are ranked in arrival order (the reference's `np.argsort(-confidence)` is not stable);
@@ -19,6 +19,21 @@ Defined where the reference is not, or differs:
 
 `voc_numpy` is the same semantics restated in plain numpy float64 (host): the tests' yardstick, pinned to the reference
 by tests/golden/eval_voc.npz.
+
+The COCO protocol (`CocoEvaluator`, `eval_coco`, `evaluate_coco_boxes`, `coco_numpy`): what the COCO splits end in --
+coco_split.py:287-298, `COCOeval.evaluate()`, `accumulate()`, `summarize()`, and the per-category table of
+`_print_detection_eval_metrics` (:254-285) -- for iouType = 'bbox': AP@[.50:.95], AP50, AP75, AP small / medium / large,
+AR@1/10/100. One C call (csrc/evaluate.hip: the same sorts and segment tables, one wavefront per (class, image) whose
+lanes own the (area range, threshold) pairs, one workgroup per (class, area range, maxDets, threshold)), float64.
+
+Defined where the reference is not: pycocotools is not part of the reference tree and is not installed, so nothing here
+was generated from it. The protocol is pinned three ways instead: `coco_numpy` restates the published algorithm
+(COCOeval `evaluateImg` / `accumulate` / `summarize` and maskApi's `bbIou`); hand-worked cases with known answers
+(tests/test_coco_eval_host.py); and, on inputs where the two protocols must agree (pairwise disjoint ground truth, no
+flags, one area range, no maxDets cut), `coco_numpy` is checked against the reference-pinned `voc_numpy`. Two choices:
+  * objects are matched by index, not by annotation id: pycocotools' `dtm == 0` confusion over an annotation whose id is
+    0 is not reproduced;
+  * the rank is (class, score descending, image index, arrival): COCOeval's stable mergesort over the per-image lists.
 """
 import numpy as np
 import torch
@@ -232,28 +247,16 @@ def _host_ints(x):
     return np.ascontiguousarray(np.asarray(x).reshape(-1), dtype=np.int32)
 
 
-class DetectionEvaluator:
-    """VOC-protocol evaluator living on `device`. Classes are 0..num_classes-1, images are the caller's indices."""
+class _DetectionStore:
+    """What both evaluators share: the detections accumulated across forwards in device buffers (doubling growth), fed
+    by `add_packed`, `add_batched` and `add_by_class`. No method reads from the device. A subclass sets `device` and
+    `num_classes`, calls `_reset_detections()` from its `reset()` and keeps its own ground truth."""
 
-    def __init__(self, num_classes, iou_thresholds=(0.5,), use_07_metric=False, device="cuda"):
-        self.num_classes = int(num_classes)
-        thr = np.asarray(iou_thresholds, np.float64).reshape(-1)
-        if self.num_classes < 1 or not 1 <= thr.size <= 16:
-            raise ValueError("DetectionEvaluator: num_classes >= 1 and 1..16 IoU thresholds")
-        self.use_07_metric = bool(use_07_metric)
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("DetectionEvaluator lives on a CUDA (HIP) device: this build has no CPU path")
-        self.iou_thresholds = torch.from_numpy(thr).to(self.device)
-        self.reset()
-
-    def reset(self):
+    def _reset_detections(self):
         self.num_rows = 0
         self.num_images = 0
         self._cap = 0
         self._det = self._img = self._cls = None
-        self._gt = []  # (boxes [k,4] float32, image ids [k] int32, labels [k] int32, difficult [k] uint8) on the device
-        self._gt_cat = None
 
     # -- growth: doubling, so that appends cost amortised O(rows)
     def _reserve(self, rows):
@@ -274,43 +277,6 @@ class DetectionEvaluator:
         if not isinstance(x, torch.Tensor):
             x = torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
         return x.to(device=self.device, dtype=dtype).contiguous()
-
-    def add_ground_truth(self, image_index, boxes, labels, difficult=None):
-        """the objects of one image: boxes [k,4] (x1,y1,x2,y2), labels [k] class indices, difficult [k] (default none)"""
-        boxes = self._dev(boxes, torch.float32).reshape(-1, 4)
-        k = boxes.size(0)
-        labels = self._dev(labels, torch.int32).reshape(-1)
-        diff = (torch.zeros((k,), dtype=torch.uint8, device=self.device) if difficult is None
-                else (self._dev(difficult, torch.int32).reshape(-1) != 0).to(torch.uint8))
-        if labels.numel() != k or diff.numel() != k:
-            raise ValueError("add_ground_truth: %d boxes, %d labels, %d difficult flags" % (k, labels.numel(), diff.numel()))
-        image_index = int(image_index)
-        if image_index < 0:
-            raise ValueError("add_ground_truth: negative image index")
-        self.num_images = max(self.num_images, image_index + 1)
-        self._gt.append((boxes, torch.full((k,), image_index, dtype=torch.int32, device=self.device), labels, diff))
-        self._gt_cat = None
-
-    def add_ground_truth_packed(self, boxes, img_ids, labels, difficult=None, num_images=None):
-        """the objects of many images at once, with per-row image ids (the ground-truth counterpart of `add_packed`;
-        ids on the device need `num_images`)"""
-        boxes = self._dev(boxes, torch.float32).reshape(-1, 4)
-        k = boxes.size(0)
-        host_img = _host_ints(img_ids)
-        if num_images is not None:
-            self.num_images = max(self.num_images, int(num_images))
-        elif host_img is None:
-            raise ValueError("add_ground_truth_packed: img_ids live on the device; pass num_images")
-        elif host_img.size:
-            self.num_images = max(self.num_images, int(host_img.max()) + 1)
-        img = self._dev(img_ids, torch.int32).reshape(-1)
-        labels = self._dev(labels, torch.int32).reshape(-1)
-        diff = (torch.zeros((k,), dtype=torch.uint8, device=self.device) if difficult is None
-                else (self._dev(difficult, torch.int32).reshape(-1) != 0).to(torch.uint8))
-        if img.numel() != k or labels.numel() != k or diff.numel() != k:
-            raise ValueError("add_ground_truth_packed: %d boxes need as many image ids, labels and flags" % k)
-        self._gt.append((boxes, img, labels, diff))
-        self._gt_cat = None
 
     def add_packed(self, dets, img_ids, cls_ids, num_images=None):
         """The primitive (and what a caller all-gathers across ranks): dets [k,5] = (x1,y1,x2,y2,score) with per-row
@@ -402,6 +368,72 @@ class DetectionEvaluator:
         offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
         return self.add_batched(flat, counts, offsets, p_img, p_cls)
 
+    def _detections(self):
+        """-> (det [n,5], img [n], cls [n]): the rows added so far"""
+        n = self.num_rows
+        if n:
+            return self._det[:n], self._img[:n], self._cls[:n]
+        ids = torch.empty((0,), dtype=torch.int32, device=self.device)
+        return torch.empty((0, 5), dtype=torch.float32, device=self.device), ids, ids
+
+
+class DetectionEvaluator(_DetectionStore):
+    """VOC-protocol evaluator living on `device`. Classes are 0..num_classes-1, images are the caller's indices."""
+
+    def __init__(self, num_classes, iou_thresholds=(0.5,), use_07_metric=False, device="cuda"):
+        self.num_classes = int(num_classes)
+        thr = np.asarray(iou_thresholds, np.float64).reshape(-1)
+        if self.num_classes < 1 or not 1 <= thr.size <= 16:
+            raise ValueError("DetectionEvaluator: num_classes >= 1 and 1..16 IoU thresholds")
+        self.use_07_metric = bool(use_07_metric)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("DetectionEvaluator lives on a CUDA (HIP) device: this build has no CPU path")
+        self.iou_thresholds = torch.from_numpy(thr).to(self.device)
+        self.reset()
+
+    def reset(self):
+        self._reset_detections()
+        self._gt = []  # (boxes [k,4] float32, image ids [k] int32, labels [k] int32, difficult [k] uint8) on the device
+        self._gt_cat = None
+
+    def add_ground_truth(self, image_index, boxes, labels, difficult=None):
+        """the objects of one image: boxes [k,4] (x1,y1,x2,y2), labels [k] class indices, difficult [k] (default none)"""
+        boxes = self._dev(boxes, torch.float32).reshape(-1, 4)
+        k = boxes.size(0)
+        labels = self._dev(labels, torch.int32).reshape(-1)
+        diff = (torch.zeros((k,), dtype=torch.uint8, device=self.device) if difficult is None
+                else (self._dev(difficult, torch.int32).reshape(-1) != 0).to(torch.uint8))
+        if labels.numel() != k or diff.numel() != k:
+            raise ValueError("add_ground_truth: %d boxes, %d labels, %d difficult flags" % (k, labels.numel(), diff.numel()))
+        image_index = int(image_index)
+        if image_index < 0:
+            raise ValueError("add_ground_truth: negative image index")
+        self.num_images = max(self.num_images, image_index + 1)
+        self._gt.append((boxes, torch.full((k,), image_index, dtype=torch.int32, device=self.device), labels, diff))
+        self._gt_cat = None
+
+    def add_ground_truth_packed(self, boxes, img_ids, labels, difficult=None, num_images=None):
+        """the objects of many images at once, with per-row image ids (the ground-truth counterpart of `add_packed`;
+        ids on the device need `num_images`)"""
+        boxes = self._dev(boxes, torch.float32).reshape(-1, 4)
+        k = boxes.size(0)
+        host_img = _host_ints(img_ids)
+        if num_images is not None:
+            self.num_images = max(self.num_images, int(num_images))
+        elif host_img is None:
+            raise ValueError("add_ground_truth_packed: img_ids live on the device; pass num_images")
+        elif host_img.size:
+            self.num_images = max(self.num_images, int(host_img.max()) + 1)
+        img = self._dev(img_ids, torch.int32).reshape(-1)
+        labels = self._dev(labels, torch.int32).reshape(-1)
+        diff = (torch.zeros((k,), dtype=torch.uint8, device=self.device) if difficult is None
+                else (self._dev(difficult, torch.int32).reshape(-1) != 0).to(torch.uint8))
+        if img.numel() != k or labels.numel() != k or diff.numel() != k:
+            raise ValueError("add_ground_truth_packed: %d boxes need as many image ids, labels and flags" % k)
+        self._gt.append((boxes, img, labels, diff))
+        self._gt_cat = None
+
     def _ground_truth(self):
         if self._gt_cat is None:
             if self._gt:
@@ -456,3 +488,403 @@ def evaluate_all_boxes(all_boxes, ground_truth, iou_thresholds=(0.5,), use_07_me
         ev.add_packed(d, np.concatenate(imgs), np.concatenate(clss), num_images=n_img)
     ev.num_images = max(ev.num_images, n_img)
     return ev.compute(curves=curves)
+
+
+# ==== the COCO protocol ======================================================================================================
+
+COCO_IOU_THRS = np.linspace(.5, 0.95, int(np.round((0.95 - .5) / .05)) + 1, endpoint=True)  # COCOeval's Params
+COCO_REC_THRS = np.linspace(.0, 1.00, int(np.round((1.00 - .0) / .01)) + 1, endpoint=True)
+COCO_AREA_RNG = np.asarray([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2]], np.float64)
+COCO_MAX_DETS = (1, 10, 100)
+COCO_EPS = float(np.spacing(1))  # 2^-52
+COCO_SUMMARY_NAMES = ("AP", "AP50", "AP75", "AP_small", "AP_medium", "AP_large", "AR_1", "AR_10", "AR_100", "AR_small",
+                      "AR_medium", "AR_large")
+
+
+def _coco_params(iou_thrs, rec_thrs, area_rng, max_dets):
+    """-> the four parameter arrays, checked against what the kernels take"""
+    iou = np.ascontiguousarray(np.asarray(COCO_IOU_THRS if iou_thrs is None else iou_thrs, np.float64).reshape(-1))
+    rec = np.ascontiguousarray(np.asarray(COCO_REC_THRS if rec_thrs is None else rec_thrs, np.float64).reshape(-1))
+    area = np.ascontiguousarray(np.asarray(COCO_AREA_RNG if area_rng is None else area_rng, np.float64).reshape(-1, 2))
+    md = np.ascontiguousarray(np.asarray(COCO_MAX_DETS if max_dets is None else max_dets, np.int64).reshape(-1))
+    if not (1 <= iou.size <= 16 and 1 <= rec.size <= 128 and 1 <= area.shape[0] <= 4 and 1 <= md.size <= 4):
+        raise ValueError("COCO parameters: 1..16 iou_thrs, 1..128 rec_thrs, 1..4 area ranges, 1..4 max_dets")
+    if (np.diff(rec) < 0).any() or (np.diff(md) < 0).any() or md[0] < 1 or md[-1] >= 1 << 30:
+        raise ValueError("COCO parameters: rec_thrs and max_dets ascend, max_dets >= 1")
+    return iou, rec, area, md.astype(np.int32)
+
+
+def _coco_is_default(iou, rec, area, md):
+    return (np.array_equal(iou, COCO_IOU_THRS) and np.array_equal(rec, COCO_REC_THRS) and
+            np.array_equal(area, COCO_AREA_RNG) and np.array_equal(md, np.asarray(COCO_MAX_DETS)))
+
+
+def _bb_iou(d, g, crowd):
+    """maskApi bbIou: d [nd,4], g [ng,4] as (x, y, w, h) float64, crowd [ng] bool -> [nd,ng]"""
+    d = d[:, None, :]
+    g = g[None, :, :]
+    iw = np.minimum(d[..., 0] + d[..., 2], g[..., 0] + g[..., 2]) - np.maximum(d[..., 0], g[..., 0])
+    ih = np.minimum(d[..., 1] + d[..., 3], g[..., 1] + g[..., 3]) - np.maximum(d[..., 1], g[..., 1])
+    i = iw * ih
+    da = d[..., 2] * d[..., 3]
+    u = np.where(crowd[None, :], np.broadcast_to(da, i.shape), da + g[..., 2] * g[..., 3] - i)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        o = i / u
+    return np.where((iw <= 0) | (ih <= 0), 0., o)
+
+
+def _last_argmax(x):
+    """x [..., ng] -> (max, the LAST index holding it) along the last axis"""
+    ng = x.shape[-1]
+    j = ng - 1 - np.argmax(x[..., ::-1], axis=-1)
+    return np.take_along_axis(x, j[..., None], -1)[..., 0], j
+
+
+def coco_numpy(det, det_img, det_cls, gt_bbox, gt_img, gt_cls, n_img, n_cls, gt_iscrowd=None, gt_area=None,
+               gt_ignore=None, iou_thrs=None, rec_thrs=None, area_rng=None, max_dets=None):
+    """The COCO evaluator's semantics in numpy float64 (host). det [n,5] = (x1,y1,x2,y2,score), gt_bbox [g,4] =
+    (x,y,w,h). -> dict(order [n], cls_offsets [K+1], segpos [n] by rank (-1: takes no part), codes uint8 [A,T,n] by rank
+    (1 TP, 2 FP, 0 ignored, 3 past max_dets[-1] or no part), matched [A,T,n] by rank (the ground-truth row matched, -1),
+    npig [K,A], precision / scores [T,R,K,A,M], recall [T,K,A,M])."""
+    iou_t, rec_t, area_r, md = _coco_params(iou_thrs, rec_thrs, area_rng, max_dets)
+    det = np.asarray(det, np.float32).reshape(-1, 5)
+    det_img = np.asarray(det_img, np.int64).reshape(-1)
+    det_cls = np.asarray(det_cls, np.int64).reshape(-1)
+    gt_bbox = np.asarray(gt_bbox, np.float32).reshape(-1, 4)
+    gt_img = np.asarray(gt_img, np.int64).reshape(-1)
+    gt_cls = np.asarray(gt_cls, np.int64).reshape(-1)
+    n, g = det.shape[0], gt_bbox.shape[0]
+    T, R, A, M = iou_t.size, rec_t.size, area_r.shape[0], md.size
+    K = int(n_cls)
+    gt64 = gt_bbox.astype(np.float64)
+    crowd = np.zeros(g, bool) if gt_iscrowd is None else np.asarray(gt_iscrowd).reshape(-1).astype(bool)
+    ign = np.zeros(g, bool) if gt_ignore is None else np.asarray(gt_ignore).reshape(-1).astype(bool)
+    area = gt64[:, 2] * gt64[:, 3] if gt_area is None else np.asarray(gt_area, np.float64).reshape(-1)
+    gt_ig = (ign | crowd)[None, :] | (area[None, :] < area_r[:, :1]) | (area[None, :] > area_r[:, 1:])  # [A,g]
+    d64 = det[:, :4].astype(np.float64)
+    dbox = np.stack((d64[:, 0], d64[:, 1], d64[:, 2] - d64[:, 0] + 1., d64[:, 3] - d64[:, 1] + 1.), 1)
+    darea = dbox[:, 2] * dbox[:, 3]
+    d_out = (darea[None, :] < area_r[:, :1]) | (darea[None, :] > area_r[:, 1:])  # [A,n]
+    score = det[:, 4].astype(np.float64)
+    thr = np.minimum(iou_t, 1 - 1e-10)
+
+    ok = (det_cls >= 0) & (det_cls < K) & (det_img >= 0) & (det_img < n_img)
+    cls_key = np.where(ok, det_cls, K)
+    order = np.lexsort((np.arange(n), det_img, -score, cls_key)).astype(np.int64)
+    cls_offsets = np.searchsorted(cls_key[order], np.arange(K + 1), side="left").astype(np.int64)
+    gok = (gt_cls >= 0) & (gt_cls < K) & (gt_img >= 0) & (gt_img < n_img)
+    segpos = np.full(n, -1, np.int64)
+    codes = np.full((A, T, n), 3, np.uint8)
+    matched = np.full((A, T, n), -1, np.int64)
+    npig = np.zeros((K, A), np.int64)
+    precision = -np.ones((T, R, K, A, M))
+    scores = -np.ones((T, R, K, A, M))
+    recall = -np.ones((T, K, A, M))
+    for k in range(K):
+        gsel = np.nonzero(gok & (gt_cls == k))[0]
+        npig[k] = (~gt_ig[:, gsel]).sum(1)
+        r0, r1 = int(cls_offsets[k]), int(cls_offsets[k + 1])
+        ranks = np.arange(r0, r1)
+        imgs = det_img[order[r0:r1]]
+        by_img = np.argsort(imgs, kind="stable")  # each image's ranks stay ascending: by score, then arrival
+        bounds = np.nonzero(np.diff(imgs[by_img]))[0] + 1
+        g_img = gt_img[gsel]
+        for seg in np.split(by_img, bounds) if r1 > r0 else []:
+            gi = gsel[g_img == imgs[seg[0]]]  # arrival order
+            seg_ranks = ranks[seg]
+            segpos[seg_ranks] = np.arange(seg_ranks.size)
+            seg_ranks = seg_ranks[:md[-1]]
+            rows = order[seg_ranks]
+            ng = gi.size
+            if ng == 0:
+                codes[:, :, seg_ranks] = np.where(d_out[:, rows], 0, 2)[:, None, :]
+                continue
+            ious = _bb_iou(dbox[rows], gt64[gi], crowd[gi])
+            ig = gt_ig[:, gi][:, None, :]  # [A,1,ng]
+            cr = crowd[gi][None, None, :]
+            taken = np.zeros((A, T, ng), bool)
+            aa, tt = np.meshgrid(np.arange(A), np.arange(T), indexing="ij")
+            for d in range(seg_ranks.size):
+                v = ious[d][None, None, :]
+                reach = v >= thr[None, :, None]
+                best_ni, j_ni = _last_argmax(np.where(~ig & ~taken & reach, v, -1.))
+                best_ig, j_ig = _last_argmax(np.where(ig & (cr | ~taken) & reach, v, -1.))
+                has_ni, has_ig = best_ni >= 0, best_ig >= 0
+                j = np.where(has_ni, j_ni, j_ig)
+                hit = has_ni | has_ig
+                taken[aa[hit], tt[hit], j[hit]] = True
+                codes[:, :, seg_ranks[d]] = np.where(has_ni, 1, np.where(has_ig | d_out[:, rows[d]][:, None], 0, 2))
+                matched[:, :, seg_ranks[d]] = np.where(hit, gi[j], -1)
+        sc = score[order[r0:r1]]
+        for a in range(A):
+            if npig[k, a] == 0:
+                continue
+            for m in range(M):
+                inside = segpos[r0:r1] < md[m]
+                for t in range(T):
+                    c = codes[a, t, r0:r1]
+                    keep = inside & ((c == 1) | (c == 2))
+                    tp = np.cumsum(c[keep] == 1).astype(np.float64)
+                    fp = np.cumsum(c[keep] == 2).astype(np.float64)
+                    nd = tp.size
+                    rc = tp / float(npig[k, a])
+                    pr = tp / (fp + tp + COCO_EPS)
+                    recall[t, k, a, m] = rc[-1] if nd else 0.
+                    pr = np.maximum.accumulate(pr[::-1])[::-1]
+                    inds = np.searchsorted(rc, rec_t, side="left")
+                    q, ss = np.zeros(R), np.zeros(R)
+                    q[inds < nd] = pr[inds[inds < nd]]
+                    ss[inds < nd] = sc[keep][inds[inds < nd]]
+                    precision[t, :, k, a, m] = q
+                    scores[t, :, k, a, m] = ss
+    return dict(order=order, cls_offsets=cls_offsets, segpos=segpos, codes=codes, matched=matched, npig=npig,
+                precision=precision, recall=recall, scores=scores)
+
+
+def coco_min_iou_margin(det, det_img, det_cls, gt_bbox, gt_img, gt_cls, n_img, iou_thrs, gt_iscrowd=None):
+    """min |bbIou - min(thr, 1 - 1e-10)| over every (detection, same class-and-image object, threshold): seeded cases assert
+    it stays above 1e-9, so that a last-bit difference in one double division cannot flip a decision"""
+    det = np.asarray(det, np.float32).reshape(-1, 5)
+    gt64 = np.asarray(gt_bbox, np.float32).reshape(-1, 4).astype(np.float64)
+    g = gt64.shape[0]
+    crowd = np.zeros(g, bool) if gt_iscrowd is None else np.asarray(gt_iscrowd).reshape(-1).astype(bool)
+    thr = np.minimum(np.asarray(iou_thrs, np.float64).reshape(-1), 1 - 1e-10)
+    d64 = det[:, :4].astype(np.float64)
+    dbox = np.stack((d64[:, 0], d64[:, 1], d64[:, 2] - d64[:, 0] + 1., d64[:, 3] - d64[:, 1] + 1.), 1)
+    dseg = np.asarray(det_cls, np.int64).reshape(-1) * n_img + np.asarray(det_img, np.int64).reshape(-1)
+    gseg = np.asarray(gt_cls, np.int64).reshape(-1) * n_img + np.asarray(gt_img, np.int64).reshape(-1)
+    margin = np.inf
+    for s in np.unique(dseg):
+        gi = np.nonzero(gseg == s)[0]
+        if gi.size == 0:
+            continue
+        ov = _bb_iou(dbox[dseg == s], gt64[gi], crowd[gi])
+        margin = min(margin, float(np.abs(ov[:, :, None] - thr[None, None, :]).min()))
+    return margin
+
+
+def _mean_valid_numpy(x):
+    x = np.asarray(x)[np.asarray(x) > -1]
+    return float(np.mean(x)) if x.size else -1.
+
+
+def coco_summarize_numpy(precision, recall):
+    """COCOeval.summarize() for the default parameters: the twelve numbers (COCO_SUMMARY_NAMES), each the mean of the
+    selected entries that are > -1, -1 when there are none"""
+    p, r = np.asarray(precision), np.asarray(recall)
+    if p.shape[:2] != (10, 101) or p.shape[3:] != (4, 3):
+        raise ValueError("summarize() is defined for COCOeval's default parameters only")
+    return np.asarray([_mean_valid_numpy(p[:, :, :, 0, 2]), _mean_valid_numpy(p[0, :, :, 0, 2]),
+                       _mean_valid_numpy(p[5, :, :, 0, 2]), _mean_valid_numpy(p[:, :, :, 1, 2]),
+                       _mean_valid_numpy(p[:, :, :, 2, 2]), _mean_valid_numpy(p[:, :, :, 3, 2]),
+                       _mean_valid_numpy(r[:, :, 0, 0]), _mean_valid_numpy(r[:, :, 0, 1]), _mean_valid_numpy(r[:, :, 0, 2]),
+                       _mean_valid_numpy(r[:, :, 1, 2]), _mean_valid_numpy(r[:, :, 2, 2]), _mean_valid_numpy(r[:, :, 3, 2])])
+
+
+def _mean_valid(x, dims=None):
+    """device: the mean of the entries > -1 (over `dims`, default all), -1 where there are none"""
+    mask = x > -1
+    dims = tuple(range(x.dim())) if dims is None else dims
+    cnt = mask.sum(dims)
+    tot = torch.where(mask, x, torch.zeros_like(x)).sum(dims)
+    return torch.where(cnt > 0, tot / cnt.clamp(min=1).to(torch.float64), torch.full_like(tot, -1.))
+
+
+class CocoEvalResult:
+    """Device tensors of one COCO `compute()`: precision / scores [T,R,K,A,M] and recall [T,K,A,M] float64 (-1 where the
+    class has no non-ignored object under the area range), npig [K,A] int32, order [n] and cls_offsets [K+1] int32; with
+    codes=True also codes uint8 [A,T,n] and segpos int32 [n], both by rank. The parameters are kept as host arrays."""
+
+    def __init__(self, precision, recall, scores, npig, order, cls_offsets, codes, segpos, params):
+        self.precision, self.recall, self.scores, self.npig = precision, recall, scores, npig
+        self.order, self.cls_offsets, self.codes, self.segpos = order, cls_offsets, codes, segpos
+        self.iou_thrs, self.rec_thrs, self.area_rng, self.max_dets = params
+
+    def summarize(self):
+        """-> [12] float64 device tensor, COCOeval.summarize()'s stats in its order (COCO_SUMMARY_NAMES). Defined for the
+        default parameters only, as COCOeval's is."""
+        if not _coco_is_default(self.iou_thrs, self.rec_thrs, self.area_rng, self.max_dets):
+            raise ValueError("summarize() is defined for COCOeval's default parameters only; precision / recall hold "
+                             "everything for others")
+        p, r = self.precision, self.recall
+        return torch.stack([_mean_valid(p[:, :, :, 0, 2]), _mean_valid(p[0, :, :, 0, 2]), _mean_valid(p[5, :, :, 0, 2]),
+                            _mean_valid(p[:, :, :, 1, 2]), _mean_valid(p[:, :, :, 2, 2]), _mean_valid(p[:, :, :, 3, 2]),
+                            _mean_valid(r[:, :, 0, 0]), _mean_valid(r[:, :, 0, 1]), _mean_valid(r[:, :, 0, 2]),
+                            _mean_valid(r[:, :, 1, 2]), _mean_valid(r[:, :, 2, 2]), _mean_valid(r[:, :, 3, 2])])
+
+    def per_class_ap(self):
+        """-> [K] float64 device tensor: the per-category AP of `_print_detection_eval_metrics` (coco_split.py:254-285),
+        the mean of precision[:, :, k, 0, -1] > -1 (-1 for a class without non-ignored objects)"""
+        return _mean_valid(self.precision[:, :, :, 0, -1], (0, 1))
+
+
+def eval_coco(det, det_img, det_cls, gt_bbox, gt_img, gt_cls, gt_area, gt_flags, n_img, n_cls, iou_thrs, rec_thrs,
+              area_rng, max_dets, params=None, codes=False):
+    """One `dana_eval_coco` call on device tensors: det [n,5] float32, ids int32, gt_bbox [g,4] float32 (x,y,w,h),
+    gt_area float64 [g], gt_flags uint8 [g] (bit 0 iscrowd, bit 1 ignore), iou_thrs [T] / rec_thrs [R] / area_rng [A,2]
+    float64 and max_dets [M] int32 -> CocoEvalResult. No synchronisation, no device-to-host copy. `params` are the host
+    copies of the four parameter arrays the result keeps for `summarize()`."""
+    det = ops._chk(det, "det")
+    dev = det.device
+    n, g = det.size(0), gt_bbox.size(0)
+    T, R, A, M = iou_thrs.numel(), rec_thrs.numel(), area_rng.numel() // 2, max_dets.numel()
+    K = int(n_cls)
+    ops._chk(det_img, "det_img", torch.int32), ops._chk(det_cls, "det_cls", torch.int32)
+    ops._chk(gt_bbox, "gt_bbox"), ops._chk(gt_img, "gt_img", torch.int32), ops._chk(gt_cls, "gt_cls", torch.int32)
+    ops._chk(gt_area, "gt_area", torch.float64), ops._chk(gt_flags, "gt_flags", torch.uint8)
+    ops._chk(iou_thrs, "iou_thrs", torch.float64), ops._chk(rec_thrs, "rec_thrs", torch.float64)
+    ops._chk(area_rng, "area_rng", torch.float64), ops._chk(max_dets, "max_dets", torch.int32)
+    if (det_img.numel() != n or det_cls.numel() != n or gt_img.numel() != g or gt_cls.numel() != g or gt_area.numel() != g
+            or gt_flags.numel() != g):
+        raise ValueError("eval_coco: id / area / flag tensors do not match %d detections / %d objects" % (n, g))
+    order = torch.empty((n,), dtype=torch.int32, device=dev)
+    cls_offsets = torch.empty((K + 1,), dtype=torch.int32, device=dev)
+    segpos = torch.empty((n,), dtype=torch.int32, device=dev)
+    cds = torch.empty((A, T, n), dtype=torch.uint8, device=dev)
+    npig = torch.empty((K, A), dtype=torch.int32, device=dev)
+    precision = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    scores = torch.empty((T, R, K, A, M), dtype=torch.float64, device=dev)
+    recall = torch.empty((T, K, A, M), dtype=torch.float64, device=dev)
+    ws = ops._ws(lib().query("dana_eval_coco_workspace_bytes", n, g, int(n_img), K, T, R, A, M), dev)
+    lib().call("dana_eval_coco", ops._p(det), ops._p(det_img), ops._p(det_cls), n, ops._p(gt_bbox), ops._p(gt_img),
+               ops._p(gt_cls), ops._p(gt_area), ops._p(gt_flags), g, int(n_img), K, ops._p(iou_thrs), T, ops._p(rec_thrs), R,
+               ops._p(area_rng), A, ops._p(max_dets), M, ops._p(order), ops._p(cls_offsets), ops._p(segpos), ops._p(cds),
+               ops._p(npig), ops._p(precision), ops._p(recall), ops._p(scores), ops._p(ws), ws.numel(), ops._stream())
+    if params is None:
+        params = (None, None, None, None)
+    return CocoEvalResult(precision, recall, scores, npig, order, cls_offsets, cds if codes else None,
+                          segpos if codes else None, params)
+
+
+class CocoEvaluator(_DetectionStore):
+    """COCO-protocol evaluator living on `device`: COCOeval for iouType = 'bbox' with its default parameters unless given.
+    Classes are 0..num_classes-1, images are the caller's indices. Detections come in as for `DetectionEvaluator`
+    (`add_packed`, `add_batched`, `add_by_class`: rows (x1,y1,x2,y2,score)); ground truth is COCO's own (x,y,w,h)."""
+
+    def __init__(self, num_classes, iou_thrs=None, rec_thrs=None, area_rng=None, max_dets=None, device="cuda"):
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError("CocoEvaluator: num_classes >= 1")
+        self.params = _coco_params(iou_thrs, rec_thrs, area_rng, max_dets)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("CocoEvaluator lives on a CUDA (HIP) device: this build has no CPU path")
+        self._params_dev = tuple(torch.from_numpy(p).to(self.device) for p in self.params)
+        self.reset()
+
+    def reset(self):
+        self._reset_detections()
+        self._gt = []  # (bbox [k,4] float32, image ids, labels int32, area [k] float64, flags [k] uint8) on the device
+        self._gt_cat = None
+
+    def _gt_rows(self, who, bbox, labels, iscrowd, area, ignore):
+        bbox = self._dev(bbox, torch.float32).reshape(-1, 4)
+        k = bbox.size(0)
+        labels = self._dev(labels, torch.int32).reshape(-1)
+        flags = torch.zeros((k,), dtype=torch.uint8, device=self.device)
+        for bit, x in ((1, iscrowd), (2, ignore)):
+            if x is not None:
+                x = self._dev(x, torch.int32).reshape(-1)
+                if x.numel() != k:
+                    raise ValueError("%s: %d objects, %d flags" % (who, k, x.numel()))
+                flags = flags | ((x != 0).to(torch.uint8) * bit)
+        if area is None:
+            b64 = bbox.to(torch.float64)
+            area = b64[:, 2] * b64[:, 3]
+        else:
+            area = self._dev(area, torch.float64).reshape(-1)
+        if labels.numel() != k or area.numel() != k:
+            raise ValueError("%s: %d objects, %d labels, %d areas" % (who, k, labels.numel(), area.numel()))
+        return bbox, labels, area.contiguous(), flags
+
+    def add_ground_truth(self, image_index, bbox_xywh, labels, iscrowd=None, area=None, ignore=None):
+        """the objects of one image: bbox [k,4] (x,y,w,h), labels [k] class indices, and per object iscrowd (default 0),
+        area (default w*h; COCO's annotation area is the segmentation's) and ignore (default 0)"""
+        bbox, labels, area, flags = self._gt_rows("add_ground_truth", bbox_xywh, labels, iscrowd, area, ignore)
+        image_index = int(image_index)
+        if image_index < 0:
+            raise ValueError("add_ground_truth: negative image index")
+        self.num_images = max(self.num_images, image_index + 1)
+        img = torch.full((bbox.size(0),), image_index, dtype=torch.int32, device=self.device)
+        self._gt.append((bbox, img, labels, area, flags))
+        self._gt_cat = None
+
+    def add_ground_truth_packed(self, bbox_xywh, img_ids, labels, iscrowd=None, area=None, ignore=None, num_images=None):
+        """the objects of many images at once, with per-row image ids (ids on the device need `num_images`)"""
+        bbox, labels, area, flags = self._gt_rows("add_ground_truth_packed", bbox_xywh, labels, iscrowd, area, ignore)
+        host_img = _host_ints(img_ids)
+        if num_images is not None:
+            self.num_images = max(self.num_images, int(num_images))
+        elif host_img is None:
+            raise ValueError("add_ground_truth_packed: img_ids live on the device; pass num_images")
+        elif host_img.size:
+            self.num_images = max(self.num_images, int(host_img.max()) + 1)
+        img = self._dev(img_ids, torch.int32).reshape(-1)
+        if img.numel() != bbox.size(0):
+            raise ValueError("add_ground_truth_packed: %d objects, %d image ids" % (bbox.size(0), img.numel()))
+        self._gt.append((bbox, img, labels, area, flags))
+        self._gt_cat = None
+
+    def _ground_truth(self):
+        if self._gt_cat is None:
+            if self._gt:
+                self._gt_cat = tuple(torch.cat([g[i] for g in self._gt], 0).contiguous() for i in range(5))
+            else:
+                e = lambda shape, dt: torch.empty(shape, dtype=dt, device=self.device)
+                self._gt_cat = (e((0, 4), torch.float32), e((0,), torch.int32), e((0,), torch.int32),
+                                e((0,), torch.float64), e((0,), torch.uint8))
+        return self._gt_cat
+
+    def compute(self, codes=False):
+        """-> CocoEvalResult (device tensors; nothing is synchronised or read back here)"""
+        gbox, gimg, gcls, garea, gflags = self._ground_truth()
+        det, img, cls = self._detections()
+        return eval_coco(det, img, cls, gbox, gimg, gcls, garea, gflags, max(self.num_images, 1), self.num_classes,
+                         *self._params_dev, params=self.params, codes=codes)
+
+
+def _annotation_arrays(objs):
+    """one image's objects -> (bbox, labels, iscrowd, area, ignore): a dict of arrays (bbox, labels and optionally
+    iscrowd / area / ignore), a tuple in that order, or a list of per-object dicts with bbox, category (the class index)
+    and optionally iscrowd / area / ignore"""
+    if isinstance(objs, dict):
+        return tuple(objs.get(k) for k in ("bbox", "labels", "iscrowd", "area", "ignore"))
+    if isinstance(objs, tuple):
+        return tuple(objs) + (None,) * (5 - len(objs))
+    bbox = np.asarray([o["bbox"] for o in objs], np.float32).reshape(-1, 4)
+    labels = np.asarray([o["category"] for o in objs], np.int32)
+    crowd = np.asarray([o.get("iscrowd", 0) for o in objs], np.int32)
+    ignore = np.asarray([o.get("ignore", 0) for o in objs], np.int32)
+    area = np.asarray([o["area"] if "area" in o else float(np.float32(o["bbox"][2])) * float(np.float32(o["bbox"][3]))
+                       for o in objs], np.float64)
+    return bbox, labels, crowd, area, ignore
+
+
+def evaluate_coco_boxes(all_boxes, annotations, iou_thrs=None, rec_thrs=None, area_rng=None, max_dets=None, device="cuda",
+                        codes=False):
+    """Drop-in for what coco_split.py:338-349 (`_write_coco_results_file` + `_do_detection_eval`) does with
+    `all_boxes`: all_boxes[j][i] is the [k,5] array (x1,y1,x2,y2,score) of class j on image i, as inference.py fills it
+    (an empty list where nothing was detected); annotations[i] are image i's objects (see `_annotation_arrays`), their
+    class indices indexing all_boxes' j. A background class 0 the caller leaves empty has no objects and comes out -1,
+    outside every mean. -> CocoEvalResult: `.summarize()` are the twelve numbers COCOeval prints, `.per_class_ap()` the
+    per-category table."""
+    C = len(all_boxes)
+    n_img = len(annotations)
+    ev = CocoEvaluator(C, iou_thrs, rec_thrs, area_rng, max_dets, device)
+    rows, imgs, clss = [], [], []
+    for j in range(C):
+        for i in range(len(all_boxes[j])):
+            d = np.asarray(all_boxes[j][i], np.float32).reshape(-1, 5)
+            if d.shape[0]:
+                rows.append(d)
+                imgs.append(np.full(d.shape[0], i, np.int32))
+                clss.append(np.full(d.shape[0], j, np.int32))
+            n_img = max(n_img, i + 1)
+    for i, objs in enumerate(annotations):
+        bbox, labels, crowd, area, ignore = _annotation_arrays(objs)
+        if len(labels):
+            ev.add_ground_truth(i, bbox, labels, crowd, area, ignore)
+    if rows:
+        ev.add_packed(np.concatenate(rows, 0), np.concatenate(imgs), np.concatenate(clss), num_images=n_img)
+    ev.num_images = max(ev.num_images, n_img)
+    return ev.compute(codes=codes)

@@ -734,7 +734,8 @@ int dana_program_run(void* program, int begin, int end);
 
 /* ---- detection evaluation: lib/datasets/voc_eval.py (the last line of inference.py, :181) ---------------------------------
  * The VOC protocol on the device, in float64: NOT COCOeval (no crowd regions, area ranges or maxDets). Evaluating at the
- * thresholds 0.50:0.05:0.95 is voc_eval called with ten `ovthresh` values, done here in one pass. */
+ * thresholds 0.50:0.05:0.95 is voc_eval called with ten `ovthresh` values, done here in one pass. The COCO protocol is
+ * dana_eval_coco, at the end of this section. */
 
 /* Grows the evaluator's detection buffers (what pascal_voc.py:268-291 writes to per-class text files and voc_eval.py:143-151
  * parses again): the packed rows of n_problems detection sets -> det[capacity][5] / det_img / det_cls from row dst_base on.
@@ -764,6 +765,35 @@ int dana_eval_ap(const float* det, const int* det_img, const int* det_cls, long 
                  const int* gt_img, const int* gt_cls, const unsigned char* gt_difficult, long g, int n_img, int n_cls,
                  const void* iou_thr, int n_thr, int use_07_metric, int* order, int* cls_offsets, void* tpfp, void* rec,
                  void* prec, void* ap, int* npos, void* workspace, size_t workspace_bytes, dana_stream_t stream);
+
+/* The COCO protocol: what lib/datasets/coco_split.py:287-298 asks of pycocotools -- COCOeval.evaluate() and accumulate()
+ * for iouType = 'bbox' with maskApi's bbIou -- restated from the published algorithm (pycocotools is not part of the
+ * reference tree). Float64, unfused. 0 for a shape dana_eval_coco refuses. */
+size_t dana_eval_coco_workspace_bytes(long n, long g, int n_img, int n_cls, int n_thr, int n_rec, int n_area,
+                                      int n_max_dets);
+/* det[n][5] = (x1, y1, x2, y2, score) with det_img / det_cls; a detection is the COCO box (x1, y1, x2 - x1 + 1,
+ * y2 - y1 + 1) of coco_split.py:308-312. Ground truth: gt_bbox[g][4] = (x, y, w, h), gt_img, gt_cls, gt_area[g] (C
+ * `double`: the annotation's area), gt_flags[g] (bytes: bit 0 = iscrowd, bit 1 = ignore). Rows whose ids are outside
+ * [0, n_img) x [0, n_cls) take no part. Parameters, all in device memory and used as given: iou_thrs[n_thr] (1..16),
+ * rec_thrs[n_rec] (1..128, ascending), area_rng[n_area][2] (1..4) as C `double`, max_dets[n_max_dets] (1..4, ascending).
+ *   order[n]: detection index by rank -- class ascending, score descending, image ascending, arrival (COCOeval's stable
+ *     mergesort over the per-image lists); cls_offsets[n_cls + 1] as in dana_eval_ap; segpos[n] by rank: the place of the
+ *     detection among those of its (class, image) by score, -1 for rows that take no part;
+ *   codes[n_area][n_thr][n] bytes by rank (evaluateImg): 1 = matched a non-ignored object, 0 = ignored (matched an
+ *     ignored object, or unmatched with its own area outside the range), 2 = unmatched, 3 = at or past max_dets[last] in
+ *     its (class, image) or taking no part. An object is ignored under a range when ignore | iscrowd | area outside; a
+ *     detection takes the available object of the largest IoU >= min(t, 1 - 1e-10) (the last of equals) among the
+ *     non-ignored ones, else among the ignored ones; a crowd stays available and its IoU divides by the detection's area;
+ *   npig[n_cls][n_area]: non-ignored objects; precision / scores [n_thr][n_rec][n_cls][n_area][n_max_dets] and recall
+ *     [n_thr][n_cls][n_area][n_max_dets] (accumulate): -1 where npig == 0.
+ * Doubles and bytes are passed as void* / const void*. Fixed positions, no sums across threads: two calls give the same
+ * bits. No synchronisation, no device-to-host copy. */
+int dana_eval_coco(const float* det, const int* det_img, const int* det_cls, long n, const float* gt_bbox,
+                   const int* gt_img, const int* gt_cls, const void* gt_area, const unsigned char* gt_flags, long g,
+                   int n_img, int n_cls, const void* iou_thrs, int n_thr, const void* rec_thrs, int n_rec,
+                   const void* area_rng, int n_area, const int* max_dets, int n_max_dets, int* order, int* cls_offsets,
+                   int* segpos, void* codes, int* npig, void* precision, void* recall, void* scores, void* workspace,
+                   size_t workspace_bytes, dana_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -4,6 +4,7 @@ the code without the evaluator forces: a device-to-host copy of all detections p
 (`evaluate.voc_numpy`), by default at a tenth of the images because it takes minutes at full size.
 
   python tools/evaluate_bench.py                       # 5 000 images x 20 classes x up to 100 detections, T = 1 and 10
+  python tools/evaluate_bench.py --protocol coco       # the same data with some crowd objects, COCOeval's defaults
   rocprofv3 --kernel-trace --stats -d DIR -- python tools/evaluate_bench.py --profile-run --thresholds 10
 
 Prints one JSON line per configuration. Synthetic seeded data: per (class, image) 0..max-dets detections (60 % of them
@@ -72,8 +73,91 @@ def fill(ev, d, n_img):
         ev.add_packed(d["det"][lo:lo + step], d["det_img"][lo:lo + step], d["det_cls"][lo:lo + step])
 
 
+def timed(compute, warmup, iters):
+    """-> (ms per call by HIP events [iters], the last result)"""
+    for _ in range(warmup):
+        res = compute()
+    torch.cuda.synchronize()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    times = []
+    for _ in range(iters):
+        e0.record()
+        res = compute()
+        e1.record()
+        e1.synchronize()
+        times.append(e0.elapsed_time(e1))
+    return np.asarray(times), res
+
+
+def coco_form(d, crowd_share=0.05, seed=7):
+    """the ground truth of make() as COCO's: (x, y, w, h) with the reference's + 1 widths, some objects crowd"""
+    b = d["gt_box"]
+    bbox = np.stack((b[:, 0], b[:, 1], b[:, 2] - b[:, 0] + 1, b[:, 3] - b[:, 1] + 1), 1).astype(np.float32)
+    crowd = (np.random.RandomState(seed).rand(b.shape[0]) < crowd_share).astype(np.uint8)
+    return bbox, crowd
+
+
+def fill_coco(ev, d, n_img):
+    bbox, crowd = coco_form(d)
+    ev.add_ground_truth_packed(bbox, d["gt_img"], d["gt_cls"], crowd, num_images=n_img)
+    step = 1 << 18
+    for lo in range(0, d["det"].shape[0], step):
+        ev.add_packed(d["det"][lo:lo + step], d["det_img"][lo:lo + step], d["det_cls"][lo:lo + step])
+    return bbox, crowd
+
+
+def main_coco(a, dev):
+    """COCOeval's default parameters (T = 10, R = 101, A = 4, M = 3) on the data of make()"""
+    d = make(a.images, a.classes, a.max_dets)
+    n, g = d["det"].shape[0], d["gt_box"].shape[0]
+    ev = E.CocoEvaluator(a.classes, device=dev)
+    fill_coco(ev, d, a.images)
+    if a.profile_run:
+        for _ in range(5):
+            res = ev.compute()
+        torch.cuda.synchronize()
+        print(json.dumps({"profile_run": True, "protocol": "coco", "n": n, "g": g, "summary": res.summarize().cpu().tolist()}))
+        return
+    times, res = timed(ev.compute, a.warmup, a.iters)
+    out = {"protocol": "coco", "images": a.images, "classes": a.classes, "detections": n, "ground_truth": g,
+           "thresholds": 10, "area_ranges": 4, "max_dets": list(E.COCO_MAX_DETS),
+           "compute_ms_median": float(np.median(times)), "compute_ms_min": float(times.min()),
+           "compute_ms_p90": float(np.percentile(times, 90)), "iters": a.iters, "warmup": a.warmup,
+           "workspace_MiB": E.lib().query("dana_eval_coco_workspace_bytes", n, g, a.images, a.classes, 10, 101, 4, 3) / 2 ** 20,
+           "summary": dict(zip(E.COCO_SUMMARY_NAMES, [round(x, 6) for x in res.summarize().cpu().tolist()]))}
+    # the nearest existing workload on the same data in the same process: the VOC compute() at T = 10
+    voc = E.DetectionEvaluator(a.classes, E.COCO_THRESHOLDS, device=dev)
+    fill(voc, d, a.images)
+    vt, _ = timed(voc.compute, a.warmup, a.iters)
+    out.update(voc_T10_compute_ms_median=float(np.median(vt)), coco_over_voc=float(np.median(times) / np.median(vt)),
+               curve_work_factor_A_times_M=12)
+    del voc
+    if a.host_scale > 0:
+        hi = max(int(a.images * a.host_scale), 1)
+        ds = make(hi, a.classes, a.max_dets, seed=1)
+        ev_small = E.CocoEvaluator(a.classes, device=dev)
+        bbox, crowd = fill_coco(ev_small, ds, hi)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        rows = ev_small._det[:ev_small.num_rows].cpu().numpy()  # what the code without the evaluator has to do
+        img, cls = ev_small._img[:ev_small.num_rows].cpu().numpy(), ev_small._cls[:ev_small.num_rows].cpu().numpy()
+        t1 = time.perf_counter()
+        ref = E.coco_numpy(rows, img, cls, bbox, ds["gt_img"], ds["gt_cls"], hi, a.classes, crowd)
+        t2 = time.perf_counter()
+        got = ev_small.compute()
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        st, _ = timed(ev_small.compute, 3, 10)
+        diff = float(np.abs(got.summarize().cpu().numpy() - E.coco_summarize_numpy(ref["precision"], ref["recall"])).max())
+        out.update(host_images=hi, host_detections=int(rows.shape[0]), host_d2h_s=t1 - t0, host_numpy_s=t2 - t1,
+                   device_same_size_wall_s=t3 - t2, device_same_size_ms_median=float(np.median(st)),
+                   host_vs_device_max_summary_diff=diff)
+    print(json.dumps(out), flush=True)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--protocol", choices=("voc", "coco"), default="voc")
     ap.add_argument("--images", type=int, default=5000)
     ap.add_argument("--classes", type=int, default=20)
     ap.add_argument("--max-dets", type=int, default=100)
@@ -86,6 +170,8 @@ def main():
     if not torch.cuda.is_available():
         raise SystemExit("evaluate_bench.py measures on the GPU; none is visible")
     dev = torch.device("cuda:0")
+    if a.protocol == "coco":
+        return main_coco(a, dev)
     d = make(a.images, a.classes, a.max_dets)
     n, g = d["det"].shape[0], d["gt_box"].shape[0]
     for T in [int(x) for x in a.thresholds.split(",")]:
