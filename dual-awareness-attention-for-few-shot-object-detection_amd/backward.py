@@ -58,15 +58,7 @@ class WeightGrads:
     def add_conv(self, key, g, x, n, h, w, c, in_stride=0, grad_stride=0, v=None):
         """v: the forward launch's kept Winograd workspace (V planes of x), if that conv ran in the F(4x4,3x3) domain"""
         self.convs[key] = c
-        if self.stream is None:
-            self._launch(key, g, x, n, h, w, c, in_stride, grad_stride, v)
-            return
-        st, keep = self._side_for_current()
-        ready = ops.record_event()
-        st.wait_event(ready)
-        keep.append((g, x, v))
-        with ops.on_stream(st):
-            self._launch(key, g, x, n, h, w, c, in_stride, grad_stride, v)
+        self.side_run(lambda: self._launch(key, g, x, n, h, w, c, in_stride, grad_stride, v), g, x, v)
 
     def side_run(self, fn, *keep):
         """fn() on the weight-gradient stream of the caller's stream, behind everything queued so far; `keep` stays
@@ -76,8 +68,7 @@ class WeightGrads:
             fn()
             return
         st, kept = self._side_for_current()
-        ready = ops.record_event()
-        st.wait_event(ready)
+        st.wait_event(ops.record_event())
         kept.append(keep)
         with ops.on_stream(st):
             fn()
@@ -103,51 +94,40 @@ class WeightGrads:
                 ent = self.compact[ck] = (ops.downsample_gather(x, n, h, w, c["cin"], c["stride"], in_stride), x)
             (x, h, w), in_stride = ent[0], 0
             c = dict(c, stride=1)
+        # into the trainer's view (scaled by the frozen BN and accumulated straight into param.grad: nothing to finish),
+        # else into the key's packed buffer, allocated by its first launch
+        out = view if view is not None else self.packed.get(key)
+        row_scale = c.get("scale") if view is not None else None
         u = c.get("u")
         if u is not None and u.size(0) == 36 and c["cin"] % 64 == 0:
             # the conv ran in the F(4x4,3x3) domain forward: so does its weight gradient (4x fewer multiplies)
-            out = view if view is not None else self.packed.get(key)
             res = ops.conv3x3_wgrad_winograd(g, x, n, h, w, c["cin"], c["cout"], in_stride=in_stride,
-                                             grad_stride=grad_stride, out=out,
-                                             row_scale=c.get("scale") if view is not None else None,
-                                             v=v)
-            if out is None:
-                self.packed[key] = res
-            return
-        if view is not None:  # scale by the frozen BN and accumulate straight into param.grad: nothing to finish
-            ops.conv2d_wgrad(g, x, n, h, w, c["cin"], c["cout"], c["k"], c["k"], c["stride"], c["pad"],
-                             in_stride=in_stride, grad_stride=grad_stride, out=view, row_scale=c.get("scale"))
-            return
-        buf = self.packed.get(key)
-        if buf is None:
-            self.packed[key] = ops.conv2d_wgrad(g, x, n, h, w, c["cin"], c["cout"], c["k"], c["k"], c["stride"],
-                                                c["pad"], in_stride=in_stride, grad_stride=grad_stride)
+                                             grad_stride=grad_stride, out=out, row_scale=row_scale, v=v)
         else:
-            ops.conv2d_wgrad(g, x, n, h, w, c["cin"], c["cout"], c["k"], c["k"], c["stride"], c["pad"],
-                             in_stride=in_stride, grad_stride=grad_stride, out=buf)
+            res = ops.conv2d_wgrad(g, x, n, h, w, c["cin"], c["cout"], c["k"], c["k"], c["stride"], c["pad"],
+                                   in_stride=in_stride, grad_stride=grad_stride, out=out, row_scale=row_scale)
+        if out is None:
+            self.packed[key] = res
 
     def join(self):
         """the caller's stream waits for every weight-gradient launch issued so far"""
-        if self.stream is None:
-            self.compact.clear()
-            del _FRESH.grads[:]
-            return
-        cur = ops.cur_stream()
-        for t in _FRESH.grads:
-            t.record_stream(cur)
+        if self.stream is not None:
+            cur = ops.cur_stream()
+            for t in _FRESH.grads:
+                t.record_stream(cur)
+            # the packed gradients were allocated in the weight-gradient stream's pool and are finished on the CALLER's
+            # stream (finish_conv): without this a buffer popped there goes back to that pool while the caller's kernel still
+            # reads it -- harmless as long as every caller had a weight-gradient stream to itself, a wrong RPN_Conv gradient
+            # with the one shared stream of round 5 (the trunk's next weight gradient took the block)
+            for t in self.packed.values():
+                t.record_stream(cur)
+            for st, keep in self.side.values():
+                if keep:
+                    done = torch.cuda.Event()
+                    done.record(st)
+                    cur.wait_event(done)
+                    del keep[:]
         del _FRESH.grads[:]
-        # the packed gradients were allocated in the weight-gradient stream's pool and are finished on the CALLER's stream
-        # (finish_conv): without this a buffer popped there goes back to that pool while the caller's kernel still reads it --
-        # harmless as long as every caller had a weight-gradient stream to itself, a wrong RPN_Conv gradient with the one
-        # shared stream of round 5 (the trunk's next weight gradient took the block)
-        for t in self.packed.values():
-            t.record_stream(cur)
-        for st, keep in self.side.values():
-            if keep:
-                done = torch.cuda.Event()
-                done.record(st)
-                cur.wait_event(done)
-                del keep[:]
         self.compact.clear()
 
     def finish_conv(self, key, c, param):
@@ -183,13 +163,6 @@ def conv_dgrad(g, n, h, w, c, residual=None, mask=None, compact_out=False, out=N
     wd, ud = _dgrad_weights(c)
     return ops.conv2d_dgrad(g, c["w"], n, h, w, c["cin"], c["cout"], c["k"], c["k"], c["stride"], c["pad"], wd=wd, ud=ud,
                             residual=residual, mask=mask, compact_out=compact_out, out=out)
-
-
-def conv_backward(g, x, n, h, w, c, grads, key, need_dx=True, in_stride=0):
-    """g: gradient w.r.t. the conv+BN output [n*oh*ow][cout] (ReLU mask already applied).
-    Records dW (raw, scale applied at finish) and returns dx [n*h*w][cin] (or None)."""
-    grads.add_conv(key, g, x, n, h, w, c, in_stride=in_stride)
-    return conv_dgrad(g, n, h, w, c) if need_dx else None
 
 
 def bottleneck_backward(g, saved, n, h, w, bp, grads, key, need_dx=True, mask_dx=True, g_masked=False):
@@ -258,26 +231,23 @@ def _block_convs(prefix, bp):
     return names
 
 
-def grad_stages(model, plan=None):
-    """[(stage, [parameter names])] in the order model_backward FINISHES the gradients: the trainer lays its flat
-    gradient buffer out in this order so that all-reduce buckets can leave while the rest of the backward runs.
-    plan: the forward's plan (the backward passes the one its context saved: asking the model for a plan INSIDE the
-    backward -- autograd runs it with gradients disabled, i.e. not `_live()` -- re-derived and pre-split every trainable
-    weight once per iteration for nothing: ~100 small launches at the head of the backward)."""
-    if type(model).__name__ in ("FasterRCNN", "MetaRCNN", "FGN", "FSOD"):
-        return frcnn_grad_stages(model, plan)
-    plan = plan if plan is not None else model._get_plan()
-    lin = lambda n: [n + ".weight", n + ".bias"]  # noqa: E731
-    st = [("box branch", lin("RCNN_bbox_pred") + [n for bi in (2, 1, 0)
-                                                 for n in _block_convs("RCNN_top.0.%d" % bi, plan["layer4"][bi])])]
-    st.append(("roi heads", lin("output_score_layer.linear2") + lin("output_score_layer.linear1")
-               + lin("rcnn_adapt_q_layer") + lin("rcnn_transform_layer") + lin("rcnn_adapt_k_layer")
-               + lin("rcnn_unary_layer")))
-    rpn_att = lin("rpn_adapt_q_layer") + lin("rpn_adapt_k_layer") + lin("rpn_unary_layer")
-    if model.semantic_enhance:
-        rpn_att += lin("rpn_channel_k_layer")
-    st.append(("rpn", lin("RCNN_rpn.RPN_cls_score") + lin("RCNN_rpn.RPN_bbox_pred") + lin("RCNN_rpn.RPN_Conv") + rpn_att))
-    for li in (2, 1):  # RCNN_base.6 (layer3) then RCNN_base.5 (layer2); layer1 is frozen
+def lin(name):
+    return [name + ".weight", name + ".bias"]
+
+
+RPN_PARAMS = lin("RCNN_rpn.RPN_cls_score") + lin("RCNN_rpn.RPN_bbox_pred") + lin("RCNN_rpn.RPN_Conv")
+
+
+def top_params(plan):
+    """RCNN_top's (layer4's) conv weights, in the order layer4_backward finishes them"""
+    return [n for bi in (2, 1, 0) for n in _block_convs("RCNN_top.0.%d" % bi, plan["layer4"][bi])]
+
+
+def base_stages(plan):
+    """one stage per trainable trunk block, last block first: RCNN_base.6 (layer3) then RCNN_base.5 (layer2); layer1 is
+    frozen"""
+    st = []
+    for li in (2, 1):
         layer = plan["layers"][li]
         for bi in reversed(range(len(layer))):
             key = "RCNN_base.%d.%d" % (4 + li, bi)
@@ -285,14 +255,42 @@ def grad_stages(model, plan=None):
     return st
 
 
-def _ready(model, names):
+def grad_stages(model, plan=None):
+    """[(stage, [parameter names])] in the order model_backward FINISHES the gradients (the model's class knows it:
+    `_grad_stages`): the trainer lays its flat gradient buffer out in this order so that all-reduce buckets can leave
+    while the rest of the backward runs.
+    plan: the forward's plan (the backward passes the one its context saved: asking the model for a plan INSIDE the
+    backward -- autograd runs it with gradients disabled, i.e. not `_live()` -- re-derived and pre-split every trainable
+    weight once per iteration for nothing: ~100 small launches at the head of the backward)."""
+    return model._grad_stages(plan if plan is not None else model._get_plan())
+
+
+def dana_grad_stages(model, plan):
+    st = [("box branch", lin("RCNN_bbox_pred") + top_params(plan))]
+    st.append(("roi heads", lin("output_score_layer.linear2") + lin("output_score_layer.linear1")
+               + lin("rcnn_adapt_q_layer") + lin("rcnn_transform_layer") + lin("rcnn_adapt_k_layer")
+               + lin("rcnn_unary_layer")))
+    rpn_att = lin("rpn_adapt_q_layer") + lin("rpn_adapt_k_layer") + lin("rpn_unary_layer")
+    if model.semantic_enhance:
+        rpn_att += lin("rpn_channel_k_layer")
+    st.append(("rpn", RPN_PARAMS + rpn_att))
+    return st + base_stages(plan)
+
+
+def sibling_grad_stages(plan, head_params):
+    """the sibling detectors (frcnn.py, fsod.py, fgn.py): one RoI stage (RCNN_bbox_pred, the class's `_head_params`,
+    layer4), the RPN, the trunk"""
+    return [("roi head", lin("RCNN_bbox_pred") + head_params + top_params(plan)), ("rpn", RPN_PARAMS)] + base_stages(plan)
+
+
+def ready(model, names):
     cb = getattr(model, "_grad_ready_cb", None)
     if cb is not None:
         cb(names)
 
 
 class _Fresh(__import__("threading").local):
-    """gradients _acc() allocated since the last WeightGrads.join() (possibly in a side stream's pool); per THREAD: under
+    """gradients acc() allocated since the last WeightGrads.join() (possibly in a side stream's pool); per THREAD: under
     nn.DataParallel every replica's backward runs in its own thread (train.py:104-105)"""
 
     def __init__(self):
@@ -302,7 +300,7 @@ class _Fresh(__import__("threading").local):
 _FRESH = _Fresh()
 
 
-def _acc(param, g):
+def acc(param, g):
     g = g.view_as(param)
     if param.grad is None:
         # (the reference's optimizer.zero_grad() sets grads to None, so the bridge path comes here every iteration.)
@@ -351,6 +349,15 @@ def _rpn_conv_plan(model, ctx):
     return c
 
 
+def _derive_dgrad_weights(blocks):
+    """the data-gradient weights of the given block plans' convs, in the order the backward needs them (each is derived
+    once per weight update: _dgrad_weights)"""
+    for bp in blocks:
+        for name in ("c3", "c2", "c1", "ds"):
+            if bp.get(name) is not None:
+                _dgrad_weights(bp[name])
+
+
 def prefetch_dgrad_weights(model, ctx, dev):
     """The backward's weight-only launches (flipped / transposed / BN-scaled data-gradient weights and their Winograd
     transforms: ~70 per iteration, 0.3-0.4 ms of kernels) issued from the SAVING FORWARD behind the RPN head, on the role
@@ -367,15 +374,9 @@ def prefetch_dgrad_weights(model, ctx, dev):
     prep.wait_event(ev0)  # (behind the optimizer's update of the weights on the caller's stream)
     with ops.on_stream(prep):
         _dgrad_weights(_rpn_conv_plan(model, ctx))
-        for bp in reversed(plan["layer4"]):
-            for name in ("c3", "c2", "c1", "ds"):
-                if bp.get(name) is not None:
-                    _dgrad_weights(bp[name])
+        _derive_dgrad_weights(reversed(plan["layer4"]))
         for layer in reversed(plan["layers"][1:]):  # (layer1 is frozen and in front of every trainable layer: no data gradient)
-            for bp in reversed(layer):
-                for name in ("c3", "c2", "c1", "ds"):
-                    if bp.get(name) is not None:
-                        _dgrad_weights(bp[name])
+            _derive_dgrad_weights(reversed(layer))
         ctx["dgw_prefetched"] = ops.record_event()
 
 
@@ -401,14 +402,14 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
                                     inside_weight=cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS[0], grad_dev=g_dev)
     ns = rpn.nc_score_out
     grads_r.linear(d_heads, ctx["rpn_x"], B * hw, nh, 512,
-                 lambda dw, db: (_acc(rpn.RPN_cls_score.weight, dw[:ns]), _acc(rpn.RPN_cls_score.bias, db[:ns]),
-                                 _acc(rpn.RPN_bbox_pred.weight, dw[ns:]), _acc(rpn.RPN_bbox_pred.bias, db[ns:])))
+                 lambda dw, db: (acc(rpn.RPN_cls_score.weight, dw[:ns]), acc(rpn.RPN_cls_score.bias, db[:ns]),
+                                 acc(rpn.RPN_bbox_pred.weight, dw[ns:]), acc(rpn.RPN_bbox_pred.bias, db[ns:])))
     _, _, d_x = ops.linear_backward(d_heads, ctx["rpn_x"], plan["rpn_head_w"], B * hw, nh, 512, need_dw=False)
     ops.relu_mask_(d_x, ctx["rpn_x"], B * hw, 512)
     if rpnw_ready is not None:
         ops.cur_stream().wait_event(rpnw_ready)
     grads_r.add_conv("RCNN_rpn.RPN_Conv", d_x, corr, B, fh, fw, c_rpn, v=ctx.get("rpn_v"))
-    _acc(rpn.RPN_Conv.bias, ops.colsum(d_x, B * hw, 512))
+    acc(rpn.RPN_Conv.bias, ops.colsum(d_x, B * hw, 512))
     d_corr = conv_dgrad(d_x, B, fh, fw, c_rpn)  # [B*hw][2048]
 
     # -- RPN-level attention (dana.py:118-154): corr = [base_feat | dense] --
@@ -423,16 +424,16 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
     ops.colmean_sub_(d_kp, B * shot, L, d)
     wq = model.rpn_adapt_q_layer.weight.detach()
     grads_r.linear(d_qp, corr, B * hw, d, 1024,
-                 lambda dw, db: (_acc(model.rpn_adapt_q_layer.weight, dw), _acc(model.rpn_adapt_q_layer.bias, db)), ldx=2048)
+                 lambda dw, db: (acc(model.rpn_adapt_q_layer.weight, dw), acc(model.rpn_adapt_q_layer.bias, db)), ldx=2048)
     ops.linear_backward(d_qp, corr, wq, B * hw, d, 1024, ldx=2048, dx_out=d_corr, dx_ld=2048, need_dw=False)
     wk = model.rpn_adapt_k_layer.weight.detach()
     grads_r.linear(d_kp, s_pe, B * K1, d, 1024,
-                 lambda dw, db: (_acc(model.rpn_adapt_k_layer.weight, dw), _acc(model.rpn_adapt_k_layer.bias, db)))
+                 lambda dw, db: (acc(model.rpn_adapt_k_layer.weight, dw), acc(model.rpn_adapt_k_layer.bias, db)))
     ops.linear_backward(d_kp, s_pe, wk, B * K1, d, 1024, dx_out=d_s_pe, dx_ld=1024, need_dw=False)
     ops.softmax_rows_backward_(d_un, unary, B * shot, L)
     wu = model.rpn_unary_layer.weight.detach()
-    _acc(model.rpn_unary_layer.weight, ops.rowdot_backward(s_pe, d_un, wu, B * K1, 1024, grad_x=d_s_pe))
-    _acc(model.rpn_unary_layer.bias, ops.colsum(d_un, B * K1, 1))
+    acc(model.rpn_unary_layer.weight, ops.rowdot_backward(s_pe, d_un, wu, B * K1, 1024, grad_x=d_s_pe))
+    acc(model.rpn_unary_layer.bias, ops.colsum(d_un, B * K1, 1))
     if model.semantic_enhance:  # BA block (dana.py:133-137)
         s_pre, ba_w = ctx["s_pre"], ctx["ba_w"]
         G = B * shot
@@ -440,30 +441,10 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
         d_w = ops.ba_backward_(d_s_pe, s_pre, ba_w, gvec, gsum, G, L, 1024, gamma=model.channel_gamma, slope=0.01)
         ops.softmax_rows_backward_(d_w, ba_w, G, L)
         wc = model.rpn_channel_k_layer.weight.detach()
-        _acc(model.rpn_channel_k_layer.weight, ops.rowdot_backward(s_pre, d_w, wc, G * L, 1024, grad_x=d_s_pe))
-        _acc(model.rpn_channel_k_layer.bias, ops.colsum(d_w, G * L, 1))
+        acc(model.rpn_channel_k_layer.weight, ops.rowdot_backward(s_pre, d_w, wc, G * L, 1024, grad_x=d_s_pe))
+        acc(model.rpn_channel_k_layer.bias, ops.colsum(d_w, G * L, 1))
     grads_r.finish_all(model, "RCNN_rpn")
     return d_corr, d_s_pe
-
-
-
-def _take_ctx(model, ctx):
-    """the saved-for-backward context to differentiate: the one handed in (the loss bridge captured it at forward time)
-    or the model's latest. A context is consumed exactly once; its tensors are released here."""
-    if ctx is None:
-        ctx = model._ctx
-    if ctx is None or ctx.get("consumed"):
-        raise RuntimeError("no saved training forward to differentiate (run a train-mode forward with grad enabled "
-                           "or model.save_for_backward = True first; each forward can be differentiated once)")
-    return ctx
-
-
-def _release_ctx(model, ctx):
-    keep = {"consumed": True}
-    ctx.clear()
-    ctx.update(keep)
-    if model._ctx is ctx:
-        model._ctx = None
 
 
 def model_backward(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
@@ -473,149 +454,127 @@ def model_backward(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
 
 
 def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
-    """(generator; pauses ONCE, where the gradients of everything except the trunk are final and every side stream is
-    joined into the caller's stream: graphs.GraphedTrainer ends one hipGraph there and starts the next, so that the
-    RCCL all-reduce of the finished buckets overlaps the trunk's backward)
+    """(generator; for DAnA it pauses ONCE, where the gradients of everything except the trunk are final and every side
+    stream is joined into the caller's stream: graphs.GraphedTrainer ends one hipGraph there and starts the next, so that
+    the RCCL all-reduce of the finished buckets overlaps the trunk's backward. The sibling detectors do not pause.)
 
     d(sum_i grad_losses[i] * loss_i)/d(parameters) for the four training losses (rpn_loss_cls, rpn_loss_bbox,
     RCNN_loss_cls, RCNN_loss_bbox) of the last `save_for_backward` forward: what train.py:141-143's
     `loss.backward()` computes, accumulated into `.grad` of the trainable parameters (BN, conv1 and layer1 are
-    frozen: dana.py:350-385)."""
-    if type(model).__name__ in ("FasterRCNN", "MetaRCNN", "FGN", "FSOD"):
-        frcnn_backward(model, grad_losses, ctx=ctx)
-        return
-    ctx = _take_ctx(model, ctx)
-    plan = ctx["plan"]
-    B, shot, way, R, Ns = ctx["B"], ctx["shot"], ctx["way"], ctx["R"], ctx["Ns"]
-    fh, fw = ctx["fh"], ctx["fw"]
-    hw = fh * fw
-    P2 = 49
-    L = ctx["s_pe"].size(1) // shot  # positions of a support map (400 for the reference's 320x320 supports)
-    n_roi = B * R
-    d, dq = model.rpn_reduce_dim, model.rcnn_reduce_dim
-    g_dev = None
-    if isinstance(grad_losses, torch.Tensor):  # upstream gradients stay on the device: no host sync in the backward
-        g_dev = grad_losses.detach().to(torch.float32).contiguous()
-        g1 = g2 = g3 = g4 = 1.0
+    frozen: dana.py:350-385). The adjoint is the class's `_backward_gen`: dana_backward_gen below, each sibling's beside its
+    forward (frcnn.py, fsod.py, fgn.py), all composed of the shared pieces that follow."""
+    yield from model._backward_gen(grad_losses, ctx)
+
+
+# ---- pieces every model's backward is composed of ------------------------------------------------------------------------
+def scale_seeds(seeds, g_dev):
+    """the fused loss kernel's gradient seeds (class seeds..., bbox seed) times the device-resident (g3, g4)"""
+    if g_dev is not None:
+        for seed in seeds[:-1]:
+            ops.scale_by_device_scalar_(seed, g_dev[2:])
+        ops.scale_by_device_scalar_(seeds[-1], g_dev[3:])
+
+
+def begin(model, grad_losses, ctx):
+    """-> (ctx, (g1, g2, g3, g4, g_dev), WeightGrads on the model's "wgrad" stream). ctx: the saved-for-backward context to
+    differentiate, the one handed in (the loss bridge captured it at forward time) or the model's latest; it is consumed
+    exactly once: trunk_backward, the last stage, releases its tensors. grad_losses: four host numbers, the alpha of the
+    first launches that consume them (g_dev None), or a tensor, which stays on the device (no host sync in the backward):
+    g_dev, read by rpn_loss_backward and scale_seeds, with ones for the host scalars."""
+    if ctx is None:
+        ctx = model._ctx
+    if ctx is None or ctx.get("consumed"):
+        raise RuntimeError("no saved training forward to differentiate (run a train-mode forward with grad enabled "
+                           "or model.save_for_backward = True first; each forward can be differentiated once)")
+    if isinstance(grad_losses, torch.Tensor):
+        g = (1.0, 1.0, 1.0, 1.0, grad_losses.detach().to(torch.float32).contiguous())
     else:
-        g1, g2, g3, g4 = [float(x) for x in grad_losses]
-    corr = ctx["corr"]
-    dev = corr.device
-    grads = WeightGrads(None if getattr(model, "_single_stream", False) else model._stream("wgrad", dev), model)
-    ug = model.unary_gamma
+        g = tuple(float(x) for x in grad_losses) + (None,)
+    stream = None if getattr(model, "_single_stream", False) else model._stream("wgrad", ctx["fc7"].device)
+    return ctx, g, WeightGrads(stream, model)
 
-    # -- the trunk's data-gradient weights (flipped / transposed / BN-scaled copies, Winograd-domain filters: ~45 small
-    #    launches that depend on the weights only) are derived at the head of the weight-gradient stream instead of one by
-    #    one in front of the trunk's data-gradient launches that need them (the chain every other launch of the trunk's
-    #    backward waits for). (Round 4 gave them a stream of their own; which hardware queue that stream landed on decided
-    #    1-2 ms of the iteration: profiles/r5_role_streams.md.) --
-    rpn = model.RCNN_rpn
-    c_rpn = _rpn_conv_plan(model, ctx)
-    dgw_ready = l4w_ready = rpnw_ready = None
-    prefetch = not getattr(model, "_single_stream", False)
-    seen = set()
 
-    def derive(saved):
-        for sv in reversed(saved):
-            for name in ("c3", "c2", "c1", "ds"):
-                c = sv["bp"].get(name)
-                if c is not None and id(c) not in seen:
-                    seen.add(id(c))
-                    _dgrad_weights(c)
+def seed_linear_grads(layer, seed, x, alpha):
+    """weight and bias gradient of a Linear whose output gradient is a loss seed [n][C] (RCNN_bbox_pred's d_bbox, a score
+    layer's d_score) times the upstream scalar alpha; x [n][in_features]: the layer's input"""
+    (n, C), k = seed.shape, layer.in_features
+    acc(layer.weight, ops.gemm_small(seed, (1, C), x, (k, 1), C, k, n, alpha=alpha))
+    acc(layer.bias, ops.colsum(seed, n, C, alpha=alpha))
 
+
+def seed_linear_dx(layer, seed, alpha):
+    """-> the gradient [n][in_features] into that layer's input (RCNN_bbox_pred: d_fc7)"""
+    (n, C), k = seed.shape, layer.in_features
+    return ops.gemm_small(seed, (C, 1), layer.weight.detach(), (k, 1), n, k, C, alpha=alpha)
+
+
+def layer4_backward(d_top, n, saved, grads):
+    """Adjoint of `_head_to_tail` over the blocks a forward saved: d_top [n][2048] into the mean over layer4's output
+    positions -> dL/d(layer4's input): the RoIAlign output (meta: the max-pooled support map), no ReLU output: not masked"""
+    npos = saved[-1]["h1"] * saved[-1]["w1"]
+    g = ops.broadcast_rows(d_top, n, npos, 2048, alpha=1.0 / npos)
+    for i, sv in enumerate(reversed(saved)):
+        g = bottleneck_backward(g, sv, sv["n"], sv["h"], sv["w"], sv["bp"], grads, sv["key"], mask_dx=i < len(saved) - 1,
+                                g_masked=i > 0)
+    return g
+
+
+def roi_features_backward(ctx, d_pooled):
+    """d_pooled [n_roi*49][1024] -> d base_feat [B*fh*fw][1024] through RoIAlign or (a saved argmax) RoIPool"""
+    B, n_roi, fh, fw = ctx["B"], ctx["B"] * ctx["R"], ctx["fh"], ctx["fw"]
+    if ctx.get("roi_argmax") is not None:
+        # cfg.POOLING_MODE == 'pool' (dana.py:183-184): every bin's gradient goes to its argmax element (ROIPool_cuda.cu:79-108)
+        g_nchw = ops.roi_pool_backward(ops.nhwc_to_nchw(d_pooled, n_roi, 1024, 7, 7), None, ctx["rois"].view(-1, 5),
+                                       ctx["roi_argmax"], 1.0 / 16.0, 7, 7, B, 1024, fh, fw)
+        return ops.nchw_to_nhwc(g_nchw).view(B * fh * fw, 1024)
+    return ops.roi_align_backward(d_pooled.view(n_roi, 7, 7, 1024), ctx["rois"].view(-1, 5), 1.0 / 16.0, 7, 7, B, 1024,
+                                  fh, fw, 0, layout=ops.NHWC).view(B * fh * fw, 1024)
+
+
+# ---- DAnA (dana.py): the stages of dana_backward_gen, named after the forward stages they differentiate ---------------
+def _dgrad_weights_ready(model, ctx, dev):
+    """The data-gradient weights (flipped / transposed / BN-scaled copies, Winograd-domain filters: ~45 small launches
+    that depend on the weights only) are derived at the head of the weight-gradient stream instead of one by one in front
+    of the data-gradient launches that need them (the chain every other launch of the trunk's backward waits for). (Round
+    4 gave them a stream of their own; which hardware queue that stream landed on decided 1-2 ms of the iteration:
+    profiles/r5_role_streams.md.) -> the events (RPN conv's, layer4's, all) are ready; None: derived in place."""
     early = ctx.get("dgw_prefetched")
     if early is not None:
         # round 6: the saving forward already issued them on the weight-gradient stream, under its own trunk
         # (prefetch_dgrad_weights): the backward's three chains start at once instead of behind ~70 weight-only launches
-        rpnw_ready = l4w_ready = dgw_ready = early
-    elif prefetch:
-        prep = model._stream("wgrad", dev)  # (at the head of the weight-gradient stream: nothing is queued there yet)
-        ev0 = ops.record_event()
-        prep.wait_event(ev0)
-        with ops.on_stream(prep):
-            # (in the order the backward needs them: the RPN chain and the box branch start at once, then the trunk)
-            _dgrad_weights(c_rpn)
-            rpnw_ready = ops.record_event()
-            derive(ctx["l4_saved"])
-            l4w_ready = ops.record_event()
-            derive(ctx["q_saved"])
-            dgw_ready = ops.record_event()
+        return early, early, early
+    if getattr(model, "_single_stream", False):
+        return None, None, None
+    prep = model._stream("wgrad", dev)  # (at the head of the weight-gradient stream: nothing is queued there yet)
+    prep.wait_event(ops.record_event())
+    with ops.on_stream(prep):
+        # (in the order the backward needs them: the RPN chain and the box branch start at once, then the trunk)
+        _dgrad_weights(_rpn_conv_plan(model, ctx))
+        rpnw_ready = ops.record_event()
+        _derive_dgrad_weights(sv["bp"] for sv in reversed(ctx["l4_saved"]))
+        l4w_ready = ops.record_event()
+        _derive_dgrad_weights(sv["bp"] for sv in reversed(ctx["q_saved"]))
+        return rpnw_ready, l4w_ready, ops.record_event()
 
-    # -- RPN chain (_rpn_chain). It depends on the forward's saved tensors only and meets the RoI stage's gradients in
-    #    base_feat / the support maps, so it runs on a stream of its own FROM THE START of the backward, beside the box
-    #    branch and the RoI heads (round 4: it used to follow them on the caller's stream, 1.4 ms of launches with nothing
-    #    beside them). Under stream capture its weight gradients stay inline on the chain's stream (a side stream forked
-    #    from an already forked stream crashes hipStreamEndCapture on ROCm 7.2). Issuing the chain even earlier -- from the
-    #    eager forward, right behind the RPN head, under the proposal layer and the host round trip -- was built and
-    #    measured: +-0 (18.10 / 18.03 vs 18.07 ms): the eager iteration is host-bound there, the chain's ~100 launches
-    #    delay the host's count read by what they save on the GPU. Letting every side stream enter the capture through
-    #    an event of the capturing stream itself (a flat fork structure) does not avoid that crash either (measured). --
-    main = ops.cur_stream()
-    single = getattr(model, "_single_stream", False)
-    capturing = torch.cuda.is_current_stream_capturing()
-    rpn_early = not single
-    rpn_out = rpn_done = None
-    rpn_start = ops.record_event() if rpn_early else None
 
-    def launch_rpn_chain():
-        rpn_stream = model._stream("support", dev)  # (the forward's support stream: idle in the backward)
-        rpn_stream.wait_event(rpn_start)
-        with ops.on_stream(rpn_stream):
-            grads_r = WeightGrads(None if capturing else model._stream("wgrad", dev), model)
-            out = _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready)
-            for t_ in out:
-                t_.record_stream(main)
-            return out, ops.record_event()
+def _box_branch_backward(model, ctx, grads, d_bbox, g4):
+    """RCNN_bbox_pred <- mean <- layer4 (dana.py:246,387-389) -> d pooled [n_roi*49][1024]"""
+    seed_linear_grads(model.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
+    d_fc7 = seed_linear_dx(model.RCNN_bbox_pred, d_bbox, g4)
+    return layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads)
 
-    if rpn_early:  # (issued FIRST: its two 300 us launches buy the host the time to issue the other chains; round 4: 1.2 ms)
-        rpn_out, rpn_done = launch_rpn_chain()
 
-    # -- seeds: d RCNN losses / d (scores, bbox_pred) were written by the fused loss kernel (dana_rcnn_loss);
-    #    the upstream scalars g3 / g4 ride as alpha on the first launches that consume them --
-    d_score_pos, d_score_neg, d_bbox = ctx["loss_seeds"]
-    if g_dev is not None:
-        ops.scale_by_device_scalar_(d_score_pos, g_dev[2:])
-        ops.scale_by_device_scalar_(d_score_neg, g_dev[2:])
-        ops.scale_by_device_scalar_(d_bbox, g_dev[3:])
-
-    # -- box branch: RCNN_bbox_pred <- mean <- layer4 (dana.py:246,387-389). Independent of the attention heads until
-    #    the two gradients of the pooled features meet, so it runs on the forward's layer4 stream: the heads' backward
-    #    (many small launches) fills the CUs its big launches leave idle in their tails. --
-    main = ops.cur_stream()
-    # (under stream capture the box branch stays on the caller's stream: a weight-gradient side stream forked from an
-    # already forked stream crashes hipStreamEndCapture on ROCm 7.2 -- tools/graph_debug.py modes 8 / 12 / 13)
-    l4_stream = main if (getattr(model, "_single_stream", False) or torch.cuda.is_current_stream_capturing()) \
-        else model._stream("layer4", dev)
-    seeds_ready = ops.record_event()
-    stages = grad_stages(model, plan)
-    with ops.on_stream(l4_stream):
-        l4_stream.wait_event(seeds_ready)
-        if l4w_ready is not None:
-            l4_stream.wait_event(l4w_ready)
-        wb = model.RCNN_bbox_pred.weight.detach()
-        _acc(model.RCNN_bbox_pred.weight,
-             ops.gemm_small(d_bbox, (1, 4), ctx["fc7"], (2048, 1), 4, 2048, n_roi, alpha=g4))
-        _acc(model.RCNN_bbox_pred.bias, ops.colsum(d_bbox, n_roi, 4, alpha=g4))
-        d_fc7 = ops.gemm_small(d_bbox, (4, 1), wb, (2048, 1), n_roi, 2048, 4, alpha=g4)
-        l4 = ctx["l4_saved"]
-        npos = l4[-1]["h1"] * l4[-1]["w1"]
-        g = ops.broadcast_rows(d_fc7, n_roi, npos, 2048, alpha=1.0 / npos)
-        for i, sv in enumerate(reversed(l4)):  # the first block's input is the RoIAlign output: no ReLU in front of it
-            g = bottleneck_backward(g, sv, sv["n"], sv["h"], sv["w"], sv["bp"], grads, sv["key"],
-                                    mask_dx=i < len(l4) - 1, g_masked=i > 0)
-        d_pooled = g  # [n_roi*49][1024]
-        d_pooled.record_stream(main)
-        grads.finish_all(model, "RCNN_top")
-        _ready(model, stages[0][1])
-        box_done = ops.record_event()
-
-    # -- RoI-level attention heads (dana.py:248-292), positive then negative supports --
-    q_pe, q2, sp_pe, k2, un2 = ctx["q_pe"], ctx["q2"], ctx["sp_pe"], ctx["k2"], ctx["un2"]
-    K2, K2p = ctx["K2"], ctx["K2p"]
+def _roi_heads_backward(model, ctx, grads, d_scores, g3):
+    """RoI-level attention heads (dana.py:248-292), positive then negative supports. -> what both heads accumulate into:
+    (d_q2, d_trq) of the query side's Q projection and transform input, (d_k2, d_un2, d_sp_pe) of the support side's keys,
+    unary term and PE-added maps, d_wt: the attended half of rcnn_transform_layer's weight gradient."""
+    B, shot, way, R, Ns = ctx["B"], ctx["shot"], ctx["way"], ctx["R"], ctx["Ns"]
+    P2, n_roi, dq, rd, ug = 49, B * R, model.rcnn_reduce_dim, model.rcnn_dim, model.unary_gamma
+    q2, sp_pe, k2, un2, K2p = ctx["q2"], ctx["sp_pe"], ctx["k2"], ctx["un2"], ctx["K2p"]
+    dev = q2.device
     wt = model.rcnn_transform_layer.weight.detach()
-    w1 = model.output_score_layer.linear1.weight.detach()
-    w2 = model.output_score_layer.linear2.weight.detach()
-    rd = model.rcnn_dim
+    lin1, lin2 = model.output_score_layer.linear1, model.output_score_layer.linear2
+    w1 = lin1.weight.detach()
     nhid = w1.size(0)
     d_q2 = torch.zeros((n_roi * P2, dq), dtype=torch.float32, device=dev)
     d_trq = torch.zeros((n_roi * P2, rd), dtype=torch.float32, device=dev)
@@ -626,15 +585,11 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
     d_sw = None
     for hc in ctx["heads"]:
         off = hc["offset"]
-        hi = 0 if off == 0 else 1  # rows of cls_score_all: positive-support scores first (dana.py:194)
-        ds = d_score_pos if hi == 0 else d_score_neg
-        _acc(model.output_score_layer.linear2.weight,
-             ops.gemm_small(ds, (1, 2), hc["hid"], (nhid, 1), 2, nhid, n_roi, alpha=g3))
-        _acc(model.output_score_layer.linear2.bias, ops.colsum(ds, n_roi, 2, alpha=g3))
-        d_hid = ops.gemm_small(ds, (2, 1), w2, (nhid, 1), n_roi, nhid, 2, alpha=g3)
+        ds = d_scores[0 if off == 0 else 1]  # rows of cls_score_all: positive-support scores first (dana.py:194)
+        seed_linear_grads(lin2, ds, hc["hid"], g3)
+        d_hid = seed_linear_dx(lin2, ds, g3)
         ops.relu_mask_(d_hid, hc["hid"], n_roi, nhid)
-        lin1 = model.output_score_layer.linear1
-        grads.linear(d_hid, hc["tr"], n_roi, nhid, P2 * rd, lambda dw, db: (_acc(lin1.weight, dw), _acc(lin1.bias, db)))
+        grads.linear(d_hid, hc["tr"], n_roi, nhid, P2 * rd, lambda dw, db: (acc(lin1.weight, dw), acc(lin1.bias, db)))
         _, _, d_tr = ops.linear_backward(d_hid, hc["tr"], w1, n_roi, nhid, P2 * rd, need_dw=False)
         ops.axpy_rows_(d_trq, d_tr, n_roi * P2, rd)
         if hc["dense"] is None:
@@ -643,21 +598,17 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
             # attended tensor, its two GEMMs against Wt_a and the two K = 1024 attention adjoints per head do not exist
             if d_sw is None:
                 d_sw = torch.zeros((Ns * P2, rd), dtype=torch.float32, device=dev)
-            d_qh = _attention_backward(d_tr, rd, hc["sc2"], un2.view(-1)[off * P2:], q2, k2.view(-1)[off * P2 * dq:],
-                                       ctx["sw"].view(-1)[off * P2 * rd:], B, R * P2, shot, P2, K2p, dq, ug,
-                                       way * shot * P2 * dq, way * shot * P2 * rd, way * shot * P2,
-                                       d_k2.view(-1)[off * P2 * dq:], d_sw.view(-1)[off * P2 * rd:],
-                                       d_un2.view(-1)[off * P2:], vw=rd)
+            d_att, vw, val, d_val = d_tr, rd, ctx["sw"], d_sw
         else:
             grads.linear(d_tr, hc["dense"], n_roi * P2, rd, 1024,
                          lambda dw, db: ops.axpy_rows_(d_wt.view(-1)[1024:], dw, rd, 1024, ld_y=2048))
-            _, _, d_dense = ops.linear_backward(d_tr, hc["dense"], wt.view(-1)[1024:], n_roi * P2, rd, 1024, ldw=2048,
-                                                need_dw=False)
-            d_qh = _attention_backward(d_dense, 1024, hc["sc2"], un2.view(-1)[off * P2:], q2, k2.view(-1)[off * P2 * dq:],
-                                       sp_pe.view(-1)[off * P2 * 1024:], B, R * P2, shot, P2, K2p, dq, ug,
-                                       way * shot * P2 * dq, way * shot * P2 * 1024, way * shot * P2,
-                                       d_k2.view(-1)[off * P2 * dq:], d_sp_pe.view(-1)[off * P2 * 1024:],
-                                       d_un2.view(-1)[off * P2:])
+            _, _, d_att = ops.linear_backward(d_tr, hc["dense"], wt.view(-1)[1024:], n_roi * P2, rd, 1024, ldw=2048,
+                                              need_dw=False)
+            vw, val, d_val = 1024, sp_pe, d_sp_pe
+        d_qh = _attention_backward(d_att, vw, hc["sc2"], un2.view(-1)[off * P2:], q2, k2.view(-1)[off * P2 * dq:],
+                                   val.view(-1)[off * P2 * vw:], B, R * P2, shot, P2, K2p, dq, ug, way * shot * P2 * dq,
+                                   way * shot * P2 * vw, way * shot * P2, d_k2.view(-1)[off * P2 * dq:],
+                                   d_val.view(-1)[off * P2 * vw:], d_un2.view(-1)[off * P2:], vw=vw)
         ops.axpy_rows_(d_q2, d_qh, n_roi * P2, dq)
     if d_sw is not None:
         # sw = sp_pe . Wt_a^T (once per support, both heads): d Wt_a = d_sw^T . sp_pe, d sp_pe += d_sw . Wt_a
@@ -665,79 +616,59 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
                      lambda dw, db: ops.axpy_rows_(d_wt.view(-1)[1024:], dw, rd, 1024, ld_y=2048))
         ops.linear_backward(d_sw, sp_pe, wt.view(-1)[1024:], Ns * P2, rd, 1024, ldw=2048, dx_out=d_sp_pe, dx_ld=1024,
                             need_dw=False)
+    return d_q2, d_trq, d_k2, d_un2, d_sp_pe, d_wt
 
-    # -- RoI-level query side: Q projection + the q half of rcnn_transform_layer; PE is additive --
-    ops.colmean_sub_(d_q2, n_roi, P2, dq)
+
+def _roi_query_backward(model, ctx, grads, d_q2, d_trq, d_wt):
+    """RoI-level query side: Q projection + the q half of rcnn_transform_layer; PE is additive. -> d q_pe [n_roi*49][1024],
+    the heads' gradient into the pooled features"""
+    rows, dq, rd, q_pe = ctx["B"] * ctx["R"] * 49, model.rcnn_reduce_dim, model.rcnn_dim, ctx["q_pe"]
+    ops.colmean_sub_(d_q2, rows // 49, 49, dq)
     wq2 = model.rcnn_adapt_q_layer.weight.detach()
-    grads.linear(d_q2, q_pe, n_roi * P2, dq, 1024,
-                 lambda dw, db: (_acc(model.rcnn_adapt_q_layer.weight, dw), _acc(model.rcnn_adapt_q_layer.bias, db)))
-    _, _, d_q_pe = ops.linear_backward(d_q2, q_pe, wq2, n_roi * P2, dq, 1024, need_dw=False)
+    grads.linear(d_q2, q_pe, rows, dq, 1024,
+                 lambda dw, db: (acc(model.rcnn_adapt_q_layer.weight, dw), acc(model.rcnn_adapt_q_layer.bias, db)))
+    _, _, d_q_pe = ops.linear_backward(d_q2, q_pe, wq2, rows, dq, 1024, need_dw=False)
 
     def _transform_grads(dw, db):  # (both halves of rcnn_transform_layer's weight gradient are in d_wt now)
         ops.axpy_rows_(d_wt, dw, rd, 1024, ld_y=2048)
-        _acc(model.rcnn_transform_layer.weight, d_wt)
-        _acc(model.rcnn_transform_layer.bias, db)
+        acc(model.rcnn_transform_layer.weight, d_wt)
+        acc(model.rcnn_transform_layer.bias, db)
 
-    grads.linear(d_trq, q_pe, n_roi * P2, rd, 1024, _transform_grads)
-    ops.linear_backward(d_trq, q_pe, wt, n_roi * P2, rd, 1024, ldw=2048, dx_out=d_q_pe, dx_ld=1024, need_dw=False)
-    main.wait_event(box_done)
-    ops.axpy_rows_(d_pooled, d_q_pe, n_roi * P2, 1024)
-    if ctx.get("roi_argmax") is not None:
-        # cfg.POOLING_MODE == 'pool' (dana.py:183-184): every bin's gradient goes to its argmax element (ROIPool_cuda.cu:79-108)
-        g_nchw = ops.roi_pool_backward(ops.nhwc_to_nchw(d_pooled, n_roi, 1024, 7, 7), None, ctx["rois"].view(-1, 5),
-                                       ctx["roi_argmax"], 1.0 / 16.0, 7, 7, B, 1024, fh, fw)
-        d_bf = ops.nchw_to_nhwc(g_nchw).view(B * fh * fw, 1024)
-    else:
-        d_bf = ops.roi_align_backward(d_pooled.view(n_roi, 7, 7, 1024), ctx["rois"].view(-1, 5), 1.0 / 16.0, 7, 7, B, 1024,
-                                      fh, fw, 0, layout=ops.NHWC)  # [B][fh][fw][1024]
+    grads.linear(d_trq, q_pe, rows, rd, 1024, _transform_grads)
+    ops.linear_backward(d_trq, q_pe, model.rcnn_transform_layer.weight.detach(), rows, rd, 1024, ldw=2048, dx_out=d_q_pe,
+                        dx_ld=1024, need_dw=False)
+    return d_q_pe
 
-    # -- RoI-level support side: K projection, unary term, PE, 14x14 average pool (dana.py:105-108,271-277) --
+
+def _roi_support_backward(model, ctx, grads, d_k2, d_un2, d_sp_pe):
+    """RoI-level support side: K projection, unary term, PE, 14x14 average pool (dana.py:105-108,271-277)
+    -> d_sup [Ns][L][1024], the gradient into the support trunk's output"""
+    Ns, P2, dq, sp_pe, un2 = ctx["Ns"], 49, model.rcnn_reduce_dim, ctx["sp_pe"], ctx["un2"]
     ops.colmean_sub_(d_k2, Ns, P2, dq)
     wk2 = model.rcnn_adapt_k_layer.weight.detach()
     grads.linear(d_k2, sp_pe, Ns * P2, dq, 1024,
-                 lambda dw, db: (_acc(model.rcnn_adapt_k_layer.weight, dw), _acc(model.rcnn_adapt_k_layer.bias, db)))
+                 lambda dw, db: (acc(model.rcnn_adapt_k_layer.weight, dw), acc(model.rcnn_adapt_k_layer.bias, db)))
     ops.linear_backward(d_k2, sp_pe, wk2, Ns * P2, dq, 1024, dx_out=d_sp_pe, dx_ld=1024, need_dw=False)
     ops.softmax_rows_backward_(d_un2, un2, Ns, P2)
     wu2 = model.rcnn_unary_layer.weight.detach()
-    _acc(model.rcnn_unary_layer.weight, ops.rowdot_backward(sp_pe, d_un2, wu2, Ns * P2, 1024, grad_x=d_sp_pe))
-    _acc(model.rcnn_unary_layer.bias, ops.colsum(d_un2, Ns * P2, 1))
+    acc(model.rcnn_unary_layer.weight, ops.rowdot_backward(sp_pe, d_un2, wu2, Ns * P2, 1024, grad_x=d_sp_pe))
+    acc(model.rcnn_unary_layer.bias, ops.colsum(d_un2, Ns * P2, 1))
     (sh_, sw_), pool = ctx["sup_map"], ctx["sup_pool"]
-    d_sup = ops.avgpool_backward(d_sp_pe, Ns, sh_, sw_, 1024, pool[0], pool[1])  # [Ns][L][1024]
-    grads.join()  # (the heads' Linear weight / bias gradients were accumulated on the weight-gradient stream)
-    _ready(model, stages[1][1])
+    return ops.avgpool_backward(d_sp_pe, Ns, sh_, sw_, 1024, pool[0], pool[1])
 
-    if rpn_early:
-        main.wait_event(rpn_done)
-        for n_ in stages[2][1]:  # (gradients first allocated on the chain's streams are read on the caller's from here on)
-            g_ = model.get_parameter(n_).grad
-            if g_ is not None:
-                g_.record_stream(main)
-    else:
-        rpn_out = _rpn_chain(model, ctx, g1, g2, g_dev, grads, rpnw_ready)
-    d_corr, d_s_pe = rpn_out
-    K1 = shot * L
-    for b in range(B):  # the positive supports' PE-added maps (dana.py:103,130)
-        ops.axpy_rows_(d_sup.view(-1)[b * way * shot * L * 1024:], d_s_pe[b], K1, 1024)
-    grads.finish_all(model, "RCNN_rpn")
-    _ready(model, stages[2][1])
-    if dgw_ready is not None:
-        ops.cur_stream().wait_event(dgw_ready)
-    yield "heads, RPN and attention done; trunk next"
 
-    # -- trunk: query (RoIAlign + RPN paths meet in base_feat) and supports; layer3, layer2 (layer1 is frozen) --
-    ops.axpy_rows_(d_corr, d_bf, B * hw, 1024, ld_y=2048)
-    g = torch.empty((B * hw, 1024), dtype=torch.float32, device=dev)
-    ops.axpy_rows_(g, d_corr, B * hw, 1024, ld_x=2048, accumulate=False)
-    #    block by block for both batches, so that each block's weight gradient is final (and may be all-reduced)
-    #    while the earlier blocks are still being differentiated
-    gq, gs = g, d_sup.view(Ns * L, 1024)
-    qs, ss = ctx["q_saved"], ctx["s_saved"]
+def trunk_backward(model, ctx, grads, gq, gs=None):
+    """The last stage of every model's backward: layer3, layer2 of the trunk (conv1, layer1 and every BN are frozen) from
+    gq = d base_feat and, if the model differentiates its supports, gs = d(support trunk output). Block by block for both
+    batches (shared weights), so that each block's weight gradient is final (and may be all-reduced) while the earlier
+    blocks are differentiated; merged where the forward saved the [query | support] buffers. Releases the context."""
+    qs, ss = ctx["q_saved"], ctx.get("s_saved") or []
     ms = ctx.get("m_saved") or []
     merged_ok = len(ms) == len(qs) and getattr(model, "merge_backward", True)
     nblk = len(qs)
     gm = None  # dL/d(block output) of both batches in one buffer (while the blocks run merged)
     for i in range(nblk - 1, -1, -1):
-        sq, s_ = qs[i], ss[i]
+        sq, s_ = qs[i], ss[i] if gs is not None else None
         bp = sq["bp"]
         if merged_ok and bp["ds"] is None and bp["c1"]["stride"] == 1 and i > 0:
             sm = ms[i]
@@ -746,7 +677,7 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
                 if i == nblk - 1:  # (the last block's outputs live in corr / sup: mask per batch, then join)
                     ops.relu_mask_(gq, sq["o3"], sm["mq_out"], cout, ld_act=sq.get("o3_ld", 0))
                     ops.relu_mask_(gs, s_["o3"], sm["m_out"] - sm["mq_out"], cout, ld_act=s_.get("o3_ld", 0))
-                gm = torch.empty((sm["m_out"], cout), dtype=torch.float32, device=dev)
+                gm = torch.empty((sm["m_out"], cout), dtype=torch.float32, device=gq.device)
                 ops.axpy_rows_(gm, gq, sm["mq_out"], cout, accumulate=False)
                 ops.axpy_rows_(gm[sm["mq_out"]:], gs, sm["m_out"] - sm["mq_out"], cout, accumulate=False)
             gm = bottleneck_backward_merged(gm, sq, s_, sm, bp, grads, sq["key"])
@@ -755,320 +686,130 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
             gm = None
             gq = bottleneck_backward(gq, sq, sq["n"], sq["h"], sq["w"], sq["bp"], grads, sq["key"], need_dx=i > 0,
                                      g_masked=i < nblk - 1)
-            gs = bottleneck_backward(gs, s_, s_["n"], s_["h"], s_["w"], s_["bp"], grads, s_["key"], need_dx=i > 0,
-                                     g_masked=i < nblk - 1)
+            if gs is not None:
+                gs = bottleneck_backward(gs, s_, s_["n"], s_["h"], s_["w"], s_["bp"], grads, s_["key"], need_dx=i > 0,
+                                         g_masked=i < nblk - 1)
         grads.finish_all(model, sq["key"] + ".")
-        _ready(model, _block_convs(sq["key"], sq["bp"]))
+        ready(model, _block_convs(sq["key"], sq["bp"]))
     assert not grads.packed
-    _release_ctx(model, ctx)
+    ctx.clear()
+    ctx["consumed"] = True
+    if model._ctx is ctx:
+        model._ctx = None
 
 
-# ---- sibling model `frcnn` (lib/model/framework/faster_rcnn.py): the same adjoints without the attention ----------------
-def frcnn_grad_stages(model, plan=None):
-    plan = plan if plan is not None else model._get_plan()
-    lin = lambda n: [n + ".weight", n + ".bias"]  # noqa: E731
-    cls = "RCNN_cls_score.0" if type(model).__name__ == "MetaRCNN" else "RCNN_cls_score"  # meta.py:199-201: a Sequential
-    extra = []
-    if type(model).__name__ == "FSOD":  # fsod.py:29-75: the three relation heads replace RCNN_cls_score
-        st = [("roi head", lin("RCNN_bbox_pred") + lin("global_fc_1") + lin("global_fc_2") + lin("global_cls_score")
-               + ["corr_conv.weight"] + lin("corr_cls_score") + ["patch_conv_1.weight", "patch_conv_2.weight",
-                                                                 "patch_conv_3.weight"] + lin("patch_cls_score")
-               + [n for bi in (2, 1, 0) for n in _block_convs("RCNN_top.0.%d" % bi, plan["layer4"][bi])])]
-        st.append(("rpn", lin("RCNN_rpn.RPN_cls_score") + lin("RCNN_rpn.RPN_bbox_pred") + lin("RCNN_rpn.RPN_Conv")))
-        for li in (2, 1):
-            layer = plan["layers"][li]
-            for bi in reversed(range(len(layer))):
-                key = "RCNN_base.%d.%d" % (4 + li, bi)
-                st.append((key, _block_convs(key, layer[bi])))
-        return st
-    if type(model).__name__ == "FGN":  # fgn.py:29-41: the relation head's two convs and their (trainable) BatchNorms
-        extra = ["cls_conv2.weight", "cls_conv1.weight"] + lin("bn2") + lin("bn1")
-    st = [("roi head", lin("RCNN_bbox_pred") + lin(cls) + extra
-           + [n for bi in (2, 1, 0) for n in _block_convs("RCNN_top.0.%d" % bi, plan["layer4"][bi])])]
-    st.append(("rpn", lin("RCNN_rpn.RPN_cls_score") + lin("RCNN_rpn.RPN_bbox_pred") + lin("RCNN_rpn.RPN_Conv")))
-    for li in (2, 1):
-        layer = plan["layers"][li]
-        for bi in reversed(range(len(layer))):
-            key = "RCNN_base.%d.%d" % (4 + li, bi)
-            st.append((key, _block_convs(key, layer[bi])))
-    return st
+def dana_backward_gen(model, grad_losses, ctx=None):
+    """DAnARCNN's adjoint (model_backward_gen): from the start the RPN chain on the forward's support stream, the box branch
+    on its layer4 stream and the RoI heads on the caller's, joined where they meet; one pause; then the trunk."""
+    ctx, (g1, g2, g3, g4, g_dev), grads = begin(model, grad_losses, ctx)
+    dev, main = ctx["corr"].device, ops.cur_stream()
+    single = getattr(model, "_single_stream", False)
+    capturing = torch.cuda.is_current_stream_capturing()
+    rpnw_ready, l4w_ready, dgw_ready = _dgrad_weights_ready(model, ctx, dev)
 
+    # -- RPN chain (_rpn_chain). It depends on the forward's saved tensors only and meets the RoI stage's gradients in
+    #    base_feat / the support maps, so it runs on a stream of its own FROM THE START of the backward, beside the box
+    #    branch and the RoI heads (round 4: it used to follow them on the caller's stream, 1.4 ms of launches with nothing
+    #    beside them). Under stream capture its weight gradients stay inline on the chain's stream (a side stream forked
+    #    from an already forked stream crashes hipStreamEndCapture on ROCm 7.2). Issuing the chain even earlier -- from the
+    #    eager forward, right behind the RPN head, under the proposal layer and the host round trip -- was built and
+    #    measured: +-0 (18.10 / 18.03 vs 18.07 ms): the eager iteration is host-bound there, the chain's ~100 launches
+    #    delay the host's count read by what they save on the GPU. Letting every side stream enter the capture through
+    #    an event of the capturing stream itself (a flat fork structure) does not avoid that crash either (measured). --
+    if not single:  # (issued FIRST: its two 300 us launches buy the host the time to issue the other chains; round 4: 1.2 ms)
+        rpn_stream = model._stream("support", dev)  # (the forward's support stream: idle in the backward)
+        rpn_stream.wait_event(ops.record_event())
+        with ops.on_stream(rpn_stream):
+            grads_r = WeightGrads(None if capturing else model._stream("wgrad", dev), model)
+            rpn_out = _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready)
+            for t_ in rpn_out:
+                t_.record_stream(main)
+            rpn_done = ops.record_event()
 
-def frcnn_backward(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
-    """d(sum_i grad_losses[i] * loss_i)/d(parameters) of the last training forward of FasterRCNN (faster_rcnn.py:31-105)
-    or MetaRCNN (meta.py:39-142): RoI head <- mean <- layer4 <- RoIAlign, RPN losses <- heads <- 3x3 conv, both into
-    base_feat, then layer3 / layer2 of the trunk (conv1, layer1 and every BN are frozen: faster_rcnn.py:129-160).
-    meta adds the class-attentive vectors: score = Linear(fc7 * mean_shots(sigmoid(mean(layer4(maxpool2(trunk(support)))))))
-    for the positive and the negative supports, so its support batch is differentiated through layer4 and the trunk too."""
-    ctx = _take_ctx(model, ctx)
-    meta = type(model).__name__ == "MetaRCNN"
-    fgn = type(model).__name__ == "FGN"
-    fsod = type(model).__name__ == "FSOD"
-    plan, B, R, fh, fw = ctx["plan"], ctx["B"], ctx["R"], ctx["fh"], ctx["fw"]
-    n_roi, hw = B * R, fh * fw
-    g_dev = None
-    if isinstance(grad_losses, torch.Tensor):  # upstream gradients stay on the device: no host sync in the backward
-        g_dev = grad_losses.detach().to(torch.float32).contiguous()
-        g1 = g2 = g3 = g4 = 1.0
-        for seed, k in zip(ctx["loss_seeds"], (2, 2, 3) if (meta or fgn or fsod) else (2, 3)):  # (cls seeds..., bbox seed) x (g3, g4)
-            ops.scale_by_device_scalar_(seed, g_dev[k:])
+    # -- seeds: d RCNN losses / d (scores, bbox_pred) were written by the fused loss kernel (dana_rcnn_loss);
+    #    the upstream scalars g3 / g4 ride as alpha on the first launches that consume them --
+    d_score_pos, d_score_neg, d_bbox = ctx["loss_seeds"]
+    scale_seeds(ctx["loss_seeds"], g_dev)
+
+    # -- box branch. Independent of the attention heads until the two gradients of the pooled features meet, so it runs
+    #    on the forward's layer4 stream: the heads' backward (many small launches) fills the CUs its big launches leave
+    #    idle in their tails. (Under stream capture it stays on the caller's stream: a weight-gradient side stream forked
+    #    from an already forked stream crashes hipStreamEndCapture on ROCm 7.2 -- tools/graph_debug.py modes 8 / 12 / 13) --
+    l4_stream = main if (single or capturing) else model._stream("layer4", dev)
+    seeds_ready = ops.record_event()
+    stages = grad_stages(model, ctx["plan"])
+    with ops.on_stream(l4_stream):
+        l4_stream.wait_event(seeds_ready)
+        if l4w_ready is not None:
+            l4_stream.wait_event(l4w_ready)
+        d_pooled = _box_branch_backward(model, ctx, grads, d_bbox, g4)  # [n_roi*49][1024]
+        d_pooled.record_stream(main)
+        grads.finish_all(model, "RCNN_top")
+        ready(model, stages[0][1])
+        box_done = ops.record_event()
+
+    # -- RoI stage on the caller's stream: heads, query side (it meets the box branch in the pooled features), support side --
+    d_q2, d_trq, d_k2, d_un2, d_sp_pe, d_wt = _roi_heads_backward(model, ctx, grads, (d_score_pos, d_score_neg), g3)
+    d_q_pe = _roi_query_backward(model, ctx, grads, d_q2, d_trq, d_wt)
+    main.wait_event(box_done)
+    ops.axpy_rows_(d_pooled, d_q_pe, d_q_pe.size(0), 1024)
+    d_bf = roi_features_backward(ctx, d_pooled)
+    d_sup = _roi_support_backward(model, ctx, grads, d_k2, d_un2, d_sp_pe)  # [Ns][L][1024]
+    grads.join()  # (the heads' Linear weight / bias gradients were accumulated on the weight-gradient stream)
+    ready(model, stages[1][1])
+
+    if not single:
+        main.wait_event(rpn_done)
+        for n_ in stages[2][1]:  # (gradients first allocated on the chain's streams are read on the caller's from here on)
+            g_ = model.get_parameter(n_).grad
+            if g_ is not None:
+                g_.record_stream(main)
     else:
-        g1, g2, g3, g4 = [float(x) for x in grad_losses]
-    fc7 = ctx["fc7"]
-    dev = fc7.device
-    grads = WeightGrads(None if getattr(model, "_single_stream", False) else model._stream("wgrad", dev), model)
-    stages = frcnn_grad_stages(model, plan)
-    gs = None
-    if meta:
-        d_pos, d_neg, d_bbox = ctx["loss_seeds"]  # written by the fused mined-loss kernel (dana_rcnn_loss)
-        lin_c = model.RCNN_cls_score[0]
-        wc = lin_c.weight.detach()
-        d_fc7 = ops.gemm_small(d_bbox, (4, 1), model.RCNN_bbox_pred.weight.detach(), (2048, 1), n_roi, 2048, 4, alpha=g4)
-        Ns, shot, way = ctx["Ns"], ctx["shot"], ctx["way"]
-        att = ctx["att"]
-        d_att = torch.zeros((B, way * shot, 2048), dtype=torch.float32, device=dev)
-        for hc in ctx["heads"]:
-            ds = d_pos if hc["offset"] == 0 else d_neg
-            _acc(lin_c.weight, ops.gemm_small(ds, (1, 2), hc["comb"], (2048, 1), 2, 2048, n_roi, alpha=g3))
-            _acc(lin_c.bias, ops.colsum(ds, n_roi, 2, alpha=g3))
-            d_comb = ops.gemm_small(ds, (2, 1), wc, (2048, 1), n_roi, 2048, 2, alpha=g3)
-            d_fc7.add_(ops.scale_rows_by_group(d_comb, hc["vec"], n_roi, R, 2048))
-            # the shots' mean of the attentive vectors: d vec[b] = sum over the image's rois of d_comb * fc7
-            d_vec = (d_comb * fc7).view(B, R, 2048).sum(1) / shot
-            d_att[:, hc["offset"]:hc["offset"] + shot] += d_vec.unsqueeze(1)
-        d_pre = (d_att.view(Ns, 2048) * att * (1.0 - att)).contiguous()  # sigmoid adjoint (meta.py:250)
-        sl4 = ctx["sl4_saved"]
-        npos_s = sl4[-1]["h1"] * sl4[-1]["w1"]
-        g = ops.broadcast_rows(d_pre, Ns, npos_s, 2048, alpha=1.0 / npos_s)
-        for i, sv in enumerate(reversed(sl4)):  # the first block's input is the max-pooled map: its ReLU adjoint is the trunk's
-            g = bottleneck_backward(g, sv, sv["n"], sv["h"], sv["w"], sv["bp"], grads, sv["key"], mask_dx=i < len(sl4) - 1,
-                                    g_masked=i > 0)
-        # 2x2 / 2 max pool (meta.py:247) back onto the support maps: the window's (first) maximum takes the gradient
-        (sh_, sw_), (mh, mw) = ctx["sup_hw"], ctx["mp_hw"]
-        gs = ops.maxpool2x2s2_backward(ctx["sup"].view(Ns * sh_ * sw_, 1024), g.contiguous().view(Ns * mh * mw, 1024), Ns, sh_,
-                                       sw_, 1024)
-    elif fsod:
-        # -- multi-relation head (fsod.py:181-249): score = (global + local-correlation + patch) / 10 for the positive
-        #    and the negative support; every [roi | support] concatenation is a split layer (roi half + support half) --
-        d_pos, d_neg, d_bbox = ctx["loss_seeds"]
-        Ns, shot, way, L = ctx["Ns"], ctx["shot"], ctx["way"], ctx["L"]
-        P2, d, dq_ = 49, 1024, 256
-        pooled, g_roi, corr_roi = ctx["pooled"], ctx["g_roi"], ctx["corr_roi"]
-        d_fc7 = ops.gemm_small(d_bbox, (4, 1), model.RCNN_bbox_pred.weight.detach(), (2048, 1), n_roi, 2048, 4, alpha=g4)
-        w1 = model.global_fc_1.weight.detach()
-        w2 = model.global_fc_2.weight.detach()
-        wg = model.global_cls_score.weight.detach()
-        wcc = model.corr_conv.weight.detach().view(d, d).contiguous()
-        wcs = model.corr_cls_score.weight.detach()
-        wp1 = model.patch_conv_1.weight.detach().view(dq_, 2 * d).contiguous()
-        wp3 = model.patch_conv_3.weight.detach().view(d, dq_).contiguous()
-        wps = model.patch_cls_score.weight.detach()
-        c_p2 = dict(cin=dq_, cout=dq_, k=3, stride=1, pad=0, w=ctx["wp2"], scale=None, u=None)
-        d_pooled_head = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
-        d_g_roi = torch.zeros((n_roi, d), dtype=torch.float32, device=dev)
-        d_corr_roi = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
-        gs = torch.zeros((Ns * L, 1024), dtype=torch.float32, device=dev)  # d(support trunk output)
-        d_w1 = torch.zeros((d, 2 * d), dtype=torch.float32, device=dev)
-        d_wp1 = torch.zeros((dq_, 2 * d), dtype=torch.float32, device=dev)
-        d_wcc = torch.zeros((d, d), dtype=torch.float32, device=dev)
-        d_pos_kernel = None  # d(pooled positive support) from the attention RPN, added below
+        rpn_out = _rpn_chain(model, ctx, g1, g2, g_dev, grads, rpnw_ready)
+    d_corr, d_s_pe = rpn_out
+    K1 = d_s_pe.size(1)  # shot * L rows per image
+    for b in range(ctx["B"]):  # the positive supports' PE-added maps (dana.py:103,130)
+        ops.axpy_rows_(d_sup.view(-1)[b * ctx["way"] * K1 * 1024:], d_s_pe[b], K1, 1024)
+    grads.finish_all(model, "RCNN_rpn")
+    ready(model, stages[2][1])
+    if dgw_ready is not None:
+        ops.cur_stream().wait_event(dgw_ready)
+    yield "heads, RPN and attention done; trunk next"
 
-        def to_supports(d_map, offset):  # mean over the shots (fsod.py:98-101): every shot gets d_map / shot
-            for b_ in range(B):
-                for s_ in range(shot):
-                    ops.axpy_rows_(gs.view(-1)[(b_ * way * shot + offset + s_) * L * 1024:], d_map[b_], L, 1024,
-                                   alpha=1.0 / shot)
+    # -- trunk: the RoIAlign and the RPN paths meet in base_feat (the first half of corr's columns) --
+    ops.axpy_rows_(d_corr, d_bf, d_bf.size(0), 1024, ld_y=2048)
+    g = torch.empty_like(d_bf)
+    ops.axpy_rows_(g, d_corr, d_bf.size(0), 1024, ld_x=2048, accumulate=False)
+    trunk_backward(model, ctx, grads, g, d_sup.view(-1, 1024))
 
-        d_supports = {}
-        for hc in ctx["heads"]:
-            ds = (d_pos if hc["offset"] == 0 else d_neg)
-            a3 = g3 / 10.0  # fsod.py:237: the three scores are summed and divided by 10
-            support = hc["support"]
-            d_support = torch.zeros((B * P2, d), dtype=torch.float32, device=dev)
-            # .. global relation: Linear(2) <- relu fc2 <- relu fc1([mean(roi) | mean(support)])
-            _acc(model.global_cls_score.weight, ops.gemm_small(ds, (1, 2), hc["h2"], (d, 1), 2, d, n_roi, alpha=a3))
-            _acc(model.global_cls_score.bias, ops.colsum(ds, n_roi, 2, alpha=a3))
-            d_h2 = ops.gemm_small(ds, (2, 1), wg, (d, 1), n_roi, d, 2, alpha=a3)
-            ops.relu_mask_(d_h2, hc["h2"], n_roi, d)
-            dw2, db2, d_h1 = ops.linear_backward(d_h2, hc["h1"], w2, n_roi, d, d)
-            _acc(model.global_fc_2.weight, dw2)
-            _acc(model.global_fc_2.bias, db2)
-            ops.relu_mask_(d_h1, hc["h1"], n_roi, d)
-            dw1r, db1, _ = ops.linear_backward(d_h1, g_roi, w1, n_roi, d, d, ldw=2 * d, dx_out=d_g_roi, dx_ld=d)
-            ops.axpy_rows_(d_w1, dw1r, d, d, ld_y=2 * d)
-            _acc(model.global_fc_1.bias, db1)
-            d_gs = ops.spatial_mean(d_h1, B, R, d)  # the support half was broadcast over the image's R rois
-            d_gs.mul_(float(R))
-            dw1s = ops.gemm_small(d_gs, (1, d), hc["m_sup"], (d, 1), d, d, B)            # [d][d] = d_gs^T . mean(support)
-            ops.axpy_rows_(d_w1.view(-1)[d:], dw1s, d, d, ld_y=2 * d)
-            d_m_sup = ops.gemm_small(d_gs, (d, 1), w1.view(-1)[d:], (2 * d, 1), B, d, d)  # [B][d] = d_gs . w1[:, d:]
-            ops.broadcast_rows(d_m_sup, B, P2, d, alpha=1.0 / P2, out=d_support)
-            # .. local correlation: Linear(2) <- sum over the 49 positions of corr_conv(roi) * corr_conv(support)
-            _acc(model.corr_cls_score.weight, ops.gemm_small(ds, (1, 2), hc["oc"], (d, 1), 2, d, n_roi, alpha=a3))
-            _acc(model.corr_cls_score.bias, ops.colsum(ds, n_roi, 2, alpha=a3))
-            d_oc = ops.gemm_small(ds, (2, 1), wcs, (d, 1), n_roi, d, 2, alpha=a3)        # [n][1024] = a 1x1 output map
-            g_feat, g_kern = ops.depthwise_corr_backward(d_oc, corr_roi, hc["corr_sup"], n_roi, 7, 7, d, 7, 7,
-                                                         maps_per_kernel=R)
-            ops.axpy_rows_(d_corr_roi, g_feat, n_roi * P2, d)
-            dwc_s, _, _ = ops.linear_backward(g_kern.view(B * P2, d), support.view(B * P2, d), wcc, B * P2, d, d,
-                                              dx_out=d_support, dx_ld=d)
-            ops.axpy_rows_(d_wcc, dwc_s, d, d)
-            # .. patch relation: Linear(2) <- avgpool3 <- relu 1x1 <- relu 3x3 <- avgpool 3/1 <- relu 1x1([roi | support])
-            _acc(model.patch_cls_score.weight, ops.gemm_small(ds, (1, 2), hc["x4"], (d, 1), 2, d, n_roi, alpha=a3))
-            _acc(model.patch_cls_score.bias, ops.colsum(ds, n_roi, 2, alpha=a3))
-            d_x4 = ops.gemm_small(ds, (2, 1), wps, (d, 1), n_roi, d, 2, alpha=a3)
-            d_x3 = ops.avgpool_backward(d_x4, n_roi, 3, 3, d, 3, 1).view(n_roi * 9, d)
-            ops.relu_mask_(d_x3, hc["x3"], n_roi * 9, d)
-            dwp3, _, d_x2 = ops.linear_backward(d_x3, hc["x2"], wp3, n_roi * 9, d, dq_)
-            _acc(model.patch_conv_3.weight, dwp3.view(d, dq_, 1, 1))
-            ops.relu_mask_(d_x2, hc["x2"], n_roi * 9, dq_)
-            grads.add_conv("patch_conv_2", d_x2, hc["x1"].view(n_roi * 25, dq_), n_roi, 5, 5, c_p2)
-            d_x1 = conv_dgrad(d_x2, n_roi, 5, 5, c_p2)
-            d_x0 = ops.avgpool_backward(d_x1, n_roi, 7, 7, dq_, 3, 1).view(n_roi * P2, dq_)
-            ops.relu_mask_(d_x0, hc["x0"], n_roi * P2, dq_)
-            dwp1r, _, _ = ops.linear_backward(d_x0, pooled.view(n_roi * P2, d), wp1, n_roi * P2, dq_, d, ldw=2 * d,
-                                              dx_out=d_pooled_head, dx_ld=d)
-            ops.axpy_rows_(d_wp1, dwp1r, dq_, d, ld_y=2 * d)
-            d_p_sup = ops.spatial_mean(d_x0, B, R, P2 * dq_)  # the support half was broadcast over the image's rois
-            d_p_sup.mul_(float(R))
-            dwp1s, _, _ = ops.linear_backward(d_p_sup.view(B * P2, dq_), support.view(B * P2, d), wp1.view(-1)[d:],
-                                              B * P2, dq_, d, ldw=2 * d, dx_out=d_support, dx_ld=d)
-            ops.axpy_rows_(d_wp1.view(-1)[d:], dwp1s, dq_, d, ld_y=2 * d)
-            d_supports[hc["offset"]] = d_support
-        # the roi halves shared by both heads: mean over the 49 positions, corr_conv(rois)
-        ops.broadcast_rows(d_g_roi, n_roi, P2, d, alpha=1.0 / P2, out=d_pooled_head)
-        dwc_r, _, _ = ops.linear_backward(d_corr_roi, pooled.view(n_roi * P2, d), wcc, n_roi * P2, d, d,
-                                          dx_out=d_pooled_head, dx_ld=d)
-        ops.axpy_rows_(d_wcc, dwc_r, d, d)
-        _acc(model.global_fc_1.weight, d_w1)
-        _acc(model.patch_conv_1.weight, d_wp1.view(dq_, 2 * d, 1, 1))
-        _acc(model.corr_conv.weight, d_wcc.view(d, d, 1, 1))
-    elif fgn:
-        # -- relation head (fgn.py:145-165): Linear <- ReLU/BN2 <- conv2 <- ReLU/BN1 <- (support half + roi half) of conv1;
-        #    bn1 / bn2 are ORDINARY BatchNorms in train mode: their adjoint goes through the batch statistics --
-        d_pos, d_neg, d_bbox = ctx["loss_seeds"]
-        Ns, shot, way, L = ctx["Ns"], ctx["shot"], ctx["way"], ctx["L"]
-        lin_c, wl = model.RCNN_cls_score, ctx["wl"]
-        d_fc7 = ops.gemm_small(d_bbox, (4, 1), model.RCNN_bbox_pred.weight.detach(), (2048, 1), n_roi, 2048, 4, alpha=g4)
-        for bn_ in (model.bn1, model.bn2):
-            for p_ in (bn_.weight, bn_.bias):
-                if p_.grad is None:
-                    p_.grad = torch.zeros_like(p_)
-        c2 = dict(cin=512, cout=128, k=3, stride=1, pad=0, w=ctx["w2"], scale=None, u=None)
-        d_roi_half = torch.zeros((n_roi * 25, 512), dtype=torch.float32, device=dev)
-        gs = torch.zeros((Ns * L, 1024), dtype=torch.float32, device=dev)  # d(support trunk output)
-        w1g = model.cls_conv1.weight
 
-        def acc_w1_half(packed, lo):  # packed [512][3*3*1024] -> cls_conv1.weight.grad[:, lo:lo+1024] (OIHW)
-            tmp = torch.empty((512, 1024, 3, 3), dtype=torch.float32, device=dev)
-            ops.unpack_conv_weight_grad(packed, tmp, 512, 1024, 3, 3, accumulate=False)
-            if w1g.grad is None:
-                w1g.grad = torch.zeros_like(w1g)
-            w1g.grad[:, lo:lo + 1024].add_(tmp)
-
-        def to_supports(d_map, offset):  # mean over the shots (fgn.py:57-60): every shot gets d_map / shot
-            for b_ in range(B):
-                for s_ in range(shot):
-                    ops.axpy_rows_(gs.view(-1)[(b_ * way * shot + offset + s_) * L * 1024:], d_map[b_], L, 1024,
-                                   alpha=1.0 / shot)
-
-        for hc in ctx["heads"]:
-            ds = d_pos if hc["offset"] == 0 else d_neg
-            dwl = ops.gemm_small(ds, (1, 2), hc["x2"], (1152, 1), 2, 1152, n_roi, alpha=g3)   # [2][(h,w,c)]
-            _acc(lin_c.weight, dwl.view(2, 9, 128).permute(0, 2, 1).reshape(2, 1152))            # -> the NCHW flatten (c,h,w)
-            _acc(lin_c.bias, ops.colsum(ds, n_roi, 2, alpha=g3))
-            d_x2 = ops.gemm_small(ds, (2, 1), wl, (1152, 1), n_roi, 1152, 2, alpha=g3).view(n_roi * 9, 128)
-            ops.relu_mask_(d_x2, hc["x2"], n_roi * 9, 128)
-            x2_pre, m2, v2 = hc["bn2"]
-            d_x2pre = ops.bn_train_backward(d_x2, x2_pre, m2, v2, model.bn2.weight, model.bn2.eps, n_roi * 9, 128,
-                                            model.bn2.weight.grad, model.bn2.bias.grad)
-            grads.add_conv("cls_conv2", d_x2pre, hc["x1"], n_roi, 5, 5, c2)
-            d_x1 = conv_dgrad(d_x2pre, n_roi, 5, 5, c2, mask=hc["x1"])  # (+ the ReLU adjoint of bn1's output)
-            x1_pre, m1, v1 = hc["bn1"]
-            d_x1pre = ops.bn_train_backward(d_x1, x1_pre, m1, v1, model.bn1.weight, model.bn1.eps, n_roi * 25, 512,
-                                            model.bn1.weight.grad, model.bn1.bias.grad)
-            ops.axpy_rows_(d_roi_half, d_x1pre, n_roi * 25, 512)
-            d_s_half = ops.spatial_mean(d_x1pre, B, R, 25 * 512)  # broadcast over the image's R rois: sum = R * mean
-            d_s_half.mul_(float(R))
-            acc_w1_half(ops.conv2d_wgrad(d_s_half, hc["support"], B, 7, 7, 1024, 512, 3, 3, 1, 0), 0)
-            d_support = ops.conv2d_dgrad(d_s_half, ctx["w1_sup"], B, 7, 7, 1024, 512, 3, 3, 1, 0)   # [B*49][1024]
-            to_supports(ops.avgpool_backward(d_support, B, 20, 20, 1024, 14, 1), hc["offset"])          # AvgPool2d(14, 1)
-        acc_w1_half(ops.conv2d_wgrad(d_roi_half, ctx["pooled"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0), 1024)
-        d_pooled_head = ops.conv2d_dgrad(d_roi_half, ctx["w1_roi"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0)  # [n*49][1024]
-    else:
-        d_cls, d_bbox = ctx["loss_seeds"]  # d(loss_cls + loss_bbox) / d(cls_score, bbox_pred)
-        C = d_cls.size(1)
-        _acc(model.RCNN_cls_score.weight, ops.gemm_small(d_cls, (1, C), fc7, (2048, 1), C, 2048, n_roi, alpha=g3))
-        _acc(model.RCNN_cls_score.bias, ops.colsum(d_cls, n_roi, C, alpha=g3))
-        d_fc7 = ops.gemm_small(d_bbox, (4, 1), model.RCNN_bbox_pred.weight.detach(), (2048, 1), n_roi, 2048, 4, alpha=g4)
-        d_fc7.add_(ops.gemm_small(d_cls, (C, 1), model.RCNN_cls_score.weight.detach(), (2048, 1), n_roi, 2048, C, alpha=g3))
-    _acc(model.RCNN_bbox_pred.weight, ops.gemm_small(d_bbox, (1, 4), fc7, (2048, 1), 4, 2048, n_roi, alpha=g4))
-    _acc(model.RCNN_bbox_pred.bias, ops.colsum(d_bbox, n_roi, 4, alpha=g4))
-    l4 = ctx["l4_saved"]
-    npos = l4[-1]["h1"] * l4[-1]["w1"]
-    g = ops.broadcast_rows(d_fc7, n_roi, npos, 2048, alpha=1.0 / npos)
-    for i, sv in enumerate(reversed(l4)):  # the first block's input is the RoIAlign output: no ReLU in front of it
-        g = bottleneck_backward(g, sv, sv["n"], sv["h"], sv["w"], sv["bp"], grads, sv["key"], mask_dx=i < len(l4) - 1,
-                                g_masked=i > 0)
-    grads.finish_all(model, "RCNN_top")
-    if fsod:
-        grads.finish_all(model, "patch_conv_2")
-        ops.axpy_rows_(g, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the relation heads' roi halves
-    if fgn:
-        grads.finish_all(model, "cls_conv2")
-        ops.axpy_rows_(g, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the relation head's roi half
-    _ready(model, stages[0][1])
-    d_bf = ops.roi_align_backward(g.view(n_roi, 7, 7, 1024), ctx["rois"].view(-1, 5), 1.0 / 16.0, 7, 7, B, 1024, fh, fw,
-                                  0, layout=ops.NHWC).view(B * hw, 1024)
-    # -- RPN (rpn.py:58-115) on base_feat --
-    rpn = model.RCNN_rpn
-    nh = ctx["nh"]
+# ---- the sibling detectors (frcnn.py, fsod.py, fgn.py): shared pieces of their backwards ----------------------------------
+def sibling_rpn_backward(model, ctx, g1, g2, g_dev, grads, residual=None):
+    """Adjoint of the siblings' RPN (rpn.py:58-115): RPN losses -> heads -> ReLU -> 3x3 conv, with the weight and bias
+    gradients of the heads and of RPN_Conv. -> the gradient into the RPN's input [B*rfh*rfw][1024] (+ residual), in that
+    input's own geometry (fsod: the correlation map is smaller than base_feat); the model differentiates it from there."""
+    plan, B, rpn, nh = ctx["plan"], ctx["B"], model.RCNN_rpn, ctx["nh"]
     d_heads = ops.rpn_loss_backward(ctx["rpn_heads"], nh, ctx["at"], ctx["rpn_l"], g1, g2, sigma=3.0,
                                     inside_weight=cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS[0], grad_dev=g_dev)
-    rfh, rfw = ctx.get("rfh", fh), ctx.get("rfw", fw)  # the RPN input's own geometry (fsod: the correlation map is smaller)
+    rfh, rfw = ctx.get("rfh", ctx["fh"]), ctx.get("rfw", ctx["fw"])
     rhw = rfh * rfw
     dwh, dbh, d_x = ops.linear_backward(d_heads, ctx["rpn_x"], plan["rpn_head_w"], B * rhw, nh, 512)
     ns = rpn.nc_score_out
-    _acc(rpn.RPN_cls_score.weight, dwh[:ns])
-    _acc(rpn.RPN_cls_score.bias, dbh[:ns])
-    _acc(rpn.RPN_bbox_pred.weight, dwh[ns:])
-    _acc(rpn.RPN_bbox_pred.bias, dbh[ns:])
+    acc(rpn.RPN_cls_score.weight, dwh[:ns])
+    acc(rpn.RPN_cls_score.bias, dbh[:ns])
+    acc(rpn.RPN_bbox_pred.weight, dwh[ns:])
+    acc(rpn.RPN_bbox_pred.bias, dbh[ns:])
     ops.relu_mask_(d_x, ctx["rpn_x"], B * rhw, 512)
-    c_rpn = dict(cin=rpn.din, cout=512, k=3, stride=1, pad=1, w=plan["rpn_conv_w"], scale=None, u=plan["rpn_conv_u"])
+    c_rpn = _rpn_conv_plan(model, ctx)
     grads.add_conv("RCNN_rpn.RPN_Conv", d_x, ctx["rpn_feat"], B, rfh, rfw, c_rpn)
-    _acc(rpn.RPN_Conv.bias, ops.colsum(d_x, B * rhw, 512))
-    if fsod:
-        # attention RPN (fsod.py:109-116): the RPN ran on the depth-wise correlation of base_feat with the pooled positive
-        # support -> d base = full correlation of d rfeat with that kernel + RoIAlign path; d kernel -> positive supports
-        d_rfeat = conv_dgrad(d_x, B, rfh, rfw, c_rpn)
-        gq, d_pos_kernel = ops.depthwise_corr_backward(d_rfeat, ctx["base"], ctx["pos"], B, fh, fw, 1024, 7, 7)
-        ops.axpy_rows_(gq, d_bf, B * hw, 1024)
-        ops.axpy_rows_(d_supports[0], d_pos_kernel.view(B * 49, 1024), B * 49, 1024)
-        for off_, d_sup_ in d_supports.items():  # AvgPool2d(14, 1) of the shots' mean map (fsod.py:98-101)
-            to_supports(ops.avgpool_backward(d_sup_, B, 20, 20, 1024, 14, 1), off_)
-    elif fgn:
-        # the RPN ran on base_feat * pos_rpn[image] (fgn.py:75-82): d base = d rfeat * pos_rpn + RoIAlign path, and
-        # d pos_rpn[image] = sum over the pixels of d rfeat * base -> AvgPool2d(20) -> the positive supports' mean map
-        d_rfeat = conv_dgrad(d_x, B, fh, fw, c_rpn)
-        gq = ops.scale_rows_by_group(d_rfeat, ctx["pos_rpn"], B * hw, hw, 1024)
-        ops.axpy_rows_(gq, d_bf, B * hw, 1024)
-        d_pos_rpn = (d_rfeat * ctx["base"]).view(B, hw, 1024).sum(1).contiguous()
-        to_supports(ops.broadcast_rows(d_pos_rpn, B, ctx["L"], 1024, alpha=1.0 / ctx["L"]).view(B, ctx["L"], 1024), 0)
-    else:
-        gq = conv_dgrad(d_x, B, fh, fw, c_rpn, residual=d_bf)  # d base_feat = RPN path + RoIAlign path
-    grads.finish_all(model, "RCNN_rpn")
-    _ready(model, stages[1][1])
-    qs, ss = ctx["q_saved"], ctx.get("s_saved") or []
-    nblk = len(qs)
-    for i in range(nblk - 1, -1, -1):  # query batch and (meta) support batch, block by block: shared weights
-        sq = qs[i]
-        gq = bottleneck_backward(gq, sq, sq["n"], sq["h"], sq["w"], sq["bp"], grads, sq["key"], need_dx=i > 0,
-                                 g_masked=i < nblk - 1)
-        if gs is not None:
-            s_ = ss[i]
-            gs = bottleneck_backward(gs, s_, s_["n"], s_["h"], s_["w"], s_["bp"], grads, s_["key"], need_dx=i > 0,
-                                     g_masked=i < nblk - 1)
-        grads.finish_all(model, sq["key"] + ".")
-        _ready(model, _block_convs(sq["key"], sq["bp"]))
-    assert not grads.packed
-    _release_ctx(model, ctx)
+    acc(rpn.RPN_Conv.bias, ops.colsum(d_x, B * rhw, 512))
+    return conv_dgrad(d_x, B, rfh, rfw, c_rpn, residual=residual)
+
+
+def shot_mean_backward(gs, d_map, ctx, offset):
+    """Adjoint of the mean over the shots [offset, offset + shot) of every episode's support maps (fsod.py:98-101,
+    fgn.py:57-60): d_map [B][L][1024] / shot into those shots' rows of gs [Ns*L][1024] = d(support trunk output)"""
+    shot, way, L = ctx["shot"], ctx["way"], ctx["L"]
+    for b in range(ctx["B"]):
+        for s in range(shot):
+            ops.axpy_rows_(gs.view(-1)[(b * way * shot + offset + s) * L * 1024:], d_map[b], L, 1024, alpha=1.0 / shot)

@@ -951,6 +951,16 @@ class DAnARCNN(nn.Module):
             self._grad_anchor = torch.zeros(1, device=dev, requires_grad=True)
         return _LossBridge.apply(self._grad_anchor, self, *losses)
 
+    # the model's adjoint and the order it finishes the gradients in: backward.model_backward_gen / grad_stages look
+    # them up through the class, and every sibling detector overrides both beside its forward
+    def _backward_gen(self, grad_losses, ctx=None):
+        from . import backward as BW
+        return BW.dana_backward_gen(self, grad_losses, ctx)
+
+    def _grad_stages(self, plan):
+        from . import backward as BW
+        return BW.dana_grad_stages(self, plan)
+
     @staticmethod
     def _support_batch(support_ims, B, way, shot):
         """support_ims [B, way*shot, 3, S, S] (or any shape with those images) -> [B*way*shot, 3, S, S]"""

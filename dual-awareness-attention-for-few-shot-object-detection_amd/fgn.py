@@ -7,11 +7,12 @@ operators.
   (512->128) -> BatchNorm -> ReLU -> Linear(1152, 2). The concatenation never exists (the support half of the first conv
   is computed once per image and added as a residual). bn1 / bn2 are ORDINARY BatchNorm layers, unlike the trunk's:
   batch statistics and running-statistics updates in train mode (`dana_batch_stats`), running statistics in eval mode.
-Same parameter tree as the reference class. Trainable: backward.frcnn_backward's `fgn` branch (train-mode BatchNorm
-adjoints, the split first conv, the channel re-weighting of the RPN input, the support trunk)."""
+Same parameter tree as the reference class. Trainable: `FGN._backward` (train-mode BatchNorm adjoints, the split first
+conv, the channel re-weighting of the RPN input, the support trunk)."""
 import torch
 import torch.nn as nn
 
+from . import backward as BW
 from . import ops
 from .dana import ClassSweep
 from .frcnn import FasterRCNN
@@ -161,7 +162,83 @@ class FGN(FasterRCNN):
             ctx.update(loss_seeds=seeds, sup=sup, Ns=Ns, shot=shot, way=way, L=L, pos_rpn=pos_rpn, pooled=pooled,
                        w1_sup=w1_sup, w1_roi=w1_roi, w2=w2, wl=wl)
             self._ctx = ctx
-            if bridge:  # loss.backward() (train.py:141-143) runs backward.frcnn_backward (fgn branch) on the HIP kernels
+            if bridge:  # loss.backward() (train.py:141-143) runs self._backward on the HIP kernels
                 rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
                     dev, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label)
+
+    # ---- training backward ---------------------------------------------------------------------------------------------
+    # fgn.py:29-41: the relation head's two convs and their (trainable) BatchNorms
+    _head_params = BW.lin("RCNN_cls_score") + ["cls_conv2.weight", "cls_conv1.weight"] + BW.lin("bn2") + BW.lin("bn1")
+
+    def _relation_head_backward(self, ctx, grads, g3, gs):
+        """Adjoint of both `head` calls of the forward (fgn.py:145-165): Linear <- ReLU/BN2 <- conv2 <- ReLU/BN1 <- (support
+        half + roi half) of conv1; bn1 / bn2 are ORDINARY BatchNorms in train mode: their adjoint goes through the batch
+        statistics. The support halves go into gs (d support trunk output); -> d pooled [n_roi*49][1024] through the roi half"""
+        d_pos, d_neg, _ = ctx["loss_seeds"]
+        B, R, lin_c, wl = ctx["B"], ctx["R"], self.RCNN_cls_score, ctx["wl"]
+        n_roi, dev = B * R, gs.device
+        for bn_ in (self.bn1, self.bn2):
+            for p_ in (bn_.weight, bn_.bias):
+                if p_.grad is None:
+                    p_.grad = torch.zeros_like(p_)
+        c2 = dict(cin=512, cout=128, k=3, stride=1, pad=0, w=ctx["w2"], scale=None, u=None)
+        d_roi_half = torch.zeros((n_roi * 25, 512), dtype=torch.float32, device=dev)
+        w1g = self.cls_conv1.weight
+
+        def acc_w1_half(packed, lo):  # packed [512][3*3*1024] -> cls_conv1.weight.grad[:, lo:lo+1024] (OIHW)
+            tmp = torch.empty((512, 1024, 3, 3), dtype=torch.float32, device=dev)
+            ops.unpack_conv_weight_grad(packed, tmp, 512, 1024, 3, 3, accumulate=False)
+            if w1g.grad is None:
+                w1g.grad = torch.zeros_like(w1g)
+            w1g.grad[:, lo:lo + 1024].add_(tmp)
+
+        for hc in ctx["heads"]:
+            ds = d_pos if hc["offset"] == 0 else d_neg
+            dwl = ops.gemm_small(ds, (1, 2), hc["x2"], (1152, 1), 2, 1152, n_roi, alpha=g3)   # [2][(h,w,c)]
+            BW.acc(lin_c.weight, dwl.view(2, 9, 128).permute(0, 2, 1).reshape(2, 1152))          # -> the NCHW flatten (c,h,w)
+            BW.acc(lin_c.bias, ops.colsum(ds, n_roi, 2, alpha=g3))
+            d_x2 = ops.gemm_small(ds, (2, 1), wl, (1152, 1), n_roi, 1152, 2, alpha=g3).view(n_roi * 9, 128)
+            ops.relu_mask_(d_x2, hc["x2"], n_roi * 9, 128)
+            x2_pre, m2, v2 = hc["bn2"]
+            d_x2pre = ops.bn_train_backward(d_x2, x2_pre, m2, v2, self.bn2.weight, self.bn2.eps, n_roi * 9, 128,
+                                            self.bn2.weight.grad, self.bn2.bias.grad)
+            grads.add_conv("cls_conv2", d_x2pre, hc["x1"], n_roi, 5, 5, c2)
+            d_x1 = BW.conv_dgrad(d_x2pre, n_roi, 5, 5, c2, mask=hc["x1"])  # (+ the ReLU adjoint of bn1's output)
+            x1_pre, m1, v1 = hc["bn1"]
+            d_x1pre = ops.bn_train_backward(d_x1, x1_pre, m1, v1, self.bn1.weight, self.bn1.eps, n_roi * 25, 512,
+                                            self.bn1.weight.grad, self.bn1.bias.grad)
+            ops.axpy_rows_(d_roi_half, d_x1pre, n_roi * 25, 512)
+            d_s_half = ops.spatial_mean(d_x1pre, B, R, 25 * 512)  # broadcast over the image's R rois: sum = R * mean
+            d_s_half.mul_(float(R))
+            acc_w1_half(ops.conv2d_wgrad(d_s_half, hc["support"], B, 7, 7, 1024, 512, 3, 3, 1, 0), 0)
+            d_support = ops.conv2d_dgrad(d_s_half, ctx["w1_sup"], B, 7, 7, 1024, 512, 3, 3, 1, 0)  # [B*49][1024]
+            BW.shot_mean_backward(gs, ops.avgpool_backward(d_support, B, 20, 20, 1024, 14, 1), ctx, hc["offset"])  # 14, 1
+        acc_w1_half(ops.conv2d_wgrad(d_roi_half, ctx["pooled"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0), 1024)
+        return ops.conv2d_dgrad(d_roi_half, ctx["w1_roi"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0)
+
+    def _backward(self, ctx, g, grads):
+        """frcnn's adjoint with the relation head in place of the plain RCNN_cls_score and the channel re-weighting in front
+        of the RPN; the supports are differentiated through the trunk"""
+        g1, g2, g3, g4, g_dev = g
+        B, n_roi, hw, L, d_bbox = ctx["B"], ctx["B"] * ctx["R"], ctx["fh"] * ctx["fw"], ctx["L"], ctx["loss_seeds"][2]
+        d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g4)
+        gs = torch.zeros((ctx["Ns"] * L, 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
+        d_pooled_head = self._relation_head_backward(ctx, grads, g3, gs)
+        BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
+        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads)
+        grads.finish_all(self, "RCNN_top")
+        grads.finish_all(self, "cls_conv2")
+        ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the head's roi half
+        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        d_rfeat = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads)
+        # the RPN ran on base_feat * pos_rpn[image] (fgn.py:75-82): d base = d rfeat * pos_rpn + RoIAlign path, and
+        # d pos_rpn[image] = sum over the pixels of d rfeat * base -> AvgPool2d(20) -> the positive supports' mean map
+        gq = ops.scale_rows_by_group(d_rfeat, ctx["pos_rpn"], B * hw, hw, 1024)
+        ops.axpy_rows_(gq, d_bf, B * hw, 1024)
+        d_pos_rpn = (d_rfeat * ctx["base"]).view(B, hw, 1024).sum(1).contiguous()
+        BW.shot_mean_backward(gs, ops.broadcast_rows(d_pos_rpn, B, L, 1024, alpha=1.0 / L).view(B, L, 1024), ctx, 0)
+        grads.finish_all(self, "RCNN_rpn")
+        BW.ready(self, BW.RPN_PARAMS)
+        BW.trunk_backward(self, ctx, grads, gq, gs)

@@ -3,11 +3,13 @@ lib/model/framework/faster_rcnn.py:17-203 on the SAME HIP operators as the DAnA 
 Caffe ResNet-50 trunk -> RPN -> proposal layer -> (train) anchor / proposal targets -> RoIAlign or RoIPool ->
 layer4 -> RCNN_cls_score / RCNN_bbox_pred -> losses. Same parameter tree and state_dict keys as the reference class.
 `frcnn` and `meta` are trainable on the HIP kernels too: a training forward saves its context and hands the four losses
-to autograd (`_LossBridge`), `loss.backward()` runs backward.frcnn_backward / meta_backward (POOLING_MODE 'align')."""
+to autograd (`_LossBridge`), `loss.backward()` runs the class's own `_backward` (POOLING_MODE 'align'), composed of the
+shared pieces of backward.py."""
 import numpy as np
 import torch
 import torch.nn as nn
 
+from . import backward as BW
 from . import ops
 from .config import cfg
 from .dana import ClassSweep, DAnARCNN, SupportCache, _RPNParams
@@ -107,7 +109,7 @@ class FasterRCNN(DAnARCNN):
         anchor_gt = gt_boxes if anchor_gt_boxes is None else anchor_gt_boxes.data
         inputs_ready = ops.record_event()
         main = ops.cur_stream()
-        # ctx (frcnn only): everything backward.frcnn_backward needs is saved into it
+        # ctx (training): everything the model's `_backward` needs is saved into it
         base, fh, fw = self._rcnn_base(im_data, plan, save=ctx["q_saved"] if ctx is not None else None)  # faster_rcnn.py:43
         # -- RPN (rpn.py:58-115) on base_feat (or on the model's own RPN input) --
         rfeat, rh, rw = (base, fh, fw) if rpn_input is None else rpn_input(base, B, fh, fw, plan)
@@ -179,18 +181,56 @@ class FasterRCNN(DAnARCNN):
                 RCNN_loss_cls, RCNN_loss_bbox = l2[0], l2[1]
                 ctx.update(loss_seeds=(d_cls, d_bbox))
                 self._ctx = ctx
-                if bridge:  # loss.backward() (train.py:141-143) runs backward.frcnn_backward on the HIP kernels
+                if bridge:  # loss.backward() (train.py:141-143) runs self._backward on the HIP kernels
                     rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
                         im_data.device, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob.view(B, R, -1), bbox_pred.view(B, R, -1), rpn_loss_cls, rpn_loss_bbox,
                 RCNN_loss_cls, RCNN_loss_bbox, st["rois_label"])
 
 
+    # ---- training backward: backward.model_backward_gen / grad_stages dispatch to these through the class --------------
+    _head_params = BW.lin("RCNN_cls_score")  # the RoI head's own trainable parameters (every sibling names its own)
+
+    def _grad_stages(self, plan):
+        return BW.sibling_grad_stages(plan, self._head_params)
+
+    def _backward_gen(self, grad_losses, ctx=None):
+        """(DAnARCNN._backward_gen's generator contract; a sibling's backward, `_backward`, never pauses.) g = (g1, g2, g3, g4,
+        g_dev) of backward.begin; the loss seeds are scaled by the device-resident ones here"""
+        ctx, g, grads = BW.begin(self, grad_losses, ctx)
+        BW.scale_seeds(ctx["loss_seeds"], g[4])
+        self._backward(ctx, g, grads)
+        yield from ()
+
+    def _backward(self, ctx, g, grads):
+        """d(sum_i grad_losses[i] * loss_i)/d(parameters) of the last training forward (faster_rcnn.py:31-105): RCNN_cls_score
+        and RCNN_bbox_pred into fc7, then everything below it"""
+        d_cls, d_bbox = ctx["loss_seeds"]  # d(loss_cls + loss_bbox) / d(cls_score, bbox_pred)
+        BW.seed_linear_grads(self.RCNN_cls_score, d_cls, ctx["fc7"], g[2])
+        d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g[3])
+        d_fc7.add_(BW.seed_linear_dx(self.RCNN_cls_score, d_cls, g[2]))
+        self._backward_below_fc7(ctx, g, grads, d_bbox, d_fc7)
+
+    def _backward_below_fc7(self, ctx, g, grads, d_bbox, d_fc7, gs=None):
+        """what frcnn and meta share below the RoI head: mean <- layer4 <- RoIAlign, RPN losses <- heads <- 3x3 conv, both into
+        base_feat, then layer3 / layer2 of the trunk for the query batch and (meta: gs) the support batch"""
+        g1, g2, _, g4, g_dev = g
+        BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
+        d_pooled = BW.layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads)
+        grads.finish_all(self, "RCNN_top")
+        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        gq = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads, residual=d_bf)  # d base_feat = RPN + RoIAlign paths
+        grads.finish_all(self, "RCNN_rpn")
+        BW.ready(self, BW.RPN_PARAMS)
+        BW.trunk_backward(self, ctx, grads, gq, gs)
+
+
 class MetaRCNN(FasterRCNN):
     """Sibling model `meta` (utils.py:113-114): Meta R-CNN, lib/model/framework/meta.py:18-251. The Predictor-head
     Remodeling Network turns every support image into a class-attentive vector, sigmoid(mean(layer4(maxpool2(trunk)))),
     the shots' mean multiplies the RoI features channel-wise in front of a 2-way Linear; positive + negative supports
-    and the 1:2:1 hard-negative-mined loss as in DAnA. Trainable: backward.meta_backward."""
+    and the 1:2:1 hard-negative-mined loss as in DAnA. Trainable: `_backward` below."""
 
     def __init__(self, classes, num_layers=50, pretrained=False, num_way=2, num_shot=5):
         self.n_way, self.n_shot = num_way, num_shot
@@ -281,7 +321,33 @@ class MetaRCNN(FasterRCNN):
             if ctx is not None:
                 ctx.update(loss_seeds=seeds, att=att, sup=sup, sup_hw=(sh_, sw_), mp_hw=(mh, mw), Ns=Ns, shot=shot, way=way)
                 self._ctx = ctx
-                if bridge:  # loss.backward() (train.py:141-143) runs backward.meta_backward on the HIP kernels
+                if bridge:  # loss.backward() (train.py:141-143) runs self._backward on the HIP kernels
                     rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
                         im_data.device, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label)
+
+    _head_params = BW.lin("RCNN_cls_score.0")  # meta.py:199-201: a Sequential
+
+    def _backward(self, ctx, g, grads):
+        """frcnn's adjoint (meta.py:39-142) plus the class-attentive vectors: score = Linear(fc7 * mean_shots(sigmoid(mean(
+        layer4(maxpool2(trunk(support))))))) for the positive and the negative supports, so the support batch is
+        differentiated through layer4 and the trunk too"""
+        d_pos, d_neg, d_bbox = ctx["loss_seeds"]  # written by the fused mined-loss kernel (dana_rcnn_loss)
+        B, R, Ns, shot, way, fc7, att = ctx["B"], ctx["R"], ctx["Ns"], ctx["shot"], ctx["way"], ctx["fc7"], ctx["att"]
+        d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g[3])
+        d_att = torch.zeros((B, way * shot, 2048), dtype=torch.float32, device=fc7.device)
+        for hc in ctx["heads"]:
+            ds = d_pos if hc["offset"] == 0 else d_neg
+            BW.seed_linear_grads(self.RCNN_cls_score[0], ds, hc["comb"], g[2])
+            d_comb = BW.seed_linear_dx(self.RCNN_cls_score[0], ds, g[2])
+            d_fc7.add_(ops.scale_rows_by_group(d_comb, hc["vec"], B * R, R, 2048))
+            # the shots' mean of the attentive vectors: d vec[b] = sum over the image's rois of d_comb * fc7
+            d_vec = (d_comb * fc7).view(B, R, 2048).sum(1) / shot
+            d_att[:, hc["offset"]:hc["offset"] + shot] += d_vec.unsqueeze(1)
+        d_pre = (d_att.view(Ns, 2048) * att * (1.0 - att)).contiguous()  # sigmoid adjoint (meta.py:250)
+        d_mp = BW.layer4_backward(d_pre, Ns, ctx["sl4_saved"], grads)
+        # 2x2 / 2 max pool (meta.py:247) back onto the support maps: the window's (first) maximum takes the gradient
+        (sh_, sw_), (mh, mw) = ctx["sup_hw"], ctx["mp_hw"]
+        gs = ops.maxpool2x2s2_backward(ctx["sup"].view(Ns * sh_ * sw_, 1024), d_mp.contiguous().view(Ns * mh * mw, 1024), Ns,
+                                       sh_, sw_, 1024)
+        self._backward_below_fc7(ctx, g, grads, d_bbox, d_fc7, gs)

@@ -8,11 +8,12 @@ lib/model/framework/fsod.py:19-327 on the same HIP operators (SURVEY.md 8f row N
   3x3/1 average pool, 3x3 conv, 1x1 conv, average pool -> 2-way); the three scores are summed and divided by 10.
   The [roi | support] concatenations never exist: the 1x1 layers are split into their roi and support halves, the
   support half is computed once per image and added as a residual.
-Same parameter tree as the reference class. Trainable: backward.frcnn_backward's `fsod` branch (the three relation heads,
-the depth-wise correlation adjoints of the attention RPN and of the local-correlation head, the support trunk)."""
+Same parameter tree as the reference class. Trainable: `FSOD._backward` (the three relation heads, the depth-wise
+correlation adjoints of the attention RPN and of the local-correlation head, the support trunk)."""
 import torch
 import torch.nn as nn
 
+from . import backward as BW
 from . import ops
 from .dana import ClassSweep
 from .frcnn import FasterRCNN
@@ -181,7 +182,122 @@ class FSOD(FasterRCNN):
             ctx.update(loss_seeds=seeds, Ns=Ns, shot=shot, way=way, L=L, pos=pos, pooled=pooled, g_roi=g_roi,
                        corr_roi=corr_roi, wp2=wp2)
             self._ctx = ctx
-            if bridge:  # loss.backward() (train.py:141-143) runs backward.frcnn_backward (fsod branch) on the HIP kernels
+            if bridge:  # loss.backward() (train.py:141-143) runs self._backward on the HIP kernels
                 rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox = self._loss_bridge(
                     dev, (rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox))
         return (st["rois"], cls_prob, bbox_pred, rpn_loss_cls, rpn_loss_bbox, RCNN_loss_cls, RCNN_loss_bbox, rois_label)
+
+    # ---- training backward ---------------------------------------------------------------------------------------------
+    _head_params = (BW.lin("global_fc_1") + BW.lin("global_fc_2") + BW.lin("global_cls_score") + ["corr_conv.weight"]
+                    + BW.lin("corr_cls_score") + ["patch_conv_1.weight", "patch_conv_2.weight", "patch_conv_3.weight"]
+                    + BW.lin("patch_cls_score"))  # fsod.py:29-75: the three relation heads replace RCNN_cls_score
+
+    def _relation_heads_backward(self, ctx, grads, a3):
+        """Adjoint of both `head` calls of the forward (fsod.py:181-249): score = (global + local-correlation + patch) / 10
+        for the positive and the negative support (a3 = g3 / 10); every [roi | support] concatenation is a split layer (roi
+        half + support half). -> (d pooled [n_roi*49][1024] through the roi halves, {offset: d support [B*49][1024]})"""
+        d_pos, d_neg, _ = ctx["loss_seeds"]
+        B, R = ctx["B"], ctx["R"]
+        n_roi, P2, d, dq_ = B * R, 49, 1024, 256
+        pooled, g_roi, corr_roi = ctx["pooled"], ctx["g_roi"], ctx["corr_roi"]
+        dev = pooled.device
+        w1 = self.global_fc_1.weight.detach()
+        w2 = self.global_fc_2.weight.detach()
+        wcc = self.corr_conv.weight.detach().view(d, d).contiguous()
+        wp1 = self.patch_conv_1.weight.detach().view(dq_, 2 * d).contiguous()
+        wp3 = self.patch_conv_3.weight.detach().view(d, dq_).contiguous()
+        c_p2 = dict(cin=dq_, cout=dq_, k=3, stride=1, pad=0, w=ctx["wp2"], scale=None, u=None)
+        d_pooled_head = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
+        d_g_roi = torch.zeros((n_roi, d), dtype=torch.float32, device=dev)
+        d_corr_roi = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
+        d_w1 = torch.zeros((d, 2 * d), dtype=torch.float32, device=dev)
+        d_wp1 = torch.zeros((dq_, 2 * d), dtype=torch.float32, device=dev)
+        d_wcc = torch.zeros((d, d), dtype=torch.float32, device=dev)
+        d_supports = {}
+        for hc in ctx["heads"]:
+            ds = (d_pos if hc["offset"] == 0 else d_neg)
+            support = hc["support"]
+            d_support = torch.zeros((B * P2, d), dtype=torch.float32, device=dev)
+            # .. global relation: Linear(2) <- relu fc2 <- relu fc1([mean(roi) | mean(support)])
+            BW.seed_linear_grads(self.global_cls_score, ds, hc["h2"], a3)
+            d_h2 = BW.seed_linear_dx(self.global_cls_score, ds, a3)
+            ops.relu_mask_(d_h2, hc["h2"], n_roi, d)
+            dw2, db2, d_h1 = ops.linear_backward(d_h2, hc["h1"], w2, n_roi, d, d)
+            BW.acc(self.global_fc_2.weight, dw2)
+            BW.acc(self.global_fc_2.bias, db2)
+            ops.relu_mask_(d_h1, hc["h1"], n_roi, d)
+            dw1r, db1, _ = ops.linear_backward(d_h1, g_roi, w1, n_roi, d, d, ldw=2 * d, dx_out=d_g_roi, dx_ld=d)
+            ops.axpy_rows_(d_w1, dw1r, d, d, ld_y=2 * d)
+            BW.acc(self.global_fc_1.bias, db1)
+            d_gs = ops.spatial_mean(d_h1, B, R, d)  # the support half was broadcast over the image's R rois
+            d_gs.mul_(float(R))
+            dw1s = ops.gemm_small(d_gs, (1, d), hc["m_sup"], (d, 1), d, d, B)            # [d][d] = d_gs^T . mean(support)
+            ops.axpy_rows_(d_w1.view(-1)[d:], dw1s, d, d, ld_y=2 * d)
+            d_m_sup = ops.gemm_small(d_gs, (d, 1), w1.view(-1)[d:], (2 * d, 1), B, d, d)  # [B][d] = d_gs . w1[:, d:]
+            ops.broadcast_rows(d_m_sup, B, P2, d, alpha=1.0 / P2, out=d_support)
+            # .. local correlation: Linear(2) <- sum over the 49 positions of corr_conv(roi) * corr_conv(support)
+            BW.seed_linear_grads(self.corr_cls_score, ds, hc["oc"], a3)
+            d_oc = BW.seed_linear_dx(self.corr_cls_score, ds, a3)  # [n][1024] = a 1x1 output map
+            g_feat, g_kern = ops.depthwise_corr_backward(d_oc, corr_roi, hc["corr_sup"], n_roi, 7, 7, d, 7, 7,
+                                                         maps_per_kernel=R)
+            ops.axpy_rows_(d_corr_roi, g_feat, n_roi * P2, d)
+            dwc_s, _, _ = ops.linear_backward(g_kern.view(B * P2, d), support.view(B * P2, d), wcc, B * P2, d, d,
+                                              dx_out=d_support, dx_ld=d)
+            ops.axpy_rows_(d_wcc, dwc_s, d, d)
+            # .. patch relation: Linear(2) <- avgpool3 <- relu 1x1 <- relu 3x3 <- avgpool 3/1 <- relu 1x1([roi | support])
+            BW.seed_linear_grads(self.patch_cls_score, ds, hc["x4"], a3)
+            d_x4 = BW.seed_linear_dx(self.patch_cls_score, ds, a3)
+            d_x3 = ops.avgpool_backward(d_x4, n_roi, 3, 3, d, 3, 1).view(n_roi * 9, d)
+            ops.relu_mask_(d_x3, hc["x3"], n_roi * 9, d)
+            dwp3, _, d_x2 = ops.linear_backward(d_x3, hc["x2"], wp3, n_roi * 9, d, dq_)
+            BW.acc(self.patch_conv_3.weight, dwp3.view(d, dq_, 1, 1))
+            ops.relu_mask_(d_x2, hc["x2"], n_roi * 9, dq_)
+            grads.add_conv("patch_conv_2", d_x2, hc["x1"].view(n_roi * 25, dq_), n_roi, 5, 5, c_p2)
+            d_x1 = BW.conv_dgrad(d_x2, n_roi, 5, 5, c_p2)
+            d_x0 = ops.avgpool_backward(d_x1, n_roi, 7, 7, dq_, 3, 1).view(n_roi * P2, dq_)
+            ops.relu_mask_(d_x0, hc["x0"], n_roi * P2, dq_)
+            dwp1r, _, _ = ops.linear_backward(d_x0, pooled.view(n_roi * P2, d), wp1, n_roi * P2, dq_, d, ldw=2 * d,
+                                              dx_out=d_pooled_head, dx_ld=d)
+            ops.axpy_rows_(d_wp1, dwp1r, dq_, d, ld_y=2 * d)
+            d_p_sup = ops.spatial_mean(d_x0, B, R, P2 * dq_)  # the support half was broadcast over the image's rois
+            d_p_sup.mul_(float(R))
+            dwp1s, _, _ = ops.linear_backward(d_p_sup.view(B * P2, dq_), support.view(B * P2, d), wp1.view(-1)[d:],
+                                              B * P2, dq_, d, ldw=2 * d, dx_out=d_support, dx_ld=d)
+            ops.axpy_rows_(d_wp1.view(-1)[d:], dwp1s, dq_, d, ld_y=2 * d)
+            d_supports[hc["offset"]] = d_support
+        # the roi halves shared by both heads: mean over the 49 positions, corr_conv(rois)
+        ops.broadcast_rows(d_g_roi, n_roi, P2, d, alpha=1.0 / P2, out=d_pooled_head)
+        dwc_r, _, _ = ops.linear_backward(d_corr_roi, pooled.view(n_roi * P2, d), wcc, n_roi * P2, d, d,
+                                          dx_out=d_pooled_head, dx_ld=d)
+        ops.axpy_rows_(d_wcc, dwc_r, d, d)
+        BW.acc(self.global_fc_1.weight, d_w1)
+        BW.acc(self.patch_conv_1.weight, d_wp1.view(dq_, 2 * d, 1, 1))
+        BW.acc(self.corr_conv.weight, d_wcc.view(d, d, 1, 1))
+        return d_pooled_head, d_supports
+
+    def _backward(self, ctx, g, grads):
+        """frcnn's adjoint with the multi-relation head in place of RCNN_cls_score and the attention RPN's correlation in
+        front of the RPN; the supports are differentiated through the trunk"""
+        g1, g2, g3, g4, g_dev = g
+        B, n_roi, fh, fw, d_bbox = ctx["B"], ctx["B"] * ctx["R"], ctx["fh"], ctx["fw"], ctx["loss_seeds"][2]
+        d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g4)
+        gs = torch.zeros((ctx["Ns"] * ctx["L"], 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
+        d_pooled_head, d_supports = self._relation_heads_backward(ctx, grads, g3 / 10.0)  # fsod.py:237: (sum of 3) / 10
+        BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
+        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads)
+        grads.finish_all(self, "RCNN_top")
+        grads.finish_all(self, "patch_conv_2")
+        ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the heads' roi halves
+        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        d_rfeat = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads)
+        # attention RPN (fsod.py:109-116): the RPN ran on the depth-wise correlation of base_feat with the pooled positive
+        # support -> d base = full correlation of d rfeat with that kernel + RoIAlign path; d kernel -> positive supports
+        gq, d_pos_kernel = ops.depthwise_corr_backward(d_rfeat, ctx["base"], ctx["pos"], B, fh, fw, 1024, 7, 7)
+        ops.axpy_rows_(gq, d_bf, B * fh * fw, 1024)
+        ops.axpy_rows_(d_supports[0], d_pos_kernel.view(B * 49, 1024), B * 49, 1024)
+        for off_, d_sup_ in d_supports.items():  # AvgPool2d(14, 1) of the shots' mean map (fsod.py:98-101)
+            BW.shot_mean_backward(gs, ops.avgpool_backward(d_sup_, B, 20, 20, 1024, 14, 1), ctx, off_)
+        grads.finish_all(self, "RCNN_rpn")
+        BW.ready(self, BW.RPN_PARAMS)
+        BW.trunk_backward(self, ctx, grads, gq, gs)

@@ -160,6 +160,20 @@ def test_module_api_and_state_dict_contract():
         m.eval()(*S.episode_inputs(1, 1, 3, 64, 64))
 
 
+@pytest.mark.parametrize("name,count", [("DAnA", 70), ("frcnn", 52), ("meta", 52), ("fgn", 58), ("fsod", 64)])
+def test_grad_stages_name_every_trainable_parameter_once(name, count):
+    """backward.grad_stages finds each model's stage list through its class; together the stages are exactly the
+    requires_grad parameters, each once (Trainer.__init__ only notices a MISSING name, not a duplicate). The stub plan
+    holds what `_block_convs` reads: whether a block has a downsample conv."""
+    from dana_amd import backward as BW
+    m = dana_amd.get_model(name, pretrained=False, use_BA_block=True, way=2, shot=2, classes=["bg", "fg"])
+    blocks = lambda layer: [{"ds": True if blk.downsample is not None else None} for blk in layer]  # noqa: E731
+    plan = dict(layer4=blocks(m.RCNN_top[0]), layers=[None, blocks(m.RCNN_base[5]), blocks(m.RCNN_base[6])])
+    names = [n for _, stage in BW.grad_stages(m, plan) for n in stage]
+    assert len(names) == len(set(names)) == count
+    assert sorted(names) == sorted(n for n, p in m.named_parameters() if p.requires_grad)
+
+
 def test_config_overrides():
     assert cfg.ANCHOR_SCALES == [4, 8, 16, 32] and cfg.MAX_NUM_GT_BOXES == 50 and cfg.TRAIN.BATCH_SIZE == 128
     cfg_from_list(["TRAIN.RPN_POST_NMS_TOP_N", "1000"])

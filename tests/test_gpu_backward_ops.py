@@ -104,7 +104,7 @@ def test_mul_rows_bits_and_zero_rows_refused(dev):
 
 def test_axpy_rows(dev):
     """y (+)= alpha * x: alpha = 1 is one add (accumulate) or a copy (overwrite) -> torch's bits; alpha = 1 / shot
-    (backward.py to_supports) against float64, mag = |y| + |alpha x|"""
+    (backward.shot_mean_backward) against float64, mag = |y| + |alpha x|"""
     ops = _ops()
     g = _gen(13)
     for rows, c, ldy, ldx in [(r, 36, 40, 44) for r in ROWS] + [(5, c, c, c + 4) for c in CHANS] + [(400, 1024, 1024, 1024)]:
@@ -523,7 +523,7 @@ def test_gemm_small_vs_fp64(dev):
     K-split kernel at 64 and every tail of its 8-step loop; m = 65536 with k = 64 falls back to one lane per element"""
     ops = _ops()
     g = _gen(41)
-    # production (backward.py:597-634): d scores^T . hid  ((1, 2) / (nhid, 1)),  d bbox . W  ((4, 1) / (2048, 1))
+    # production (backward.seed_linear_grads / seed_linear_dx): d scores^T . hid  ((1, 2) / (nhid, 1)),  d bbox . W  ((4, 1) / (2048, 1))
     _gemm_small_case(ops, dev, g, 2, 1024, 256, True, False, False, False, 0.5)
     _gemm_small_case(ops, dev, g, 256, 2048, 4, False, False, False, False, 0.25)
     _gemm_small_case(ops, dev, g, 4, 2048, 256, True, False, False, False, 1.0)

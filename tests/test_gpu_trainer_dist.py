@@ -109,7 +109,7 @@ def test_two_rank_training_iteration_replayed_from_launch_programs(dev):
 
 
 def test_two_rank_training_iteration_of_the_frcnn_sibling(dev):
-    """the same exchange for the plain Faster R-CNN sibling (backward.frcnn_backward marks its own gradient stages)"""
+    """the same exchange for the plain Faster R-CNN sibling (FasterRCNN._backward marks its own gradient stages)"""
     single = _run(1, True, "frcnn")[0]
     same = _run(2, True, "frcnn")
     assert np.array_equal(same[0][2], same[1][2])  # the replicas stay bit-identical
