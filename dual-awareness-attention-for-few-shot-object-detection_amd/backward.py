@@ -199,7 +199,7 @@ def bottleneck_backward(g, saved, n, h, w, bp, grads, key, need_dx=True, mask_dx
 
 def bottleneck_backward_merged(g, sq, ss, sm, bp, grads, key):
     """bottleneck_backward for an identity-shortcut block (no downsample, stride 1) over the [query | support] buffers of
-    DAnARCNN._rcnn_base_dual: g = dL/d(o3) of BOTH batches in one [Mq + Ms][cout] tensor, ReLU adjoint applied. The three
+    DAnARCNN._trunk_gen's two-segment walk: g = dL/d(o3) of BOTH batches in one [Mq + Ms][cout] tensor, ReLU adjoint applied. The three
     1x1 convs are row-wise contractions -- their weight gradients and data gradients run ONCE over all rows (half the
     launches, twice the reduction length per weight-gradient slice); the 3x3 conv in the middle keeps one call per batch
     (its Winograd tiles follow the image geometry), writing into the two row ranges of one buffer. -> dL/dx, merged, with

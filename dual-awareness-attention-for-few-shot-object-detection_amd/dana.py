@@ -15,6 +15,7 @@ Data layout in HBM (all fp32):
   conv weights  ``[cout][kh][kw][cin]``; nn.Linear weights ``[out][in]`` used as stored.
   frozen BN     folded to per-channel scale/shift applied in the conv epilogue (dana.py:362-385).
 """
+import contextlib
 import math
 import time
 import weakref
@@ -143,6 +144,19 @@ class _LossBridge(torch.autograd.Function):
         return None, None, None, None, None, None
 
 
+_HERE = contextlib.nullcontext()
+
+
+def _on(stream):
+    """`with` for the launches of a batch segment (DAnARCNN._conv): on its stream, or (None) on the current one"""
+    return _HERE if stream is None else ops.on_stream(stream)
+
+
+def _rows(t, row):
+    """t's rows from `row` on (a missing operand stays None)"""
+    return t[row:] if row and t is not None else t
+
+
 class DAnARCNN(nn.Module):
     """Dual-Awareness-Attention Faster R-CNN (dana.py:19,327)."""
 
@@ -172,16 +186,14 @@ class DAnARCNN(nn.Module):
         # measured break-even: F(4x4) pays from 128 input channels (layer2), F(2x2) from 256 (its transformed tensors
         # are 4x the input instead of 2.25x)
         self.winograd_min_cin = 128
-        self.fuse_downsample = True  # first block of a layer: expand + downsample 1x1 convs as one contraction
-        self.fuse_tail = True  # conv2 + conv3 of layer1's identity blocks as one launch
-        # False (measured faster): support trunk on its own stream, concurrent with the query trunk;
-        # True: query + support batches share every trunk launch (dana_conv2d_nhwc_dual)
         self.presplit_weights = True  # weights as bf16x3 planes, split once per version
-        # query + support batch through ONE set of activation buffers (_rcnn_base_dual; merge_from says which stages also share
-        # their launches). 0: two independent _rcnn_base calls
+        # False (measured faster): support trunk on its own stream, concurrent with the query trunk: two one-segment walks
+        # (_trunk_gen), each with its own buffers;
+        # True: query + support batch as two segments of ONE set of activation buffers (merge_from says which stages also
+        # share their launches, dana_conv2d_nhwc_dual)
         self.merge_trunk = False
         # first trunk stage whose convs run as ONE launch over both batches (0: stem + layer1 .. 2: layer3 only, 3: none);
-        # the stages in front of it run the two batches on two streams (_rcnn_base_dual)
+        # the stages in front of it run the two batches as two launches on two streams
         self.merge_from = 0
         # forward-only runs: RoI-level positional encoding folded into one fused query projection (see _roi_query_fold)
         self.fold_roi_pe = True
@@ -486,85 +498,252 @@ class DAnARCNN(nn.Module):
         return e[1], e[2], tfull
 
     # ---- trunk -----------------------------------------------------------------------------------
+    # The trunk code works on a list of BATCH SEGMENTS: (images, (h, w), first row in the activation buffer, stream -- None:
+    # the current one). One segment is a batch with buffers of its own: every sibling, encode_supports, the cached forward,
+    # layer4, and each of the default forward's two alternated trunks. Two segments are the query and the support batch in
+    # one set of [query rows | support rows] buffers (merge_trunk): a conv is either one launch per segment on the segment's
+    # stream, or -- `merged`, both segments on the current stream -- ONE `*_dual` launch over both.
     @staticmethod
-    def _conv(x, n, h, w, c, relu, residual=None, res_stride=0, out=None, out_stride=0, in_stride=0, keep_v=None):
-        if c.get("u") is not None and residual is None:
-            return ops.conv3x3_winograd(x, n, h, w, c["cin"], c.get("us") or c["u"], c["cout"], scale=c["scale"],
-                                        shift=c["shift"], relu=relu, in_stride=in_stride, out=out, out_stride=out_stride,
-                                        keep_v=keep_v)
-        return ops.conv2d_nhwc(x, n, h, w, c["cin"], c.get("ws") or c["w"], c["cout"], c["k"], c["k"], c["stride"], c["pad"],
-                               scale=c["scale"], shift=c["shift"], residual=residual, relu=relu,
-                               in_stride=in_stride, out=out, out_stride=out_stride, res_stride=res_stride)
+    def _b(c):
+        """B operand of a contraction: the weight's three bf16 planes where the plan split them, else the fp32 rows"""
+        return c.get("ws") or c["w"]
 
-    def _bottleneck(self, x, n, h, w, bp, out=None, out_stride=0, in_stride=0, save=None, key=None):
-        """save: optional list; receives dict(x, o1, o2, o3, h1, w1, ...) for backward.bottleneck_backward"""
-        o1, h1, w1 = self._conv(x, n, h, w, bp["c1"], True, in_stride=in_stride)
-        c2, c3 = bp["c2"], bp["c3"]
-        if (getattr(self, "fuse_tail", True) and save is None and bp["ds"] is None and c2["cout"] == 64 and c2["k"] == 3 and c2["stride"] == 1
-                and c2.get("u") is None and c2.get("ws") is not None and c3.get("ws") is not None):
+    @staticmethod
+    def _grid(segs, size):
+        """the segments on the grid that a layer maps theirs to (size: (h, w) -> (oh, ow)), rows packed in the same order"""
+        out, row = [], 0
+        for n, (h, w), _, st in segs:
+            hw = size(h, w)
+            out.append((n, hw, row, st))
+            row += n * hw[0] * hw[1]
+        return out
+
+    @staticmethod
+    def _dest(segs, cols, outs, alloc, dev):
+        """where a launch over `segs` writes, per segment (row view, row stride): `outs` as given, else the row ranges of
+        one fresh [all rows][cols] buffer (alloc: the two-segment walk's shared-buffer rule)"""
+        if outs is not None:
+            return outs
+        n, (h, w), row, _ = segs[-1]
+        rows = row + n * h * w
+        o = alloc(rows, cols) if alloc is not None else torch.empty((rows, cols), dtype=torch.float32, device=dev)
+        return [(_rows(o, s[2]), cols) for s in segs]
+
+    def _conv(self, segs, osegs, x, c, relu, merged=False, res=None, res_stride=0, outs=None, in_stride=0, keep=None,
+              alloc=None, stem=False):
+        """one conv (+ folded BN, residual, ReLU) of the trunk, x's rows on `segs` -> rows on `osegs`. Not merged: one launch
+        per segment, on its stream, over its row views; merged (two segments): ONE `*_dual` launch. keep: per segment a list
+        that receives the Winograd V planes. -> the output buffer (with `outs`: the first segment's)"""
+        cin, cout, k, sd, pd = 4 if stem else c["cin"], c["cout"], c["k"], c["stride"], c["pad"]
+        u = c.get("u")
+        # Winograd where the plan made filters and no residual is added. A merged launch exists for F(4x4) filters writing one
+        # [query | support] buffer only (else: the direct dual conv); the per-segment launches take whatever the filter is
+        wino = u is not None and res is None and (not merged or (u.size(0) == 36 and outs is None))
+        b = (c.get("us") or u) if wino else self._b(c)
+        dest = self._dest(osegs, cout, outs, alloc, x.device)
+        if merged:
+            (n0, (h0, w0), _, _), (n1, (h1, w1), _, _) = segs
+            (o0, s0), (o1, s1) = dest
+            if wino:
+                ops.conv3x3_winograd_dual(x, n0, h0, w0, n1, h1, w1, cin, b, cout, scale=c["scale"], shift=c["shift"],
+                                          relu=relu, out=o0)
+            else:
+                ops.conv2d_nhwc_dual(x, n0, h0, w0, n1, h1, w1, cin, b, cout, k, k, sd, pd, scale=c["scale"],
+                                     shift=c["shift"], res0=res, res1=_rows(res, osegs[1][2]), relu=relu, in_stride=in_stride,
+                                     out0=o0, out1=o1, out0_stride=s0, out1_stride=s1, res0_stride=res_stride,
+                                     res1_stride=res_stride, stem=stem)
+            return o0
+        for i, ((n, (h, w), row, st), (o, ld)) in enumerate(zip(segs, dest)):
+            with _on(st):
+                if wino:
+                    ops.conv3x3_winograd(_rows(x, row), n, h, w, cin, b, cout, scale=c["scale"], shift=c["shift"], relu=relu,
+                                         in_stride=in_stride, out=o, out_stride=ld,
+                                         keep_v=keep[i] if keep is not None else None)
+                else:
+                    ops.conv2d_nhwc(_rows(x, row), n, h, w, cin, b, cout, k, k, sd, pd, scale=c["scale"], shift=c["shift"],
+                                    residual=_rows(res, osegs[i][2]), relu=relu, in_stride=in_stride, out=o, out_stride=ld,
+                                    res_stride=res_stride, stem=stem)
+        return dest[0][0]
+
+    def _stem(self, segs, ims, c, merged, alloc):
+        """layout change, 7x7 / 2 stem conv, ceil-mode 3x3 / 2 max-pool (RCNN_base[0:4]) -> (x, segs on the pooled grid)"""
+        csegs = self._grid(segs, lambda h, w: ((h - 1) // 2 + 1, (w - 1) // 2 + 1))  # (7x7, stride 2, pad 3)
+        psegs = self._grid(csegs, ops.maxpool_out_size)
+        dev = ims[0].device
+        x4, xs, xp = (self._dest(g, cols, None, alloc, dev) for g, cols in ((segs, 4), (csegs, 64), (psegs, 64)))
+        # merged: both layout changes, ONE conv launch, both pools; else each segment's whole chain in turn, on its stream
+        for g in ([slice(None)] if merged else [slice(i, i + 1) for i in range(len(segs))]):
+            for im, (o, _), (_, _, _, st) in zip(ims[g], x4[g], segs[g]):
+                with _on(st):
+                    ops.nchw_to_nhwc(im, cpad=4, out=o)
+            self._conv(segs[g], csegs[g], x4[0][0], c, True, merged, outs=xs[g], stem=True)
+            for (n, (h, w), row, st), (o, _) in zip(csegs[g], xp[g]):
+                with _on(st):
+                    ops.maxpool3x3s2_ceil(_rows(xs[0][0], row), n, h, w, 64, out=o)
+        return xp[0][0], psegs
+
+    def _block(self, segs, x, bp, merged=False, outs=None, in_stride=0, saves=None, key=None, alloc=None, save_m=None):
+        """one Bottleneck (resnet.py:66-108) over the batch segments of x -> (o3, segs on the block's output grid, outs).
+        outs: per segment (buffer, or None for a fresh one; row stride) that the block's result goes to instead of a dense
+        [all rows][cout] buffer. saves: per segment a list (None: nothing is saved) that receives dict(x, o1, o2, o3, h1, w1, ...) for
+        backward.bottleneck_backward (row views of the segments' buffers); save_m: a list that receives the [query | support]
+        buffers themselves (backward.bottleneck_backward_merged). in_stride: row stride of x (per-segment launches only)"""
+        if merged and in_stride:
+            raise ValueError("a merged block reads dense rows")
+        if saves is not None and saves[0] is None:
+            saves = None
+        c1, c2, c3, ds = bp["c1"], bp["c2"], bp["c3"], bp["ds"]
+        dev, cout, sd = x.device, c3["cout"], c1["stride"]
+        osegs = self._grid(segs, lambda h, w: ((h - 1) // sd + 1, (w - 1) // sd + 1))  # (the 1x1 conv1 carries the stride)
+        calloc = None if merged else alloc  # (a merged launch's output is written and read on the caller's stream alone)
+        o1 = self._conv(segs, osegs, x, c1, True, merged, in_stride=in_stride, alloc=calloc)
+
+        def given():
+            # the buffers the caller names (query features in corr's first half, ...). A fresh one that a side stream
+            # writes follows the shared-buffer rule whatever the mode: allocated -- an event recorded -- behind conv2
+            if outs is None:
+                return None
+            return [(t if t is not None else alloc(n * h * w, ld) if i and alloc is not None else
+                     torch.empty((n * h * w, ld), dtype=torch.float32, device=dev), ld)
+                    for i, ((n, (h, w), _, _), (t, ld)) in enumerate(zip(osegs, outs))]
+
+        if (not merged and saves is None and ds is None and c2["cout"] == 64 and c2["k"] == 3 and c2["stride"] == 1
+                and c2.get("u") is None and c2["ws"] is not None and c3["ws"] is not None):
             # conv2 -> conv3 in one launch (layer1's identity blocks; nothing of a frozen layer is saved for the backward)
-            return ops.bottleneck_tail(o1, n, h1, w1, c2["cin"], c2["ws"], c2["scale"], c2["shift"], c3["ws"], c3["scale"],
-                                       c3["shift"], c3["cout"], residual=x, res_stride=in_stride, out=out,
-                                       out_stride=out_stride)
-        kv = [] if save is not None else None  # conv2's Winograd-domain input (V planes) for its weight gradient
-        o2, _, _ = self._conv(o1, n, h1, w1, bp["c2"], True, keep_v=kv)
-        v2 = kv[0] if kv else None
-        if bp.get("cat") is not None and getattr(self, "fuse_downsample", True) and ops.get_mfma_mode() != 0:
-            c3, ds = bp["c3"], bp["ds"]
-            o3, _, _ = ops.conv1x1_cat2(o2, c3["cin"], x, ds["cin"], n, h, w, ds["stride"], bp["cat"].get("ws") or bp["cat"]["w"],
-                                        bp["cat"]["shift"], c3["cout"], relu=True, a1_stride=in_stride, out=out,
-                                        out_stride=out_stride)
-            if save is not None:
-                save.append(dict(x=x, o1=o1, o2=o2, o3=o3, h1=h1, w1=w1, n=n, h=h, w=w, bp=bp, key=key, o3_ld=out_stride, v2=v2))
-            return o3, h1, w1
-        if bp["ds"] is not None:
-            res, _, _ = self._conv(x, n, h, w, bp["ds"], False, in_stride=in_stride)
-            rs = 0
+            outs = given()
+            dest = self._dest(osegs, cout, outs, calloc, dev)
+            for (n, _, row, st), (_, (h1, w1), orow, _), (o, ld) in zip(segs, osegs, dest):
+                with _on(st):
+                    ops.bottleneck_tail(_rows(o1, orow), n, h1, w1, c2["cin"], c2["ws"], c2["scale"], c2["shift"], c3["ws"],
+                                        c3["scale"], c3["shift"], cout, residual=_rows(x, row), res_stride=in_stride, out=o,
+                                        out_stride=ld)
+            return dest[0][0], osegs, outs
+        keep = [[] for _ in segs] if saves is not None else None  # conv2's Winograd-domain input (V planes), per segment, for
+        o2 = self._conv(osegs, osegs, o1, c2, True, merged, keep=keep, alloc=calloc)  # its weight gradient
+        outs = given()
+        if bp.get("cat") is not None and ops.get_mfma_mode() != 0:
+            # expand conv + downsample conv as ONE contraction over the concatenated channels (_block_plan)
+            cat = bp["cat"]
+            dest = self._dest(osegs, cout, outs, calloc, dev)
+            if merged:
+                (n0, (h0, w0), _, _), (n1, (h1, w1), _, _) = segs
+                ops.conv1x1_cat2_dual(o2, c3["cin"], x, ds["cin"], n0, h0, w0, n1, h1, w1, ds["stride"], self._b(cat),
+                                      cat["shift"], cout, relu=True, out0=dest[0][0], out1=dest[1][0],
+                                      out0_stride=dest[0][1], out1_stride=dest[1][1])
+            else:
+                for (n, (h, w), row, st), (_, _, orow, _), (o, ld) in zip(segs, osegs, dest):
+                    with _on(st):
+                        ops.conv1x1_cat2(_rows(o2, orow), c3["cin"], _rows(x, row), ds["cin"], n, h, w, ds["stride"],
+                                         self._b(cat), cat["shift"], cout, relu=True, a1_stride=in_stride, out=o, out_stride=ld)
+            o3 = dest[0][0]
         else:
             res, rs = x, in_stride
-        o3, _, _ = self._conv(o2, n, h1, w1, bp["c3"], True, residual=res, res_stride=rs, out=out,
-                              out_stride=out_stride)
-        if save is not None:
-            save.append(dict(x=x, o1=o1, o2=o2, o3=o3, h1=h1, w1=w1, n=n, h=h, w=w, bp=bp, key=key, o3_ld=out_stride, v2=v2))
+            if ds is not None:
+                res, rs = self._conv(segs, osegs, x, ds, False, merged, in_stride=in_stride, alloc=calloc), 0
+            o3 = self._conv(osegs, osegs, o2, c3, True, merged, res=res, res_stride=rs, outs=outs, alloc=calloc)
+        if saves is not None:
+            for i, ((n, (h, w), row, _), (_, (h1, w1), orow, _)) in enumerate(zip(segs, osegs)):
+                sx, s1, s2, s3 = x, o1, o2, o3
+                if len(segs) > 1:
+                    m, mo = n * h * w, n * h1 * w1
+                    sx, s1, s2, s3 = x[row:row + m], o1[orow:orow + mo], o2[orow:orow + mo], o3[orow:orow + mo]
+                s3, ld = outs[i] if outs is not None else (s3, 0)
+                saves[i].append(dict(x=sx, o1=s1, o2=s2, o3=s3, h1=h1, w1=w1, n=n, h=h, w=w, bp=bp, key=key, o3_ld=ld,
+                                     v2=keep[i][0] if keep[i] else None))
+            if save_m is not None:
+                save_m.append(dict(x=x, o1=o1, o2=o2, o3=None if outs is not None else o3, mq_in=segs[1][2],
+                                   mq_out=osegs[1][2], m_in=x.size(0), m_out=o1.size(0)))
+        return o3, osegs, outs
+
+    def _bottleneck(self, x, n, h, w, bp, out=None, out_stride=0, in_stride=0, save=None, key=None):
+        """one Bottleneck on one batch with its own buffers -> (o3, h1, w1); save: optional list (see _block)"""
+        o3, ((_, (h1, w1), _, _),), _ = self._block([(n, (h, w), 0, None)], x, bp, in_stride=in_stride, key=key,
+                                                    outs=[(out, out_stride)] if out is not None else None,
+                                                    saves=[save])
         return o3, h1, w1
 
-    def _rcnn_base(self, im, plan, out_stride=0, out_buf=None, save=None):
-        """RCNN_base (dana.py:344-345) on NCHW input -> (NHWC flat buffer [n*h*w][out_stride or 1024], h, w).
-        out_buf: write the result there (row stride out_stride) instead of allocating."""
-        gen = self._rcnn_base_gen(im, plan, out_stride, out_buf, save)
+    @staticmethod
+    def _drain(gen):
         try:
             while True:
                 next(gen)
         except StopIteration as done:
             return done.value
 
-    def _rcnn_base_gen(self, im, plan, out_stride=0, out_buf=None, save=None):
-        """_rcnn_base as a generator that pauses after the stem and after every bottleneck block: the forward issues the
-        query and the support trunk ALTERNATELY (each on its own stream), so both streams have work from the step's first
-        launch on -- issued one after the other, the second trunk's first kernel reaches the GPU a millisecond of host
-        time after the first's, and until then one stream of dependent launches has the chip to itself"""
-        n, _, H, W = im.shape
-        x4 = ops.nchw_to_nhwc(im, cpad=4)
-        st = plan["stem"]
-        x, h, w = ops.conv2d_nhwc(x4, n, H, W, 4, st.get("ws") or st["w"], 64, 7, 7, 2, 3, scale=st["scale"],
-                                  shift=st["shift"], relu=True, stem=True)
-        x, h, w = ops.maxpool3x3s2_ceil(x, n, h, w, 64)
+    def _rcnn_base(self, im, plan, out_stride=0, out_buf=None, save=None):
+        """RCNN_base (dana.py:344-345) on NCHW input -> (NHWC flat buffer [n*h*w][out_stride or 1024], h, w).
+        out_buf: write the result there (row stride out_stride) instead of allocating."""
+        x, ((_, (h, w), _, _),), _ = self._drain(self._trunk_gen(
+            [im], plan, outs=[(out_buf, out_stride)], saves=[save]))
+        return x, h, w
+
+    def _trunk_gen(self, ims, plan, outs=((None, 0),), saves=None, side=None, merge_from=None, save_m=None):
+        """RCNN_base (dana.py:344-345) on one NCHW batch, or on the query batch AND the support batch (dana.py:98,100: the
+        same weights) as two segments of one set of [query pixels | support pixels][channels] buffers
+        -> (last block's o3, segments on its grid, per segment (the block's output, row stride)).
+        A generator that pauses after the stem and after every bottleneck block: the default forward issues the query and
+        the support trunk -- two one-segment walks -- ALTERNATELY (each on its own stream), so both streams have work from
+        the step's first launch on -- issued one after the other, the second trunk's first kernel reaches the GPU a
+        millisecond of host time after the first's, and until then one stream of dependent launches has the chip to itself.
+        outs: per batch (buffer, or None for a fresh one; row stride) of the last block's output; stride 0: dense, fresh.
+        saves: per batch a list that receives the per-block dicts of `_block` (layer1 is frozen: nothing from there).
+        Two batches: stages >= `merge_from` (0: stem + layer1, 1: layer2, 2: layer3) issue ONE launch per conv over both
+        -- the 1x1 / stride-1 convs see a plain GEMM over all rows, the strided / 3x3 / stem convs carry the two image
+        geometries (`*_dual` entry points), the Winograd 3x3s run two input transforms, one batched plane GEMM over all
+        tiles and two output transforms. The stages in front of it run the two batches as two launches on two streams (the
+        caller's and `side`) over the two row ranges of the same buffers: the big early layers fill the chip alone and
+        overlap each other's tails, the tile-starved late layers share their launches."""
+        two, dev = len(ims) > 1, ims[0].device
+        alloc = None
+        if two:
+            main = ops.cur_stream()
+            if side == main:
+                side = None  # (bench.py's per-launch timing pass: the same launches, one stream)
+
+            def alloc(rows, cols):
+                """a buffer both streams write (their own row ranges). It comes from the CALLER's stream pool: the block may
+                have been released a moment ago by an op of that stream whose kernel is still queued (a workspace, an op's
+                own output), which is safe for later work of that stream only -- so the support stream waits for the
+                caller's stream to reach this point before it touches the buffer (it may not run ahead of the allocation)"""
+                t = torch.empty((rows, cols), dtype=torch.float32, device=dev)
+                if side is not None:
+                    t.record_stream(side)
+                    ev = torch.cuda.Event()
+                    ev.record(main)
+                    side.wait_event(ev)
+                return t
+
+        def join(segs):
+            """the support chain joins the caller's stream: everything after it is issued there"""
+            if side is not None:
+                main.wait_event(ops.record_event(side))
+            return [(n, hw, row, None) for n, hw, row, _ in segs]
+
+        merged = two and merge_from <= 0
+        segs, row = [], 0
+        for i, im in enumerate(ims):
+            n, _, H, W = im.shape
+            segs.append((n, (H, W), row, side if i and not merged else None))
+            row += n * H * W
+        x, segs = self._stem(segs, ims, plan["stem"], merged, alloc)
         yield
         nl = len(plan["layers"])
-        for li, layer in enumerate(plan["layers"]):
+        stall = getattr(self, "_debug_stall", None) if two else None  # tests: (layer, spin cycles) -- hold the caller's
+        for li, layer in enumerate(plan["layers"]):                  # stream back in front of every two-launch block there
+            if two and not merged and li >= merge_from:
+                segs, merged = join(segs), True
             for bi, bp in enumerate(layer):
                 last = (li == nl - 1) and (bi == len(layer) - 1)
-                out = None
-                if last and out_stride:
-                    hh = (h - 1) // bp["c1"]["stride"] + 1
-                    ww = (w - 1) // bp["c1"]["stride"] + 1
-                    out = out_buf if out_buf is not None else torch.empty((n * hh * ww, out_stride),
-                                                                          dtype=torch.float32, device=im.device)
-                x, h, w = self._bottleneck(x, n, h, w, bp, out=out, out_stride=out_stride if last else 0,
-                                           save=save if li > 0 else None, key="RCNN_base.%d.%d" % (4 + li, bi))
+                if stall is not None and not merged and li == stall[0]:
+                    torch.cuda._sleep(int(stall[1]))
+                x, segs, dest = self._block(segs, x, bp, merged, outs=outs if last and outs[0][1] else None,
+                                            saves=saves if li > 0 else None, key="RCNN_base.%d.%d" % (4 + li, bi), alloc=alloc,
+                                            save_m=save_m)
                 if not last:
                     yield
-        return x, h, w
+        if two and not merged:
+            segs = join(segs)
+        return x, segs, dest
 
     @staticmethod
     def _feat_size(H, W):
@@ -574,176 +753,6 @@ class DAnARCNN(nn.Module):
         for _ in range(2):
             h, w = (h - 1) // 2 + 1, (w - 1) // 2 + 1
         return h, w
-
-    def _rcnn_base_dual(self, im, sup_ims, plan, dev, save_q=None, save_s=None, sup_stream=None, merge_from=0, save_m=None):
-        """RCNN_base on the query batch AND the support batch (dana.py:98,100: the same weights). Every activation is one
-        buffer [query pixels | support pixels][channels]. Stages >= `merge_from` (0: stem + layer1, 1: layer2, 2: layer3)
-        issue ONE launch per conv over both batches -- the 1x1 / stride-1 convs see a plain GEMM over all rows, the strided
-        / 3x3 / stem convs carry the two image geometries (`*_dual` entry points), the Winograd 3x3s run two input
-        transforms, one batched plane GEMM over all tiles and two output transforms. The stages in front of it run the two
-        batches as two launches on two streams (the caller's and `sup_stream`) over the two row ranges of the same buffers:
-        the big early layers fill the chip alone and overlap each other's tails, the tile-starved late layers share
-        their launches. -> (corr [B*h*w][2048] with base_feat in channels 0..1023, (h, w), sup [Ns*sh*sw][1024], (sh, sw));
-        save_q / save_s receive the per-block dicts of `_bottleneck` (views of the merged buffers)."""
-        n0, _, H0, W0 = im.shape
-        n1, _, H1, W1 = sup_ims.shape
-        main = ops.cur_stream()
-        if sup_stream is None or sup_stream == main:
-            sup_stream = main  # (bench.py's per-launch timing pass: the same launches, one stream)
-        two = [merge_from > 0]  # currently issuing the two batches as two launches (on two streams)
-
-        def buf(rows, cols):
-            """a buffer both streams write (their own row ranges). It comes from the CALLER's stream pool: the block may
-            have been released a moment ago by an op of that stream whose kernel is still queued (a workspace, an op's own
-            output), which is safe for later work of that stream only -- so the support stream waits for the caller's
-            stream to reach this point before it touches the buffer (it may not run ahead of the allocation)"""
-            t = torch.empty((rows, cols), dtype=torch.float32, device=dev)
-            if sup_stream is not main:
-                t.record_stream(sup_stream)
-                ev = torch.cuda.Event()
-                ev.record(main)
-                sup_stream.wait_event(ev)
-            return t
-
-        def on_sup():
-            return torch.cuda.stream(sup_stream)
-
-        def join():
-            """the support chain joins the caller's stream: everything after it is one launch over both batches"""
-            if two[0]:
-                if sup_stream is not main:
-                    ev = torch.cuda.Event()
-                    ev.record(sup_stream)
-                    main.wait_event(ev)
-                two[0] = False
-
-        m0i, m1i = n0 * H0 * W0, n1 * H1 * W1
-        x4 = buf(m0i + m1i, 4)
-        st = plan["stem"]
-        stw = st.get("ws") or st["w"]
-        g0, g1 = ((H0 + 6 - 7) // 2 + 1, (W0 + 6 - 7) // 2 + 1), ((H1 + 6 - 7) // 2 + 1, (W1 + 6 - 7) // 2 + 1)
-        p0, p1 = ops.maxpool_out_size(*g0), ops.maxpool_out_size(*g1)
-        mq, ms_ = n0 * g0[0] * g0[1], n1 * g1[0] * g1[1]
-        xs = buf(mq + ms_, 64)
-        xp = buf(n0 * p0[0] * p0[1] + n1 * p1[0] * p1[1], 64)
-        ops.nchw_to_nhwc(im, cpad=4, out=x4)
-        if two[0]:
-            ops.conv2d_nhwc(x4, n0, H0, W0, 4, stw, 64, 7, 7, 2, 3, scale=st["scale"], shift=st["shift"], relu=True,
-                            stem=True, out=xs, out_stride=64)
-            ops.maxpool3x3s2_ceil(xs, n0, g0[0], g0[1], 64, out=xp)
-            with on_sup():
-                ops.nchw_to_nhwc(sup_ims, cpad=4, out=x4[m0i:])
-                ops.conv2d_nhwc(x4[m0i:], n1, H1, W1, 4, stw, 64, 7, 7, 2, 3, scale=st["scale"], shift=st["shift"],
-                                relu=True, stem=True, out=xs[mq:], out_stride=64)
-                ops.maxpool3x3s2_ceil(xs[mq:], n1, g1[0], g1[1], 64, out=xp[n0 * p0[0] * p0[1]:])
-        else:
-            ops.nchw_to_nhwc(sup_ims, cpad=4, out=x4[m0i:])
-            ops.conv2d_nhwc_dual(x4, n0, H0, W0, n1, H1, W1, 4, stw, 64, 7, 7, 2, 3, scale=st["scale"], shift=st["shift"],
-                                 relu=True, stem=True, out0=xs, out1=xs[mq:], out0_stride=64, out1_stride=64)
-            ops.maxpool3x3s2_ceil(xs, n0, g0[0], g0[1], 64, out=xp)
-            ops.maxpool3x3s2_ceil(xs[mq:], n1, g1[0], g1[1], 64, out=xp[n0 * p0[0] * p0[1]:])
-        x, g0, g1 = xp, p0, p1
-        split = ops.get_mfma_mode() != 0
-        fuse_ds = getattr(self, "fuse_downsample", True) and split
-
-        def conv(xin, gi0, gi1, c, relu, res=None, out0=None, out1=None, s0=0, s1=0, keep=None):
-            """one conv over both batches -> (merged output or out0, (oh0, ow0), (oh1, ow1))"""
-            st_, k_, pd = c["stride"], c["k"], c["pad"]
-            h0 = ((gi0[0] + 2 * pd - k_) // st_ + 1, (gi0[1] + 2 * pd - k_) // st_ + 1)
-            h1 = ((gi1[0] + 2 * pd - k_) // st_ + 1, (gi1[1] + 2 * pd - k_) // st_ + 1)
-            mi, mo = n0 * gi0[0] * gi0[1], n0 * h0[0] * h0[1]
-            wino = c.get("u") is not None and res is None and (c["u"].size(0) == 36 or two[0])
-            if two[0]:
-                if out0 is None:
-                    o = buf(mo + n1 * h1[0] * h1[1], c["cout"])
-                    out0, out1, s0, s1 = o, o[mo:], c["cout"], c["cout"]
-                else:
-                    o = out0
-                r0, r1 = (res, res[mo:]) if res is not None else (None, None)
-                for grp, (xi, n_, gi, oo, so, rr) in enumerate(((xin, n0, gi0, out0, s0, r0), (xin[mi:], n1, gi1, out1, s1, r1))):
-                    with (on_sup() if grp else torch.cuda.stream(main)):
-                        if wino:
-                            ops.conv3x3_winograd(xi, n_, gi[0], gi[1], c["cin"], c.get("us") or c["u"], c["cout"],
-                                                 scale=c["scale"], shift=c["shift"], relu=relu, out=oo, out_stride=so,
-                                                 keep_v=keep[grp] if keep is not None else None)
-                        else:
-                            ops.conv2d_nhwc(xi, n_, gi[0], gi[1], c["cin"], c.get("ws") or c["w"], c["cout"], k_, k_, st_, pd,
-                                            scale=c["scale"], shift=c["shift"], residual=rr, relu=relu, out=oo, out_stride=so)
-                return o, h0, h1
-            if wino and out0 is None:
-                return (ops.conv3x3_winograd_dual(xin, n0, gi0[0], gi0[1], n1, gi1[0], gi1[1], c["cin"], c.get("us") or c["u"],
-                                                  c["cout"], scale=c["scale"], shift=c["shift"], relu=relu), gi0, gi1)
-            r0, r1 = (res, res[mo:]) if res is not None else (None, None)
-            o0, _, _, _ = ops.conv2d_nhwc_dual(xin, n0, gi0[0], gi0[1], n1, gi1[0], gi1[1], c["cin"], c.get("ws") or c["w"],
-                                               c["cout"], k_, k_, st_, pd, scale=c["scale"], shift=c["shift"], res0=r0,
-                                               res1=r1, relu=relu, out0=out0, out1=out1, out0_stride=s0, out1_stride=s1)
-            return o0, h0, h1
-
-        corr = sup = None
-        nl = len(plan["layers"])
-        stall = getattr(self, "_debug_stall", None)  # tests: (layer, spin cycles) -- hold the caller's stream back there
-        for li, layer in enumerate(plan["layers"]):
-            if li >= merge_from:
-                join()
-            for bi, bp in enumerate(layer):
-                last = (li == nl - 1) and (bi == len(layer) - 1)
-                if stall is not None and two[0] and li == stall[0]:
-                    torch.cuda._sleep(int(stall[1]))
-                o1, h0, h1 = conv(x, g0, g1, bp["c1"], True)
-                c2, c3 = bp["c2"], bp["c3"]
-                if (two[0] and li == 0 and getattr(self, "fuse_tail", True) and bp["ds"] is None and c2["cout"] == 64
-                        and c2["k"] == 3 and c2["stride"] == 1 and c2.get("u") is None and c2.get("ws") is not None
-                        and c3.get("ws") is not None):
-                    # layer1's identity blocks (frozen: nothing saved): conv2 -> conv3 as one launch per batch
-                    m0o, mi = n0 * h0[0] * h0[1], n0 * g0[0] * g0[1]
-                    o3 = buf(m0o + n1 * h1[0] * h1[1], c3["cout"])
-                    for grp, (r0_, ri_, n_, hh) in enumerate(((0, 0, n0, h0), (m0o, mi, n1, h1))):
-                        with (on_sup() if grp else torch.cuda.stream(main)):
-                            ops.bottleneck_tail(o1[r0_:], n_, hh[0], hh[1], c2["cin"], c2["ws"], c2["scale"], c2["shift"], c3["ws"],
-                                                c3["scale"], c3["shift"], c3["cout"], residual=x[ri_:], out=o3[r0_:],
-                                                out_stride=c3["cout"], res_stride=c3["cout"])
-                    x, g0, g1 = o3, h0, h1
-                    continue
-                kv = ([], []) if (li > 0 and save_q is not None) else None  # conv2's V planes, per batch, for its weight gradient
-                o2, _, _ = conv(o1, h0, h1, bp["c2"], True, keep=kv)
-                m0o, mi = n0 * h0[0] * h0[1], n0 * g0[0] * g0[1]
-                out0 = out1 = None
-                s0 = s1 = 0
-                if last:
-                    corr = torch.empty((m0o, 2048), dtype=torch.float32, device=dev)
-                    sup = buf(n1 * h1[0] * h1[1], 1024)
-                    out0, out1, s0, s1 = corr, sup, 2048, 1024
-                if bp.get("cat") is not None and fuse_ds:
-                    c3, ds = bp["c3"], bp["ds"]
-                    wc = bp["cat"].get("ws") or bp["cat"]["w"]
-                    if two[0]:
-                        o3 = buf(m0o + n1 * h1[0] * h1[1], c3["cout"])
-                        ops.conv1x1_cat2(o2, c3["cin"], x, ds["cin"], n0, g0[0], g0[1], ds["stride"], wc, bp["cat"]["shift"],
-                                         c3["cout"], relu=True, out=o3, out_stride=c3["cout"])
-                        with on_sup():
-                            ops.conv1x1_cat2(o2[m0o:], c3["cin"], x[mi:], ds["cin"], n1, g1[0], g1[1], ds["stride"], wc,
-                                             bp["cat"]["shift"], c3["cout"], relu=True, out=o3[m0o:], out_stride=c3["cout"])
-                    else:
-                        o3, _, _, _ = ops.conv1x1_cat2_dual(o2, c3["cin"], x, ds["cin"], n0, g0[0], g0[1], n1, g1[0], g1[1],
-                                                            ds["stride"], wc, bp["cat"]["shift"], c3["cout"], relu=True,
-                                                            out0=out0, out1=out1, out0_stride=s0, out1_stride=s1)
-                else:
-                    res = conv(x, g0, g1, bp["ds"], False)[0] if bp["ds"] is not None else x
-                    o3, _, _ = conv(o2, h0, h1, bp["c3"], True, res=res, out0=out0, out1=out1, s0=s0, s1=s1)
-                if li > 0 and save_q is not None:  # (layer1 is frozen: nothing to differentiate there)
-                    key = "RCNN_base.%d.%d" % (4 + li, bi)
-                    save_q.append(dict(x=x[:mi], o1=o1[:m0o], o2=o2[:m0o], o3=corr if last else o3[:m0o], h1=h0[0], w1=h0[1],
-                                       n=n0, h=g0[0], w=g0[1], bp=bp, key=key, o3_ld=s0,
-                                       v2=kv[0][0] if kv and kv[0] else None))
-                    save_s.append(dict(x=x[mi:], o1=o1[m0o:], o2=o2[m0o:], o3=sup if last else o3[m0o:], h1=h1[0], w1=h1[1],
-                                       n=n1, h=g1[0], w=g1[1], bp=bp, key=key, o3_ld=s1 if last else 0,
-                                       v2=kv[1][0] if kv and kv[1] else None))
-                    if save_m is not None:  # the [query | support] buffers themselves: backward.bottleneck_backward_merged
-                        save_m.append(dict(x=x, o1=o1, o2=o2, o3=None if last else o3, mq_in=mi, mq_out=m0o,
-                                           m_in=x.size(0), m_out=o1.size(0)))
-                x, g0, g1 = o3, h0, h1
-        join()
-        return corr, g0, sup, g1
 
     # ---- the support side: query-independent, shared by the forward and encode_supports ------------------------
     def _check_support_map(self, sh_, sw_):
@@ -1219,9 +1228,10 @@ class DAnARCNN(nn.Module):
         save_q, save_s = (ctx["q_saved"], ctx["s_saved"]) if ctx is not None else (None, None)
         sup_stream.wait_event(f.inputs_ready)
         if f.merge[0]:
-            corr, (fh, fw), sfeat, (sh_, sw_) = self._rcnn_base_dual(
-                im_data, sup_ims, plan, dev, save_q=save_q, save_s=save_s, sup_stream=sup_stream, merge_from=f.merge[1],
-                save_m=ctx["m_saved"] if ctx is not None else None)
+            _, (q, s), ((corr, _), (sfeat, _)) = self._drain(self._trunk_gen(
+                [im_data, sup_ims], plan, outs=[(None, 2048), (None, 1024)], saves=[save_q, save_s], side=sup_stream,
+                merge_from=f.merge[1], save_m=ctx["m_saved"] if ctx is not None else None))
+            (fh, fw), (sh_, sw_) = q[1], s[1]
             trunk_done = ops.record_event()
             sup_stream.wait_event(trunk_done)
         else:
@@ -1229,8 +1239,8 @@ class DAnARCNN(nn.Module):
             if sup_stream != main:
                 # alternate issue, block by block: support trunk on its stream, query trunk on the caller's -- both streams
                 # have work from the step's first launch on, however slow the host is (8 ranks share one)
-                g_s = self._rcnn_base_gen(sup_ims, plan, save=save_s)
-                g_q = self._rcnn_base_gen(im_data, plan, out_stride=2048, out_buf=corr, save=save_q)
+                g_s = self._trunk_gen([sup_ims], plan, saves=[save_s])
+                g_q = self._trunk_gen([im_data], plan, outs=[(corr, 2048)], saves=[save_q])
                 r_s = r_q = None
                 while r_s is None or r_q is None:
                     if r_q is None:
@@ -1244,7 +1254,7 @@ class DAnARCNN(nn.Module):
                                 next(g_s)
                             except StopIteration as done_:
                                 r_s = done_.value
-                sfeat, sh_, sw_ = r_s
+                sfeat, ((_, (sh_, sw_), _, _),), _ = r_s
             else:  # (single-stream passes: bench.py's per-launch timing)
                 sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s)
                 self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=save_q)

@@ -102,6 +102,36 @@ def test_launch_program_executor_reissues_recorded_calls_without_a_gpu():
     ops.set_mfma_mode(prev)
 
 
+def test_launch_trace_formatter_masks_pointers_and_numbers_streams_and_events():
+    """tools/launch_trace.py: the text form of a launch sequence that two commits are diffed by -- pointers as 0 / p (their
+    values change from run to run), every other argument as it is, streams and events as ordinals by first appearance"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
+    try:
+        from launch_trace import Trace
+    finally:
+        sys.path.pop(0)
+    protos = _lib.parse_header()
+    t = Trace(protos)
+    st_a, st_b = type("St", (), dict(cuda_stream=0x7f00))(), type("St", (), dict(cuda_stream=0x9f00))()
+    ev_a, ev_b = object(), object()
+    t.add_call(None, "dana_maxpool3x3s2_ceil_nhwc", (0x1000, 0x2000, 2, 35, 50, 64, 0x9f00))
+    t.event("rec", ev_a, st_b)
+    t.event("wait", ev_a, st_a)
+    t.add_call(None, "dana_conv2d_nhwc", (0x1000, 0x3000, 0x4000, 0x5000, ctypes.c_void_p(0x6000), None, 2, 9, 13, 128, 512, 1, 1,
+                                          1, 0, 0, 2048, 0, 257, 0x7f00))
+    t.add_call(None, "dana_roi_align_forward", (None, ctypes.c_void_p(None), 0x10, 1, 8, 8, 8, 0, 0.0625, 7, 7, 0, 0, 0, 0, None,
+                                                None, 0, None))
+    t.event("rec", ev_b, st_a)
+    assert t.lines == [
+        "dana_maxpool3x3s2_ceil_nhwc p p 2 35 50 64 s0",
+        "rec e0 s0",
+        "wait e0 s1",
+        "dana_conv2d_nhwc p p p p p 0 2 9 13 128 512 1 1 1 0 0 2048 0 257 s1",
+        "dana_roi_align_forward 0 0 p 1 8 8 8 0 0.0625 7 7 0 0 0 0 0 0 0 s2",  # (the null stream is a stream of its own)
+        "rec e1 s1",
+    ]
+
+
 def test_mfma_mode_switch_roundtrip_and_errors():
     """dana_set_mfma_mode / dana_get_mfma_mode (host-side state only: no GPU needed)"""
     L = _lib.lib()

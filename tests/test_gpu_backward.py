@@ -507,7 +507,7 @@ def test_backward_on_the_role_streams_equals_the_single_stream_backward(dev):
             assert float((got[k] - ref[k]).abs().max()) <= tol, (rep, k)
 
 
-@pytest.mark.parametrize("merge_from", [0, 2, 3])
+@pytest.mark.parametrize("merge_from", [0, 1, 2, 3])
 def test_merged_trunk_modes_equal_the_two_stream_trunk(dev, mfma_mode, merge_from):
     """DAnARCNN.merge_trunk: query + support batch through one set of [query | support] activation buffers, the stages
     >= merge_from with ONE launch per conv over both batches (dual-geometry contraction / dual-group Winograd), the
@@ -590,7 +590,7 @@ def test_two_stream_trunk_in_shared_buffers_does_not_race_on_recycled_blocks(dev
     """The Trainer's forward (merge_trunk, merge_from 3) runs the query and the support batch on two streams over the row
     ranges of shared buffers that come from the caller's stream pool. A block that pool hands out may still be in use by a
     queued kernel of the caller's stream (an op's workspace, released in stream order): the support stream must not
-    touch it before the caller's stream got there (`buf()` in `_rcnn_base_dual`). Regression: two processes sharing one
+    touch it before the caller's stream got there (`alloc()` in `_trunk_gen`). Regression: two processes sharing one
     GPU produced wrong losses. Here the caller's stream is held back inside the trunk -- a spin kernel in front of every
     block of one layer -- so that the support stream WOULD run ahead of it."""
     import dana_amd
