@@ -2,9 +2,18 @@
 model call and `all_boxes[j][i] = cls_dets` -- de-normalise the regression deltas, decode them on the rois,
 clip, rescale to the original image, threshold the fg score, sort, NMS (utils.py:312-317) -- as ONE C call
 (decode + device sort + on-device NMS) and one small D2H read for the variable-length result.
-`detections_batched` does the same for B images in one C call and one D2H read of the per-image counts."""
+`detections_batched` does the same for B images in one C call and one D2H read of the per-image counts.
+
+`merge_detections` combines such lists on the device (csrc/merge.hip): what utils.py:182-204 (generate_pseudo_label) does
+with the per-shot lists of an image -- cat, sort by score, one more NMS over the union -- and the `max_per_image` cut over
+an image's class lists (inference.py:70), as one C call over all lists and one D2H read of the output layout;
+`ensemble_shots` and `cap_per_image` are the two uses spelled out. `as_gt_boxes` turns merged lists into the
+gt_boxes / num_boxes tensors of a train-mode forward (pseudo-labels are trained on, utils.py:130-179) without leaving the
+device. `merge_numpy` is the merge restated in numpy float64 (host): the tests' yardstick, pinned to the reference's own
+chain by tests/golden/merge_dets.npz."""
 import ctypes
 
+import numpy as np
 import torch
 
 from . import ops
@@ -39,7 +48,8 @@ def detections(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=Fa
 
 
 def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive):
-    """the batched call itself -> (dets [max(B*R,1),5] packed device buffer, host int32 counts [B], offsets [B+1])"""
+    """the batched call itself -> (dets [max(B*R,1),5] packed device buffer, host int32 counts [B], offsets [B+1], and the
+    device int32 tensor counts | offsets [2B+1] the host pair was read from)"""
     if rois.dim() != 3 or rois.size(2) != 5:
         raise ValueError("detections_batched: rois must be [B, R, 5], got %s" % (tuple(rois.shape),))
     B, R = rois.size(0), rois.size(1)
@@ -61,7 +71,7 @@ def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive
                int(bool(nms_inclusive)), ops._p(dets), layout.data_ptr(), layout.data_ptr() + 4 * B, ops._p(ws),
                ws.numel(), ops._stream())
     host = layout.cpu()
-    return dets, host[:B], host[B:]
+    return dets, host[:B], host[B:], layout
 
 
 def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False):
@@ -69,7 +79,7 @@ def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_incl
     list of B cls_dets [K_b,5], each equal to `detections()` on its image. One C call (decode over B*R rows, B-row sort,
     B NMS problems, packed compaction) and ONE D2H read of the per-image counts / offsets. with_layout=True also returns
     the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]])."""
-    dets, counts, offsets = _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive)
+    dets, counts, offsets, _ = _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive)
     out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(counts.numel())]
     return (out, counts, offsets) if with_layout else out
 
@@ -77,8 +87,9 @@ def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_incl
 class ClassDetections(list):
     """`detections_by_class(with_layout=True)`: the nested list dets[b][c] itself, plus the one device buffer its entries
     are views of -- `packed` [rows,5], host int32 `counts` [B*C] and `offsets` [B*C+1] of problem p = b*C + c -- which is
-    what `evaluate.DetectionEvaluator.add_by_class` appends in one launch instead of slicing B*C tensors apart."""
-    packed = counts = offsets = None
+    what `evaluate.DetectionEvaluator.add_by_class` appends in one launch instead of slicing B*C tensors apart. `layout_dev`
+    is the same layout where the device wrote it (int32 [2*B*C+1]: counts | offsets), which `merge_detections` reads in place."""
+    packed = counts = offsets = layout_dev = None
     num_classes = 0
 
 
@@ -97,11 +108,245 @@ def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=
     if C < 1 or rois.size(0) != B * C:
         raise ValueError("detections_by_class: %d problems for %d images x %d classes" % (rois.size(0), B, C))
     info_p = ops.repeat_rows_grouped(im_info, 1, 3, C, B * C, ld_src=im_info.size(1))
-    packed, counts, offsets = _detections_packed(rois, cls_prob, bbox_pred, info_p, thresh, nms_inclusive)
+    packed, counts, offsets, layout = _detections_packed(rois, cls_prob, bbox_pred, info_p, thresh, nms_inclusive)
     flat = [packed[int(offsets[p]):int(offsets[p]) + int(counts[p])] for p in range(B * C)]
     nested = [flat[b * C:(b + 1) * C] for b in range(B)]
     if not with_layout:
         return nested
     out = ClassDetections(nested)
-    out.packed, out.counts, out.offsets, out.num_classes = packed, counts, offsets, C
+    out.packed, out.counts, out.offsets, out.num_classes, out.layout_dev = packed, counts, offsets, C, layout
     return out
+
+
+# ---- merging detection lists ---------------------------------------------------------------------------------------------
+
+class MergedDetections(ClassDetections):
+    """`merge_detections(with_layout=True)`: the list of merged lists (views of `packed`), the host `counts` [n] / `offsets`
+    [n+1] and device `layout_dev` of a `ClassDetections`, plus per packed row the device int32 `group` (which of the list's
+    `groups` inputs the row came from) and `row` (its row inside that input). `total` = rows in all lists."""
+    group = row = None
+    total = 0
+
+    def list_index(self):
+        """host int32 [total]: the output list of every packed row (what `add_packed` takes as image ids, mapped through
+        the caller's image indices)"""
+        c = self.counts.numpy().astype(np.int64)
+        return np.repeat(np.arange(c.size, dtype=np.int32), c)
+
+
+def _nms_pair(nms_thresh):
+    """the `nms_thresh` argument -> (do_nms, threshold): "cfg" is cfg.TEST.NMS, None turns NMS off"""
+    if nms_thresh is None:
+        return 0, 0.0
+    return 1, float(cfg.TEST.NMS if isinstance(nms_thresh, str) and nms_thresh == "cfg" else nms_thresh)
+
+
+def _packed_layout(dets, who):
+    """a ClassDetections-like object or a tuple (packed, counts, offsets) -> (packed [rows,5] device, P, host counts and
+    offsets as numpy int64 or None when the layout lives on the device only, device pointers of counts [P] and
+    offsets [>=P], and the tensors that keep those pointers alive)"""
+    if isinstance(dets, (tuple, list)) and not hasattr(dets, "packed"):
+        if len(dets) != 3:
+            raise ValueError("%s: pass a ClassDetections or a tuple (packed, counts, offsets)" % who)
+        packed, counts, offsets, layout = dets[0], dets[1], dets[2], None
+    else:
+        packed, counts, offsets = dets.packed, dets.counts, dets.offsets
+        layout = getattr(dets, "layout_dev", None)
+    if packed is None or counts is None or offsets is None:
+        raise ValueError("%s: the detections carry no packed layout (detections_by_class(..., with_layout=True))" % who)
+    packed = ops._chk(packed.reshape(-1, 5), "packed")
+    on_dev = [isinstance(x, torch.Tensor) and x.is_cuda for x in (counts, offsets)]
+    if all(on_dev) and layout is None:
+        counts, offsets = ops._chk(counts.reshape(-1), "counts", torch.int32), ops._chk(offsets.reshape(-1), "offsets", torch.int32)
+        P = counts.numel()
+        if offsets.numel() < P:
+            raise ValueError("%s: %d counts but %d offsets" % (who, P, offsets.numel()))
+        return packed, P, None, None, counts.data_ptr(), offsets.data_ptr(), (counts, offsets)
+    if any(on_dev):
+        raise ValueError("%s: counts and offsets must both be host or both be device int32 tensors" % who)
+    hc = np.asarray(counts).reshape(-1).astype(np.int64)
+    ho = np.asarray(offsets).reshape(-1).astype(np.int64)
+    P = hc.size
+    if ho.size < P or (hc < 0).any() or (ho[:P] < 0).any() or (P and int((ho[:P] + hc).max()) > packed.size(0)):
+        raise ValueError("%s: counts / offsets do not describe rows of the packed buffer" % who)
+    if layout is None or layout.numel() < 2 * P:
+        layout = ops._h2d_int32(np.concatenate((hc, ho[:P])).astype(np.int32), packed.device)
+    layout = ops._chk(layout, "layout_dev", torch.int32)
+    return packed, P, hc, ho, layout.data_ptr(), layout.data_ptr() + 4 * P, (layout,)
+
+
+def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_dets=0, with_layout=False, capacity=None):
+    """Merge every `groups` consecutive detection lists into one, on the device: concatenate in group order, sort by score
+    (descending, stable: equal scores keep concatenation order -- lower group first, then lower row), greedy NMS at
+    `nms_thresh` ("cfg": cfg.TEST.NMS; None: no NMS, a pure merge), keep the first `max_dets` (0: all). The chain of
+    utils.py:192-199 for every list at once; every output row is a bit-for-bit copy of an input row.
+
+    `dets`: a `ClassDetections` (problem p goes to list p // groups) or a tuple (packed [rows,5], counts [P], offsets [P+])
+    with host or device int32 layout. -> list of P // groups tensors [K_l,5]; with_layout=True a `MergedDetections`,
+    which also carries `packed`, `counts`, `offsets`, `layout_dev`, `group`, `row`. One C call, one D2H read (the output
+    layout). The frame a list is sorted in (`capacity` rows) is sized from the host counts; with a device-only layout
+    pass `capacity` (>= the longest concatenation), because nothing is read back to find it."""
+    groups = int(groups)
+    if groups < 1:
+        raise ValueError("merge_detections: groups must be >= 1, got %d" % groups)
+    packed, P, hc, _, p_counts, p_offsets, alive = _packed_layout(dets, "merge_detections")
+    if P % groups:
+        raise ValueError("merge_detections: %d lists are not a multiple of groups = %d" % (P, groups))
+    n_lists = P // groups
+    dev = packed.device
+    if hc is not None:
+        need = int(hc.reshape(n_lists, groups).sum(1).max()) if n_lists else 0
+        if capacity is None:
+            capacity = need
+        elif int(capacity) < need:
+            raise ValueError("merge_detections: capacity %d is below the longest concatenation (%d rows)" % (int(capacity), need))
+        rows_cap = min(int(hc.sum()), n_lists * int(capacity))
+    elif capacity is None:
+        raise ValueError("merge_detections: a device-only layout needs capacity (nothing is read back to size the frame)")
+    else:
+        rows_cap = n_lists * int(capacity)
+    capacity = int(capacity)
+    do_nms, thr = _nms_pair(nms_thresh)
+    out = torch.empty((max(rows_cap, 1), 5), dtype=torch.float32, device=dev)
+    ibuf = torch.empty((2 * max(rows_cap, 1) + 2 * n_lists + 1,), dtype=torch.int32, device=dev)  # group | row | counts | offsets
+    slot = max(rows_cap, 1)
+    group, row, layout = ibuf[:slot], ibuf[slot:2 * slot], ibuf[2 * slot:]
+    ws = ops._ws(lib().query("dana_detect_merge_workspace_bytes", n_lists, groups, capacity), dev)
+    lib().call("dana_detect_merge", ops._p(packed), p_counts, p_offsets, n_lists, groups, capacity, do_nms, thr,
+               int(bool(nms_inclusive)), int(max_dets), ops._p(out), group.data_ptr(), row.data_ptr(), layout.data_ptr(),
+               layout.data_ptr() + 4 * n_lists, ops._p(ws), ws.numel(), ops._stream())
+    del alive
+    host = layout.cpu()
+    counts, offsets = host[:n_lists], host[n_lists:]
+    lists = [out[int(offsets[i]):int(offsets[i]) + int(counts[i])] for i in range(n_lists)]
+    if not with_layout:
+        return lists
+    m = MergedDetections(lists)
+    m.packed, m.counts, m.offsets, m.layout_dev, m.num_classes = out, counts, offsets, layout, 1
+    m.total = int(offsets[n_lists])
+    m.group, m.row = group[:m.total], row[:m.total]
+    return m
+
+
+def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0):
+    """The shot ensemble of utils.py:182-204: `cd` = detections_by_class(..., with_layout=True) of a sweep whose cached
+    sets are laid out as set c*shots + s (class c seen through its shot s alone: a model built with num_shot=1 and
+    encode_supports(shots.view(C*S, 1, 3, 320, 320))). -> `merge_detections(cd, shots)` as dets[b][c], a
+    `MergedDetections` that `DetectionEvaluator.add_by_class` / `CocoEvaluator.add_by_class` take unchanged."""
+    shots = int(shots)
+    if shots < 1 or cd.num_classes % shots:
+        raise ValueError("ensemble_shots: %d sets per image are not a multiple of shots = %d" % (cd.num_classes, shots))
+    C, B = cd.num_classes // shots, len(cd)
+    m = merge_detections(cd, shots, nms_thresh, nms_inclusive, max_dets, with_layout=True)
+    out = MergedDetections([list(m[b * C:(b + 1) * C]) for b in range(B)])
+    out.packed, out.counts, out.offsets, out.layout_dev, out.num_classes = m.packed, m.counts, m.offsets, m.layout_dev, C
+    out.total, out.group, out.row = m.total, m.group, m.row
+    return out
+
+
+def cap_per_image(cd, max_per_image=100):
+    """The `max_per_image` cut of a Faster R-CNN test loop (inference.py:70) on the device: image b's num_classes lists of
+    `cd` = detections_by_class(..., with_layout=True) merged by score with NMS off and cut to its best `max_per_image`
+    rows. -> `MergedDetections` of B tensors; `group` is each row's class index, so
+    `ev.add_packed(m.packed[:m.total], image_indices[m.list_index()], m.group)` appends the capped detections."""
+    return merge_detections(cd, cd.num_classes, nms_thresh=None, max_dets=int(max_per_image), with_layout=True)
+
+
+def as_gt_boxes(merged, im_info, labels=1, score_thresh=0.5, max_boxes=None):
+    """Pseudo-labels as a train-mode forward takes them (fs_loader.py:325): `merged` = n detection lists, one per image
+    (a `MergedDetections` / `ClassDetections` or a tuple (packed, counts, offsets)), im_info [n,3]. Image b's first
+    `max_boxes` (default cfg.MAX_NUM_GT_BOXES) rows with score > score_thresh (0.5: plot_box's threshold, utils.py:304)
+    become (x1, y1, x2, y2) * im_info[b][2] -- back to network-input coordinates, the inverse of inference.py:125 -- with
+    label labels[b] (a number, or [n] values); zero rows pad the rest.
+    -> (gt_boxes [n, max_boxes, 5] float32, num_boxes [n] int64), both on the device; nothing is read back."""
+    packed, P, _, _, p_counts, p_offsets, alive = _packed_layout(merged, "as_gt_boxes")
+    max_boxes = int(cfg.MAX_NUM_GT_BOXES if max_boxes is None else max_boxes)
+    dev = packed.device
+    im_info = ops._chk(im_info.reshape(-1, im_info.size(-1)).float().contiguous(), "im_info")
+    if im_info.size(0) != P or im_info.size(1) < 3:
+        raise ValueError("as_gt_boxes: %d lists need im_info [%d, 3], got %s" % (P, P, tuple(im_info.shape)))
+    if isinstance(labels, torch.Tensor):
+        lab = labels.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+    else:
+        lab = torch.full((P,), float(labels), dtype=torch.float32, device=dev)
+    if lab.numel() != P:
+        raise ValueError("as_gt_boxes: %d lists but %d labels" % (P, lab.numel()))
+    gt_boxes = torch.empty((P, max_boxes, 5), dtype=torch.float32, device=dev)
+    num_boxes = torch.empty((P,), dtype=torch.int64, device=dev)
+    lib().call("dana_dets_to_gt_boxes", ops._p(packed), p_counts, p_offsets, ops._p(im_info), im_info.size(1), ops._p(lab), P,
+               float(score_thresh), max_boxes, ops._p(gt_boxes), num_boxes.data_ptr(), ops._stream())
+    del alive
+    return gt_boxes, num_boxes
+
+
+def _iou_rows(box, rest):
+    """IoU of one box against rows, float64, legacy +1 widths (nms_cpu.cpp:30-60)"""
+    area = (box[2] - box[0] + 1.) * (box[3] - box[1] + 1.)
+    areas = (rest[:, 2] - rest[:, 0] + 1.) * (rest[:, 3] - rest[:, 1] + 1.)
+    w = np.maximum(np.minimum(box[2], rest[:, 2]) - np.maximum(box[0], rest[:, 0]) + 1., 0.)
+    h = np.maximum(np.minimum(box[3], rest[:, 3]) - np.maximum(box[1], rest[:, 1]) + 1., 0.)
+    inter = w * h
+    return inter / (area + areas - inter)
+
+
+def merge_numpy(lists_per_problem, groups, nms_thresh, nms_inclusive=False, max_dets=0):
+    """`merge_detections` restated in numpy (host): lists_per_problem = P arrays [k,5] (float32 values), list l merges
+    problems l*groups .. l*groups + groups - 1. Concatenation, `np.argsort(-score, kind="stable")`, greedy NMS with +1
+    widths in float64 (`>`, or `>=` with nms_inclusive; nms_thresh None: none), the first max_dets (0: all).
+    -> dict(dets: list of float32 [K_l,5], group / row: lists of int32 [K_l], counts int32 [n], offsets int32 [n+1],
+    margin: the smallest |IoU - nms_thresh| over every suppression decision taken -- a kept box against each later box not
+    yet suppressed --, inf when there was none)."""
+    groups = int(groups)
+    P = len(lists_per_problem)
+    if groups < 1 or P % groups:
+        raise ValueError("merge_numpy: %d lists are not a multiple of groups = %d" % (P, groups))
+    out_d, out_g, out_r, margin = [], [], [], np.inf
+    for l in range(P // groups):
+        parts = [np.asarray(lists_per_problem[l * groups + g], np.float32).reshape(-1, 5) for g in range(groups)]
+        cat = np.concatenate(parts, 0)
+        grp = np.concatenate([np.full(len(q), g, np.int32) for g, q in enumerate(parts)])
+        row = np.concatenate([np.arange(len(q), dtype=np.int32) for q in parts])
+        order = np.argsort(-cat[:, 4].astype(np.float64), kind="stable")
+        n = order.size
+        if nms_thresh is None:
+            kept = np.arange(n)
+        else:
+            box = cat[order, :4].astype(np.float64)
+            dead = np.zeros(n, bool)
+            kept = []
+            for i in range(n):
+                if dead[i]:
+                    continue
+                kept.append(i)
+                if max_dets > 0 and len(kept) >= max_dets:
+                    break
+                live = np.nonzero(~dead[i + 1:])[0] + i + 1
+                if live.size:
+                    iou = _iou_rows(box[i], box[live])
+                    margin = min(margin, float(np.abs(iou - float(nms_thresh)).min()))
+                    dead[live[(iou >= nms_thresh) if nms_inclusive else (iou > nms_thresh)]] = True
+            kept = np.asarray(kept, np.int64)
+        if max_dets > 0:
+            kept = kept[:max_dets]
+        sel = order[kept]
+        out_d.append(cat[sel])
+        out_g.append(grp[sel])
+        out_r.append(row[sel])
+    counts = np.asarray([len(d) for d in out_d], np.int32)
+    offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+    return dict(dets=out_d, group=out_g, row=out_r, counts=counts, offsets=offsets, margin=margin)
+
+
+def gt_boxes_numpy(lists, im_scale, labels, score_thresh=0.5, max_boxes=50):
+    """`as_gt_boxes` restated in numpy float32 (host): the multiply is the same single fp32 operation"""
+    n = len(lists)
+    gt = np.zeros((n, max_boxes, 5), np.float32)
+    num = np.zeros(n, np.int64)
+    lab = np.broadcast_to(np.asarray(labels, np.float32), (n,))
+    for b, d in enumerate(lists):
+        d = np.asarray(d, np.float32).reshape(-1, 5)
+        d = d[d[:, 4] > np.float32(score_thresh)][:max_boxes]
+        gt[b, :len(d), :4] = d[:, :4] * np.float32(im_scale[b])
+        gt[b, :len(d), 4] = lab[b]
+        num[b] = len(d)
+    return gt, num

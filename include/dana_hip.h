@@ -161,6 +161,36 @@ int dana_detect_postprocess_batched(const float* rois, const float* cls_prob, co
                                     int* counts, int* offsets, void* workspace, size_t workspace_bytes,
                                     dana_stream_t stream);
 
+/* Merging detection lists (utils.py:182-204, generate_pseudo_label: torch.cat of the per-shot lists, torch.sort by score,
+ * nms(..., cfg.TEST.NMS) over the union; and the max_per_image cut over an image's class lists, inference.py:70).
+ * dets_in is a packed buffer of rows (x1, y1, x2, y2, score); input problem p = l*groups + g has counts_in[p] rows starting
+ * at row offsets_in[p] (the layout dana_detect_postprocess_batched writes; both arrays are read on the DEVICE). For every
+ * output list l < n_lists independently: (1) concatenate its `groups` input lists in group order; (2) sort by score,
+ * descending and STABLE -- equal scores keep concatenation order, lower group first, then lower row (torch.sort leaves ties
+ * undefined; this is the evaluators' arrival-order rule); (3) if do_nms, greedy NMS at nms_thresh under dana_nms' contract
+ * (legacy +1 widths, `>` or, with nms_inclusive, `>=`); (4) keep the first max_dets survivors (max_dets <= 0: all);
+ * (5) write them packed in list order: dets_out[sum K_l][5] (capacity n_lists*capacity rows), counts_out[n_lists],
+ * offsets_out[n_lists + 1], and per output row its source, group_out = g and row_out = the row inside list (l, g). Every
+ * output row is a bit-for-bit copy of an input row. `capacity` is the row count of the padded frame a list is sorted in,
+ * >= max over l of sum_g counts_in[l*groups + g] and <= 520 064 (what dana_nms takes per problem); the entry point cannot
+ * check the lower bound without a host read, so a smaller value truncates a list's concatenation at `capacity` rows -- it
+ * never writes outside the frame. n_lists <= 65 535. n_lists == 0 or capacity == 0 zero the output layout and return. */
+size_t dana_detect_merge_workspace_bytes(int n_lists, int groups, int capacity);
+int dana_detect_merge(const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
+                      int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, float* dets_out,
+                      int* group_out, int* row_out, int* counts_out, int* offsets_out, void* workspace,
+                      size_t workspace_bytes, dana_stream_t stream);
+
+/* Detection lists -> the ground-truth tensors of a train-mode forward (fs_loader.py:325; pseudo-labels are trained on,
+ * utils.py:130-179): one list per image in the packed layout above (counts[B], offsets[B], device). Image b's first
+ * max_boxes rows with score > score_thresh, in list order, become gt_boxes[b][i] = (x1, y1, x2, y2) * im_info[b][2] (back
+ * from original-image to network-input coordinates, the inverse of inference.py:125; one fp32 multiply each), labels[b];
+ * the remaining rows of gt_boxes[B][max_boxes][5] are zero; num_boxes[b] (int64) = rows written. im_info rows are
+ * im_info_stride (>= 3) floats apart. */
+int dana_dets_to_gt_boxes(const float* dets, const int* counts, const int* offsets, const float* im_info,
+                          int im_info_stride, const float* labels, int B, float score_thresh, int max_boxes,
+                          float* gt_boxes, long long* num_boxes, dana_stream_t stream);
+
 /* Cached support sets (dana.SupportCache): for every tensor t < n_tensors and image b < B, copy block index[b] (block_bytes[t]
  * bytes) of tensor t's sources into block b of its destination, all in ONE launch. src_ptrs / dst_ptrs are DEVICE arrays of
  * n_tensors device pointers (const void* const* / void* const*), block_bytes a device array; index[B] is read on the device,
