@@ -10,6 +10,7 @@
 //             over the concatenated keys of all shots (K = shot*L).
 #include "common.h"
 #include "../../include/dana_hip.h"
+#include "attn_segments.h"
 #include <float.h>
 
 namespace {
@@ -173,6 +174,20 @@ attn_softmax_unary_kernel(float* __restrict__ scores, const float* __restrict__ 
   for (int l = nseg * L + lane; l < kpad; l += 64) r[l] = 0.f;
 }
 
+// attn_softmax_unary_kernel with a per-segment scale seg_scale[b(r)][seg] in place of out_scale (attn_segments.h)
+__global__ void __launch_bounds__(256)
+attn_softmax_unary_w_kernel(float* __restrict__ scores, const float* __restrict__ unary,
+                            const float* __restrict__ seg_scale, long rows, long rows_per_batch, long unary_batch_stride,
+                            long scale_batch_stride, int nseg, int L, long ld, int kpad, float ugamma) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long b = row / rows_per_batch;
+  float* r = scores + row * ld;
+  attn_softmax_unary_row_w(r, r, unary + b * unary_batch_stride, seg_scale + b * scale_batch_stride, nseg, L, kpad, ugamma,
+                           lane);
+}
+
 }  // namespace
 
 extern "C" {
@@ -236,6 +251,21 @@ int dana_attn_softmax_unary(float* scores, const float* unary, long rows, long r
       scores, unary, rows, rows_per_batch, unary_batch_stride > 0 ? unary_batch_stride : (long)nseg * length, nseg,
       length, ld, kpad, unary_gamma, out_scale);
   DANA_CHECK_LAUNCH("dana_attn_softmax_unary");
+  return DANA_OK;
+}
+
+int dana_attn_softmax_unary_w(float* scores, const float* unary, long rows, long rows_per_batch, long unary_batch_stride,
+                              int nseg, int length, long ld, int kpad, float unary_gamma, const float* seg_scale,
+                              long scale_batch_stride, dana_stream_t stream) {
+  DANA_CHECK_ARG(rows >= 0 && rows_per_batch > 0 && nseg > 0 && length > 0 && ld >= (long)nseg * length &&
+                     kpad <= ld,
+                 "dana_attn_softmax_unary_w: bad shape");
+  if (rows == 0) return DANA_OK;
+  DANA_CHECK_ARG(scores && unary && seg_scale, "dana_attn_softmax_unary_w: null pointer");
+  attn_softmax_unary_w_kernel<<<dana_ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(
+      scores, unary, seg_scale, rows, rows_per_batch, unary_batch_stride > 0 ? unary_batch_stride : (long)nseg * length,
+      scale_batch_stride > 0 ? scale_batch_stride : (long)nseg, nseg, length, ld, kpad, unary_gamma);
+  DANA_CHECK_LAUNCH("dana_attn_softmax_unary_w");
   return DANA_OK;
 }
 

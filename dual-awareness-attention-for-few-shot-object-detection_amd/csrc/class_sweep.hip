@@ -7,6 +7,7 @@
 // every class of an image, as inference.py:70-140 does to fill all_boxes[j][i].
 #include "common.h"
 #include "../../include/dana_hip.h"
+#include "attn_segments.h"
 #include <float.h>
 
 namespace {
@@ -87,6 +88,23 @@ attn_softmax_unary_sweep_kernel(const float* __restrict__ scores, float* __restr
     for (int l = lane; l < L; l += 64) x[l] = (x[l] / s + ugamma * u[sgm * L + l]) * out_scale;
   }
   for (int l = nseg * L + lane; l < kpad; l += 64) r[l] = 0.f;
+}
+
+// attn_softmax_unary_sweep_kernel with a per-segment scale seg_scale[p][seg] in place of out_scale (attn_segments.h)
+__global__ void __launch_bounds__(256)
+attn_softmax_unary_sweep_w_kernel(const float* __restrict__ scores, float* __restrict__ out,
+                                  const float* __restrict__ unary, const float* __restrict__ seg_scale, long rows, long hw,
+                                  int C, long unary_stride, long scale_stride, int nseg, int L, long ld_in, long ld_out,
+                                  int kpad, float ugamma) {
+  const int lane = threadIdx.x & 63;
+  const long row = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= rows) return;
+  const long bi = row / C;
+  const int c = (int)(row - bi * C);
+  const long b = bi / hw, i = bi - b * hw;
+  const long p = b * C + c;
+  attn_softmax_unary_row_w(scores + row * ld_in, out + (p * hw + i) * ld_out, unary + p * unary_stride,
+                           seg_scale + p * scale_stride, nseg, L, kpad, ugamma, lane);
 }
 
 // dst row (p*rows + i) <- src row ((p / group)*rows + i), `cols` floats each; one thread per float
@@ -203,6 +221,23 @@ int dana_attn_softmax_unary_sweep(const float* scores, float* out, const float* 
       scores, out, unary, rows, hw, C, unary_stride > 0 ? unary_stride : (long)nseg * length, nseg, length, ld_in, ld_out,
       kpad, unary_gamma, out_scale);
   DANA_CHECK_LAUNCH("dana_attn_softmax_unary_sweep");
+  return DANA_OK;
+}
+
+int dana_attn_softmax_unary_sweep_w(const float* scores, float* out, const float* unary, int B, int C, long hw,
+                                    long unary_stride, int nseg, int length, long ld_in, long ld_out, int kpad,
+                                    float unary_gamma, const float* seg_scale, long scale_stride, dana_stream_t stream) {
+  DANA_CHECK_ARG(B >= 0 && C > 0 && hw > 0 && nseg > 0 && length > 0 && ld_in >= (long)nseg * length &&
+                     ld_out >= (long)nseg * length && kpad <= ld_out,
+                 "dana_attn_softmax_unary_sweep_w: bad shape B=%d C=%d hw=%ld nseg=%d L=%d", B, C, hw, nseg, length);
+  if (B == 0) return DANA_OK;
+  DANA_CHECK_ARG(scores && out && unary && seg_scale, "dana_attn_softmax_unary_sweep_w: null pointer");
+  DANA_CHECK_ARG(scores != out, "dana_attn_softmax_unary_sweep_w: out of place only (rows move)");
+  const long rows = (long)B * C * hw;
+  attn_softmax_unary_sweep_w_kernel<<<dana_ceil_div(rows, 4), 256, 0, (hipStream_t)stream>>>(
+      scores, out, unary, seg_scale, rows, hw, C, unary_stride > 0 ? unary_stride : (long)nseg * length,
+      scale_stride > 0 ? scale_stride : (long)nseg, nseg, length, ld_in, ld_out, kpad, unary_gamma);
+  DANA_CHECK_LAUNCH("dana_attn_softmax_unary_sweep_w");
   return DANA_OK;
 }
 

@@ -902,6 +902,30 @@ class DAnARCNN(nn.Module):
         return dict(kp=(shot * L, d), unary=(shot, L), s_t=(1024, shot * L), k2=(shot * P2, dq), un2=(shot, P2),
                     sw=(shot * P2, rd), sp_pe=(shot * P2, 1024))
 
+    def _cache_shot_blocks(self, sup_map):
+        """name -> (rows, floats per block): every cached tensor of a set is [rows][shot][block], `shot` independent blocks
+        (each shot is attended on its own and the results are averaged: dana.py:126-150, :268-281), which is what lets a
+        SupportCache serve shot views. A model whose cached tensors mix the shots returns None (and says why in
+        `_no_shot_views`)."""
+        L, P2 = sup_map[0] * sup_map[1], cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        d, dq, rd = self.rpn_reduce_dim, self.rcnn_reduce_dim, self.rcnn_dim
+        return dict(kp=(1, L * d), unary=(1, L), s_t=(1024, L), k2=(1, P2 * dq), un2=(1, P2), sw=(1, P2 * rd),
+                    sp_pe=(1, P2 * 1024))
+
+    def _check_shot_counts(self, num_shots, C, shot):
+        """encode_supports' num_shots -> a tuple of C counts in [1, shot], or None"""
+        if num_shots is None:
+            return None
+        if torch.is_tensor(num_shots):
+            if num_shots.is_cuda:
+                raise ValueError("encode_supports: num_shots takes host values (a sequence or a CPU tensor)")
+            num_shots = num_shots.reshape(-1).tolist()
+        counts = tuple(int(n) for n in num_shots)
+        if len(counts) != C or any(n < 1 or n > shot for n in counts):
+            raise ValueError("encode_supports: num_shots %s for %d sets of up to %d shots (one count per set, 1 <= n <= "
+                             "shot)" % (list(counts), C, shot))
+        return counts
+
     def _check_support_sets(self, support_ims):
         """encode_supports' input checks -> (C, shot, device)"""
         if self.training:
@@ -918,12 +942,16 @@ class DAnARCNN(nn.Module):
             raise ValueError("encode_supports: no support set")
         return C, shot, support_ims.device
 
-    def encode_supports(self, support_ims):
+    def encode_supports(self, support_ims, num_shots=None):
         """support_ims [C, shot, 3, S, S] (C support sets, e.g. one per class) -> SupportCache: the eval forward's
         query-independent support work (support trunk, RPN-level and RoI-level support chains), done once per set with the
         launches an uncached B = 1 forward issues for it. `model(im_data, im_info, gt_boxes, num_boxes, cache)` then runs
-        the query side only (inference.py:82-103 draws each class's shots once and reuses them for every query)."""
+        the query side only (inference.py:82-103 draws each class's shots once and reuses them for every query).
+        num_shots: a host sequence of C counts 1 <= n_c <= shot for ragged sets -- slots >= n_c of support_ims[c] are
+        ignored: they are encoded with the rest (every shot's blocks depend on that shot alone) and stay in the cache, but
+        no shot view can name them, so no forward reads them (`cache.shot_counts`)."""
         C, shot, dev = self._check_support_sets(support_ims)
+        counts = self._check_shot_counts(num_shots, C, shot)
         plan = self._get_plan()
         product = self.attention_type == "product"
         stream = ops.cur_stream()
@@ -939,7 +967,7 @@ class DAnARCNN(nn.Module):
                 per_set.append(dict(kp=kp, unary=unary, s_t=s_t, k2=k2, un2=un2, sw=sw, sp_pe=None if sw is not None else sp_pe))
             tensors = {k: (None if per_set[0][k] is None else torch.stack([p_[k].reshape(-1) for p_ in per_set]))
                        for k in self._cache_layout(shot, (sh_, sw_))}
-        return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev)
+        return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev, counts=counts)
 
     # ---- stages shared with the sibling detectors (frcnn.py, fgn.py, fsod.py) ------------------------------------
     def _saving_ctx(self, lists, align_only_for=None):
@@ -1123,7 +1151,8 @@ class DAnARCNN(nn.Module):
                             NP=B * Cs,  # problems: the RPN stage from the attention on and the RoI stage run over them
                             im_info=im_info.data.float().contiguous(), gt_boxes=gt_boxes.data, shot=self.n_shot,
                             way=self.n_way if training else 1,  # eval reshapes supports as [*, n_shot] (dana.py:111)
-                            product=self.attention_type == "product", inter=getattr(self, "_capture", None))
+                            product=self.attention_type == "product", inter=getattr(self, "_capture", None),
+                            seg_w=None)  # (per-problem segment scales of a cached forward over views of unequal length)
         tl = getattr(self, "_timeline", None)  # optional host-side phase clock (debug)
         f.tick = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None else (lambda label: None)
         f.tick("begin")
@@ -1218,8 +1247,15 @@ class DAnARCNN(nn.Module):
             # cached supports (encode_supports): the query-independent support side was computed once per support set;
             # one launch gathers image b's set into this forward's B-batched buffers (a sweep gathers B*C sets, the
             # selection repeated for every image: image b's C blocks are contiguous), the query side runs unchanged
-            sup = dict(f.cache._gather(f.NP, f.sweep._index(B) if f.sweep is not None else None), map=f.cache.sup_map,
-                       rpn_done=None, roi_done=None)
+            # (shot views: the gather picks shot blocks as well, the query side runs with shot = m, the longest view;
+            #  f.seg_w [NP][m] = 1/len(view) per real slot when the views' lengths differ, else None)
+            if f.sweep is not None:
+                fields, f.shot, f.seg_w = f.cache._gather_views(f.NP, f.sweep._index(B), f.sweep._views(B))
+            else:
+                fields, f.shot, f.seg_w = f.cache._gather_views(f.NP)
+            if ctx is not None:
+                ctx.update(shot=f.shot)
+            sup = dict(fields, map=f.cache.sup_map, rpn_done=None, roi_done=None)
             corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
             self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
             f.mark("trunk (query + support)")
@@ -1295,7 +1331,11 @@ class DAnARCNN(nn.Module):
             ops.gemm_nt(qp, kp, hw, Cs * K1, d, out=scores, ldc=Cs * K1, batch=B, batch_a=hw * d, batch_b=Cs * K1 * d,
                         batch_c=hw * Cs * K1, alpha=1.0 / math.sqrt(d))
             a_p = torch.empty((NP, hw, K1), dtype=torch.float32, device=dev)
-            ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, 1.0 / f.shot)
+            if f.seg_w is not None:
+                ops.attn_softmax_unary_sweep_w(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, f.seg_w)
+            else:
+                ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma,
+                                             1.0 / f.shot)
             att = torch.empty((NP * hw, 1024), dtype=torch.float32, device=dev)  # problem p's attended rows
             ops.gemm_nt(a_p, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=att, ldc=1024, batch=NP, batch_a=hw * K1,
                         batch_b=1024 * K1, batch_c=hw * 1024)
@@ -1305,7 +1345,10 @@ class DAnARCNN(nn.Module):
             scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
             ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
                         alpha=1.0 / math.sqrt(d))
-            ops.attn_softmax_unary_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, 1.0 / f.shot)
+            if f.seg_w is not None:
+                ops.attn_softmax_unary_w_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, f.seg_w)
+            else:
+                ops.attn_softmax_unary_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, 1.0 / f.shot)
             ops.gemm_nt(scores, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=corr.view(-1)[1024:], ldc=2048, batch=B,
                         batch_a=hw * K1, batch_b=1024 * K1, batch_c=hw * 2048)
             if f.product:
@@ -1500,8 +1543,12 @@ class DAnARCNN(nn.Module):
             sc2 = torch.empty((NP, R * P2, K2p), dtype=torch.float32, device=dev)
             ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=NP, batch_a=R * P2 * qld,
                         batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
-            ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, 1.0 / shot,
-                                    unary_batch_stride=way * shot * P2)
+            if f.seg_w is not None:  # (eval, cached: way = 1, offset = 0)
+                ops.attn_softmax_unary_w_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, f.seg_w,
+                                          unary_batch_stride=way * shot * P2)
+            else:
+                ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, 1.0 / shot,
+                                        unary_batch_stride=way * shot * P2)
             if sw is not None:
                 swt = ops.transpose_batched(sw.view(-1)[offset * P2 * rd_:], NP, K2, rd_, ldi=rd_, ldo=K2p,
                                             in_batch=way * shot * P2 * rd_)  # [B][64][K2p], zero padded
@@ -1553,6 +1600,74 @@ class DAnARCNN(nn.Module):
         return prob_all, cls_prob, cls_score, neg_score
 
 
+def _is_shot_spec_leaf(x):
+    return x is None or isinstance(x, (int, np.integer)) and not isinstance(x, bool)
+
+
+def resolve_shot_views(shots, sets, counts, each=False):
+    """The shot views of a call, host only (no device): -> (sets, views), views[p] an ordered tuple of distinct shot
+    indices of set sets[p], each < counts[sets[p]] (the set's real shots).
+    shots: ONE spec for every problem -- None (all real shots of the set), an int k (shots 0..k-1: the nested K-shot
+    subsets) or a flat sequence of shot indices -- or a sequence of len(sets) specs, one per problem (recognised by an
+    element that is itself None or a sequence; per-problem ints k go as range(k)). "each" (each=True callers: a sweep)
+    expands every listed set into its S one-shot views, problem c*S + s = shot s of sets[c]; the listed sets must have
+    equal counts. ValueError: empty view, duplicates, device tensors, a bad spec; IndexError: a shot >= counts[set]."""
+    sets = [int(c) for c in sets]
+
+    def host_list(x):
+        if torch.is_tensor(x):
+            if x.is_cuda:
+                raise ValueError("shots= takes host values (ints, sequences or CPU tensors), not device tensors")
+            return x.reshape(-1).tolist()
+        return x
+
+    def one(spec, c):
+        n = int(counts[c])
+        spec = host_list(spec)
+        if spec is None:
+            return tuple(range(n))
+        if _is_shot_spec_leaf(spec):
+            k = int(spec)
+            if k < 1:
+                raise ValueError("shots=%d: a view needs at least one shot" % k)
+            if k > n:
+                raise IndexError("shots=%d: set %d has %d shots" % (k, c, n))
+            return tuple(range(k))
+        if isinstance(spec, str) or not hasattr(spec, "__iter__"):
+            raise ValueError("shots: %r is not a view (None, an int or a sequence of shot indices)" % (spec,))
+        view = []
+        for v in spec:
+            if v is None or not _is_shot_spec_leaf(v):
+                raise ValueError("shots: %r is not a shot index" % (v,))
+            view.append(int(v))
+        if not view:
+            raise ValueError("shots: empty view for set %d" % c)
+        if len(set(view)) != len(view):
+            raise ValueError("shots: view %s of set %d names a shot twice" % (view, c))
+        bad = [v for v in view if v < 0 or v >= n]
+        if bad:
+            raise IndexError("shots: %s outside the %d shots of set %d" % (bad, n, c))
+        return tuple(view)
+
+    shots = host_list(shots)
+    if isinstance(shots, str):
+        if shots != "each" or not each:
+            raise ValueError("shots=%r: %s" % (shots, "only a sweep takes shots='each'" if shots == "each" else
+                                               "the only string spec is 'each'"))
+        ns = sorted({int(counts[c]) for c in sets})
+        if len(ns) != 1:
+            raise ValueError("shots='each': the listed sets have different shot counts %s; sweep them by count" % ns)
+        return [c for c in sets for _ in range(ns[0])], [(s_,) for _ in sets for s_ in range(ns[0])]
+    per_problem = (not _is_shot_spec_leaf(shots) and hasattr(shots, "__iter__")
+                   and any(v is None or (hasattr(v, "__iter__") and not isinstance(v, str)) for v in shots))
+    if per_problem:
+        shots = list(shots)
+        if len(shots) != len(sets):
+            raise ValueError("shots: %d per-problem specs for %d problems" % (len(shots), len(sets)))
+        return sets, [one(sp, c) for sp, c in zip(shots, sets)]
+    return sets, [one(shots, c) for c in sets]
+
+
 class SupportCache:
     """The query-independent support tensors of C support sets (encode_supports), per set as the model's
     `_cache_layout` names them. DAnA:
@@ -1563,9 +1678,14 @@ class SupportCache:
     `model(im_data, im_info, gt_boxes, num_boxes, cache)`: query image b uses set index[b] -- `select(indices)`, else the
     identity when C == B and a broadcast when C == 1. The forward gathers the selected sets into B-batched buffers the cache
     owns (one launch, dana_gather_blocks, index read on the device: a recorded replay follows later `select` calls).
+    Every tensor is `shot` independent blocks, so `select(indices, shots=)` / `sweep(classes, shots=)` serve shot VIEWS of a
+    set (`resolve_shot_views`: K-shot subsets, single shots, ragged sets encoded with `num_shots=`): problems whose view is
+    not range(shot) are gathered by dana_gather_shot_blocks into m-shot buffers (m = the longest view of the call; padding
+    slots zeroed, w [P][m] = 1/len(view) or 0) and the query side runs with shot = m; views of unequal length scale the
+    attention per segment by w (dana_attn_softmax_unary_w / _sweep_w). Needs the model's `_cache_shot_blocks`.
     The cache records what it was built under; a forward after any of it changed raises ("re-encode")."""
 
-    def __init__(self, model, tensors, shot, sup_map, pool, state, dev):
+    def __init__(self, model, tensors, shot, sup_map, pool, state, dev, counts=None):
         self._model = weakref.ref(model)
         self._t = {k: v for k, v in tensors.items() if v is not None}
         self.shot, self.sup_map, self.pool, self.device = shot, tuple(sup_map), pool, torch.device(dev)
@@ -1578,9 +1698,36 @@ class SupportCache:
         self._index = None      # device int32 [capacity]: what dana_gather_blocks reads
         self._index_host = None  # what the device index holds
         self._bufs = {}         # B -> (gathered tensors, device tables)
+        # shot views. _blocks: name -> (rows, floats per shot block) of a set's [rows][shot][block] tensor, or None when
+        # the model's cached tensors are not per-shot blocks (_no_shot_views says why)
+        self._blocks = model._cache_shot_blocks(sup_map)
+        self._no_shot_views = getattr(model, "_no_shot_views", None)
+        self._counts = tuple(int(n) for n in counts) if counts is not None else (shot,) * self._C
+        if len(self._counts) != self._C or any(n < 1 or n > shot for n in self._counts):
+            raise ValueError("SupportCache: shot counts %s for %d sets of %d shots" % (list(self._counts), self._C, shot))
+        self._sel_views = None   # the views of the last select(), or None: every selected set's real shots
+        self._view = None        # device int32 [capacity][shot], -1 padded: what dana_gather_shot_blocks reads
+        self._view_host = None   # what the device view table holds
+        self._vbufs = {}         # (P, m) -> (gathered m-shot tensors, device tables, n tensors, w [P][m])
+        self._mode = None        # the last prepared forward: None (identity views) or (m, weighted)
 
     def __len__(self):
         return self._C
+
+    @property
+    def shot_counts(self):
+        """the number of real shots of every set (encode_supports' num_shots; `shot` each without it)"""
+        return self._counts
+
+    def _views(self, shots, sets, each=False):
+        """-> (sets, views or None): `resolve_shot_views`, None when every view is the identity range(shot)"""
+        if self._blocks is None and (shots is not None or self._counts != (self.shot,) * self._C):
+            raise NotImplementedError("shot views (shots=, num_shots=): " + (self._no_shot_views or "not declared by the model"))
+        if shots is None and all(self._counts[c] == self.shot for c in sets):
+            return list(sets), None
+        sets, views = resolve_shot_views(shots, sets, self._counts, each=each)
+        ident = tuple(range(self.shot))
+        return sets, (None if all(v == ident for v in views) else views)
 
     @property
     def nbytes(self):
@@ -1600,9 +1747,10 @@ class SupportCache:
         from . import _lib
         return _lib.RECORDER is not None or torch.cuda.is_current_stream_capturing()
 
-    def select(self, indices):
-        """query image b of the next forwards uses support set indices[b] (a host sequence or a CPU tensor of length B).
-        Validated on the host, written into the device index the gather reads."""
+    def select(self, indices, shots=None):
+        """query image b of the next forwards uses support set indices[b] (a host sequence or a CPU tensor of length B),
+        and of it the shots `shots` names (`resolve_shot_views`; default: all real shots). Validated on the host, written
+        into the device index (and view table) the gather reads."""
         if torch.is_tensor(indices):
             if indices.is_cuda:
                 raise ValueError("SupportCache.select takes host indices (a sequence or a CPU tensor)")
@@ -1613,12 +1761,17 @@ class SupportCache:
         bad = [i for i in idx if i < 0 or i >= self._C]
         if bad:
             raise IndexError("SupportCache.select: indices %s outside [0, %d)" % (bad, self._C))
-        self._sel = idx
+        _, views = self._views(shots, idx)
+        self._sel, self._sel_views = idx, views
         self._write_index(idx)
+        if views is not None:
+            self._write_views(views)
 
-    def sweep(self, classes=None):
+    def sweep(self, classes=None, shots=None):
         """-> ClassSweep: `model(im_data, im_info, gt_boxes, num_boxes, cache.sweep(classes))` runs every query image
-        against each listed set (default: all C, in order). classes: a host sequence or a CPU tensor of set indices."""
+        against each listed set (default: all C, in order). classes: a host sequence or a CPU tensor of set indices.
+        shots: the view of every class, or one per class (`resolve_shot_views`); "each" expands every class into its S
+        one-shot views, problem c*S + s of an image = shot s of class c (postprocess.ensemble_shots' layout)."""
         if classes is None:
             idx = list(range(self._C))
         else:
@@ -1632,7 +1785,8 @@ class SupportCache:
         bad = [i for i in idx if i < 0 or i >= self._C]
         if bad:
             raise IndexError("SupportCache.sweep: indices %s outside [0, %d)" % (bad, self._C))
-        return ClassSweep(self, idx)
+        idx, views = self._views(shots, idx, each=True)
+        return ClassSweep(self, idx, views)
 
     def _resolve(self, B):
         if self._sel is not None:
@@ -1656,11 +1810,30 @@ class SupportCache:
         self._index[:len(idx)].copy_(torch.tensor(idx, dtype=torch.int32))
         self._index_host = list(idx)
 
-    def _prepare(self, B, idx=None):
+    def _write_views(self, views):
+        """the view table of the next gather: row p = views[p], -1 padded to `shot`"""
+        rows = [list(v) + [-1] * (self.shot - len(v)) for v in views]
+        if rows == self._view_host:
+            return
+        if self._active_recording():
+            raise RuntimeError("SupportCache: the shot views changed inside a recording / capture: select before it")
+        if self._view is None or self._view.size(0) < len(rows):
+            self._view = torch.full((max(len(rows), self._C, 16), self.shot), -1, dtype=torch.int32, device=self.device)
+        self._view[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int32))
+        self._view_host = rows
+
+    def _prepare(self, B, idx=None, views=None):
         """host-side set-up of a forward that gathers B sets (selection written, gathered buffers + pointer tables
-        allocated): what a recording or capture must find done. idx: the B set indices (a class sweep's), else the
-        selection / default for B images"""
-        self._write_index(self._resolve(B) if idx is None else idx)
+        allocated): what a recording or capture must find done. idx, views: the B set indices and their shot views (a
+        class sweep's), else the selection / default for B images. Sets self._mode: None (identity views: the whole-set
+        buffers) or (m, weighted)"""
+        if idx is None:
+            idx = self._resolve(B)
+            views = self._sel_views if self._sel is not None else self._views(None, idx)[1]
+        self._write_index(idx)
+        if views is not None:
+            return self._prepare_views(B, views)
+        self._mode = None
         if (self._C == 1 and B == 1) or B in self._bufs:
             return
         if self._active_recording():
@@ -1675,9 +1848,48 @@ class SupportCache:
                             [self._t[k][0].numel() * 4 for k in names]], dtype=torch.int64).to(self.device)
         self._bufs[B] = (dst, tab, len(names))
 
-    def _gather(self, B, idx=None):
+    def _prepare_views(self, P, views):
+        if len(views) != P:
+            raise RuntimeError("SupportCache: %d shot views for %d problems" % (len(views), P))
+        self._write_views(views)
+        m = max(len(v) for v in views)
+        self._mode = (m, any(len(v) != m for v in views))
+        if (P, m) in self._vbufs:
+            return
+        if self._active_recording():
+            raise RuntimeError("SupportCache: first (P, m) = (%d, %d) view forward inside a recording / capture: run one "
+                               "eagerly first" % (P, m))
+        names = [k for k in self.FIELDS if k in self._t]
+        shapes = self._model()._cache_layout(m, self.sup_map)
+        dst = {k: torch.empty((P,) + shapes[k], dtype=torch.float32, device=self.device) for k in names}
+        for k in names:
+            rows, block = self._blocks[k]
+            if self._t[k][0].numel() != rows * self.shot * block or dst[k][0].numel() != rows * m * block:
+                raise RuntimeError("SupportCache: tensor %s is not [%d][shot][%d] per set" % (k, rows, block))
+        tab = torch.tensor([[self._t[k].data_ptr() for k in names], [dst[k].data_ptr() for k in names],
+                            [self._blocks[k][0] for k in names], [self._blocks[k][1] * 4 for k in names]],
+                           dtype=torch.int64).to(self.device)
+        self._vbufs[(P, m)] = (dst, tab, len(names), torch.zeros((P, m), dtype=torch.float32, device=self.device))
+
+    def _gather_views(self, P, idx=None, views=None):
+        """-> ({name: the P problems' tensors}, m, w): `_gather` when every view is the identity (m = shot, w None), else
+        one dana_gather_shot_blocks launch into the (P, m) buffers; w [P][m] when the views' lengths differ, else None"""
+        self._prepare(P, idx, views)
+        if self._mode is None:
+            return self._gather(P, idx, prepared=True), self.shot, None
+        m, weighted = self._mode
+        dst, tab, n, w = self._vbufs[(P, m)]
+        from ._lib import lib
+        lib().call("dana_gather_shot_blocks", tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(), tab[3].data_ptr(), n,
+                   self._index.data_ptr(), self._view.data_ptr(), w.data_ptr(), self._C, self.shot, m, P, ops._stream())
+        return {k: dst.get(k) for k in self.FIELDS}, m, (w if weighted else None)
+
+    def _gather(self, B, idx=None, prepared=False):
         """-> {name: the B selected sets in the forward's layout}, gathered by one launch (none for one set, one image)"""
-        self._prepare(B, idx)
+        if not prepared:
+            self._prepare(B, idx)
+            if self._mode is not None:
+                raise NotImplementedError("shot views: " + (self._no_shot_views or "this forward does not take them"))
         if self._C == 1 and B == 1:
             return {k: (self._t[k].view(self._shapes[k]) if k in self._t else None) for k in self.FIELDS}
         dst, tab, n = self._bufs[B]
@@ -1694,10 +1906,11 @@ class ClassSweep:
     outputs are laid out as the replicated call `model(im.repeat_interleave(C, 0), ..., cache)` after
     `cache.select(classes * B)` lays them out: rois [B*C, R, 5] (column 0 = p), cls_prob [B*C*R, 2], bbox_pred [B*C*R, 4]."""
 
-    __slots__ = ("cache", "classes")
+    __slots__ = ("cache", "classes", "views")
 
-    def __init__(self, cache, classes):
-        self.cache, self.classes = cache, tuple(classes)
+    def __init__(self, cache, classes, views=None):
+        # views: the shot view of every listed problem (SupportCache.sweep's shots=), None: every set whole
+        self.cache, self.classes, self.views = cache, tuple(classes), (None if views is None else tuple(views))
 
     def __len__(self):
         return len(self.classes)
@@ -1705,6 +1918,10 @@ class ClassSweep:
     def _index(self, B):
         """the gather index of a B-image forward: the class list repeated for every image"""
         return list(self.classes) * B
+
+    def _views(self, B):
+        """the shot views of a B-image forward, or None"""
+        return None if self.views is None else list(self.views) * B
 
     def __repr__(self):
         return "ClassSweep(%d sets: %s)" % (len(self.classes), list(self.classes))

@@ -54,13 +54,23 @@ class FasterRCNN(DAnARCNN):
         """what a sibling's SupportCache depends on besides the support images (every state_dict tensor is in _sig)"""
         return (self._sig(), str(dev), type(self).__name__, int(self.n_shot))
 
-    def encode_supports(self, support_ims):
+    # meta, fsod and fgn average over the shots WHILE encoding (one class vector / kernel per set), so a set's cached
+    # tensors are not per-shot blocks: no shot views, no ragged sets
+    _no_shot_views = ("this detector averages over a set's shots while it encodes them (one vector per set), so its "
+                      "cached tensors have no per-shot blocks to pick from: encode the shots you want as their own sets")
+
+    def _cache_shot_blocks(self, sup_map):
+        return None
+
+    def encode_supports(self, support_ims, num_shots=None):
         """support_ims [C, shot, 3, 320, 320] -> SupportCache of the model's per-set support tensors (`_cache_layout`),
         each set built by `_support_set` with the launches an uncached B = 1 eval forward issues for it. The forward takes
         the cache (or cache.select / cache.sweep) in place of support images, as DAnARCNN's does."""
         if self._support_set is None:
             raise TypeError("%s is the plain Faster R-CNN (faster_rcnn.py): it has no support branch, so there are no "
                             "support sets to encode" % type(self).__name__)
+        if num_shots is not None:
+            raise NotImplementedError("encode_supports(num_shots=): " + self._no_shot_views)
         C, shot, dev = self._check_support_sets(support_ims)
         if tuple(support_ims.shape[-2:]) != (320, 320):
             raise RuntimeError("support images must be 320x320 (a 20x20 stride-16 map) for a cached support set, got %dx%d"

@@ -1284,6 +1284,49 @@ def attn_softmax_unary_(scores, unary, rows, rows_per_batch, nseg, length, ld, k
     return scores
 
 
+def attn_softmax_unary_w_(scores, unary, rows, rows_per_batch, nseg, length, ld, kpad, unary_gamma, seg_scale,
+                          unary_batch_stride=0, scale_batch_stride=0):
+    """attn_softmax_unary_ with a per-segment scale seg_scale [batches][nseg (or scale_batch_stride)] in place of
+    out_scale; a segment whose scale is 0 is not read and comes back as zeros"""
+    _chk(scores, "scores")
+    _chk(unary, "unary")
+    _chk(seg_scale, "seg_scale")
+    lib().call("dana_attn_softmax_unary_w", _p(scores), _p(unary), rows, rows_per_batch, unary_batch_stride, nseg, length,
+               ld, kpad, float(unary_gamma), _p(seg_scale), scale_batch_stride, _stream())
+    return scores
+
+
+def attn_softmax_unary_sweep_w(scores, out, unary, B, C, hw, nseg, length, ld_in, ld_out, kpad, unary_gamma, seg_scale,
+                               unary_stride=0, scale_stride=0):
+    """attn_softmax_unary_sweep with a per-segment scale seg_scale [B*C][nseg (or scale_stride)] in place of out_scale"""
+    _chk(scores, "scores")
+    _chk(out, "out")
+    _chk(unary, "unary")
+    _chk(seg_scale, "seg_scale")
+    lib().call("dana_attn_softmax_unary_sweep_w", _p(scores), _p(out), _p(unary), B, C, hw, unary_stride, nseg, length,
+               ld_in, ld_out, kpad, float(unary_gamma), _p(seg_scale), scale_stride, _stream())
+    return out
+
+
+def gather_shot_blocks(srcs, rows, blocks, index, view, m):
+    """dana_gather_shot_blocks on its own (SupportCache drives it with cached tables): srcs[t] [n_sets][rows[t]][shot]
+    [blocks[t]] float32, index [P] and view [P][shot] int32 on the device -> ([P][rows[t]][m][blocks[t]] per tensor, w [P][m])"""
+    P, shot, dev = index.numel(), view.size(1), index.device
+    _chk(index, "index", torch.int32)
+    _chk(view, "view", torch.int32)
+    for t, r, b in zip(srcs, rows, blocks):
+        _chk(t, "src")
+        if t.numel() != t.size(0) * r * shot * b:
+            raise ValueError("gather_shot_blocks: a source is not [n_sets][%d][%d][%d]" % (r, shot, b))
+    dsts = [torch.empty((P, r, m, b), dtype=torch.float32, device=dev) for r, b in zip(rows, blocks)]
+    w = torch.empty((P, m), dtype=torch.float32, device=dev)
+    tab = torch.tensor([[t.data_ptr() for t in srcs], [t.data_ptr() for t in dsts], list(rows), [b * 4 for b in blocks]],
+                       dtype=torch.int64).to(dev)
+    lib().call("dana_gather_shot_blocks", _p(tab[0]), _p(tab[1]), _p(tab[2]), _p(tab[3]), len(srcs), _p(index), _p(view),
+               _p(w), srcs[0].size(0), shot, m, P, _stream())
+    return dsts, w
+
+
 def attn_softmax_unary_sweep(scores, out, unary, B, C, hw, nseg, length, ld_in, ld_out, kpad, unary_gamma, out_scale,
                              unary_stride=0):
     """class sweep: attn_softmax_unary_ over rows (b, i, c) of scores [B][hw][C][ld_in], written out of place to row

@@ -230,8 +230,8 @@ def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_de
 
 def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0):
     """The shot ensemble of utils.py:182-204: `cd` = detections_by_class(..., with_layout=True) of a sweep whose cached
-    sets are laid out as set c*shots + s (class c seen through its shot s alone: a model built with num_shot=1 and
-    encode_supports(shots.view(C*S, 1, 3, 320, 320))). -> `merge_detections(cd, shots)` as dets[b][c], a
+    problems are laid out as c*shots + s (class c seen through its shot s alone: `cache.sweep(classes, shots="each")`
+    on a k-shot cache, or a num_shot=1 model's cache of C*S one-shot sets). -> `merge_detections(cd, shots)` as dets[b][c], a
     `MergedDetections` that `DetectionEvaluator.add_by_class` / `CocoEvaluator.add_by_class` take unchanged."""
     shots = int(shots)
     if shots < 1 or cd.num_classes % shots:

@@ -393,10 +393,13 @@ class ProgramDAnA:
             B = self.inputs[0].size(0)
             # selection written, gathered buffers allocated: outside the recording
             if sw is not None:
-                self.cache._prepare(B * len(sw), sw._index(B))
+                self.cache._prepare(B * len(sw), sw._index(B), sw._views(B))
             else:
                 self.cache._prepare(B)
             self._cache_index = self.cache._index
+            # shot views: the recording is of one (m, weighted) -- m-shot launch shapes, scalar or per-segment softmax
+            # scale -- and of one view table, read on the device like the index
+            self._cache_mode, self._cache_view = self.cache._mode, self.cache._view
         torch.cuda.synchronize(dev)
         self._device_rng = bool(getattr(model, "device_rng", False)) and model.training
         if self._device_rng:
@@ -438,6 +441,18 @@ class ProgramDAnA:
         model._rng_calls = calls0 + (1 if self._device_rng else 0)
         torch.cuda.synchronize(dev)
 
+    def _check_cache_buffers(self, cache):
+        if cache._index is not self._cache_index:
+            raise RuntimeError("the SupportCache's index buffer was reallocated after the recording: record a new runner")
+        if cache._mode != self._cache_mode:
+            def say(mode):
+                return "whole sets" if mode is None else "shot views of %d slots, %s lengths" % (
+                    mode[0], "unequal" if mode[1] else "equal")
+            raise RuntimeError("ProgramDAnA was recorded with %s and called with %s (other launch shapes): record a new "
+                               "runner for it" % (say(self._cache_mode), say(cache._mode)))
+        if cache._mode is not None and cache._view is not self._cache_view:
+            raise RuntimeError("the SupportCache's view table was reallocated after the recording: record a new runner")
+
     def __call__(self, *inputs):
         sw = _class_sweep(inputs)
         if (sw is None) != (self.sweep_n is None) or (sw is not None and (sw.cache is not self.cache or len(sw) != self.sweep_n)):
@@ -448,9 +463,8 @@ class ProgramDAnA:
         if sw is not None:
             B = self.inputs[0].size(0)
             sw.cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
-            sw.cache._prepare(B * self.sweep_n, sw._index(B))  # the sweep's classes into the index the replay reads
-            if sw.cache._index is not self._cache_index:
-                raise RuntimeError("the SupportCache's index buffer was reallocated after the recording: record a new runner")
+            sw.cache._prepare(B * self.sweep_n, sw._index(B), sw._views(B))  # the sweep's classes into the index the replay reads
+            self._check_cache_buffers(sw.cache)
         cache = _support_cache(inputs)
         if sw is None and cache is not self.cache:
             raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: record a new runner for it" % (
@@ -459,8 +473,7 @@ class ProgramDAnA:
         if sw is None and cache is not None:
             cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
             cache._prepare(self.inputs[0].size(0))  # (the selection's length must still be the recorded batch)
-            if cache._index is not self._cache_index:
-                raise RuntimeError("the SupportCache's index buffer was reallocated after the recording: record a new runner")
+            self._check_cache_buffers(cache)
         for s, t in zip(self.inputs, inputs):
             if torch.is_tensor(t) and t is not s:
                 s.copy_(t, non_blocking=True)

@@ -197,6 +197,16 @@ int dana_dets_to_gt_boxes(const float* dets, const int* counts, const int* offse
  * so a recorded replay gathers the selection of the moment. Indices outside [0, n_sets) copy nothing. */
 int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* block_bytes, int n_tensors,
                        const int* index, int n_sets, int B, dana_stream_t stream);
+/* Shot views of cached sets (SupportCache.select / sweep with shots=): dana_gather_blocks with a shot axis. Tensor t of a set
+ * is [rows[t]][shot][block_bytes[t]]; problem p < P's destination is [rows[t]][m][block_bytes[t]]. Slot j < m takes shot block
+ * view[p*shot + j] of set index[p]; a slot whose view entry is -1 (padding; any entry outside [0, shot) counts as padding) is
+ * written as zeros and nothing is read for it. w[p*m + j] = 1.0f / (real slots of problem p), 0 on padding. src_ptrs,
+ * dst_ptrs, rows, block_bytes are DEVICE arrays of n_tensors entries; index [P], view [P][shot] and w [P][m] are device
+ * memory too (a recorded replay gathers the selection of the moment). One launch; a set index outside [0, n_sets) writes
+ * nothing. 1 <= m <= shot <= 64. */
+int dana_gather_shot_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* rows, const long long* block_bytes,
+                            int n_tensors, const int* index, const int* view, float* w, int n_sets, int shot, int m, int P,
+                            dana_stream_t stream);
 
 /* ---- class sweep (dana.SupportCache.sweep): B query images x C cached support sets as B*C problems p = b*C + c, the
  * per-class forward of dana.py:87-220 for every class of an image (inference.py:70-140 fills all_boxes[j][i] with it).
@@ -208,6 +218,12 @@ int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long lo
 int dana_attn_softmax_unary_sweep(const float* scores, float* out, const float* unary, int B, int C, long hw,
                                   long unary_stride, int nseg, int length, long ld_in, long ld_out, int kpad,
                                   float unary_gamma, float out_scale, dana_stream_t stream);
+/* ... with a per-segment scale in place of out_scale: segment s of a row of problem p is scaled by
+ * seg_scale[p*scale_stride + s] (scale_stride <= 0: nseg). A segment whose scale is 0 is not read and written as +0.0f.
+ * Equal scales give the bits of dana_attn_softmax_unary_sweep. */
+int dana_attn_softmax_unary_sweep_w(const float* scores, float* out, const float* unary, int B, int C, long hw,
+                                    long unary_stride, int nseg, int length, long ld_in, long ld_out, int kpad,
+                                    float unary_gamma, const float* seg_scale, long scale_stride, dana_stream_t stream);
 /* dst row p*rows + i <- src row (p / group)*rows + i (`cols` floats), p < n_blocks: a problem's copy of its image's rows
  * (im_info of proposal_layer.py:49-190 / inference.py:106-140 per problem) */
 int dana_repeat_rows_grouped(const float* src, float* dst, long rows, int cols, long ld_src, long ld_dst, int group,
@@ -446,6 +462,12 @@ int dana_ba_apply(float* s, const float* w, int groups, int length, int dim, lon
 int dana_attn_softmax_unary(float* scores, const float* unary, long rows, long rows_per_batch, long unary_batch_stride,
                             int nseg, int length, long ld, int kpad, float unary_gamma, float out_scale,
                             dana_stream_t stream);
+/* ... with a per-segment scale in place of out_scale (shot views of unequal length): segment s of a row of batch
+ * b = row / rows_per_batch is scaled by seg_scale[b*scale_batch_stride + s] (scale_batch_stride <= 0: nseg). A segment
+ * whose scale is 0 is not read and written as +0.0f. Equal scales give the bits of dana_attn_softmax_unary. */
+int dana_attn_softmax_unary_w(float* scores, const float* unary, long rows, long rows_per_batch, long unary_batch_stride,
+                              int nseg, int length, long ld, int kpad, float unary_gamma, const float* seg_scale,
+                              long scale_batch_stride, dana_stream_t stream);
 
 /* ---- training targets for the sampled RoIs: lib/model/rpn/proposal_target_layer_cascade.py:33-213 ---- */
 
