@@ -2,8 +2,11 @@
 variant S). What `loss.backward()` does through autograd + cuDNN/cuBLAS in the reference (train.py:141-143) is
 assembled here from the C-ABI building blocks: data gradients on the forward implicit-GEMM kernel with
 transformed weights, weight gradients on the split-M TN MFMA kernel, and the element-wise adjoints of
-backward.hip. Frozen BatchNorm (dana.py:362-385) only scales gradients; BN parameters, conv1/bn1/layer1 get none
-(dana.py:350-360, cfg.RESNET.FIXED_BLOCKS = 1).
+backward.hip. Frozen BatchNorm (dana.py:362-385) only scales gradients; BN parameters and conv1/bn1 get none, and
+neither do the trunk stages that cfg.RESNET.FIXED_BLOCKS froze when the model was built (dana.py:350-360): the saving
+forward derives t, the first trainable trunk stage, from the parameters' requires_grad (`first_trainable_stage`) and
+stores it in its context; every piece below reads it there and neither saves, differentiates nor derives weights for
+the stages in front of it (t = 3, the frozen-trunk fine-tuning stage: nothing below layer4, the RPN and the heads).
 
 `model_backward` is the whole-model adjoint: it consumes the context a `save_for_backward` forward left in
 `model._ctx` and accumulates `.grad` on every trainable parameter, checked against autograd of the oracle
@@ -238,16 +241,46 @@ def lin(name):
 RPN_PARAMS = lin("RCNN_rpn.RPN_cls_score") + lin("RCNN_rpn.RPN_bbox_pred") + lin("RCNN_rpn.RPN_Conv")
 
 
+def _stage_convs(model, li):
+    """[(name, parameter)] of the conv weights of trunk stage li (0: layer1 .. 2: layer3), in module order"""
+    prefix = "RCNN_base.%d." % (4 + li)
+    return [(prefix + n, p) for n, p in model.RCNN_base[4 + li].named_parameters()
+            if ".conv" in n or n.endswith("downsample.0.weight")]
+
+
+def first_trainable_stage(model):
+    """t, the first trunk stage the backward differentiates: 0 (layer1) .. 2 (layer3), 3: the whole trunk is frozen. The
+    parameters' requires_grad decide -- what `_init_modules` set from cfg.RESNET.FIXED_BLOCKS (dana.py:354-360). The
+    trainable stages must form a suffix layer_t .. layer3 (a gradient cannot skip a stage's weights on its way down and
+    nothing is saved in front of t) and a stage's conv weights must agree with each other: ValueError naming the first
+    parameter that breaks either rule. Stem and BatchNorms are frozen always and not looked at."""
+    flags, first = [], []
+    for li in range(3):
+        convs = _stage_convs(model, li)
+        for n, p in convs:
+            if p.requires_grad != convs[0][1].requires_grad:
+                raise ValueError("%s has requires_grad=%s while %s has %s: the conv weights of one trunk stage train or "
+                                 "freeze together" % (n, p.requires_grad, convs[0][0], convs[0][1].requires_grad))
+        flags.append(convs[0][1].requires_grad)
+        first.append(convs[0][0])
+    for li in (1, 2):
+        if flags[li - 1] and not flags[li]:
+            raise ValueError("%s is frozen behind the trainable %s: the trainable trunk stages must be a suffix "
+                             "(layer_t .. layer3), as cfg.RESNET.FIXED_BLOCKS sets them" % (first[li], first[li - 1]))
+    return 3 - sum(flags)
+
+
 def top_params(plan):
     """RCNN_top's (layer4's) conv weights, in the order layer4_backward finishes them"""
     return [n for bi in (2, 1, 0) for n in _block_convs("RCNN_top.0.%d" % bi, plan["layer4"][bi])]
 
 
-def base_stages(plan):
-    """one stage per trainable trunk block, last block first: RCNN_base.6 (layer3) then RCNN_base.5 (layer2); layer1 is
-    frozen"""
+def base_stages(plan, t):
+    """one stage per trainable trunk block, last block first: RCNN_base.6 (layer3) down to RCNN_base.(4 + t); the stages
+    in front of t (first_trainable_stage; 1: layer1 is frozen, the reference's default) have none. t has no default:
+    a list that silently disagrees with the parameters' flags is what this argument exists to prevent"""
     st = []
-    for li in (2, 1):
+    for li in range(2, t - 1, -1):
         layer = plan["layers"][li]
         for bi in reversed(range(len(layer))):
             key = "RCNN_base.%d.%d" % (4 + li, bi)
@@ -255,17 +288,20 @@ def base_stages(plan):
     return st
 
 
-def grad_stages(model, plan=None):
+def grad_stages(model, plan=None, t=None):
     """[(stage, [parameter names])] in the order model_backward FINISHES the gradients (the model's class knows it:
     `_grad_stages`): the trainer lays its flat gradient buffer out in this order so that all-reduce buckets can leave
     while the rest of the backward runs.
     plan: the forward's plan (the backward passes the one its context saved: asking the model for a plan INSIDE the
     backward -- autograd runs it with gradients disabled, i.e. not `_live()` -- re-derived and pre-split every trainable
-    weight once per iteration for nothing: ~100 small launches at the head of the backward)."""
-    return model._grad_stages(plan if plan is not None else model._get_plan())
+    weight once per iteration for nothing: ~100 small launches at the head of the backward).
+    t: the first trainable trunk stage (the backward passes its context's); None: from the parameters' requires_grad."""
+    return model._grad_stages(plan if plan is not None else model._get_plan(), t)
 
 
-def dana_grad_stages(model, plan):
+def dana_grad_stages(model, plan, t=None):
+    """t None: read off the model's parameters (first_trainable_stage)"""
+    t = first_trainable_stage(model) if t is None else t
     st = [("box branch", lin("RCNN_bbox_pred") + top_params(plan))]
     st.append(("roi heads", lin("output_score_layer.linear2") + lin("output_score_layer.linear1")
                + lin("rcnn_adapt_q_layer") + lin("rcnn_transform_layer") + lin("rcnn_adapt_k_layer")
@@ -274,13 +310,14 @@ def dana_grad_stages(model, plan):
     if model.semantic_enhance:
         rpn_att += lin("rpn_channel_k_layer")
     st.append(("rpn", RPN_PARAMS + rpn_att))
-    return st + base_stages(plan)
+    return st + base_stages(plan, t)
 
 
-def sibling_grad_stages(plan, head_params):
+def sibling_grad_stages(plan, head_params, t):
     """the sibling detectors (frcnn.py, fsod.py, fgn.py): one RoI stage (RCNN_bbox_pred, the class's `_head_params`,
     layer4), the RPN, the trunk"""
-    return [("roi head", lin("RCNN_bbox_pred") + head_params + top_params(plan)), ("rpn", RPN_PARAMS)] + base_stages(plan)
+    return ([("roi head", lin("RCNN_bbox_pred") + head_params + top_params(plan)), ("rpn", RPN_PARAMS)]
+            + base_stages(plan, t))
 
 
 def ready(model, names):
@@ -319,15 +356,17 @@ def _attention_backward(d_dense, ld_dd, a, unary, q, k_, s_mat, Bn, rows_b, nseg
       d_dense [Bn*rows_b][vw] (row stride ld_dd; vw = width of the value rows s_mat: 1024, or 64 where the values are the
       re-associated table S . Wt_a^T of the RoI heads); a = the saved attention [Bn][rows_b][Kp]; q [Bn*rows_b][dq];
       k_ / s_mat / unary: key, value and unary rows of image b start at b * k_batch / s_batch / u_batch (floats).
-    Accumulates into d_k_out (rows of image b at b*k_batch), d_s_out (b*s_batch), d_u_out (b*u_batch); returns d_q."""
+    Accumulates into d_k_out (rows of image b at b*k_batch), d_s_out (b*s_batch; None: nobody reads the values' gradient,
+    its launch is not issued), d_u_out (b*u_batch); returns d_q."""
     dev = a.device
     K = nseg * L
     dA = torch.zeros((Bn, rows_b, Kp), dtype=torch.float32, device=dev)
     ops.gemm_nt(d_dense, s_mat, rows_b, K, vw, lda=ld_dd, out=dA, ldc=Kp, batch=Bn, batch_a=rows_b * ld_dd,
                 batch_b=s_batch, batch_c=rows_b * Kp)
     # d s[b] += a[b]^T . d_dense[b], every image in one launch (a's zero-padded columns K..Kp-1 are computed, not stored)
-    ops.gemm_tn_batched(a, d_dense, Bn, rows_b, Kp, vw, d_s_out, ldy=Kp, ldx=ld_dd, batch_y=rows_b * Kp,
-                        batch_x=rows_b * ld_dd, batch_out=s_batch, n_valid=K)
+    if d_s_out is not None:
+        ops.gemm_tn_batched(a, d_dense, Bn, rows_b, Kp, vw, d_s_out, ldy=Kp, ldx=ld_dd, batch_y=rows_b * Kp,
+                            batch_x=rows_b * ld_dd, batch_out=s_batch, n_valid=K)
     ops.colsum_batched(dA, Bn, rows_b, K, d_u_out, ld=Kp, x_batch=rows_b * Kp, out_batch=u_batch, alpha=ugamma / nseg)
     ops.attn_softmax_unary_backward_(dA, a, unary, Bn * rows_b, rows_b, nseg, L, Kp, Kp, ugamma, 1.0 / nseg,
                                      1.0 / math.sqrt(dq), unary_batch_stride=u_batch)
@@ -349,11 +388,12 @@ def _rpn_conv_plan(model, ctx):
     return c
 
 
-def _derive_dgrad_weights(blocks):
+def _derive_dgrad_weights(blocks, no_dx=None):
     """the data-gradient weights of the given block plans' convs, in the order the backward needs them (each is derived
-    once per weight update: _dgrad_weights)"""
+    once per weight update: _dgrad_weights). no_dx: a block plan whose input gradient nobody reads (layer4's first block
+    over a frozen trunk): its conv1 / downsample conv need none"""
     for bp in blocks:
-        for name in ("c3", "c2", "c1", "ds"):
+        for name in ("c3", "c2") if bp is no_dx else ("c3", "c2", "c1", "ds"):
             if bp.get(name) is not None:
                 _dgrad_weights(bp[name])
 
@@ -374,8 +414,9 @@ def prefetch_dgrad_weights(model, ctx, dev):
     prep.wait_event(ev0)  # (behind the optimizer's update of the weights on the caller's stream)
     with ops.on_stream(prep):
         _dgrad_weights(_rpn_conv_plan(model, ctx))
-        _derive_dgrad_weights(reversed(plan["layer4"]))
-        for layer in reversed(plan["layers"][1:]):  # (layer1 is frozen and in front of every trainable layer: no data gradient)
+        t = ctx["t"]
+        _derive_dgrad_weights(reversed(plan["layer4"]), no_dx=plan["layer4"][0] if t == 3 else None)
+        for layer in reversed(plan["layers"][t:]):  # (the stages in front of t are frozen: no data gradient reaches them)
             _derive_dgrad_weights(reversed(layer))
         ctx["dgw_prefetched"] = ops.record_event()
 
@@ -384,7 +425,10 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
     """Adjoint of the RPN branch: RPN losses -> heads -> 3x3 conv -> RPN-level attention (rpn.py:58-115, dana.py:118-154),
     on the CURRENT stream. It reads the forward's saved tensors only; -> (d_corr [B*hw][2048]: the gradient into
     [base_feat | attended], d_s_pe [B][shot*L][1024]: into the positive supports' PE-added maps). Weight gradients of the
-    branch are accumulated into .grad (through grads_r) before it returns."""
+    branch are accumulated into .grad (through grads_r) before it returns.
+    Over a frozen trunk (ctx["t"] == 3) nothing reads the two results: the launches that only complete them (the Q
+    projection's data gradient; without the BA block every launch into d_s_pe) are not issued, d_s_pe lives up to the BA
+    block's adjoint (rpn_channel_k_layer's gradient needs it there) and the chain returns (None, None)."""
     plan = ctx["plan"]
     B, shot = ctx["B"], ctx["shot"]
     fh, fw = ctx["fh"], ctx["fw"]
@@ -394,6 +438,7 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
     corr = ctx["corr"]
     dev = corr.device
     ug = model.unary_gamma
+    trunk = ctx["t"] < 3
     c_rpn = _rpn_conv_plan(model, ctx)
     # -- RPN: losses -> heads -> 3x3 conv (rpn.py:58-115) --
     rpn = model.RCNN_rpn
@@ -415,7 +460,7 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
     # -- RPN-level attention (dana.py:118-154): corr = [base_feat | dense] --
     K1 = shot * L
     s_pe, kp, qp, unary = ctx["s_pe"], ctx["kp"], ctx["qp"], ctx["unary"]
-    d_s_pe = torch.zeros((B, K1, 1024), dtype=torch.float32, device=dev)
+    d_s_pe = torch.zeros((B, K1, 1024), dtype=torch.float32, device=dev) if trunk or model.semantic_enhance else None
     d_kp = torch.zeros((B * K1, d), dtype=torch.float32, device=dev)
     d_un = torch.zeros((B * shot, L), dtype=torch.float32, device=dev)
     d_qp = _attention_backward(d_corr.view(-1)[1024:], 2048, ctx["scores"], unary, qp, kp, s_pe, B, hw, shot, L, K1, d,
@@ -425,11 +470,13 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
     wq = model.rpn_adapt_q_layer.weight.detach()
     grads_r.linear(d_qp, corr, B * hw, d, 1024,
                  lambda dw, db: (acc(model.rpn_adapt_q_layer.weight, dw), acc(model.rpn_adapt_q_layer.bias, db)), ldx=2048)
-    ops.linear_backward(d_qp, corr, wq, B * hw, d, 1024, ldx=2048, dx_out=d_corr, dx_ld=2048, need_dw=False)
+    if trunk:
+        ops.linear_backward(d_qp, corr, wq, B * hw, d, 1024, ldx=2048, dx_out=d_corr, dx_ld=2048, need_dw=False)
     wk = model.rpn_adapt_k_layer.weight.detach()
     grads_r.linear(d_kp, s_pe, B * K1, d, 1024,
                  lambda dw, db: (acc(model.rpn_adapt_k_layer.weight, dw), acc(model.rpn_adapt_k_layer.bias, db)))
-    ops.linear_backward(d_kp, s_pe, wk, B * K1, d, 1024, dx_out=d_s_pe, dx_ld=1024, need_dw=False)
+    if d_s_pe is not None:
+        ops.linear_backward(d_kp, s_pe, wk, B * K1, d, 1024, dx_out=d_s_pe, dx_ld=1024, need_dw=False)
     ops.softmax_rows_backward_(d_un, unary, B * shot, L)
     wu = model.rpn_unary_layer.weight.detach()
     acc(model.rpn_unary_layer.weight, ops.rowdot_backward(s_pe, d_un, wu, B * K1, 1024, grad_x=d_s_pe))
@@ -441,10 +488,11 @@ def _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready=None):
         d_w = ops.ba_backward_(d_s_pe, s_pre, ba_w, gvec, gsum, G, L, 1024, gamma=model.channel_gamma, slope=0.01)
         ops.softmax_rows_backward_(d_w, ba_w, G, L)
         wc = model.rpn_channel_k_layer.weight.detach()
-        acc(model.rpn_channel_k_layer.weight, ops.rowdot_backward(s_pre, d_w, wc, G * L, 1024, grad_x=d_s_pe))
+        acc(model.rpn_channel_k_layer.weight,
+            ops.rowdot_backward(s_pre, d_w, wc, G * L, 1024, grad_x=d_s_pe if trunk else None))
         acc(model.rpn_channel_k_layer.bias, ops.colsum(d_w, G * L, 1))
     grads_r.finish_all(model, "RCNN_rpn")
-    return d_corr, d_s_pe
+    return (d_corr, d_s_pe) if trunk else (None, None)
 
 
 def model_backward(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
@@ -460,9 +508,10 @@ def model_backward_gen(model, grad_losses=(1.0, 1.0, 1.0, 1.0), ctx=None):
 
     d(sum_i grad_losses[i] * loss_i)/d(parameters) for the four training losses (rpn_loss_cls, rpn_loss_bbox,
     RCNN_loss_cls, RCNN_loss_bbox) of the last `save_for_backward` forward: what train.py:141-143's
-    `loss.backward()` computes, accumulated into `.grad` of the trainable parameters (BN, conv1 and layer1 are
-    frozen: dana.py:350-385). The adjoint is the class's `_backward_gen`: dana_backward_gen below, each sibling's beside its
-    forward (frcnn.py, fsod.py, fgn.py), all composed of the shared pieces that follow."""
+    `loss.backward()` computes, accumulated into `.grad` of the trainable parameters (BN, conv1 and the first
+    cfg.RESNET.FIXED_BLOCKS trunk stages are frozen: dana.py:350-385; their `.grad` stays None). The adjoint is the
+    class's `_backward_gen`: dana_backward_gen below, each sibling's beside its forward (frcnn.py, fsod.py, fgn.py), all
+    composed of the shared pieces that follow."""
     yield from model._backward_gen(grad_losses, ctx)
 
 
@@ -508,14 +557,15 @@ def seed_linear_dx(layer, seed, alpha):
     return ops.gemm_small(seed, (C, 1), layer.weight.detach(), (k, 1), n, k, C, alpha=alpha)
 
 
-def layer4_backward(d_top, n, saved, grads):
+def layer4_backward(d_top, n, saved, grads, need_dx=True):
     """Adjoint of `_head_to_tail` over the blocks a forward saved: d_top [n][2048] into the mean over layer4's output
-    positions -> dL/d(layer4's input): the RoIAlign output (meta: the max-pooled support map), no ReLU output: not masked"""
+    positions -> dL/d(layer4's input): the RoIAlign output (meta: the max-pooled support map), no ReLU output: not masked.
+    need_dx False (a frozen trunk: the input's gradient has no reader): the first block's data gradients are not run -> None"""
     npos = saved[-1]["h1"] * saved[-1]["w1"]
     g = ops.broadcast_rows(d_top, n, npos, 2048, alpha=1.0 / npos)
     for i, sv in enumerate(reversed(saved)):
         g = bottleneck_backward(g, sv, sv["n"], sv["h"], sv["w"], sv["bp"], grads, sv["key"], mask_dx=i < len(saved) - 1,
-                                g_masked=i > 0)
+                                g_masked=i > 0, need_dx=need_dx or i < len(saved) - 1)
     return g
 
 
@@ -551,23 +601,25 @@ def _dgrad_weights_ready(model, ctx, dev):
         # (in the order the backward needs them: the RPN chain and the box branch start at once, then the trunk)
         _dgrad_weights(_rpn_conv_plan(model, ctx))
         rpnw_ready = ops.record_event()
-        _derive_dgrad_weights(sv["bp"] for sv in reversed(ctx["l4_saved"]))
+        _derive_dgrad_weights((sv["bp"] for sv in reversed(ctx["l4_saved"])),
+                              no_dx=ctx["l4_saved"][0]["bp"] if ctx["t"] == 3 else None)
         l4w_ready = ops.record_event()
         _derive_dgrad_weights(sv["bp"] for sv in reversed(ctx["q_saved"]))
         return rpnw_ready, l4w_ready, ops.record_event()
 
 
 def _box_branch_backward(model, ctx, grads, d_bbox, g4):
-    """RCNN_bbox_pred <- mean <- layer4 (dana.py:246,387-389) -> d pooled [n_roi*49][1024]"""
+    """RCNN_bbox_pred <- mean <- layer4 (dana.py:246,387-389) -> d pooled [n_roi*49][1024] (None over a frozen trunk)"""
     seed_linear_grads(model.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
     d_fc7 = seed_linear_dx(model.RCNN_bbox_pred, d_bbox, g4)
-    return layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads)
+    return layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads, need_dx=ctx["t"] < 3)
 
 
 def _roi_heads_backward(model, ctx, grads, d_scores, g3):
     """RoI-level attention heads (dana.py:248-292), positive then negative supports. -> what both heads accumulate into:
     (d_q2, d_trq) of the query side's Q projection and transform input, (d_k2, d_un2, d_sp_pe) of the support side's keys,
-    unary term and PE-added maps, d_wt: the attended half of rcnn_transform_layer's weight gradient."""
+    unary term and PE-added maps (None over a frozen trunk, ctx["t"] == 3: the support trunk is its only reader), d_wt: the
+    attended half of rcnn_transform_layer's weight gradient."""
     B, shot, way, R, Ns = ctx["B"], ctx["shot"], ctx["way"], ctx["R"], ctx["Ns"]
     P2, n_roi, dq, rd, ug = 49, B * R, model.rcnn_reduce_dim, model.rcnn_dim, model.unary_gamma
     q2, sp_pe, k2, un2, K2p = ctx["q2"], ctx["sp_pe"], ctx["k2"], ctx["un2"], ctx["K2p"]
@@ -578,7 +630,7 @@ def _roi_heads_backward(model, ctx, grads, d_scores, g3):
     nhid = w1.size(0)
     d_q2 = torch.zeros((n_roi * P2, dq), dtype=torch.float32, device=dev)
     d_trq = torch.zeros((n_roi * P2, rd), dtype=torch.float32, device=dev)
-    d_sp_pe = torch.zeros((Ns * P2, 1024), dtype=torch.float32, device=dev)
+    d_sp_pe = torch.zeros((Ns * P2, 1024), dtype=torch.float32, device=dev) if ctx["t"] < 3 else None
     d_k2 = torch.zeros((Ns * P2, dq), dtype=torch.float32, device=dev)
     d_un2 = torch.zeros((Ns, P2), dtype=torch.float32, device=dev)
     d_wt = torch.zeros_like(wt)
@@ -608,26 +660,30 @@ def _roi_heads_backward(model, ctx, grads, d_scores, g3):
         d_qh = _attention_backward(d_att, vw, hc["sc2"], un2.view(-1)[off * P2:], q2, k2.view(-1)[off * P2 * dq:],
                                    val.view(-1)[off * P2 * vw:], B, R * P2, shot, P2, K2p, dq, ug, way * shot * P2 * dq,
                                    way * shot * P2 * vw, way * shot * P2, d_k2.view(-1)[off * P2 * dq:],
-                                   d_val.view(-1)[off * P2 * vw:], d_un2.view(-1)[off * P2:], vw=vw)
+                                   d_val.view(-1)[off * P2 * vw:] if d_val is not None else None,
+                                   d_un2.view(-1)[off * P2:], vw=vw)
         ops.axpy_rows_(d_q2, d_qh, n_roi * P2, dq)
     if d_sw is not None:
         # sw = sp_pe . Wt_a^T (once per support, both heads): d Wt_a = d_sw^T . sp_pe, d sp_pe += d_sw . Wt_a
         grads.linear(d_sw, sp_pe, Ns * P2, rd, 1024,
                      lambda dw, db: ops.axpy_rows_(d_wt.view(-1)[1024:], dw, rd, 1024, ld_y=2048))
-        ops.linear_backward(d_sw, sp_pe, wt.view(-1)[1024:], Ns * P2, rd, 1024, ldw=2048, dx_out=d_sp_pe, dx_ld=1024,
-                            need_dw=False)
+        if d_sp_pe is not None:
+            ops.linear_backward(d_sw, sp_pe, wt.view(-1)[1024:], Ns * P2, rd, 1024, ldw=2048, dx_out=d_sp_pe, dx_ld=1024,
+                                need_dw=False)
     return d_q2, d_trq, d_k2, d_un2, d_sp_pe, d_wt
 
 
 def _roi_query_backward(model, ctx, grads, d_q2, d_trq, d_wt):
     """RoI-level query side: Q projection + the q half of rcnn_transform_layer; PE is additive. -> d q_pe [n_roi*49][1024],
-    the heads' gradient into the pooled features"""
+    the heads' gradient into the pooled features (over a frozen trunk: the weight gradients only, -> None)"""
     rows, dq, rd, q_pe = ctx["B"] * ctx["R"] * 49, model.rcnn_reduce_dim, model.rcnn_dim, ctx["q_pe"]
     ops.colmean_sub_(d_q2, rows // 49, 49, dq)
     wq2 = model.rcnn_adapt_q_layer.weight.detach()
     grads.linear(d_q2, q_pe, rows, dq, 1024,
                  lambda dw, db: (acc(model.rcnn_adapt_q_layer.weight, dw), acc(model.rcnn_adapt_q_layer.bias, db)))
-    _, _, d_q_pe = ops.linear_backward(d_q2, q_pe, wq2, rows, dq, 1024, need_dw=False)
+    d_q_pe = None
+    if ctx["t"] < 3:
+        _, _, d_q_pe = ops.linear_backward(d_q2, q_pe, wq2, rows, dq, 1024, need_dw=False)
 
     def _transform_grads(dw, db):  # (both halves of rcnn_transform_layer's weight gradient are in d_wt now)
         ops.axpy_rows_(d_wt, dw, rd, 1024, ld_y=2048)
@@ -635,31 +691,38 @@ def _roi_query_backward(model, ctx, grads, d_q2, d_trq, d_wt):
         acc(model.rcnn_transform_layer.bias, db)
 
     grads.linear(d_trq, q_pe, rows, rd, 1024, _transform_grads)
-    ops.linear_backward(d_trq, q_pe, model.rcnn_transform_layer.weight.detach(), rows, rd, 1024, ldw=2048, dx_out=d_q_pe,
-                        dx_ld=1024, need_dw=False)
+    if d_q_pe is not None:
+        ops.linear_backward(d_trq, q_pe, model.rcnn_transform_layer.weight.detach(), rows, rd, 1024, ldw=2048,
+                            dx_out=d_q_pe, dx_ld=1024, need_dw=False)
     return d_q_pe
 
 
 def _roi_support_backward(model, ctx, grads, d_k2, d_un2, d_sp_pe):
     """RoI-level support side: K projection, unary term, PE, 14x14 average pool (dana.py:105-108,271-277)
-    -> d_sup [Ns][L][1024], the gradient into the support trunk's output"""
+    -> d_sup [Ns][L][1024], the gradient into the support trunk's output (d_sp_pe None, a frozen trunk: the weight
+    gradients only, -> None)"""
     Ns, P2, dq, sp_pe, un2 = ctx["Ns"], 49, model.rcnn_reduce_dim, ctx["sp_pe"], ctx["un2"]
     ops.colmean_sub_(d_k2, Ns, P2, dq)
     wk2 = model.rcnn_adapt_k_layer.weight.detach()
     grads.linear(d_k2, sp_pe, Ns * P2, dq, 1024,
                  lambda dw, db: (acc(model.rcnn_adapt_k_layer.weight, dw), acc(model.rcnn_adapt_k_layer.bias, db)))
-    ops.linear_backward(d_k2, sp_pe, wk2, Ns * P2, dq, 1024, dx_out=d_sp_pe, dx_ld=1024, need_dw=False)
+    if d_sp_pe is not None:
+        ops.linear_backward(d_k2, sp_pe, wk2, Ns * P2, dq, 1024, dx_out=d_sp_pe, dx_ld=1024, need_dw=False)
     ops.softmax_rows_backward_(d_un2, un2, Ns, P2)
     wu2 = model.rcnn_unary_layer.weight.detach()
     acc(model.rcnn_unary_layer.weight, ops.rowdot_backward(sp_pe, d_un2, wu2, Ns * P2, 1024, grad_x=d_sp_pe))
     acc(model.rcnn_unary_layer.bias, ops.colsum(d_un2, Ns * P2, 1))
+    if d_sp_pe is None:
+        return None
     (sh_, sw_), pool = ctx["sup_map"], ctx["sup_pool"]
     return ops.avgpool_backward(d_sp_pe, Ns, sh_, sw_, 1024, pool[0], pool[1])
 
 
 def trunk_backward(model, ctx, grads, gq, gs=None):
-    """The last stage of every model's backward: layer3, layer2 of the trunk (conv1, layer1 and every BN are frozen) from
-    gq = d base_feat and, if the model differentiates its supports, gs = d(support trunk output). Block by block for both
+    """The last stage of every model's backward: the trunk stages the forward saved, layer3 down to layer_t (ctx["t"]; conv1,
+    every BN and the stages in front of t are frozen; t = 3: nothing was saved, gq and gs are None and only the context is
+    released) from gq = d base_feat and, if the model differentiates its supports, gs = d(support trunk output). The first
+    saved block computes no input gradient: nothing in front of it trains. Block by block for both
     batches (shared weights), so that each block's weight gradient is final (and may be all-reduced) while the earlier
     blocks are differentiated; merged where the forward saved the [query | support] buffers. Releases the context."""
     qs, ss = ctx["q_saved"], ctx.get("s_saved") or []
@@ -703,6 +766,7 @@ def dana_backward_gen(model, grad_losses, ctx=None):
     on its layer4 stream and the RoI heads on the caller's, joined where they meet; one pause; then the trunk."""
     ctx, (g1, g2, g3, g4, g_dev), grads = begin(model, grad_losses, ctx)
     dev, main = ctx["corr"].device, ops.cur_stream()
+    trunk = ctx["t"] < 3  # a frozen trunk: no launch whose results only the trunk's backward would read (DESIGN.md)
     single = getattr(model, "_single_stream", False)
     capturing = torch.cuda.is_current_stream_capturing()
     rpnw_ready, l4w_ready, dgw_ready = _dgrad_weights_ready(model, ctx, dev)
@@ -723,7 +787,8 @@ def dana_backward_gen(model, grad_losses, ctx=None):
             grads_r = WeightGrads(None if capturing else model._stream("wgrad", dev), model)
             rpn_out = _rpn_chain(model, ctx, g1, g2, g_dev, grads_r, rpnw_ready)
             for t_ in rpn_out:
-                t_.record_stream(main)
+                if t_ is not None:
+                    t_.record_stream(main)
             rpn_done = ops.record_event()
 
     # -- seeds: d RCNN losses / d (scores, bbox_pred) were written by the fused loss kernel (dana_rcnn_loss);
@@ -737,13 +802,14 @@ def dana_backward_gen(model, grad_losses, ctx=None):
     #    from an already forked stream crashes hipStreamEndCapture on ROCm 7.2 -- tools/graph_debug.py modes 8 / 12 / 13) --
     l4_stream = main if (single or capturing) else model._stream("layer4", dev)
     seeds_ready = ops.record_event()
-    stages = grad_stages(model, ctx["plan"])
+    stages = grad_stages(model, ctx["plan"], ctx["t"])
     with ops.on_stream(l4_stream):
         l4_stream.wait_event(seeds_ready)
         if l4w_ready is not None:
             l4_stream.wait_event(l4w_ready)
         d_pooled = _box_branch_backward(model, ctx, grads, d_bbox, g4)  # [n_roi*49][1024]
-        d_pooled.record_stream(main)
+        if d_pooled is not None:
+            d_pooled.record_stream(main)
         grads.finish_all(model, "RCNN_top")
         ready(model, stages[0][1])
         box_done = ops.record_event()
@@ -752,8 +818,10 @@ def dana_backward_gen(model, grad_losses, ctx=None):
     d_q2, d_trq, d_k2, d_un2, d_sp_pe, d_wt = _roi_heads_backward(model, ctx, grads, (d_score_pos, d_score_neg), g3)
     d_q_pe = _roi_query_backward(model, ctx, grads, d_q2, d_trq, d_wt)
     main.wait_event(box_done)
-    ops.axpy_rows_(d_pooled, d_q_pe, d_q_pe.size(0), 1024)
-    d_bf = roi_features_backward(ctx, d_pooled)
+    d_bf = None
+    if trunk:
+        ops.axpy_rows_(d_pooled, d_q_pe, d_q_pe.size(0), 1024)
+        d_bf = roi_features_backward(ctx, d_pooled)
     d_sup = _roi_support_backward(model, ctx, grads, d_k2, d_un2, d_sp_pe)  # [Ns][L][1024]
     grads.join()  # (the heads' Linear weight / bias gradients were accumulated on the weight-gradient stream)
     ready(model, stages[1][1])
@@ -767,9 +835,10 @@ def dana_backward_gen(model, grad_losses, ctx=None):
     else:
         rpn_out = _rpn_chain(model, ctx, g1, g2, g_dev, grads, rpnw_ready)
     d_corr, d_s_pe = rpn_out
-    K1 = d_s_pe.size(1)  # shot * L rows per image
-    for b in range(ctx["B"]):  # the positive supports' PE-added maps (dana.py:103,130)
-        ops.axpy_rows_(d_sup.view(-1)[b * ctx["way"] * K1 * 1024:], d_s_pe[b], K1, 1024)
+    if trunk:
+        K1 = d_s_pe.size(1)  # shot * L rows per image
+        for b in range(ctx["B"]):  # the positive supports' PE-added maps (dana.py:103,130)
+            ops.axpy_rows_(d_sup.view(-1)[b * ctx["way"] * K1 * 1024:], d_s_pe[b], K1, 1024)
     grads.finish_all(model, "RCNN_rpn")
     ready(model, stages[2][1])
     if dgw_ready is not None:
@@ -777,6 +846,9 @@ def dana_backward_gen(model, grad_losses, ctx=None):
     yield "heads, RPN and attention done; trunk next"
 
     # -- trunk: the RoIAlign and the RPN paths meet in base_feat (the first half of corr's columns) --
+    if not trunk:
+        trunk_backward(model, ctx, grads, None)
+        return
     ops.axpy_rows_(d_corr, d_bf, d_bf.size(0), 1024, ld_y=2048)
     g = torch.empty_like(d_bf)
     ops.axpy_rows_(g, d_corr, d_bf.size(0), 1024, ld_x=2048, accumulate=False)
@@ -787,7 +859,8 @@ def dana_backward_gen(model, grad_losses, ctx=None):
 def sibling_rpn_backward(model, ctx, g1, g2, g_dev, grads, residual=None):
     """Adjoint of the siblings' RPN (rpn.py:58-115): RPN losses -> heads -> ReLU -> 3x3 conv, with the weight and bias
     gradients of the heads and of RPN_Conv. -> the gradient into the RPN's input [B*rfh*rfw][1024] (+ residual), in that
-    input's own geometry (fsod: the correlation map is smaller than base_feat); the model differentiates it from there."""
+    input's own geometry (fsod: the correlation map is smaller than base_feat); the model differentiates it from there.
+    Over a frozen trunk (ctx["t"] == 3) the conv's data gradient has no reader: not run, -> None."""
     plan, B, rpn, nh = ctx["plan"], ctx["B"], model.RCNN_rpn, ctx["nh"]
     d_heads = ops.rpn_loss_backward(ctx["rpn_heads"], nh, ctx["at"], ctx["rpn_l"], g1, g2, sigma=3.0,
                                     inside_weight=cfg.TRAIN.RPN_BBOX_INSIDE_WEIGHTS[0], grad_dev=g_dev)
@@ -803,6 +876,8 @@ def sibling_rpn_backward(model, ctx, g1, g2, g_dev, grads, residual=None):
     c_rpn = _rpn_conv_plan(model, ctx)
     grads.add_conv("RCNN_rpn.RPN_Conv", d_x, ctx["rpn_feat"], B, rfh, rfw, c_rpn)
     acc(rpn.RPN_Conv.bias, ops.colsum(d_x, B * rhw, 512))
+    if ctx["t"] == 3:
+        return None
     return conv_dgrad(d_x, B, rfh, rfw, c_rpn, residual=residual)
 
 

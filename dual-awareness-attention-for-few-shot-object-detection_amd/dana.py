@@ -670,14 +670,14 @@ class DAnARCNN(nn.Module):
         except StopIteration as done:
             return done.value
 
-    def _rcnn_base(self, im, plan, out_stride=0, out_buf=None, save=None):
+    def _rcnn_base(self, im, plan, out_stride=0, out_buf=None, save=None, save_from=1):
         """RCNN_base (dana.py:344-345) on NCHW input -> (NHWC flat buffer [n*h*w][out_stride or 1024], h, w).
-        out_buf: write the result there (row stride out_stride) instead of allocating."""
+        out_buf: write the result there (row stride out_stride) instead of allocating. save / save_from: see _trunk_gen."""
         x, ((_, (h, w), _, _),), _ = self._drain(self._trunk_gen(
-            [im], plan, outs=[(out_buf, out_stride)], saves=[save]))
+            [im], plan, outs=[(out_buf, out_stride)], saves=[save], save_from=save_from))
         return x, h, w
 
-    def _trunk_gen(self, ims, plan, outs=((None, 0),), saves=None, side=None, merge_from=None, save_m=None):
+    def _trunk_gen(self, ims, plan, outs=((None, 0),), saves=None, side=None, merge_from=None, save_m=None, save_from=1):
         """RCNN_base (dana.py:344-345) on one NCHW batch, or on the query batch AND the support batch (dana.py:98,100: the
         same weights) as two segments of one set of [query pixels | support pixels][channels] buffers
         -> (last block's o3, segments on its grid, per segment (the block's output, row stride)).
@@ -686,7 +686,9 @@ class DAnARCNN(nn.Module):
         the step's first launch on -- issued one after the other, the second trunk's first kernel reaches the GPU a
         millisecond of host time after the first's, and until then one stream of dependent launches has the chip to itself.
         outs: per batch (buffer, or None for a fresh one; row stride) of the last block's output; stride 0: dense, fresh.
-        saves: per batch a list that receives the per-block dicts of `_block` (layer1 is frozen: nothing from there).
+        saves: per batch a list that receives the per-block dicts of `_block` for the stages >= save_from, the saving
+        forward's ctx["t"] (backward.first_trainable_stage; 1: layer1 is frozen, 3: the whole trunk). The stages in front of it
+        are frozen: they issue the launches of a forward that saves nothing (layer1's fused conv2 + conv3 tail included).
         Two batches: stages >= `merge_from` (0: stem + layer1, 1: layer2, 2: layer3) issue ONE launch per conv over both
         -- the 1x1 / stride-1 convs see a plain GEMM over all rows, the strided / 3x3 / stem convs carry the two image
         geometries (`*_dual` entry points), the Winograd 3x3s run two input transforms, one batched plane GEMM over all
@@ -737,7 +739,7 @@ class DAnARCNN(nn.Module):
                 if stall is not None and not merged and li == stall[0]:
                     torch.cuda._sleep(int(stall[1]))
                 x, segs, dest = self._block(segs, x, bp, merged, outs=outs if last and outs[0][1] else None,
-                                            saves=saves if li > 0 else None, key="RCNN_base.%d.%d" % (4 + li, bi), alloc=alloc,
+                                            saves=saves if li >= save_from else None, key="RCNN_base.%d.%d" % (4 + li, bi), alloc=alloc,
                                             save_m=save_m)
                 if not last:
                     yield
@@ -980,7 +982,10 @@ class DAnARCNN(nn.Module):
             return bridge, None
         if align_only_for is not None and cfg.POOLING_MODE != "align":
             raise NotImplementedError("the HIP backward of %s covers POOLING_MODE 'align'" % align_only_for)
-        return bridge, {k: [] for k in lists}
+        # t, the first trainable trunk stage, is read off the parameters HERE, once per saving forward: what this forward
+        # saves and what its backward differentiates both follow ctx["t"], so the two cannot disagree
+        from . import backward as BW
+        return bridge, dict({k: [] for k in lists}, t=BW.first_trainable_stage(self))
 
     def _loss_bridge(self, dev, losses):
         """hand the four losses to autograd: loss.backward() runs the model's HIP backward (backward.model_backward)"""
@@ -994,9 +999,9 @@ class DAnARCNN(nn.Module):
         from . import backward as BW
         return BW.dana_backward_gen(self, grad_losses, ctx)
 
-    def _grad_stages(self, plan):
+    def _grad_stages(self, plan, t=None):
         from . import backward as BW
-        return BW.dana_grad_stages(self, plan)
+        return BW.dana_grad_stages(self, plan, t)
 
     @staticmethod
     def _support_batch(support_ims, B, way, shot):
@@ -1262,11 +1267,12 @@ class DAnARCNN(nn.Module):
             return corr, (fh, fw), sup
         sup_ims = self._support_batch(support_ims, B, f.way, shot)
         save_q, save_s = (ctx["q_saved"], ctx["s_saved"]) if ctx is not None else (None, None)
+        save_from = ctx["t"] if ctx is not None else 3
         sup_stream.wait_event(f.inputs_ready)
         if f.merge[0]:
             _, (q, s), ((corr, _), (sfeat, _)) = self._drain(self._trunk_gen(
                 [im_data, sup_ims], plan, outs=[(None, 2048), (None, 1024)], saves=[save_q, save_s], side=sup_stream,
-                merge_from=f.merge[1], save_m=ctx["m_saved"] if ctx is not None else None))
+                merge_from=f.merge[1], save_m=ctx["m_saved"] if ctx is not None else None, save_from=save_from))
             (fh, fw), (sh_, sw_) = q[1], s[1]
             trunk_done = ops.record_event()
             sup_stream.wait_event(trunk_done)
@@ -1275,8 +1281,8 @@ class DAnARCNN(nn.Module):
             if sup_stream != main:
                 # alternate issue, block by block: support trunk on its stream, query trunk on the caller's -- both streams
                 # have work from the step's first launch on, however slow the host is (8 ranks share one)
-                g_s = self._trunk_gen([sup_ims], plan, saves=[save_s])
-                g_q = self._trunk_gen([im_data], plan, outs=[(corr, 2048)], saves=[save_q])
+                g_s = self._trunk_gen([sup_ims], plan, saves=[save_s], save_from=save_from)
+                g_q = self._trunk_gen([im_data], plan, outs=[(corr, 2048)], saves=[save_q], save_from=save_from)
                 r_s = r_q = None
                 while r_s is None or r_q is None:
                     if r_q is None:
@@ -1292,8 +1298,8 @@ class DAnARCNN(nn.Module):
                                 r_s = done_.value
                 sfeat, ((_, (sh_, sw_), _, _),), _ = r_s
             else:  # (single-stream passes: bench.py's per-launch timing)
-                sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s)
-                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=save_q)
+                sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s, save_from=save_from)
+                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=save_q, save_from=save_from)
         self._check_support_map(sh_, sw_)
         f.mark("trunk (query + support)")
         with ops.on_stream(sup_stream):

@@ -91,7 +91,8 @@ class FGN(FasterRCNN):
         bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "heads"), align_only_for="fgn")
         self._ctx = None
         if cached is None:
-            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
+            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None,
+                                            save_from=ctx["t"] if ctx is not None else 3)  # [Ns*400][1024]
             if (sh_, sw_) != (20, 20):
                 raise RuntimeError("support images must be 320x320 (fgn.py:34-35: AvgPool2d(20) / AvgPool2d(14, 1) of a 20x20 map)")
             L = sh_ * sw_
@@ -174,10 +175,11 @@ class FGN(FasterRCNN):
     def _relation_head_backward(self, ctx, grads, g3, gs):
         """Adjoint of both `head` calls of the forward (fgn.py:145-165): Linear <- ReLU/BN2 <- conv2 <- ReLU/BN1 <- (support
         half + roi half) of conv1; bn1 / bn2 are ORDINARY BatchNorms in train mode: their adjoint goes through the batch
-        statistics. The support halves go into gs (d support trunk output); -> d pooled [n_roi*49][1024] through the roi half"""
+        statistics. The support halves go into gs (d support trunk output); -> d pooled [n_roi*49][1024] through the roi half.
+        gs None (a frozen trunk, ctx["t"] == 3): the data gradients of conv1's two halves have no reader and are not run -> None"""
         d_pos, d_neg, _ = ctx["loss_seeds"]
         B, R, lin_c, wl = ctx["B"], ctx["R"], self.RCNN_cls_score, ctx["wl"]
-        n_roi, dev = B * R, gs.device
+        n_roi, dev = B * R, ctx["pooled"].device
         for bn_ in (self.bn1, self.bn2):
             for p_ in (bn_.weight, bn_.bias):
                 if p_.grad is None:
@@ -212,27 +214,39 @@ class FGN(FasterRCNN):
             d_s_half = ops.spatial_mean(d_x1pre, B, R, 25 * 512)  # broadcast over the image's R rois: sum = R * mean
             d_s_half.mul_(float(R))
             acc_w1_half(ops.conv2d_wgrad(d_s_half, hc["support"], B, 7, 7, 1024, 512, 3, 3, 1, 0), 0)
-            d_support = ops.conv2d_dgrad(d_s_half, ctx["w1_sup"], B, 7, 7, 1024, 512, 3, 3, 1, 0)  # [B*49][1024]
-            BW.shot_mean_backward(gs, ops.avgpool_backward(d_support, B, 20, 20, 1024, 14, 1), ctx, hc["offset"])  # 14, 1
+            if gs is not None:
+                d_support = ops.conv2d_dgrad(d_s_half, ctx["w1_sup"], B, 7, 7, 1024, 512, 3, 3, 1, 0)  # [B*49][1024]
+                BW.shot_mean_backward(gs, ops.avgpool_backward(d_support, B, 20, 20, 1024, 14, 1), ctx, hc["offset"])  # 14, 1
         acc_w1_half(ops.conv2d_wgrad(d_roi_half, ctx["pooled"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0), 1024)
+        if gs is None:
+            return None
         return ops.conv2d_dgrad(d_roi_half, ctx["w1_roi"], n_roi, 7, 7, 1024, 512, 3, 3, 1, 0)
 
     def _backward(self, ctx, g, grads):
         """frcnn's adjoint with the relation head in place of the plain RCNN_cls_score and the channel re-weighting in front
-        of the RPN; the supports are differentiated through the trunk"""
+        of the RPN; the supports are differentiated through the trunk (where it trains: ctx["t"] < 3)"""
         g1, g2, g3, g4, g_dev = g
         B, n_roi, hw, L, d_bbox = ctx["B"], ctx["B"] * ctx["R"], ctx["fh"] * ctx["fw"], ctx["L"], ctx["loss_seeds"][2]
         d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g4)
-        gs = torch.zeros((ctx["Ns"] * L, 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
+        trunk = ctx["t"] < 3
+        gs = None
+        if trunk:
+            gs = torch.zeros((ctx["Ns"] * L, 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
         d_pooled_head = self._relation_head_backward(ctx, grads, g3, gs)
         BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
-        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads)
+        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads, need_dx=trunk)
         grads.finish_all(self, "RCNN_top")
         grads.finish_all(self, "cls_conv2")
-        ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the head's roi half
-        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
-        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        if trunk:
+            ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the head's roi half
+        BW.ready(self, self._grad_stages(ctx["plan"], ctx["t"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled) if trunk else None
         d_rfeat = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads)
+        if not trunk:  # frozen trunk: base_feat, the channel weights and the support maps have no trainable producer
+            grads.finish_all(self, "RCNN_rpn")
+            BW.ready(self, BW.RPN_PARAMS)
+            BW.trunk_backward(self, ctx, grads, None)
+            return
         # the RPN ran on base_feat * pos_rpn[image] (fgn.py:75-82): d base = d rfeat * pos_rpn + RoIAlign path, and
         # d pos_rpn[image] = sum over the pixels of d rfeat * base -> AvgPool2d(20) -> the positive supports' mean map
         gq = ops.scale_rows_by_group(d_rfeat, ctx["pos_rpn"], B * hw, hw, 1024)

@@ -120,7 +120,8 @@ class FasterRCNN(DAnARCNN):
         inputs_ready = ops.record_event()
         main = ops.cur_stream()
         # ctx (training): everything the model's `_backward` needs is saved into it
-        base, fh, fw = self._rcnn_base(im_data, plan, save=ctx["q_saved"] if ctx is not None else None)  # faster_rcnn.py:43
+        base, fh, fw = self._rcnn_base(im_data, plan, save=ctx["q_saved"] if ctx is not None else None,
+                                       save_from=ctx["t"] if ctx is not None else 3)  # faster_rcnn.py:43
         # -- RPN (rpn.py:58-115) on base_feat (or on the model's own RPN input) --
         rfeat, rh, rw = (base, fh, fw) if rpn_input is None else rpn_input(base, B, fh, fw, plan)
         base_hw = (fh, fw)
@@ -201,8 +202,9 @@ class FasterRCNN(DAnARCNN):
     # ---- training backward: backward.model_backward_gen / grad_stages dispatch to these through the class --------------
     _head_params = BW.lin("RCNN_cls_score")  # the RoI head's own trainable parameters (every sibling names its own)
 
-    def _grad_stages(self, plan):
-        return BW.sibling_grad_stages(plan, self._head_params)
+    def _grad_stages(self, plan, t=None):
+        """t None: read off the parameters (backward.first_trainable_stage); the backward passes its context's"""
+        return BW.sibling_grad_stages(plan, self._head_params, BW.first_trainable_stage(self) if t is None else t)
 
     def _backward_gen(self, grad_losses, ctx=None):
         """(DAnARCNN._backward_gen's generator contract; a sibling's backward, `_backward`, never pauses.) g = (g1, g2, g3, g4,
@@ -223,13 +225,16 @@ class FasterRCNN(DAnARCNN):
 
     def _backward_below_fc7(self, ctx, g, grads, d_bbox, d_fc7, gs=None):
         """what frcnn and meta share below the RoI head: mean <- layer4 <- RoIAlign, RPN losses <- heads <- 3x3 conv, both into
-        base_feat, then layer3 / layer2 of the trunk for the query batch and (meta: gs) the support batch"""
+        base_feat, then the trainable stages of the trunk (ctx["t"]) for the query batch and (meta: gs) the support batch.
+        Over a frozen trunk (t = 3) neither layer4's input gradient, the RoIAlign adjoint nor the RPN conv's data gradient
+        is run: nothing would read them"""
         g1, g2, _, g4, g_dev = g
+        trunk = ctx["t"] < 3
         BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
-        d_pooled = BW.layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads)
+        d_pooled = BW.layer4_backward(d_fc7, ctx["B"] * ctx["R"], ctx["l4_saved"], grads, need_dx=trunk)
         grads.finish_all(self, "RCNN_top")
-        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
-        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        BW.ready(self, self._grad_stages(ctx["plan"], ctx["t"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled) if trunk else None
         gq = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads, residual=d_bf)  # d base_feat = RPN + RoIAlign paths
         grads.finish_all(self, "RCNN_rpn")
         BW.ready(self, BW.RPN_PARAMS)
@@ -299,7 +304,8 @@ class MetaRCNN(FasterRCNN):
         # PRN (meta.py:241-251) on every support image
         sup_ims = self._support_batch(support_ims, B, way, shot)
         Ns = sup_ims.size(0)
-        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)
+        sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None,
+                                        save_from=ctx["t"] if ctx is not None else 3)
         mp, mh, mw = ops.maxpool2x2s2(sup, Ns, sh_, sw_, 1024)
         att = ops.sigmoid_(self._head_to_tail(mp, Ns, mh, mw, plan, save=ctx["sl4_saved"] if ctx is not None else None))
         wb, bb = self._w(self.RCNN_bbox_pred)
@@ -355,9 +361,11 @@ class MetaRCNN(FasterRCNN):
             d_vec = (d_comb * fc7).view(B, R, 2048).sum(1) / shot
             d_att[:, hc["offset"]:hc["offset"] + shot] += d_vec.unsqueeze(1)
         d_pre = (d_att.view(Ns, 2048) * att * (1.0 - att)).contiguous()  # sigmoid adjoint (meta.py:250)
-        d_mp = BW.layer4_backward(d_pre, Ns, ctx["sl4_saved"], grads)
-        # 2x2 / 2 max pool (meta.py:247) back onto the support maps: the window's (first) maximum takes the gradient
-        (sh_, sw_), (mh, mw) = ctx["sup_hw"], ctx["mp_hw"]
-        gs = ops.maxpool2x2s2_backward(ctx["sup"].view(Ns * sh_ * sw_, 1024), d_mp.contiguous().view(Ns * mh * mw, 1024), Ns,
-                                       sh_, sw_, 1024)
+        d_mp = BW.layer4_backward(d_pre, Ns, ctx["sl4_saved"], grads, need_dx=ctx["t"] < 3)
+        gs = None
+        if d_mp is not None:  # (None: the trunk is frozen, the support maps' gradient has no reader)
+            # 2x2 / 2 max pool (meta.py:247) back onto the support maps: the window's (first) maximum takes the gradient
+            (sh_, sw_), (mh, mw) = ctx["sup_hw"], ctx["mp_hw"]
+            gs = ops.maxpool2x2s2_backward(ctx["sup"].view(Ns * sh_ * sw_, 1024), d_mp.contiguous().view(Ns * mh * mw, 1024),
+                                           Ns, sh_, sw_, 1024)
         self._backward_below_fc7(ctx, g, grads, d_bbox, d_fc7, gs)

@@ -102,7 +102,8 @@ class FSOD(FasterRCNN):
         bridge, ctx = self._saving_ctx(("q_saved", "l4_saved", "s_saved", "heads"), align_only_for="fsod")
         self._ctx = None
         if cached is None:
-            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None)  # [Ns*400][1024]
+            sup, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=ctx["s_saved"] if ctx is not None else None,
+                                            save_from=ctx["t"] if ctx is not None else 3)  # [Ns*400][1024]
             if (sh_, sw_) != (20, 20):
                 raise RuntimeError("support images must be 320x320 (fsod.py:44: AvgPool2d(14) of a 20x20 map -> 7x7)")
             L = sh_ * sw_
@@ -195,20 +196,23 @@ class FSOD(FasterRCNN):
     def _relation_heads_backward(self, ctx, grads, a3):
         """Adjoint of both `head` calls of the forward (fsod.py:181-249): score = (global + local-correlation + patch) / 10
         for the positive and the negative support (a3 = g3 / 10); every [roi | support] concatenation is a split layer (roi
-        half + support half). -> (d pooled [n_roi*49][1024] through the roi halves, {offset: d support [B*49][1024]})"""
+        half + support half). -> (d pooled [n_roi*49][1024] through the roi halves, {offset: d support [B*49][1024]}).
+        Over a frozen trunk (ctx["t"] == 3) both results have no reader: their buffers are not made and every launch that
+        only writes into them (the Linears' data gradients -- linear_backward(need_dx=False) --, the global relation's
+        support half, the roi halves' broadcast) is not issued; the weight gradients stay -> (None, {})"""
         d_pos, d_neg, _ = ctx["loss_seeds"]
         B, R = ctx["B"], ctx["R"]
         n_roi, P2, d, dq_ = B * R, 49, 1024, 256
         pooled, g_roi, corr_roi = ctx["pooled"], ctx["g_roi"], ctx["corr_roi"]
-        dev = pooled.device
+        dev, trunk = pooled.device, ctx["t"] < 3
         w1 = self.global_fc_1.weight.detach()
         w2 = self.global_fc_2.weight.detach()
         wcc = self.corr_conv.weight.detach().view(d, d).contiguous()
         wp1 = self.patch_conv_1.weight.detach().view(dq_, 2 * d).contiguous()
         wp3 = self.patch_conv_3.weight.detach().view(d, dq_).contiguous()
         c_p2 = dict(cin=dq_, cout=dq_, k=3, stride=1, pad=0, w=ctx["wp2"], scale=None, u=None)
-        d_pooled_head = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
-        d_g_roi = torch.zeros((n_roi, d), dtype=torch.float32, device=dev)
+        d_pooled_head = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev) if trunk else None
+        d_g_roi = torch.zeros((n_roi, d), dtype=torch.float32, device=dev) if trunk else None
         d_corr_roi = torch.zeros((n_roi * P2, d), dtype=torch.float32, device=dev)
         d_w1 = torch.zeros((d, 2 * d), dtype=torch.float32, device=dev)
         d_wp1 = torch.zeros((dq_, 2 * d), dtype=torch.float32, device=dev)
@@ -217,7 +221,7 @@ class FSOD(FasterRCNN):
         for hc in ctx["heads"]:
             ds = (d_pos if hc["offset"] == 0 else d_neg)
             support = hc["support"]
-            d_support = torch.zeros((B * P2, d), dtype=torch.float32, device=dev)
+            d_support = torch.zeros((B * P2, d), dtype=torch.float32, device=dev) if trunk else None
             # .. global relation: Linear(2) <- relu fc2 <- relu fc1([mean(roi) | mean(support)])
             BW.seed_linear_grads(self.global_cls_score, ds, hc["h2"], a3)
             d_h2 = BW.seed_linear_dx(self.global_cls_score, ds, a3)
@@ -226,15 +230,16 @@ class FSOD(FasterRCNN):
             BW.acc(self.global_fc_2.weight, dw2)
             BW.acc(self.global_fc_2.bias, db2)
             ops.relu_mask_(d_h1, hc["h1"], n_roi, d)
-            dw1r, db1, _ = ops.linear_backward(d_h1, g_roi, w1, n_roi, d, d, ldw=2 * d, dx_out=d_g_roi, dx_ld=d)
+            dw1r, db1, _ = ops.linear_backward(d_h1, g_roi, w1, n_roi, d, d, ldw=2 * d, need_dx=trunk, dx_out=d_g_roi, dx_ld=d)
             ops.axpy_rows_(d_w1, dw1r, d, d, ld_y=2 * d)
             BW.acc(self.global_fc_1.bias, db1)
             d_gs = ops.spatial_mean(d_h1, B, R, d)  # the support half was broadcast over the image's R rois
             d_gs.mul_(float(R))
             dw1s = ops.gemm_small(d_gs, (1, d), hc["m_sup"], (d, 1), d, d, B)            # [d][d] = d_gs^T . mean(support)
             ops.axpy_rows_(d_w1.view(-1)[d:], dw1s, d, d, ld_y=2 * d)
-            d_m_sup = ops.gemm_small(d_gs, (d, 1), w1.view(-1)[d:], (2 * d, 1), B, d, d)  # [B][d] = d_gs . w1[:, d:]
-            ops.broadcast_rows(d_m_sup, B, P2, d, alpha=1.0 / P2, out=d_support)
+            if trunk:
+                d_m_sup = ops.gemm_small(d_gs, (d, 1), w1.view(-1)[d:], (2 * d, 1), B, d, d)  # [B][d] = d_gs . w1[:, d:]
+                ops.broadcast_rows(d_m_sup, B, P2, d, alpha=1.0 / P2, out=d_support)
             # .. local correlation: Linear(2) <- sum over the 49 positions of corr_conv(roi) * corr_conv(support)
             BW.seed_linear_grads(self.corr_cls_score, ds, hc["oc"], a3)
             d_oc = BW.seed_linear_dx(self.corr_cls_score, ds, a3)  # [n][1024] = a 1x1 output map
@@ -242,7 +247,7 @@ class FSOD(FasterRCNN):
                                                          maps_per_kernel=R)
             ops.axpy_rows_(d_corr_roi, g_feat, n_roi * P2, d)
             dwc_s, _, _ = ops.linear_backward(g_kern.view(B * P2, d), support.view(B * P2, d), wcc, B * P2, d, d,
-                                              dx_out=d_support, dx_ld=d)
+                                              need_dx=trunk, dx_out=d_support, dx_ld=d)
             ops.axpy_rows_(d_wcc, dwc_s, d, d)
             # .. patch relation: Linear(2) <- avgpool3 <- relu 1x1 <- relu 3x3 <- avgpool 3/1 <- relu 1x1([roi | support])
             BW.seed_linear_grads(self.patch_cls_score, ds, hc["x4"], a3)
@@ -257,40 +262,50 @@ class FSOD(FasterRCNN):
             d_x0 = ops.avgpool_backward(d_x1, n_roi, 7, 7, dq_, 3, 1).view(n_roi * P2, dq_)
             ops.relu_mask_(d_x0, hc["x0"], n_roi * P2, dq_)
             dwp1r, _, _ = ops.linear_backward(d_x0, pooled.view(n_roi * P2, d), wp1, n_roi * P2, dq_, d, ldw=2 * d,
-                                              dx_out=d_pooled_head, dx_ld=d)
+                                              need_dx=trunk, dx_out=d_pooled_head, dx_ld=d)
             ops.axpy_rows_(d_wp1, dwp1r, dq_, d, ld_y=2 * d)
             d_p_sup = ops.spatial_mean(d_x0, B, R, P2 * dq_)  # the support half was broadcast over the image's rois
             d_p_sup.mul_(float(R))
             dwp1s, _, _ = ops.linear_backward(d_p_sup.view(B * P2, dq_), support.view(B * P2, d), wp1.view(-1)[d:],
-                                              B * P2, dq_, d, ldw=2 * d, dx_out=d_support, dx_ld=d)
+                                              B * P2, dq_, d, ldw=2 * d, need_dx=trunk, dx_out=d_support, dx_ld=d)
             ops.axpy_rows_(d_wp1.view(-1)[d:], dwp1s, dq_, d, ld_y=2 * d)
             d_supports[hc["offset"]] = d_support
         # the roi halves shared by both heads: mean over the 49 positions, corr_conv(rois)
-        ops.broadcast_rows(d_g_roi, n_roi, P2, d, alpha=1.0 / P2, out=d_pooled_head)
+        if trunk:
+            ops.broadcast_rows(d_g_roi, n_roi, P2, d, alpha=1.0 / P2, out=d_pooled_head)
         dwc_r, _, _ = ops.linear_backward(d_corr_roi, pooled.view(n_roi * P2, d), wcc, n_roi * P2, d, d,
-                                          dx_out=d_pooled_head, dx_ld=d)
+                                          need_dx=trunk, dx_out=d_pooled_head, dx_ld=d)
         ops.axpy_rows_(d_wcc, dwc_r, d, d)
         BW.acc(self.global_fc_1.weight, d_w1)
         BW.acc(self.patch_conv_1.weight, d_wp1.view(dq_, 2 * d, 1, 1))
         BW.acc(self.corr_conv.weight, d_wcc.view(d, d, 1, 1))
-        return d_pooled_head, d_supports
+        return (d_pooled_head, d_supports) if trunk else (None, {})
 
     def _backward(self, ctx, g, grads):
         """frcnn's adjoint with the multi-relation head in place of RCNN_cls_score and the attention RPN's correlation in
-        front of the RPN; the supports are differentiated through the trunk"""
+        front of the RPN; the supports are differentiated through the trunk (where it trains: ctx["t"] < 3)"""
         g1, g2, g3, g4, g_dev = g
         B, n_roi, fh, fw, d_bbox = ctx["B"], ctx["B"] * ctx["R"], ctx["fh"], ctx["fw"], ctx["loss_seeds"][2]
+        trunk = ctx["t"] < 3
         d_fc7 = BW.seed_linear_dx(self.RCNN_bbox_pred, d_bbox, g4)
-        gs = torch.zeros((ctx["Ns"] * ctx["L"], 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
+        gs = None
+        if trunk:
+            gs = torch.zeros((ctx["Ns"] * ctx["L"], 1024), dtype=torch.float32, device=d_fc7.device)  # d(support trunk output)
         d_pooled_head, d_supports = self._relation_heads_backward(ctx, grads, g3 / 10.0)  # fsod.py:237: (sum of 3) / 10
         BW.seed_linear_grads(self.RCNN_bbox_pred, d_bbox, ctx["fc7"], g4)
-        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads)
+        d_pooled = BW.layer4_backward(d_fc7, n_roi, ctx["l4_saved"], grads, need_dx=trunk)
         grads.finish_all(self, "RCNN_top")
         grads.finish_all(self, "patch_conv_2")
-        ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the heads' roi halves
-        BW.ready(self, self._grad_stages(ctx["plan"])[0][1])
-        d_bf = BW.roi_features_backward(ctx, d_pooled)
+        if trunk:
+            ops.axpy_rows_(d_pooled, d_pooled_head, n_roi * 49, 1024)  # the pooled features also feed the heads' roi halves
+        BW.ready(self, self._grad_stages(ctx["plan"], ctx["t"])[0][1])
+        d_bf = BW.roi_features_backward(ctx, d_pooled) if trunk else None
         d_rfeat = BW.sibling_rpn_backward(self, ctx, g1, g2, g_dev, grads)
+        if not trunk:  # frozen trunk: base_feat, the correlation kernel and the support maps have no trainable producer
+            grads.finish_all(self, "RCNN_rpn")
+            BW.ready(self, BW.RPN_PARAMS)
+            BW.trunk_backward(self, ctx, grads, None)
+            return
         # attention RPN (fsod.py:109-116): the RPN ran on the depth-wise correlation of base_feat with the pooled positive
         # support -> d base = full correlation of d rfeat with that kernel + RoIAlign path; d kernel -> positive supports
         gq, d_pos_kernel = ops.depthwise_corr_backward(d_rfeat, ctx["base"], ctx["pos"], B, fh, fw, 1024, 7, 7)

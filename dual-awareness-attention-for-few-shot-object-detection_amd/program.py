@@ -496,7 +496,10 @@ class ProgramTrainer:
     device memory; `step()` refreshes it (`trainer.upload_hyper()`) in front of the first program. So
     `trainer.adjust_learning_rate` -- or any per-iteration schedule assigned to `trainer.lr` -- takes effect on the next
     `step()` with the same programs; `rerecord()` is only needed after what a recording really bakes in (shapes, cfg, mode,
-    momentum / weight decay / clip on-off).
+    momentum / weight decay / clip on-off, and which trunk stages train: a recorded step belongs to the first trainable
+    stage t it was recorded under -- cfg.RESNET.FIXED_BLOCKS at construction --, its launches save and differentiate the
+    stages >= t only; after changing a trunk parameter's requires_grad build a new Trainer, whose flat buffers hold what
+    trains, and `rerecord()`).
 
         pt = ProgramTrainer(trainer, *example_inputs)
         out = pt.step(*inputs)          # the model's 8-tuple (static tensors)"""

@@ -162,6 +162,13 @@ _ADAM_BETAS = (0.9, 0.999)  # torch.optim.Adam's defaults (train.py:84-85), as o
 
 
 class Trainer:
+    """The training iteration of the module docstring for DAnA and its siblings. Which trunk stages train is read off the
+    parameters' requires_grad, as the model's constructor set them from cfg.RESNET.FIXED_BLOCKS (0: layer1 trains too ..
+    3: the frozen-trunk fine-tuning stage; a freeze that is not a prefix of the trunk raises ValueError here, as in the
+    saving forward): the flat buffers hold the trainable parameters only, a frozen parameter keeps `.grad is None`, and
+    each step's forward saves -- and its backward differentiates -- the trainable stages alone. The buffers are laid
+    out once: after changing requires_grad build a new Trainer (and `rerecord()` a ProgramTrainer on it)."""
+
     def __init__(self, model, lr, momentum=None, weight_decay=None, double_bias=None, bias_decay=None,
                  process_group=None, bucket_bytes=32 << 20, optimizer="sgd", always_reduce=False, clip_norm=None):
         if optimizer not in ("sgd", "adam"):  # train.py:84-87
