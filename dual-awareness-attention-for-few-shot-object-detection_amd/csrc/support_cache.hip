@@ -106,7 +106,77 @@ gather_shot_blocks_kernel(const char* const* __restrict__ src, char* const* __re
   }
 }
 
+// Support bank (dana.SupportBank): the weight-independent support tensors of a pool of N images -- map_pe [N][L][C], the
+// trunk map + PE, and pool_pe [N][P][C], its average pool + PE -- are encoded once; a training iteration over a frozen trunk
+// names its B*way*shot supports by bank row. Slot s = (b, r), r = s % (way*shot), with n = index[s]:
+//   every slot    pool_pe[n] -> block s of sp_pe [B*way*shot][P][C]
+//   r < shot      map_pe[n]  -> block (b, r) of s_pe [B][shot*L][C]   (the positives come first: dana.py:103-104)
+// grid (gx, slots): workgroup row s walks the slot's 16-byte units, the P*C/4 of the pooled block first, then (positives)
+// the L*C/4 of the map block; a workgroup takes BANK_UNROLL * 256 consecutive units, each lane BANK_UNROLL of them 256
+// apart (all loads issued before the first store). Workgroups past a negative slot's pooled units leave at once.
+constexpr int BANK_UNROLL = 4;
+
+__global__ void __launch_bounds__(256)
+bank_gather_episode_kernel(const float4* __restrict__ map_pe, const float4* __restrict__ pool_pe,
+                           const int* __restrict__ index, int n_bank, int ws, int shot, long long map_units,
+                           long long pool_units, float4* __restrict__ s_pe, float4* __restrict__ sp_pe) {
+  const int s = blockIdx.y;
+  const int r = s % ws, b = s / ws;
+  const bool positive = r < shot;
+  const long long total = pool_units + (positive ? map_units : 0);
+  const long long u0 = (long long)blockIdx.x * (BANK_UNROLL * 256) + threadIdx.x;
+  if (u0 - threadIdx.x >= total) return;
+  const int n = index[s];
+  if (n < 0 || n >= n_bank) return;  // (validated on the host; never read outside the bank)
+  const float4* src_pool = pool_pe + (long long)n * pool_units;
+  const float4* src_map = map_pe + (long long)n * map_units;
+  float4* dst_pool = sp_pe + (long long)s * pool_units;
+  float4* dst_map = s_pe + ((long long)b * shot + r) * map_units;  // (read for positives only)
+  // (a unit past the slot's end reads the slot's last unit again, total >= 1 here, and stores nothing: the loads carry no
+  //  branch, so all BANK_UNROLL of them are in flight before the first store waits)
+  float4 v[BANK_UNROLL];
+#pragma unroll
+  for (int k = 0; k < BANK_UNROLL; ++k) {
+    const long long u = min(u0 + (long long)k * 256, total - 1);
+    const float4* src = u < pool_units ? src_pool + u : src_map + (u - pool_units);
+    v[k] = *src;
+  }
+  asm volatile("" ::: "memory");  // (keeps the compiler from sinking each load into its store's branch)
+#pragma unroll
+  for (int k = 0; k < BANK_UNROLL; ++k) {
+    const long long u = u0 + (long long)k * 256;
+    if (u < total) {
+      float4* dst = u < pool_units ? dst_pool + u : dst_map + (u - pool_units);
+      *dst = v[k];
+    }
+  }
+}
+
 extern "C" {
+
+int dana_bank_gather_episode(const float* map_pe, const float* pool_pe, const int* index, int n_bank, int B, int way,
+                             int shot, int map_rows, int pool_rows, int channels, float* s_pe, float* sp_pe,
+                             dana_stream_t stream) {
+  DANA_CHECK_ARG(n_bank >= 0 && B >= 0 && way >= 1 && shot >= 1 && map_rows >= 0 && pool_rows >= 0 && channels >= 4 &&
+                     channels % 4 == 0,
+                 "dana_bank_gather_episode: bad shape n_bank=%d B=%d way=%d shot=%d map_rows=%d pool_rows=%d channels=%d "
+                 "(channels a multiple of 4)", n_bank, B, way, shot, map_rows, pool_rows, channels);
+  const long long slots = (long long)B * way * shot;
+  DANA_CHECK_ARG(slots <= 65535, "dana_bank_gather_episode: B*way*shot = %lld support slots (at most 65535)", slots);
+  const long long map_units = (long long)map_rows * (channels / 4), pool_units = (long long)pool_rows * (channels / 4);
+  if (slots == 0 || map_units + pool_units == 0) return DANA_OK;
+  DANA_CHECK_ARG(map_pe && pool_pe && index && s_pe && sp_pe && n_bank > 0, "dana_bank_gather_episode: null pointer");
+  DANA_CHECK_ARG((((uintptr_t)map_pe | (uintptr_t)pool_pe | (uintptr_t)s_pe | (uintptr_t)sp_pe) & 15) == 0,
+                 "dana_bank_gather_episode: the four tensors must be 16-byte aligned");
+  const long long per_wg = (long long)BANK_UNROLL * 256;
+  const long long gx = (map_units + pool_units + per_wg - 1) / per_wg;
+  DANA_CHECK_ARG(gx <= 0x7fffffffLL, "dana_bank_gather_episode: %lld workgroups per slot", gx);
+  bank_gather_episode_kernel<<<dim3((unsigned)gx, (unsigned)slots), 256, 0, (hipStream_t)stream>>>(
+      (const float4*)map_pe, (const float4*)pool_pe, index, n_bank, way * shot, shot, map_units, pool_units, (float4*)s_pe,
+      (float4*)sp_pe);
+  DANA_CHECK_LAUNCH("dana_bank_gather_episode");
+  return DANA_OK;
+}
 
 int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* block_bytes, int n_tensors,
                        const int* index, int n_sets, int B, dana_stream_t stream) {

@@ -771,11 +771,16 @@ class DAnARCNN(nn.Module):
         """RPN-level support side (dana.py:126-145) on `stream` (the current one): PE, BA block, K projection + column mean,
         unary term + softmax, S^T of the positive supports of B images -> (s_pe, kp [B*shot*L][d], unary [B*shot][L],
         s_t [B][1024][shot*L])"""
-        d = self.rpn_reduce_dim
-        K1 = shot * L
         s_pe = torch.empty((B, shot * L, 1024), dtype=torch.float32, device=dev)
         # positives = the first `shot` supports of each image (dana.py:103), way * shot maps apart: one launch
         ops.add_pe_groups(sup, self._pe_table(L, dev), B, shot * L, L, 1024, way * shot * L * 1024, s_pe)
+        return self._support_rpn_chain(s_pe, B, shot, L, dev, stream, ctx, branch)
+
+    def _support_rpn_chain(self, s_pe, B, shot, L, dev, stream, ctx=None, branch=True):
+        """`_support_rpn_side` from the PE-added maps of the positive supports on, s_pe [B][shot*L][1024] (written by the
+        line above, or gathered from a SupportBank; the BA block rewrites it in place) -> (s_pe, kp, unary, s_t)"""
+        d = self.rpn_reduce_dim
+        K1 = shot * L
         if self.semantic_enhance:  # BA block (dana.py:133-137)
             wc, bc = self._w(self.rpn_channel_k_layer)
             wgt = ops.rowdot(s_pe, wc, bc, B * shot * L, 1024)
@@ -818,15 +823,26 @@ class DAnARCNN(nn.Module):
         unary projections once per support (the reference recomputes them for every RoI), and the folded S.Wt^T table ->
         (sp_pe [Ns*49][1024], k2 [Ns*49][dq], un2 [Ns][49], sw [Ns*49][64] or None, pool)"""
         P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
-        dq = self.rcnn_reduce_dim
-        if (sh_, sw_) == (20, 20):
-            pool = (14, 1)  # nn.AvgPool2d(14, stride=1) (dana.py:42): 20x20 -> 7x7
-        else:
-            if sh_ != sw_:
-                raise RuntimeError("generalised supports must be square")
-            pool = (sh_ // 7, sh_ // 7)
+        pool = self._support_pool(sh_, sw_)
         sp = ops.avgpool(sup, Ns, sh_, sw_, 1024, pool[0], pool[1])  # [Ns][49][1024]
         sp_pe = ops.add_pe(sp, plan["pe49"], Ns * P2, P2, 1024)
+        k2, un2, sw = self._support_roi_chain(sp_pe, Ns, product, ctx)
+        return sp_pe, k2, un2, sw, pool
+
+    @staticmethod
+    def _support_pool(sh_, sw_):
+        """(window, stride) of the average pool that takes a support map to 7x7"""
+        if (sh_, sw_) == (20, 20):
+            return (14, 1)  # nn.AvgPool2d(14, stride=1) (dana.py:42): 20x20 -> 7x7
+        if sh_ != sw_:
+            raise RuntimeError("generalised supports must be square")
+        return (sh_ // 7, sh_ // 7)
+
+    def _support_roi_chain(self, sp_pe, Ns, product, ctx=None):
+        """`_support_roi_side` from the pooled, PE-added supports on, sp_pe [Ns*49][1024] (written by the lines above, or
+        gathered from a SupportBank; read only) -> (k2, un2, sw or None)"""
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        dq = self.rcnn_reduce_dim
         _, bk2 = self._w(self.rcnn_adapt_k_layer)
         k2b3, k2ld = self._lin_b(self.rcnn_adapt_k_layer)
         k2 = ops.gemm_nt(sp_pe, k2b3, Ns * P2, dq, 1024, ldb=k2ld, shift=bk2)
@@ -846,7 +862,7 @@ class DAnARCNN(nn.Module):
             sw = ops.gemm_nt(sp_pe, wt_a_s, Ns * P2, self.rcnn_dim, 1024, ldb=wt_a_s_ld)  # [Ns*49][64]
             if ctx is not None:
                 ctx["sw"] = sw
-        return sp_pe, k2, un2, sw, pool
+        return k2, un2, sw
 
     def _rpn_split_plan(self, plan):
         """the RPN conv's filters split by input channels (W[:, :1024] on base_feat, W[:, 1024:] on the attended rows),
@@ -970,6 +986,55 @@ class DAnARCNN(nn.Module):
             tensors = {k: (None if per_set[0][k] is None else torch.stack([p_[k].reshape(-1) for p_ in per_set]))
                        for k in self._cache_layout(shot, (sh_, sw_))}
         return SupportCache(self, tensors, shot, (sh_, sw_), pool, self._cache_state(dev), dev, counts=counts)
+
+    # ---- support bank: fine-tuning over a frozen trunk from encoded support maps ---------------------------------
+    _no_support_bank = None  # a sibling detector says here why it has none (frcnn.py)
+
+    def _bank_state(self, dev):
+        """what a SupportBank's tensors depend on besides the pool images: the trunk's parameters and buffers (nothing
+        behind RCNN_base enters a bank row, so the layers that train may move), the contraction settings, the device"""
+        cached = self._consts.get("bank_tensors")
+        if cached is None or cached[0] != str(dev):  # (module.to(device) swaps buffers: re-collect, as _sig does)
+            cached = self._consts["bank_tensors"] = (str(dev), list(self.RCNN_base.state_dict(keep_vars=True).values()))
+        return (str(dev), self.use_winograd, self.winograd_min_cin, self.winograd_tile, ops.get_mfma_mode(),
+                self.presplit_weights) + tuple(t._version for t in cached[1])
+
+    def encode_support_bank(self, images, chunk=None):
+        """images [N, 3, 320, 320] (the support pool of a fine-tuning run: finetune_loader.py:59-74 keeps K exemplars per
+        novel class and samples from them) -> SupportBank: per pool image the two support-side tensors that depend on
+        frozen weights only, map_pe [N][L][1024] (trunk map + PE: what `_support_rpn_side` hands its chain) and pool_pe
+        [N][49][1024] (average pool + PE: what `_support_roi_side` hands its chain), from the kernels the forward uses.
+        The trunk runs `chunk` images at a time (default 16) through the launches of a forward that saves nothing, under
+        no_grad, in train or eval mode (the trunk's BatchNorms are frozen in both). A train-mode forward over a frozen trunk
+        (cfg.RESNET.FIXED_BLOCKS = 3) then takes `bank.episode(index)` in place of support images and runs the query trunk
+        only."""
+        if self._no_support_bank is not None:
+            raise NotImplementedError("encode_support_bank: " + self._no_support_bank)
+        if not torch.is_tensor(images) or images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
+            raise ValueError("encode_support_bank: images must be [N, 3, S, S] with N >= 1, got %s"
+                             % (tuple(images.shape) if torch.is_tensor(images) else type(images)))
+        if not images.is_cuda:
+            raise RuntimeError("images must be a CUDA (HIP) tensor: this build has no CPU path")
+        N, dev = images.size(0), images.device
+        chunk = min(N, 16) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("encode_support_bank: chunk must be >= 1, got %d" % chunk)
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        sh_, sw_ = self._feat_size(images.size(2), images.size(3))
+        self._check_support_map(sh_, sw_)
+        L, pool = sh_ * sw_, self._support_pool(sh_, sw_)
+        with torch.no_grad():
+            plan = self._get_plan()
+            map_pe = torch.empty((N, L, 1024), dtype=torch.float32, device=dev)
+            pool_pe = torch.empty((N, P2, 1024), dtype=torch.float32, device=dev)
+            for n0 in range(0, N, chunk):
+                ims = images[n0:n0 + chunk].float().contiguous()
+                c = ims.size(0)
+                sup, _, _ = self._rcnn_base(ims, plan)
+                ops.add_pe_groups(sup, self._pe_table(L, dev), c, L, L, 1024, L * 1024, map_pe[n0:n0 + c])
+                sp = ops.avgpool(sup, c, sh_, sw_, 1024, pool[0], pool[1])
+                ops.add_pe(sp, plan["pe49"], c * P2, P2, 1024, out=pool_pe[n0:n0 + c])
+        return SupportBank(self, map_pe, pool_pe, (sh_, sw_), pool, self._bank_state(dev), dev)
 
     # ---- stages shared with the sibling detectors (frcnn.py, fgn.py, fsod.py) ------------------------------------
     def _saving_ctx(self, lists, align_only_for=None):
@@ -1146,13 +1211,25 @@ class DAnARCNN(nn.Module):
                 raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
                                    "support side from support images")
             cache._check(self, dev)
+        # a BankEpisode (bank.episode(index)): a training iteration over a frozen trunk names its supports by bank row
+        episode = support_ims if isinstance(support_ims, BankEpisode) else None
+        if episode is not None:
+            if not training:
+                raise RuntimeError("a SupportBank episode serves train-mode forwards over a frozen trunk; for inference "
+                                   "encode the support sets with model.encode_supports and pass the SupportCache")
+            from . import backward as BW
+            if BW.first_trainable_stage(self) != 3:
+                raise ValueError("a SupportBank episode needs every trunk stage frozen (build the model under "
+                                 "cfg.RESNET.FIXED_BLOCKS = 3): a bank row is a constant of the run only while layer1-3 do "
+                                 "not train, and no support-map gradient can flow into a bank")
+            episode._check(self, dev, im_data.size(0))
         if sweep is not None and cfg.POOLING_MODE != "align":
             raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
                                       "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
         B = im_data.size(0)
         Cs = len(sweep) if sweep is not None else 1
-        f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, B=B, Cs=Cs,
+        f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, episode=episode, B=B, Cs=Cs,
                             NP=B * Cs,  # problems: the RPN stage from the attention on and the RoI stage run over them
                             im_info=im_info.data.float().contiguous(), gt_boxes=gt_boxes.data, shot=self.n_shot,
                             way=self.n_way if training else 1,  # eval reshapes supports as [*, n_shot] (dana.py:111)
@@ -1265,6 +1342,28 @@ class DAnARCNN(nn.Module):
             self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
             f.mark("trunk (query + support)")
             return corr, (fh, fw), sup
+        if f.episode is not None:
+            # a bank episode (encode_support_bank): the support trunk, the positives' PE launch, the average pool and its PE
+            # are constants of a run over a frozen trunk. ONE launch gathers the episode's rows into s_pe / sp_pe and the
+            # support stream goes on at the BA block; the query trunk runs alone, whatever the merge settings say (there
+            # is no support batch to merge with), and saves nothing (ctx["t"] == 3)
+            bank = f.episode.bank
+            (sh_, sw_), Ns = bank.sup_map, B * f.way * shot
+            sup_stream.wait_event(f.inputs_ready)
+            with ops.on_stream(sup_stream):
+                s_pe, sp_pe = f.episode._gather(shot)
+                s_pe, kp, unary, s_t = self._support_rpn_chain(s_pe, B, shot, sh_ * sw_, dev, sup_stream, ctx)
+                for t_ in (kp, unary, s_t):
+                    t_.record_stream(main)
+                rpn_done = ops.record_event()
+                if ctx is not None:
+                    ctx.update(s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
+            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
+            self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None,
+                            save_from=ctx["t"] if ctx is not None else 3)
+            f.mark("trunk (query + support)")
+            return corr, (fh, fw), dict(feat=None, map=(sh_, sw_), kp=kp, unary=unary, s_t=s_t, rpn_done=rpn_done,
+                                        sp_pe=sp_pe)
         sup_ims = self._support_batch(support_ims, B, f.way, shot)
         save_q, save_s = (ctx["q_saved"], ctx["s_saved"]) if ctx is not None else (None, None)
         save_from = ctx["t"] if ctx is not None else 3
@@ -1392,7 +1491,12 @@ class DAnARCNN(nn.Module):
                 f.sup_stream.wait_event(proposals_start)
                 sh_, sw_ = sup["map"]
                 Ns = f.B * f.way * f.shot
-                sp_pe, k2, un2, sw, pool = self._support_roi_side(sup["feat"], Ns, sh_, sw_, f.plan, f.dev, f.product, ctx)
+                if f.episode is not None:  # (sp_pe came with the episode's gather: the chain starts at the K projection)
+                    sp_pe, pool = sup["sp_pe"], f.episode.bank.pool
+                    k2, un2, sw = self._support_roi_chain(sp_pe, Ns, f.product, ctx)
+                else:
+                    sp_pe, k2, un2, sw, pool = self._support_roi_side(sup["feat"], Ns, sh_, sw_, f.plan, f.dev, f.product,
+                                                                      ctx)
                 if sw is not None:
                     sw.record_stream(f.main)
                 for t_ in (sp_pe, k2, un2):
@@ -1931,3 +2035,128 @@ class ClassSweep:
 
     def __repr__(self):
         return "ClassSweep(%d sets: %s)" % (len(self.classes), list(self.classes))
+
+
+def resolve_bank_episode(index, n_bank, B, way, shot):
+    """The support rows of one training episode, host only (no device): index [B, way*shot] integers, row b the bank rows of
+    query image b's supports with its `shot` positives first (dana.py:103-104: the layout of support_ims) -> a C-contiguous
+    int32 array of that shape. Repeats are fine: one exemplar may be positive for one image and negative for another.
+    B None: any batch size >= 1. ValueError: a device tensor, a non-integer dtype, a wrong shape; IndexError: an entry
+    outside [0, n_bank)."""
+    if torch.is_tensor(index):
+        if index.is_cuda:
+            raise ValueError("a bank episode takes a host index (a numpy array, nested lists or a CPU tensor), not a device "
+                             "tensor: it is validated on the host and uploaded once")
+        index = index.numpy()
+    arr = np.asarray(index)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("a bank episode's index holds integers (bank rows), got dtype %s" % arr.dtype)
+    ws = int(way) * int(shot)
+    if arr.ndim != 2 or arr.shape[1] != ws or arr.shape[0] < 1 or (B is not None and arr.shape[0] != int(B)):
+        raise ValueError("a bank episode's index must be [%s, way*shot = %d] (per query image its %d positive supports, then "
+                         "the negatives), got %s" % ("B" if B is None else int(B), ws, int(shot), arr.shape))
+    bad = arr[(arr < 0) | (arr >= int(n_bank))]
+    if bad.size:
+        raise IndexError("bank episode: rows %s outside [0, %d)" % (sorted(set(int(v) for v in bad.reshape(-1)))[:8], int(n_bank)))
+    return np.array(arr, dtype=np.int32, order="C")  # (always a copy: the caller may go on writing its array)
+
+
+class SupportBank:
+    """The weight-independent support tensors of a pool of N images (DAnARCNN.encode_support_bank), for fine-tuning over a
+    frozen trunk (cfg.RESNET.FIXED_BLOCKS = 3): map_pe [N][L][1024], the trunk map + PE, and pool_pe [N][49][1024], its
+    average pool + PE -- everything on the support side in front of the first trained weight. (A SupportCache stores the
+    K / unary / S.Wt^T chain behind those weights, which is why it serves inference only.)
+    `ep = bank.episode(index)` names the B*way*shot supports of an iteration by bank row; `model(im_data, im_info, gt_boxes,
+    num_boxes, ep)` in train mode gathers them (one launch, dana_bank_gather_episode, index read on the device) and runs the
+    query trunk only; `ep.set(index)` names the next iteration's -- a recorded replay (program.ProgramTrainer) follows it.
+    The bank records what it was built under (the trunk's parameters and buffers, the MFMA and Winograd settings, the
+    device); using it after any of that changed raises ("re-encode")."""
+
+    def __init__(self, model, map_pe, pool_pe, sup_map, pool, state, dev):
+        self._model = weakref.ref(model)
+        self.map_pe, self.pool_pe = map_pe, pool_pe
+        self.sup_map, self.pool, self.device = tuple(sup_map), pool, torch.device(dev)
+        self._state = state
+        self._index = {}       # (B, way*shot) -> device int32 [B*way*shot]: what dana_bank_gather_episode reads
+        self._index_host = {}  # ... and what it holds
+
+    def __len__(self):
+        return self.map_pe.size(0)
+
+    def nbytes(self):
+        return sum(t.numel() * t.element_size() for t in (self.map_pe, self.pool_pe))
+
+    def _check(self, model, dev):
+        if self._model() is not model:
+            raise RuntimeError("this SupportBank was encoded by another model: re-encode the pool with this one")
+        if torch.device(dev) != self.device:
+            raise RuntimeError("this SupportBank lives on %s, the query on %s: re-encode the pool there" % (self.device, dev))
+        if model._bank_state(dev) != self._state:
+            raise RuntimeError("the model changed since encode_support_bank (the trunk's weights or buffers, the MFMA mode "
+                               "or the Winograd settings): re-encode the pool")
+
+    def episode(self, index):
+        """-> BankEpisode over index [B, way*shot] (`resolve_bank_episode`; way and shot are the model's)"""
+        return BankEpisode(self, index)
+
+    def _write_index(self, arr):
+        """arr into the device index of its shape (allocated once per shape: a recording points at it)"""
+        key = arr.shape
+        host = self._index_host.get(key)
+        if host is not None and np.array_equal(host, arr):
+            return
+        if SupportCache._active_recording():
+            raise RuntimeError("SupportBank: the episode changed inside a recording / capture: ep.set(index) before it")
+        if key not in self._index:
+            self._index[key] = torch.zeros((arr.size,), dtype=torch.int32, device=self.device)
+        # one asynchronous copy on the current stream, as Trainer.upload_hyper's: a pageable source would hold the host
+        # until the stream has drained, once per iteration. The pinned block comes from torch's host allocator, which
+        # does not hand it out again before the copy that read it has finished. The gather runs behind an event of this
+        # stream (the forward's inputs_ready), and every side stream of a step is joined before the next set()
+        staged = torch.empty((arr.size,), dtype=torch.int32, pin_memory=True)
+        staged.copy_(torch.from_numpy(arr).reshape(-1))
+        self._index[key].copy_(staged, non_blocking=True)
+        self._index_host[key] = arr.copy()
+
+
+class BankEpisode:
+    """SupportBank.episode(index): the 5th argument of a train-mode forward over a frozen trunk, in place of support_ims
+    [B, way*shot, 3, S, S] -- image b's supports are the bank rows index[b], positives first. The index lives in a device
+    buffer the bank owns (one per episode shape, shared by the bank's episodes of that shape: the forward uploads an
+    episode's index when the buffer holds another); `set(index)` rewrites it for the next iteration."""
+
+    __slots__ = ("bank", "B", "way", "shot", "_host")
+
+    def __init__(self, bank, index):
+        model = bank._model()
+        if model is None:
+            raise RuntimeError("the model of this SupportBank is gone")
+        self.bank, self.way, self.shot = bank, int(model.n_way), int(model.n_shot)
+        self._host = resolve_bank_episode(index, len(bank), None, self.way, self.shot)
+        self.B = self._host.shape[0]
+        bank._write_index(self._host)
+
+    def set(self, index):
+        """the supports of the next forwards (same shape), validated on the host and written into the device index"""
+        self._host = resolve_bank_episode(index, len(self.bank), self.B, self.way, self.shot)
+        self.bank._write_index(self._host)
+
+    @property
+    def index(self):
+        """the episode's host index [B, way*shot] (a copy)"""
+        return self._host.copy()
+
+    def _check(self, model, dev, B):
+        self.bank._check(model, dev)
+        if (self.way, self.shot) != (int(model.n_way), int(model.n_shot)):
+            raise RuntimeError("this episode was laid out for way %d, shot %d; the model now has way %d, shot %d: make a new "
+                               "one (bank.episode)" % (self.way, self.shot, model.n_way, model.n_shot))
+        if B != self.B:
+            raise RuntimeError("a bank episode of %d query images for a batch of %d" % (self.B, B))
+        self.bank._write_index(self._host)  # (a no-op unless another episode of this shape used the buffer since)
+
+    def _gather(self, shot):
+        """-> (s_pe [B][shot*L][1024], sp_pe [B*way*shot*49][1024]) of the episode, fresh buffers on the current stream,
+        written by ONE launch"""
+        bank = self.bank
+        return ops.bank_gather_episode(bank.map_pe, bank.pool_pe, bank._index[self._host.shape], self.B, self.way, shot)

@@ -62,6 +62,12 @@ class FasterRCNN(DAnARCNN):
     def _cache_shot_blocks(self, sup_map):
         return None
 
+    # a SupportBank holds what DAnA's support side reads in front of its first trained weight (trunk map + PE, its average
+    # pool + PE); the siblings encode their supports their own way (class vectors through layer4, correlation kernels ...)
+    _no_support_bank = ("the sibling detectors own their support encoders (meta's class vectors go through layer4, which "
+                        "trains; fsod and fgn pool their own kernels; the plain Faster R-CNN has no support branch), so "
+                        "DAnA's bank rows are not what their forwards read: train them from support images")
+
     def encode_supports(self, support_ims, num_shots=None):
         """support_ims [C, shot, 3, 320, 320] -> SupportCache of the model's per-set support tensors (`_cache_layout`),
         each set built by `_support_set` with the launches an uncached B = 1 eval forward issues for it. The forward takes

@@ -30,6 +30,14 @@ def _static_like(t):
     return t.detach().clone() if torch.is_tensor(t) else t
 
 
+def _refuse_bank_episode(who, inputs):
+    from .dana import BankEpisode
+    if any(isinstance(t, BankEpisode) for t in inputs):
+        raise NotImplementedError("%s does not capture a SupportBank episode (hipGraph capture of the frozen-trunk iteration "
+                                  "is unverified): replay it with program.ProgramTrainer(trainer, ..., ep), or run it "
+                                  "eagerly" % who)
+
+
 class GraphedDAnA:
     """model(*inputs) as hipGraph replays. Inputs are copied into static buffers (skipped when the caller passes the
     static buffers themselves: `runner.inputs`); outputs are static tensors, valid until the next call.
@@ -48,6 +56,7 @@ class GraphedDAnA:
         if any(isinstance(t, (SupportCache, ClassSweep)) for t in example_inputs):
             raise NotImplementedError("GraphedDAnA does not capture the cached-support forward (nor a class sweep): replay it with "
                                       "program.ProgramDAnA(model, ..., cache), or run it eagerly")
+        _refuse_bank_episode("GraphedDAnA", example_inputs)
         self.model = model
         self.inputs = [_static_like(t) for t in example_inputs]
         self.stream = torch.cuda.Stream(device=dev)
@@ -143,6 +152,7 @@ class GraphedTrainer:
         self.model = trainer.model
         if not hasattr(self.model, "_forward_gen"):
             raise RuntimeError("GraphedTrainer drives DAnARCNN (the siblings train eagerly)")
+        _refuse_bank_episode("GraphedTrainer", example_inputs)
         dev = example_inputs[0].device
         self.inputs = [_static_like(t) for t in example_inputs]
         self.stream = torch.cuda.Stream(device=dev)

@@ -1327,6 +1327,30 @@ def gather_shot_blocks(srcs, rows, blocks, index, view, m):
     return dsts, w
 
 
+def bank_gather_episode(map_pe, pool_pe, index, B, way, shot, s_pe=None, sp_pe=None):
+    """dana_bank_gather_episode: map_pe [N][L][C] and pool_pe [N][P][C] float32, index [B*way*shot] int32 on the device
+    -> (s_pe [B][shot*L][C]: the positives' map rows, sp_pe [B*way*shot*P][C]: every slot's pooled rows). s_pe / sp_pe:
+    write there instead of into fresh buffers (a slot whose index is outside [0, N) keeps what its blocks held)."""
+    _chk(map_pe, "map_pe")
+    _chk(pool_pe, "pool_pe")
+    _chk(index, "index", torch.int32)
+    if map_pe.dim() != 3 or pool_pe.dim() != 3 or pool_pe.size(0) != map_pe.size(0) or pool_pe.size(2) != map_pe.size(2):
+        raise ValueError("bank_gather_episode: map_pe [N][L][C] and pool_pe [N][P][C], got %s and %s"
+                         % (tuple(map_pe.shape), tuple(pool_pe.shape)))
+    (N, L, C), P, Ns = map_pe.shape, pool_pe.size(1), B * way * shot
+    if index.numel() != Ns:
+        raise ValueError("bank_gather_episode: %d indices for B*way*shot = %d support slots" % (index.numel(), Ns))
+    if s_pe is None:
+        s_pe = torch.empty((B, shot * L, C), dtype=torch.float32, device=map_pe.device)
+    if sp_pe is None:
+        sp_pe = torch.empty((Ns * P, C), dtype=torch.float32, device=map_pe.device)
+    if _chk(s_pe, "s_pe").numel() != B * shot * L * C or _chk(sp_pe, "sp_pe").numel() != Ns * P * C:
+        raise ValueError("bank_gather_episode: s_pe must hold [%d][%d][%d] and sp_pe [%d][%d] floats" % (B, shot * L, C, Ns * P, C))
+    lib().call("dana_bank_gather_episode", _p(map_pe), _p(pool_pe), _p(index), N, B, way, shot, L, P, C, _p(s_pe), _p(sp_pe),
+               _stream())
+    return s_pe, sp_pe
+
+
 def attn_softmax_unary_sweep(scores, out, unary, B, C, hw, nseg, length, ld_in, ld_out, kpad, unary_gamma, out_scale,
                              unary_stride=0):
     """class sweep: attn_softmax_unary_ over rows (b, i, c) of scores [B][hw][C][ld_in], written out of place to row

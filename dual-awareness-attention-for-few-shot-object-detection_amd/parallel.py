@@ -18,6 +18,12 @@ def shard_bounds(total, rank, world):
 
 def shard_episode(inputs, rank, world):
     """inputs = (im_data, im_info, gt_boxes, num_boxes, support_ims): slice dim 0 of each for `rank`."""
+    from .dana import BankEpisode
+    for t in inputs:
+        if isinstance(t, BankEpisode):
+            raise TypeError("shard_episode slices tensors; a SupportBank episode names rows of ONE device's bank and has no "
+                            "slice: every rank encodes its own bank (model.encode_support_bank) and draws the indices of "
+                            "its own share of the batch")
     b0, b1 = shard_bounds(inputs[0].size(0), rank, world)
     return tuple(t[b0:b1] for t in inputs)
 

@@ -363,6 +363,11 @@ def _class_sweep(inputs):
     return next((t for t in inputs if isinstance(t, ClassSweep)), None)
 
 
+def _bank_episode(inputs):
+    from .dana import BankEpisode
+    return next((t for t in inputs if isinstance(t, BankEpisode)), None)
+
+
 class ProgramDAnA:
     """model(*inputs) as launch-program replays (train or eval mode, host or device RNG): the eager forward's launches on
     the eager forward's streams, minus its Python. Inputs are copied into static buffers (skipped when the caller passes
@@ -510,6 +515,9 @@ class ProgramTrainer:
             raise RuntimeError("ProgramTrainer drives DAnARCNN (the siblings train eagerly)")
         dev = example_inputs[0].device
         self.inputs = [_static_like(t) for t in example_inputs]
+        # a BankEpisode in place of support_ims (dana.encode_support_bank): the programs point at the bank's tensors and at
+        # the device index of this episode's shape, which `ep.set(index)` rewrites between replays
+        self.episode = _bank_episode(example_inputs)
         snap = None
         if warmup > 0:  # eager warm-up iterations must not move the training trajectory (as in GraphedTrainer)
             import numpy as _np
@@ -622,7 +630,26 @@ class ProgramTrainer:
         # before this step's update: an eager forward that follows must re-derive them from the live weights
         self.model._epoch += 1
 
+    def _check_episode(self, inputs):
+        """a replay reads the recorded bank through the recorded index buffer: the caller's 5th argument must be an episode
+        of that bank and shape (its index of the moment is uploaded here if the buffer holds another episode's)"""
+        ep = _bank_episode(inputs)
+        if ep is None and self.episode is None:
+            return
+        if ep is None or self.episode is None:
+            raise RuntimeError("ProgramTrainer was recorded with %s and called with %s: re-record a runner for it" % (
+                "support images" if self.episode is None else "a bank episode",
+                "support images" if ep is None else "a bank episode"))
+        if ep.bank is not self.episode.bank:
+            raise RuntimeError("ProgramTrainer was recorded on an episode of another SupportBank (the programs point at "
+                               "that bank's tensors): re-record a runner for this one")
+        if ep._host.shape != self.episode._host.shape:
+            raise RuntimeError("ProgramTrainer was recorded on a bank episode of shape %s and called with %s: re-record a "
+                               "runner for it" % (self.episode._host.shape, ep._host.shape))
+        ep._check(self.model, self.inputs[0].device, self.inputs[0].size(0))  # (raises "re-encode" after a trunk change)
+
     def step(self, *inputs):
+        self._check_episode(inputs)
         for s, t in zip(self.inputs, inputs):
             if torch.is_tensor(t) and t is not s:
                 s.copy_(t, non_blocking=True)

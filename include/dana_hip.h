@@ -207,6 +207,16 @@ int dana_gather_blocks(const void* src_ptrs, const void* dst_ptrs, const long lo
 int dana_gather_shot_blocks(const void* src_ptrs, const void* dst_ptrs, const long long* rows, const long long* block_bytes,
                             int n_tensors, const int* index, const int* view, float* w, int n_sets, int shot, int m, int P,
                             dana_stream_t stream);
+/* Support bank (dana.SupportBank): the episode of a training iteration over a frozen trunk, gathered from the bank's two
+ * weight-independent tensors map_pe [n_bank][map_rows][channels] (trunk map + PE) and pool_pe [n_bank][pool_rows][channels]
+ * (average pool + PE). For every support slot s < B*way*shot with n = index[s]: pool_pe[n] -> block s of sp_pe
+ * [B*way*shot][pool_rows][channels]; and, when the slot is a positive (s % (way*shot) < shot), map_pe[n] -> block
+ * (b, j) = (s / (way*shot), s % (way*shot)) of s_pe [B][shot*map_rows][channels]. index [B*way*shot] is read on the device,
+ * so a recorded replay gathers the episode of the moment; an index outside [0, n_bank) writes nothing. One launch of 16-byte
+ * copies: channels % 4 == 0 and 16-byte aligned tensors; B*way*shot <= 65 535. */
+int dana_bank_gather_episode(const float* map_pe, const float* pool_pe, const int* index, int n_bank, int B, int way,
+                             int shot, int map_rows, int pool_rows, int channels, float* s_pe, float* sp_pe,
+                             dana_stream_t stream);
 
 /* ---- class sweep (dana.SupportCache.sweep): B query images x C cached support sets as B*C problems p = b*C + c, the
  * per-class forward of dana.py:87-220 for every class of an image (inference.py:70-140 fills all_boxes[j][i] with it).
