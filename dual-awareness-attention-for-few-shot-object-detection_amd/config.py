@@ -47,6 +47,7 @@ cfg = AttrDict(
     ANCHOR_SCALES=[4, 8, 16, 32],
     ANCHOR_RATIOS=[0.5, 1, 2],
     FEAT_STRIDE=[16],
+    PIXEL_MEANS=[[[102.9801, 115.9465, 122.7717]]],  # BGR (config.py:258): subtracted by the loaders, added back by attention.render
     CUDA=False,
     CROP_RESIZE_WITH_MAX_POOL=False,
     EXP_DIR="res50",

@@ -146,6 +146,10 @@ class _LossBridge(torch.autograd.Function):
 
 _HERE = contextlib.nullcontext()
 
+# the levels of DAnARCNN.attention_maps (attention.py). The default `levels` IS this tuple: a call that passes its own
+# names "ba" explicitly, and is told when the support form has no BA weights to show
+ATTENTION_LEVELS = ("ba", "rpn", "roi")
+
 
 def _on(stream):
     """`with` for the launches of a batch segment (DAnARCNN._conv): on its stream, or (None) on the current one"""
@@ -767,18 +771,19 @@ class DAnARCNN(nn.Module):
                                    "(dana.py:105); got a %dx%d map%s" % (sh_, sw_, "" if self.generalised_support else
                                    " (set model.generalised_support = True for maps whose sides are multiples of 7)"))
 
-    def _support_rpn_side(self, sup, B, shot, way, L, dev, stream, ctx=None, branch=True):
+    def _support_rpn_side(self, sup, B, shot, way, L, dev, stream, ctx=None, branch=True, tap=None):
         """RPN-level support side (dana.py:126-145) on `stream` (the current one): PE, BA block, K projection + column mean,
         unary term + softmax, S^T of the positive supports of B images -> (s_pe, kp [B*shot*L][d], unary [B*shot][L],
         s_t [B][1024][shot*L])"""
         s_pe = torch.empty((B, shot * L, 1024), dtype=torch.float32, device=dev)
         # positives = the first `shot` supports of each image (dana.py:103), way * shot maps apart: one launch
         ops.add_pe_groups(sup, self._pe_table(L, dev), B, shot * L, L, 1024, way * shot * L * 1024, s_pe)
-        return self._support_rpn_chain(s_pe, B, shot, L, dev, stream, ctx, branch)
+        return self._support_rpn_chain(s_pe, B, shot, L, dev, stream, ctx, branch, tap)
 
-    def _support_rpn_chain(self, s_pe, B, shot, L, dev, stream, ctx=None, branch=True):
+    def _support_rpn_chain(self, s_pe, B, shot, L, dev, stream, ctx=None, branch=True, tap=None):
         """`_support_rpn_side` from the PE-added maps of the positive supports on, s_pe [B][shot*L][1024] (written by the
-        line above, or gathered from a SupportBank; the BA block rewrites it in place) -> (s_pe, kp, unary, s_t)"""
+        line above, or gathered from a SupportBank; the BA block rewrites it in place) -> (s_pe, kp, unary, s_t).
+        tap: a dict that receives the BA block's weights, ba_w [B*shot][L] (attention_maps)"""
         d = self.rpn_reduce_dim
         K1 = shot * L
         if self.semantic_enhance:  # BA block (dana.py:133-137)
@@ -787,6 +792,8 @@ class DAnARCNN(nn.Module):
             ops.softmax_rows_(wgt, B * shot, L)
             if ctx is not None:
                 ctx.update(s_pre=s_pe.clone(), ba_w=wgt)
+            if tap is not None:
+                tap["ba_w"] = wgt
             ops.ba_apply_(s_pe, wgt, B * shot, L, 1024, gamma=self.channel_gamma, slope=0.01)
         # three independent consumers of the (BA-enhanced) support rows: K projection, unary term, S^T. The chain behind
         # the support trunk is latency-bound (small dependent launches, 0.24 ms of which the caller's stream WAITS 0.125:
@@ -1234,7 +1241,8 @@ class DAnARCNN(nn.Module):
                             im_info=im_info.data.float().contiguous(), gt_boxes=gt_boxes.data, shot=self.n_shot,
                             way=self.n_way if training else 1,  # eval reshapes supports as [*, n_shot] (dana.py:111)
                             product=self.attention_type == "product", inter=getattr(self, "_capture", None),
-                            seg_w=None)  # (per-problem segment scales of a cached forward over views of unequal length)
+                            seg_w=None,  # (per-problem segment scales of a cached forward over views of unequal length)
+                            maps=None)   # (attention_maps: the dict that receives the attention weights, unscaled)
         tl = getattr(self, "_timeline", None)  # optional host-side phase clock (debug)
         f.tick = (lambda label: tl.append((label, time.perf_counter()))) if tl is not None else (lambda label: None)
         f.tick("begin")
@@ -1403,8 +1411,8 @@ class DAnARCNN(nn.Module):
         f.mark("trunk (query + support)")
         with ops.on_stream(sup_stream):
             sfeat.record_stream(sup_stream)
-            s_pe, kp, unary, s_t = self._support_rpn_side(sfeat, B, shot, f.way, sh_ * sw_, dev, sup_stream, ctx)
-            for t_ in (kp, unary, s_t):
+            s_pe, kp, unary, s_t = self._support_rpn_side(sfeat, B, shot, f.way, sh_ * sw_, dev, sup_stream, ctx, tap=f.maps)
+            for t_ in (kp, unary, s_t) + ((f.maps["ba_w"],) if f.maps is not None and "ba_w" in f.maps else ()):
                 t_.record_stream(main)
             rpn_done = ops.record_event()
             if ctx is not None:
@@ -1420,6 +1428,9 @@ class DAnARCNN(nn.Module):
         L = sup["map"][0] * sup["map"][1]  # 20 x 20 = 400 for the reference's 320 x 320 supports (dana.py:105)
         K1 = f.shot * L
         kp, unary, s_t = sup["kp"], sup["unary"], sup["s_t"]
+        # attention_maps (f.maps): the per-shot weights themselves -- the same kernels with scale 1 (slot weights 1 / 0 over
+        # ragged views) instead of the 1 / shot that folds the mean over shots into them -- and no attended rows
+        scale, seg_w = self._attn_scale(f)
         _, bq = self._w(self.rpn_adapt_q_layer)
         qb3, qld = self._lin_b(self.rpn_adapt_q_layer)
         qp = ops.gemm_nt(corr, qb3, B * hw, d, 1024, lda=2048, ldb=qld, shift=bq)
@@ -1436,11 +1447,13 @@ class DAnARCNN(nn.Module):
             ops.gemm_nt(qp, kp, hw, Cs * K1, d, out=scores, ldc=Cs * K1, batch=B, batch_a=hw * d, batch_b=Cs * K1 * d,
                         batch_c=hw * Cs * K1, alpha=1.0 / math.sqrt(d))
             a_p = torch.empty((NP, hw, K1), dtype=torch.float32, device=dev)
-            if f.seg_w is not None:
-                ops.attn_softmax_unary_sweep_w(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, f.seg_w)
+            if seg_w is not None:
+                ops.attn_softmax_unary_sweep_w(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, seg_w)
             else:
-                ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma,
-                                             1.0 / f.shot)
+                ops.attn_softmax_unary_sweep(scores, a_p, unary, B, Cs, hw, f.shot, L, K1, K1, K1, self.unary_gamma, scale)
+            if f.maps is not None:
+                f.maps["rpn_w"] = a_p  # [NP][hw][shot*L]
+                return None
             att = torch.empty((NP * hw, 1024), dtype=torch.float32, device=dev)  # problem p's attended rows
             ops.gemm_nt(a_p, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=att, ldc=1024, batch=NP, batch_a=hw * K1,
                         batch_b=1024 * K1, batch_c=hw * 1024)
@@ -1450,10 +1463,13 @@ class DAnARCNN(nn.Module):
             scores = torch.empty((B, hw, K1), dtype=torch.float32, device=dev)
             ops.gemm_nt(qp, kp, hw, K1, d, out=scores, ldc=K1, batch=B, batch_a=hw * d, batch_b=K1 * d, batch_c=hw * K1,
                         alpha=1.0 / math.sqrt(d))
-            if f.seg_w is not None:
-                ops.attn_softmax_unary_w_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, f.seg_w)
+            if seg_w is not None:
+                ops.attn_softmax_unary_w_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, seg_w)
             else:
-                ops.attn_softmax_unary_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, 1.0 / f.shot)
+                ops.attn_softmax_unary_(scores, unary, B * hw, hw, f.shot, L, K1, K1, self.unary_gamma, scale)
+            if f.maps is not None:
+                f.maps["rpn_w"] = scores  # [B][hw][shot*L]
+                return None
             ops.gemm_nt(scores, s_t, hw, 1024, K1, lda=K1, ldb=K1, out=corr.view(-1)[1024:], ldc=2048, batch=B,
                         batch_a=hw * K1, batch_b=1024 * K1, batch_c=hw * 2048)
             if f.product:
@@ -1467,6 +1483,16 @@ class DAnARCNN(nn.Module):
             f.ctx.update(corr=corr, fh=fh, fw=fw, qp=qp, scores=scores)
         f.mark("rpn-level attention (incl. wait for support stream)")
         return att
+
+    @staticmethod
+    def _attn_scale(f):
+        """-> (scale, per-slot scales or None) of the attention softmax kernels: the forward's mean over shots (1 / shot, or a
+        ragged view's seg_w), or for attention_maps the weights as they are (1, or 1 on a real slot and 0 on a padded one)"""
+        if f.maps is None:
+            return 1.0 / f.shot, f.seg_w
+        if f.seg_w is not None and "slot_w" not in f.maps:
+            f.maps["slot_w"] = (f.seg_w > 0).to(torch.float32)
+        return 1.0, f.maps.get("slot_w")
 
     def _rpn_conv_stage(self, f, corr, att, fh, fw):
         """RPN_Conv + ReLU (rpn.py:58-63) of the NP problems -> [NP*hw][512]"""
@@ -1601,6 +1627,51 @@ class DAnARCNN(nn.Module):
             f.ctx["fc7"] = fc7
         return bbox_pred, l4_done
 
+    def _roi_query(self, f, pooled, q_pe, fold_pe, n_roi):
+        """RoI-level query projection (dana.py:259,268-270): Q of pooled + PE, column mean subtracted -> (q2, its row
+        stride, qt). fold_pe: qt [n*49][dq | 64] is the fused projection (Q and the q half of rcnn_transform_layer) with
+        the positional encoding folded in (_roi_query_fold) and q2 its first column block; else qt is None"""
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        dq, rd_ = self.rcnn_reduce_dim, self.rcnn_dim
+        _, bq2 = self._w(self.rcnn_adapt_q_layer)
+        if fold_pe:
+            wcat, wcat_ld, tfull = self._roi_query_fold(f.plan, n_roi, f.dev)
+            qld = dq + rd_
+            qt = ops.gemm_nt(pooled, wcat, n_roi * P2, qld, 1024, ldb=wcat_ld, residual=tfull, ldr=qld)  # [n*49][dq | 64]
+            q2 = qt.view(-1)
+            ops.colmean_sub_(q2, n_roi, P2, dq, ld=qld)
+            return q2, qld, qt
+        q2b3, q2ld = self._lin_b(self.rcnn_adapt_q_layer)
+        q2 = ops.gemm_nt(q_pe, q2b3, n_roi * P2, dq, 1024, ldb=q2ld, shift=bq2)
+        ops.colmean_sub_(q2, n_roi, P2, dq)
+        return q2, dq, None
+
+    def _roi_scores(self, f, q2, qld, kb, ub, R):
+        """RoI-level attention weights (dana.py:271-277) of the NP problems' R RoIs against `shot` supports' keys kb and
+        unary terms ub -> sc2 [NP][R*49][K2p]: per shot softmax + unary_gamma * unary, times the scale of `_attn_scale`;
+        columns shot*49 .. K2p - 1 zeroed"""
+        P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
+        NP, shot, way, dq = f.NP, f.shot, f.way, self.rcnn_reduce_dim
+        n_roi, K2 = NP * R, shot * P2
+        K2p = (K2 + 31) // 32 * 32
+        scale, seg_w = self._attn_scale(f)
+        sc2 = torch.empty((NP, R * P2, K2p), dtype=torch.float32, device=f.dev)
+        ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=NP, batch_a=R * P2 * qld,
+                    batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
+        if seg_w is not None:  # (eval, cached: way = 1, offset = 0)
+            ops.attn_softmax_unary_w_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, seg_w,
+                                      unary_batch_stride=way * shot * P2)
+        else:
+            ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, scale,
+                                    unary_batch_stride=way * shot * P2)
+        return sc2
+
+    def attention_maps(self, im_data, im_info, boxes, support, levels=ATTENTION_LEVELS):
+        """-> attention.AttentionMaps: where each box looks in its support shots (README "Attention Visualization"), from
+        the weights an eval forward of the same inputs computes. See attention.attention_maps."""
+        from . import attention
+        return attention.attention_maps(self, im_data, im_info, boxes, support, levels)
+
     def _roi_heads(self, f, pooled, q_pe, fold_pe, sup, rois, R, l4_done):
         """RoI-level CISA (dana.py:248-292) -> (prob_all, cls_prob, positive scores, negative scores or None)"""
         # Positive head on the caller's stream, negative head (training) on its own, joined with layer4's branch. Query
@@ -1612,18 +1683,7 @@ class DAnARCNN(nn.Module):
         dq, rd_ = self.rcnn_reduce_dim, self.rcnn_dim
         if sup["roi_done"] is not None:
             main.wait_event(sup["roi_done"])
-        _, bq2 = self._w(self.rcnn_adapt_q_layer)
-        if fold_pe:
-            wcat, wcat_ld, tfull = self._roi_query_fold(plan, n_roi, dev)
-            qld = dq + rd_
-            qt = ops.gemm_nt(pooled, wcat, n_roi * P2, qld, 1024, ldb=wcat_ld, residual=tfull, ldr=qld)  # [n*49][dq | 64]
-            q2 = qt.view(-1)
-            ops.colmean_sub_(q2, n_roi, P2, dq, ld=qld)
-        else:
-            qld = dq
-            q2b3, q2ld = self._lin_b(self.rcnn_adapt_q_layer)
-            q2 = ops.gemm_nt(q_pe, q2b3, n_roi * P2, dq, 1024, ldb=q2ld, shift=bq2)
-            ops.colmean_sub_(q2, n_roi, P2, dq)
+        q2, qld, qt = self._roi_query(f, pooled, q_pe, fold_pe, n_roi)
         K2 = shot * P2
         K2p = (K2 + 31) // 32 * 32
         _, bt_ = self._w(self.rcnn_transform_layer)
@@ -1650,15 +1710,7 @@ class DAnARCNN(nn.Module):
         def head(offset):  # offset 0: positive supports, `shot`: negatives (dana.py:189-190)
             kb = k2.view(-1)[offset * P2 * dq:]
             ub = un2.view(-1)[offset * P2:]
-            sc2 = torch.empty((NP, R * P2, K2p), dtype=torch.float32, device=dev)
-            ops.gemm_nt(q2, kb, R * P2, K2, dq, lda=qld, out=sc2, ldc=K2p, batch=NP, batch_a=R * P2 * qld,
-                        batch_b=way * shot * P2 * dq, batch_c=R * P2 * K2p, alpha=1.0 / math.sqrt(dq))
-            if f.seg_w is not None:  # (eval, cached: way = 1, offset = 0)
-                ops.attn_softmax_unary_w_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, f.seg_w,
-                                          unary_batch_stride=way * shot * P2)
-            else:
-                ops.attn_softmax_unary_(sc2, ub, n_roi * P2, R * P2, shot, P2, K2p, K2p, self.unary_gamma, 1.0 / shot,
-                                        unary_batch_stride=way * shot * P2)
+            sc2 = self._roi_scores(f, q2, qld, kb, ub, R)
             if sw is not None:
                 swt = ops.transpose_batched(sw.view(-1)[offset * P2 * rd_:], NP, K2, rd_, ldi=rd_, ldo=K2p,
                                             in_batch=way * shot * P2 * rd_)  # [B][64][K2p], zero padded

@@ -1363,6 +1363,57 @@ def attn_softmax_unary_sweep(scores, out, unary, B, C, hw, nseg, length, ld_in, 
     return out
 
 
+def attn_box_mean(attn, boxes, n, gh, gw, k=None, group=1, roi=False, cell=16.0):
+    """dana_attn_box_mean: attn [NP][rows_b][ld] (its first k columns; default ld) -> [NP][n][k], the mean of the rows
+    each box covers. roi=False: rows_b = gh*gw, boxes [NP / group][n][4] network-input pixels, the cell rectangle taken
+    in the kernel (attention.cell_rect); roi=True: rows_b = n*gh*gw, box j's rows j*gh*gw .. + gh*gw (boxes: None)"""
+    _chk(attn, "attn")
+    if attn.dim() != 3:
+        raise ValueError("attn_box_mean: attn must be [problems][rows][ld], got %s" % (tuple(attn.shape),))
+    NP, rows_b, ld = attn.shape
+    k = ld if k is None else int(k)
+    if not roi:
+        _chk(boxes, "boxes")
+        if boxes.numel() != (NP // max(int(group), 1)) * n * 4:
+            raise ValueError("attn_box_mean: boxes must hold [%d // %d][%d][4] floats, got %s"
+                             % (NP, group, n, tuple(boxes.shape)))
+    out = torch.empty((NP, max(n, 0), max(k, 0)), dtype=torch.float32, device=attn.device)
+    lib().call("dana_attn_box_mean", _p(attn), None if roi else _p(boxes), _p(out), NP, rows_b, ld, k, n, gh, gw, group,
+               1 if roi else 0, float(cell), _stream())
+    return out
+
+
+def heatmap_upsample(maps, size):
+    """dana_heatmap_upsample: [..., gh, gw] float32 -> [..., size, size], bilinear with the cv2 convention"""
+    _chk(maps, "maps")
+    if maps.dim() < 2:
+        raise ValueError("heatmap_upsample: maps must be [..., gh, gw], got %s" % (tuple(maps.shape),))
+    gh, gw = maps.shape[-2:]
+    out = torch.empty(tuple(maps.shape[:-2]) + (int(size), int(size)), dtype=torch.float32, device=maps.device)
+    lib().call("dana_heatmap_upsample", _p(maps), _p(out), maps.numel() // max(gh * gw, 1), gh, gw, int(size), _stream())
+    return out
+
+
+def heatmap_render(maps, images, table, alpha, means_bgr):
+    """dana_heatmap_render: maps [..., gh, gw] float32, images [..., 3, S, S] float32 (BGR planes minus means_bgr), table
+    [256][3] uint8 RGB -> [..., S, S, 3] uint8 RGB overlays, one launch"""
+    _chk(maps, "maps")
+    _chk(images, "images")
+    _chk(table, "table", torch.uint8)
+    if (maps.dim() < 2 or images.dim() != maps.dim() + 1 or images.shape[:-3] != maps.shape[:-2] or images.size(-3) != 3
+            or images.size(-1) != images.size(-2)):
+        raise ValueError("heatmap_render: maps [..., gh, gw] and images [..., 3, S, S] with the same leading dimensions, "
+                         "got %s and %s" % (tuple(maps.shape), tuple(images.shape)))
+    if table.numel() != 768:
+        raise ValueError("heatmap_render: the colour table holds 256 x 3 bytes")
+    gh, gw = maps.shape[-2:]
+    S = images.size(-1)
+    out = torch.empty(tuple(maps.shape[:-2]) + (S, S, 3), dtype=torch.uint8, device=maps.device)
+    lib().call("dana_heatmap_render", _p(maps), _p(images), _p(table), _p(out), maps.numel() // max(gh * gw, 1), gh, gw, S,
+               float(alpha), float(means_bgr[0]), float(means_bgr[1]), float(means_bgr[2]), _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # backward building blocks (groundwork for the training step)
 # ------------------------------------------------------------------------------------------------

@@ -857,6 +857,38 @@ int dana_eval_coco(const float* det, const int* det_img, const int* det_cls, lon
                    int* segpos, void* codes, int* npig, void* precision, void* recall, void* scores, void* workspace,
                    size_t workspace_bytes, dana_stream_t stream);
 
+/* ---- attention maps: README.md "Attention Visualization" (images/attention_visualization.jpg) ------------------------------
+ * The reference shows where a query region looks in a support image; the weights are the tensors its forward builds and
+ * drops: support_adaptive_attention_weight at the RPN level (lib/model/framework/dana.py:142-146) and at the RoI level
+ * (:273-277), support_spatial_weight of the BA block (:134-135). */
+
+/* The mean of the attention rows a box covers. attn [n_problems][rows_b][ld] (the first k columns of a row are used),
+ * out [n_problems][n][k].
+ * mode 0 (RPN level, dana.py:142-146: one row per query feature cell): rows_b = gh * gw; boxes [n_problems / group][n][4]
+ *   = (x1, y1, x2, y2) in network-input pixels, problem p reads the boxes of image p / group (a class sweep's C problems per
+ *   image). Box j averages the rows of the cells y_lo..y_hi x x_lo..x_hi, x_lo = clamp(floor(x1 / cell), 0, gw - 1),
+ *   x_hi = clamp(floor(x2 / cell), x_lo, gw - 1), the same for y with gh (cell: the feature stride, 16): the rectangle is
+ *   computed in the kernel, is never empty and never leaves the grid.
+ * mode 1 (RoI level, dana.py:273-277: gh * gw = 49 rows per RoI): rows_b = n * gh * gw, box j averages its own rows
+ *   j * gh * gw .. (j + 1) * gh * gw - 1; boxes is not read (may be null).
+ * The rows are summed in row-major order into a float64 accumulator: two calls give the same bits. float4 loads when
+ * ld % 4 == 0 and attn is 16-byte aligned. */
+int dana_attn_box_mean(const float* attn, const float* boxes, float* out, int n_problems, int rows_b, long ld, int k, int n,
+                       int gh, int gw, int group, int mode, float cell, dana_stream_t stream);
+
+/* maps [n_maps][gh][gw] -> out [n_maps][size][size]: cv2.resize(INTER_LINEAR) (the convention of dana_prep_image: sample
+ * position (d + 0.5) * g / size - 0.5, clamped at the borders), the sample position kept in double. */
+int dana_heatmap_upsample(const float* maps, float* out, long n_maps, int gh, int gw, int size, dana_stream_t stream);
+
+/* The README figure in one launch: maps [n_maps][gh][gw] upsampled as above, normalised per map by the map's own minimum
+ * and maximum (a workgroup reduction inside the launch; a constant map goes to 0), looked up in table[256][3] (RGB bytes)
+ * at round(255 t) and blended over images [n_maps][3][size][size] -- prepared as the model is fed: BGR planes minus
+ * cfg.PIXEL_MEANS (lib/model/utils/config.py:258, blob.py:35-52) -- restored with mean_b / mean_g / mean_r and clamped to
+ * 0..255: out [n_maps][size][size][3] RGB bytes (passed as void*) = round((1 - alpha) * image + alpha * colour). */
+int dana_heatmap_render(const float* maps, const float* images, const unsigned char* table, void* out, long n_maps,
+                        int gh, int gw, int size, float alpha, float mean_b, float mean_g, float mean_r,
+                        dana_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
