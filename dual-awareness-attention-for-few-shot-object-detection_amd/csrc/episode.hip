@@ -1,0 +1,281 @@
+// A batch of episodes assembled from a resident image pool: three launches driven by one plan
+// (dana_amd/pipeline.py: ImagePool, plan_episode, EpisodeAssembler) in place of pipeline.hip's per-image launches.
+//
+//   episode_queries_kernel   im_data [B][3][H][W]: inside the plan's copy window the value prep_image_kernel would have
+//                            written at prepared pixel (y_s + y, x_s + x), computed straight from the uint8 source; 0
+//                            elsewhere. Also im_info [B][3].
+//   episode_supports_kernel  fs_loader.py:116-137 composed: each output pixel evaluates the (up to) four prepared-image
+//                            pixels its second bilinear reads, then applies it as crop_resize_pad_kernel does.
+//   episode_boxes_kernel     fs_loader.py:183-315 + minibatch.py:52-54: gather, scale, shift, clamp, filter, compact.
+//
+// The arithmetic is pipeline.hip's, expression for expression (the cv2.resize restatement at its head), and this file is
+// compiled with -ffp-contract=off like it: the results have the bits of the per-image path.
+//
+// The pool: one byte buffer of packed uint8 RGB frames; offsets[row] (bytes), meta[row] = (h, w, flipped, box_off, box_cnt).
+// The plan: int32 words. Query record (EP_QWORDS, at q_off + b * EP_QWORDS), support record (EP_SWORDS, at
+// s_off + n * EP_SWORDS); doubles sit on even words. The box orders of the queries follow the records.
+#include "common.h"
+#include "../../include/dana_hip.h"
+
+namespace {
+
+enum { EP_QWORDS = 16, EP_SWORDS = 16, EP_META = 5 };
+// query record
+enum { Q_ROW = 0, Q_NORDER = 1, Q_SCALE = 2, Q_INV = 4, Q_YS = 6, Q_XS = 7, Q_COPY_H = 8, Q_COPY_W = 9, Q_CLAMP_X = 10,
+       Q_CLAMP_Y = 11, Q_CLS = 12, Q_ORDER_OFF = 13, Q_OH = 14, Q_OW = 15 };
+// support record (words 14, 15 of both: the prepared size oh, ow; the host's limits come from it, no kernel reads it)
+enum { S_ROW = 0, S_INV = 2, S_SX = 4, S_SY = 6, S_X0 = 8, S_Y0 = 9, S_CW = 10, S_CH = 11, S_RW = 12, S_RH = 13,
+       S_OH = 14, S_OW = 15 };
+
+struct Tap {
+  int s0, s1;
+  float a0, a1;
+};
+// pipeline.hip's linear_tap: s0 and s1 are always inside [0, n)
+__device__ __forceinline__ Tap linear_tap(int d, double scale, int n) {
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  if (s < 0) {
+    s = 0;
+    f = 0.f;
+  }
+  if (s >= n - 1) {
+    s = n - 1;
+    f = 0.f;
+  }
+  Tap t;
+  t.s0 = s;
+  t.s1 = min(s + 1, n - 1);
+  t.a0 = 1.f - f;
+  t.a1 = f;
+  return t;
+}
+
+__device__ __forceinline__ double plan_double(const int* rec, int word) {
+  return *reinterpret_cast<const double*>(rec + word);
+}
+
+struct Source {
+  const unsigned char* im;
+  int h, w, flipped;
+};
+// a row outside the pool, or a table entry that is no image, reads nothing: the caller writes zeros
+__device__ __forceinline__ bool source_of(const unsigned char* pool, const long long* offsets, const int* meta, int n_rows,
+                                          long pool_bytes, int row, Source& s) {
+  if (row < 0 || row >= n_rows) return false;
+  const int* m = meta + (long)row * EP_META;
+  const long off = offsets[row];
+  s.h = m[0];
+  s.w = m[1];
+  s.flipped = m[2];
+  if (s.h <= 0 || s.w <= 0 || off < 0 || off + (long)s.h * s.w * 3 > pool_bytes) return false;
+  s.im = pool + off;
+  return true;
+}
+
+// prep_image_kernel's value of channel c (BGR) at the prepared pixel whose taps are (tx, ty)
+__device__ __forceinline__ float prep_value(const Source& s, const Tap& tx, const Tap& ty, int c, float mean) {
+  const int x0 = s.flipped ? s.w - 1 - tx.s0 : tx.s0, x1 = s.flipped ? s.w - 1 - tx.s1 : tx.s1;
+  const unsigned char* r0 = s.im + (long)ty.s0 * s.w * 3;
+  const unsigned char* r1 = s.im + (long)ty.s1 * s.w * 3;
+  const int ci = 2 - c;  // output channel c (BGR) reads input channel 2 - c (RGB)
+  const float t00 = (float)r0[x0 * 3 + ci] - mean, t01 = (float)r0[x1 * 3 + ci] - mean;
+  const float t10 = (float)r1[x0 * 3 + ci] - mean, t11 = (float)r1[x1 * 3 + ci] - mean;
+  const float h0 = t00 * tx.a0 + t01 * tx.a1;
+  const float h1 = t10 * tx.a0 + t11 * tx.a1;
+  return h0 * ty.a0 + h1 * ty.a1;
+}
+
+__global__ void __launch_bounds__(256)
+episode_queries_kernel(const unsigned char* __restrict__ pool, const long long* __restrict__ offsets,
+                       const int* __restrict__ meta, int n_rows, long pool_bytes, const int* __restrict__ plan, int B,
+                       float m0, float m1, float m2, float* __restrict__ im_data, int H, int W,
+                       float* __restrict__ im_info) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long plane = (long)H * W;
+  if (i < B) {  // (H, W, im_scale): EpisodeHolders.put_query's row
+    im_info[i * 3 + 0] = (float)H;
+    im_info[i * 3 + 1] = (float)W;
+    im_info[i * 3 + 2] = (float)plan_double(plan + i * EP_QWORDS, Q_SCALE);
+  }
+  if (i >= (long)B * plane) return;
+  const int b = (int)(i / plane);
+  const long p = i % plane;
+  const int x = (int)(p % W), y = (int)(p / W);
+  const int* rec = plan + (long)b * EP_QWORDS;
+  float v[3] = {0.f, 0.f, 0.f};
+  Source s;
+  if (y < rec[Q_COPY_H] && x < rec[Q_COPY_W] &&
+      source_of(pool, offsets, meta, n_rows, pool_bytes, rec[Q_ROW], s)) {
+    const double inv = plan_double(rec, Q_INV);
+    const Tap tx = linear_tap(rec[Q_XS] + x, inv, s.w), ty = linear_tap(rec[Q_YS] + y, inv, s.h);
+    const float mean[3] = {m0, m1, m2};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = prep_value(s, tx, ty, c, mean[c]);
+  }
+  float* o = im_data + (long)b * 3 * plane + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[(long)c * plane] = v[c];
+}
+
+__global__ void __launch_bounds__(256)
+episode_supports_kernel(const unsigned char* __restrict__ pool, const long long* __restrict__ offsets,
+                        const int* __restrict__ meta, int n_rows, long pool_bytes, const int* __restrict__ plan, int N,
+                        float m0, float m1, float m2, int target, float* __restrict__ out) {
+  const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+  const long plane = (long)target * target;
+  if (i >= (long)N * plane) return;
+  const int n = (int)(i / plane);
+  const long p = i % plane;
+  const int x = (int)(p % target), y = (int)(p / target);
+  const int* rec = plan + (long)n * EP_SWORDS;
+  float v[3] = {0.f, 0.f, 0.f};
+  Source s;
+  if (x < rec[S_RW] && y < rec[S_RH] && rec[S_CW] > 0 && rec[S_CH] > 0 &&
+      source_of(pool, offsets, meta, n_rows, pool_bytes, rec[S_ROW], s)) {
+    // the second resample (crop_resize_pad_kernel): taps into the crop, whose pixels are prepared-image pixels
+    const Tap tx = linear_tap(x, plan_double(rec, S_SX), rec[S_CW]), ty = linear_tap(y, plan_double(rec, S_SY), rec[S_CH]);
+    // the first resample (prep_image_kernel) at the two prepared columns and two prepared rows those taps name
+    const double inv = plan_double(rec, S_INV);
+    const int x0 = rec[S_X0], y0 = rec[S_Y0];
+    const Tap px0 = linear_tap(x0 + tx.s0, inv, s.w), px1 = linear_tap(x0 + tx.s1, inv, s.w);
+    const Tap py0 = linear_tap(y0 + ty.s0, inv, s.h), py1 = linear_tap(y0 + ty.s1, inv, s.h);
+    const float mean[3] = {m0, m1, m2};
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+      const float h0 = prep_value(s, px0, py0, c, mean[c]) * tx.a0 + prep_value(s, px1, py0, c, mean[c]) * tx.a1;
+      const float h1 = prep_value(s, px0, py1, c, mean[c]) * tx.a0 + prep_value(s, px1, py1, c, mean[c]) * tx.a1;
+      v[c] = h0 * ty.a0 + h1 * ty.a1;
+    }
+  }
+  float* o = out + (long)n * 3 * plane + p;
+#pragma unroll
+  for (int c = 0; c < 3; ++c) o[(long)c * plane] = v[c];
+}
+
+// one wavefront per image: 64 boxes of the plan's order per pass, kept boxes compacted in order with a ballot
+__global__ void __launch_bounds__(64)
+episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const int* __restrict__ meta, int n_rows,
+                     const int* __restrict__ plan, int plan_words, int q_off, int max_num_box,
+                     float* __restrict__ gt_boxes, long long* __restrict__ num_boxes, float* __restrict__ all_boxes,
+                     long long* __restrict__ all_num_boxes) {
+  const int b = blockIdx.x, lane = threadIdx.x;
+  const int* rec = plan + q_off + (long)b * EP_QWORDS;
+  const int row = rec[Q_ROW];
+  long box_off = 0;
+  int box_cnt = 0, n_order = rec[Q_NORDER];
+  const long order_off = rec[Q_ORDER_OFF];
+  if (row >= 0 && row < n_rows) {
+    box_off = meta[(long)row * EP_META + 3];
+    box_cnt = meta[(long)row * EP_META + 4];
+  }
+  if (box_off < 0 || box_cnt < 0 || box_off + box_cnt > n_boxes_total) box_cnt = 0;
+  if (n_order < 0 || order_off < 0 || order_off + n_order > plan_words) n_order = 0;
+  const double scale = plan_double(rec, Q_SCALE);
+  const float xs = (float)rec[Q_XS], ys = (float)rec[Q_YS];
+  const int clamp_x = rec[Q_CLAMP_X], clamp_y = rec[Q_CLAMP_Y];
+  const float cls = (float)rec[Q_CLS];
+  float* fs_out = gt_boxes + (long)b * max_num_box * 5;
+  float* all_out = all_boxes + (long)b * max_num_box * 5;
+  const unsigned long long below = (1ull << lane) - 1ull;
+  int n_fs = 0, n_all = 0;  // wave-uniform
+  for (int base = 0; base < n_order && (n_fs < max_num_box || n_all < max_num_box); base += 64) {
+    const int k = base + lane;
+    const int idx = k < n_order ? plan[order_off + k] : -1;
+    bool keep = false, pos = false;
+    float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (idx >= 0 && idx < box_cnt) {
+      const float* src = boxes + (box_off + idx) * 5;
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // minibatch.py:53: the product in double, rounded into the float32 array
+        float t = (float)((double)src[j] * scale);
+        t = t - ((j & 1) ? ys : xs);  // fs_loader.py:215-216, 251-252
+        const int lim = (j & 1) ? clamp_y : clamp_x;
+        if (lim >= 0) t = fminf(fmaxf(t, 0.f), (float)lim);  // :219-220, :254-255, :281
+        v[j] = t;
+      }
+      v[4] = src[4];
+      keep = !(v[0] == v[2] || v[1] == v[3]);  // :294, :306
+      pos = keep && v[4] == cls;               // :288
+    }
+    const unsigned long long m_all = __ballot(keep), m_fs = __ballot(pos);
+    const int at_all = n_all + __popcll(m_all & below), at_fs = n_fs + __popcll(m_fs & below);
+    if (keep && at_all < max_num_box) {
+#pragma unroll
+      for (int j = 0; j < 5; ++j) all_out[(long)at_all * 5 + j] = v[j];
+    }
+    if (pos && at_fs < max_num_box) {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) fs_out[(long)at_fs * 5 + j] = v[j];
+      fs_out[(long)at_fs * 5 + 4] = 1.f;  // :291
+    }
+    n_all += __popcll(m_all);
+    n_fs += __popcll(m_fs);
+  }
+  n_all = min(n_all, max_num_box);
+  n_fs = min(n_fs, max_num_box);
+  for (int k = n_all * 5 + lane; k < max_num_box * 5; k += 64) all_out[k] = 0.f;
+  for (int k = n_fs * 5 + lane; k < max_num_box * 5; k += 64) fs_out[k] = 0.f;
+  if (lane == 0) {
+    num_boxes[b] = n_fs;
+    all_num_boxes[b] = n_all;
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int dana_episode_queries(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                         int n_rows, const int* plan, int plan_words, int q_off, int batch,
+                         const float* pixel_means_bgr, float* im_data, int height, int width, float* im_info,
+                         dana_stream_t stream) {
+  DANA_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n_rows > 0 && pool_bytes > 0, "dana_episode_queries: bad shape");
+  DANA_CHECK_ARG(q_off >= 0 && q_off % 2 == 0 && (long)q_off + (long)batch * EP_QWORDS <= plan_words,
+                 "dana_episode_queries: the query records do not fit the plan");
+  DANA_CHECK_ARG(pool && offsets && meta && plan && pixel_means_bgr && im_data && im_info,
+                 "dana_episode_queries: null pointer");
+  const long blocks = ((long)batch * height * width + 255) / 256;
+  DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_queries: too many pixels for one launch");
+  episode_queries_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+      pool, offsets, meta, n_rows, pool_bytes, plan + q_off, batch, pixel_means_bgr[0], pixel_means_bgr[1],
+      pixel_means_bgr[2], im_data, height, width, im_info);
+  DANA_CHECK_LAUNCH("dana_episode_queries");
+  return DANA_OK;
+}
+
+int dana_episode_supports(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                          int n_rows, const int* plan, int plan_words, int s_off, int n_supports,
+                          const float* pixel_means_bgr, int target, float* out_chw, dana_stream_t stream) {
+  DANA_CHECK_ARG(n_supports > 0 && target > 0 && n_rows > 0 && pool_bytes > 0, "dana_episode_supports: bad shape");
+  DANA_CHECK_ARG(s_off >= 0 && s_off % 2 == 0 && (long)s_off + (long)n_supports * EP_SWORDS <= plan_words,
+                 "dana_episode_supports: the support records do not fit the plan");
+  DANA_CHECK_ARG(pool && offsets && meta && plan && pixel_means_bgr && out_chw, "dana_episode_supports: null pointer");
+  const long blocks = ((long)n_supports * target * target + 255) / 256;
+  DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_supports: too many pixels for one launch");
+  episode_supports_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+      pool, offsets, meta, n_rows, pool_bytes, plan + s_off, n_supports, pixel_means_bgr[0], pixel_means_bgr[1],
+      pixel_means_bgr[2], target, out_chw);
+  DANA_CHECK_LAUNCH("dana_episode_supports");
+  return DANA_OK;
+}
+
+int dana_episode_boxes(const float* boxes, long n_boxes_total, const int* meta, int n_rows, const int* plan,
+                       int plan_words, int q_off, int batch, int max_num_box, float* gt_boxes, long long* num_boxes,
+                       float* all_cls_gt_boxes, long long* all_cls_num_boxes, dana_stream_t stream) {
+  DANA_CHECK_ARG(batch > 0 && max_num_box > 0 && n_rows > 0 && n_boxes_total >= 0, "dana_episode_boxes: bad shape");
+  DANA_CHECK_ARG(q_off >= 0 && q_off % 2 == 0 && (long)q_off + (long)batch * EP_QWORDS <= plan_words,
+                 "dana_episode_boxes: the query records do not fit the plan");
+  DANA_CHECK_ARG(meta && plan && gt_boxes && num_boxes && all_cls_gt_boxes && all_cls_num_boxes &&
+                     (boxes || n_boxes_total == 0),
+                 "dana_episode_boxes: null pointer");
+  episode_boxes_kernel<<<batch, 64, 0, (hipStream_t)stream>>>(boxes, n_boxes_total, meta, n_rows, plan, plan_words, q_off,
+                                                              max_num_box, gt_boxes, num_boxes, all_cls_gt_boxes,
+                                                              all_cls_num_boxes);
+  DANA_CHECK_LAUNCH("dana_episode_boxes");
+  return DANA_OK;
+}
+
+}  // extern "C"

@@ -5,6 +5,8 @@ Mirrors what the reference's loaders do per image on the CPU with cv2 / numpy:
   * `support_crop`       roi_data_layer/fs_loader.py:118-139 (crop the support box, fit it into target x target)
   * `crop_pad_chw`       fs_loader.py:186-280,318 (query crop window, ratio padding, permute(2, 0, 1))
   * `EpisodeHolders`     train.py:61-66,125-129 (persistent device holders the model is fed from)
+  * `ImagePool`, `plan_episode`, `EpisodeAssembler`   fs_loader.py:81-325 for a whole batch: resident frames, one plan
+                         made on the host, three launches (csrc/episode.hip), the same bits as the functions above
 Raw uint8 RGB frames are uploaded once; everything else happens in HBM through libdana_hip.so. The data-dependent
 host decisions (which crop window, which supports: np.random / random in fs_loader.py) stay on the host, as they
 are in the reference."""
@@ -113,3 +115,330 @@ class EpisodeHolders:
 
     def tensors(self):
         return self.im_data, self.im_info, self.gt_boxes, self.num_boxes, self.support_ims
+
+
+# ---- a batch of episodes from a resident image pool (csrc/episode.hip) ---------------------------------------------------
+# The raw frames stay on the device; per batch the host decides what the reference's loader decides with random / np.random
+# (which supports, which crop start, which box order), `plan_episode` derives everything that follows from those choices,
+# and `EpisodeAssembler.assemble` turns the plan into the holders' contents with one upload and three launches.
+
+# plan records, in int32 words (the enums of csrc/episode.hip); doubles sit on even words
+EP_QWORDS, EP_SWORDS = 16, 16
+(Q_ROW, Q_NORDER, Q_SCALE, Q_INV, Q_YS, Q_XS, Q_COPY_H, Q_COPY_W, Q_CLAMP_X, Q_CLAMP_Y, Q_CLS,
+ Q_ORDER_OFF, Q_OH, Q_OW) = 0, 1, 2, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
+S_ROW, S_INV, S_SX, S_SY, S_X0, S_Y0, S_CW, S_CH, S_RW, S_RH, S_OH, S_OW = 0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 14, 15
+
+
+class ImagePool:
+    """Raw uint8 RGB frames of different sizes in ONE device byte buffer, with their annotations beside them. Each frame
+    starts on a 16-byte boundary; its rows are packed (w * 3 bytes). A flipped roidb entry (imdb.append_flipped_images) is a
+    row of its own that shares the pixel bytes of its twin and carries its own, already flipped boxes.
+    device=None keeps the tables on the host only (what `plan_episode` reads); with a device, `freeze()` uploads the frames
+    and the tables once."""
+
+    def __init__(self, device=None):
+        self.device = None if device is None else torch.device(device)
+        self._frames = []  # (host array | device tensor, byte offset)
+        self._rows = []    # (frame index, flipped, float32 [n][5] boxes)
+        self._end = 0
+        self.frozen = False
+
+    @staticmethod
+    def _boxes(boxes):
+        if torch.is_tensor(boxes):
+            boxes = boxes.detach().cpu().numpy()
+        b = np.asarray(boxes, dtype=np.float32).reshape(-1, 5) if np.size(boxes) else np.zeros((0, 5), dtype=np.float32)
+        return np.ascontiguousarray(b)
+
+    def add(self, im_rgb_u8, boxes):
+        """im_rgb_u8: uint8 [h][w][3] (host array or device tensor); boxes: float32 [n][5] (x1, y1, x2, y2, class), unscaled
+        as in roidb['boxes'] / roidb['gt_classes'] -> the row index"""
+        if self.frozen:
+            raise RuntimeError("ImagePool.add: the pool is frozen")
+        im = im_rgb_u8 if torch.is_tensor(im_rgb_u8) else np.asarray(im_rgb_u8)
+        if im.dtype not in (torch.uint8, np.uint8) or im.ndim != 3 or im.shape[2] != 3 or im.shape[0] < 1 or im.shape[1] < 1:
+            raise ValueError("ImagePool.add: need a uint8 [h][w][3] image")
+        self._frames.append((im, self._end))
+        self._end = (self._end + im.shape[0] * im.shape[1] * 3 + 15) // 16 * 16
+        self._rows.append((len(self._frames) - 1, 0, self._boxes(boxes)))
+        return len(self._rows) - 1
+
+    def add_flipped(self, row, boxes):
+        """the horizontally flipped twin of `row` (no second copy of the pixels); boxes: the twin's, already flipped"""
+        if self.frozen:
+            raise RuntimeError("ImagePool.add_flipped: the pool is frozen")
+        if not 0 <= int(row) < len(self._rows):
+            raise IndexError("ImagePool.add_flipped: row %d outside [0, %d)" % (row, len(self._rows)))
+        frame, flipped, _ = self._rows[int(row)]
+        self._rows.append((frame, 1 - flipped, self._boxes(boxes)))
+        return len(self._rows) - 1
+
+    def freeze(self):
+        if self.frozen:
+            return self
+        n = len(self._rows)
+        self.offsets = np.array([self._frames[f][1] for f, _, _ in self._rows], dtype=np.int64)
+        self.meta = np.zeros((n, 5), dtype=np.int32)  # h, w, flipped, first box, box count
+        at = 0
+        for r, (f, flipped, bx) in enumerate(self._rows):
+            im = self._frames[f][0]
+            self.meta[r] = (im.shape[0], im.shape[1], flipped, at, bx.shape[0])
+            at += bx.shape[0]
+        self.boxes = np.concatenate([bx for _, _, bx in self._rows] + [np.zeros((0, 5), dtype=np.float32)], axis=0)
+        self.frozen = True
+        if self.device is not None:
+            staged = np.zeros((max(self._end, 16),), dtype=np.uint8)
+            for im, off in self._frames:
+                if not torch.is_tensor(im):
+                    staged[off:off + im.size] = np.ascontiguousarray(im).reshape(-1)
+            self.data = torch.from_numpy(staged).to(self.device)
+            for im, off in self._frames:
+                if torch.is_tensor(im):
+                    self.data[off:off + im.numel()] = im.to(self.device).reshape(-1)
+            self.d_offsets = torch.from_numpy(self.offsets).to(self.device)
+            self.d_meta = torch.from_numpy(self.meta).to(self.device)
+            self.d_boxes = torch.from_numpy(self.boxes if len(self.boxes) else np.zeros((1, 5), np.float32)).to(self.device)
+        self._frames = [(None, off) for _, off in self._frames]
+        return self
+
+    def __len__(self):
+        return len(self._rows)
+
+    @property
+    def nbytes(self):
+        """bytes of the frame buffer (alignment padding included)"""
+        return int(self._end)
+
+    def row_boxes(self, row):
+        return self._rows[row][2]
+
+
+class EpisodePlan:
+    """One batch of episodes as the device reads it: `words` (int32) = `batch` query records, `n_supports` support
+    records, the queries' box orders. `queries` / `supports` are the same records as dicts, for the host."""
+
+    def __init__(self, words, queries, supports, holder_hw):
+        self.words, self.queries, self.supports, self.holder_hw = words, queries, supports, holder_hw
+        self.batch, self.n_supports = len(queries), len(supports)
+        self.q_off, self.s_off = 0, len(queries) * EP_QWORDS
+
+    def boxes_numpy(self, pool, max_num_box):
+        """`episode_boxes_numpy` per query -> (gt_boxes [B][max][5], num_boxes [B], all_cls_gt_boxes, all_cls_num_boxes)"""
+        per = [episode_boxes_numpy(pool.row_boxes(q["row"]), q["order"], q["im_scale"], q["x_s"], q["y_s"], q["clamp_x"],
+                                   q["clamp_y"], q["pos_cls"], max_num_box) for q in self.queries]
+        return (np.stack([p[0] for p in per]), np.array([p[1] for p in per], dtype=np.int64),
+                np.stack([p[2] for p in per]), np.array([p[3] for p in per], dtype=np.int64))
+
+
+def _host_only(name, v):
+    if getattr(v, "is_cuda", False):
+        raise ValueError("plan_episode: %s is a device tensor; the plan is made on the host" % name)
+    return v
+
+
+def _pool_row(pool, row):
+    if not pool.frozen:
+        raise RuntimeError("plan_episode: freeze() the pool first")
+    row = int(_host_only("row", row))
+    if not 0 <= row < len(pool):
+        raise IndexError("plan_episode: pool row %d outside [0, %d)" % (row, len(pool)))
+    h, w = int(pool.meta[row, 0]), int(pool.meta[row, 1])
+    return row, h, w
+
+
+def _plan_support(pool, row, box, target_size, support_size):
+    row, h, w = _pool_row(pool, row)
+    im_scale = float(target_size) / float(min(h, w))  # blob.py:45
+    oh, ow = cv_round(h * im_scale), cv_round(w * im_scale)
+    scaled = np.asarray(_host_only("box", box), dtype=np.float32).reshape(-1)[:4] * np.float32(im_scale)
+    if not (np.abs(scaled) < 32768).all():
+        raise ValueError("plan_episode: support box %s of row %d does not fit int16 after scaling" % (list(box), row))
+    x_min, y_min, x_max, y_max = [int(v) for v in scaled.astype(np.int16)]  # fs_loader.py:120
+    box_h, box_w = y_max - y_min, x_max - x_min
+    x_lim, y_lim = min(x_max, ow - 1), min(y_max, oh - 1)  # the slice [min : max + 1] ends with the image
+    if x_min < 0 or y_min < 0 or x_lim < x_min or y_lim < y_min:
+        raise ValueError("plan_episode: support box %s lies outside its image (row %d, prepared %d x %d)"
+                         % ((x_min, y_min, x_max, y_max), row, oh, ow))
+    if box_h > box_w:  # fs_loader.py:126-133
+        rw, rh = int(box_w * (float(support_size) / float(box_h))), support_size
+    else:
+        rw, rh = support_size, (int(box_h * (float(support_size) / float(box_w))) if box_w > 0 else 0)
+    if rw <= 0 or rh <= 0:
+        raise ValueError("plan_episode: support box %s resizes to %d x %d" % ((x_min, y_min, x_max, y_max), rw, rh))
+    cw, ch = x_lim - x_min + 1, y_lim - y_min + 1
+    return dict(row=row, im_scale=im_scale, oh=oh, ow=ow, x_min=x_min, y_min=y_min, x_max=x_lim, y_max=y_lim, rw=rw, rh=rh,
+                cw=cw, ch=ch)
+
+
+def _plan_query(pool, q, holder_hw, target_size):
+    row, h, w = _pool_row(pool, q["row"])
+    ratio = float(_host_only("ratio", q["ratio"]))
+    im_scale = float(target_size) / float(min(h, w))
+    oh, ow = cv_round(h * im_scale), cv_round(w * im_scale)
+    data_h, data_w, y_s, x_s, clamp_x, clamp_y = oh, ow, 0, 0, -1, -1
+    if q.get("need_crop", False):
+        start = int(_host_only("crop_start", q.get("crop_start", 0)))
+        if ratio < 1:  # fs_loader.py:187-220: crop the height
+            trim = min(int(np.floor(data_w / ratio)), data_h)
+            y_s, data_h, clamp_y = start, trim, trim - 1
+        else:  # :222-255: crop the width
+            trim = min(int(np.ceil(data_h * ratio)), data_w)
+            x_s, data_w, clamp_x = start, trim, trim - 1
+        if start < 0 or y_s + data_h > oh or x_s + data_w > ow:
+            raise ValueError("plan_episode: crop window (start %d, size %d) leaves the prepared image (%d x %d) of row %d"
+                             % (start, trim, oh, ow, row))
+    out_h, out_w, copy_h, copy_w = pad_plan(data_h, data_w, ratio)  # :257-283
+    if ratio == 1:
+        clamp_x = copy_w if clamp_x < 0 else min(clamp_x, copy_w)  # :281 (after the crop's clamp, where both apply)
+        clamp_y = copy_h if clamp_y < 0 else min(clamp_y, copy_h)
+    if copy_h > holder_hw[0] or copy_w > holder_hw[1]:
+        raise ValueError("plan_episode: copy window %d x %d of row %d is larger than the holder (%d x %d)"
+                         % (copy_h, copy_w, row, holder_hw[0], holder_hw[1]))
+    n_box = int(pool.meta[row, 4])
+    order = q.get("order")
+    order = np.arange(n_box, dtype=np.int32) if order is None else np.asarray(_host_only("order", order)).astype(np.int32).reshape(-1)
+    if len(order) and (order.min() < 0 or order.max() >= n_box):
+        raise ValueError("plan_episode: box order of row %d names a box outside [0, %d)" % (row, n_box))
+    return dict(row=row, im_scale=im_scale, oh=oh, ow=ow, y_s=y_s, x_s=x_s, copy_h=copy_h, copy_w=copy_w, out_h=out_h,
+                out_w=out_w, clamp_x=clamp_x, clamp_y=clamp_y, pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=order)
+
+
+def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, support_size=320):
+    """Host only. queries: one dict per batch item with the loader's choices -- row, ratio (ratio_list_batch[index]),
+    pos_cls, and optionally order (the shuffled box order of fs_loader.py:183; default: as stored), need_crop with
+    crop_start (the y_s / x_s drawn at :186-255). supports: (row, box) per support slot, batch-major ([b][way * shot]
+    flattened), box = the support_db entry's unscaled (x1, y1, x2, y2). holder_hw: (H, W) of the holders' im_data.
+    -> EpisodePlan with everything that follows deterministically: scales, prepared sizes, copy windows, clamp limits, the
+    int16 support boxes and their resized sizes."""
+    queries, supports = list(queries), list(supports)
+    if queries and holder_hw is None:
+        raise ValueError("plan_episode: holder_hw is needed to plan queries")
+    qs = [_plan_query(pool, q, holder_hw, target_size) for q in queries]
+    ss = [_plan_support(pool, r, bx, target_size, support_size) for r, bx in supports]
+    n_rec = len(qs) * EP_QWORDS + len(ss) * EP_SWORDS
+    words = np.zeros((n_rec + sum(len(q["order"]) for q in qs),), dtype=np.int32)
+    f64 = words[:n_rec].view(np.float64)  # word 2k <-> double k
+    at = n_rec
+    for b, q in enumerate(qs):
+        o = b * EP_QWORDS
+        words[o + Q_ROW], words[o + Q_NORDER] = q["row"], len(q["order"])
+        f64[(o + Q_SCALE) // 2], f64[(o + Q_INV) // 2] = q["im_scale"], 1.0 / q["im_scale"]
+        words[o + Q_YS:o + Q_YS + 4] = (q["y_s"], q["x_s"], q["copy_h"], q["copy_w"])
+        words[o + Q_CLAMP_X:o + Q_CLAMP_X + 6] = (q["clamp_x"], q["clamp_y"], q["pos_cls"], at, q["oh"], q["ow"])
+        words[at:at + len(q["order"])] = q["order"]
+        at += len(q["order"])
+    for n, s in enumerate(ss):
+        o = len(qs) * EP_QWORDS + n * EP_SWORDS
+        words[o + S_ROW] = s["row"]
+        # cv2.resize(fx, fy) samples at 1 / fx, cv2.resize(dsize) at src / dst (csrc/pipeline.hip)
+        f64[(o + S_INV) // 2], f64[(o + S_SX) // 2], f64[(o + S_SY) // 2] = 1.0 / s["im_scale"], s["cw"] / s["rw"], s["ch"] / s["rh"]
+        words[o + S_X0:o + S_X0 + 8] = (s["x_min"], s["y_min"], s["cw"], s["ch"], s["rw"], s["rh"], s["oh"], s["ow"])
+    return EpisodePlan(words, qs, ss, None if holder_hw is None else (int(holder_hw[0]), int(holder_hw[1])))
+
+
+def episode_boxes_numpy(boxes, order, im_scale, x_s, y_s, clamp_x, clamp_y, pos_cls, max_num_box):
+    """minibatch.py:52-54 + fs_loader.py:183-315 for one image, in numpy. boxes: float32 [n][5] unscaled; clamp_x / clamp_y:
+    upper clamp limit of that axis, < 0 for none -> (fs_gt_boxes [max][5], num_boxes, all-class gt_boxes [max][5], its count)"""
+    src = np.asarray(boxes, dtype=np.float32).reshape(-1, 5)[np.asarray(order, dtype=np.int64).reshape(-1)]
+    gt = np.empty((src.shape[0], 5), dtype=np.float32)
+    gt[:, 0:4] = src[:, 0:4].astype(np.float64) * float(im_scale)  # the product in double, rounded by the assignment
+    gt[:, 4] = src[:, 4]
+    gt[:, 0:4:2] -= np.float32(x_s)  # :215-216, :251-252
+    gt[:, 1:4:2] -= np.float32(y_s)
+    if clamp_x >= 0:
+        gt[:, 0:4:2] = np.clip(gt[:, 0:4:2], np.float32(0), np.float32(clamp_x))  # :219-220, :254-255, :281
+    if clamp_y >= 0:
+        gt[:, 1:4:2] = np.clip(gt[:, 1:4:2], np.float32(0), np.float32(clamp_y))
+    fs = gt[gt[:, 4] == pos_cls].copy()  # :286-291
+    fs[:, 4] = 1.0
+    out = []
+    for g in (fs, gt):  # :294-315
+        g = g[~((g[:, 0] == g[:, 2]) | (g[:, 1] == g[:, 3]))]
+        n = min(g.shape[0], max_num_box)
+        pad = np.zeros((max_num_box, 5), dtype=np.float32)
+        pad[:n] = g[:n]
+        out += [pad, n]
+    return tuple(out)
+
+
+class EpisodeAssembler:
+    """`assemble(plan)`: one asynchronous plan upload and three launches fill `holders` (whose addresses never change: a
+    ProgramTrainer recorded on holders.tensors() follows every later assemble) plus `all_cls_gt_boxes`, the loader's sixth
+    return. Nothing here waits for the device except when a plan buffer comes round again while its batch is still queued:
+    the buffers rotate behind an event each."""
+
+    def __init__(self, pool, holders=None, pixel_means=None, support_size=None, n_buffers=2):
+        if pool.device is None or not pool.frozen:
+            raise RuntimeError("EpisodeAssembler: needs a frozen ImagePool on a device")
+        self.pool, self.holders = pool, holders
+        self.support_size = (holders.support_size if holders is not None else 320) if support_size is None else support_size
+        means = np.asarray(cfg.PIXEL_MEANS if pixel_means is None else pixel_means, dtype=np.float32).reshape(-1)
+        self._means = (ctypes.c_float * 3)(*[float(m) for m in means[:3]])  # kept alive: a recorded launch points at it
+        self._means_p = ctypes.cast(self._means, ctypes.c_void_p)
+        if holders is not None:
+            self.all_cls_gt_boxes = torch.zeros_like(holders.gt_boxes)
+            self.all_cls_num_boxes = torch.zeros_like(holders.num_boxes)
+        self._ring = [[None, None, None] for _ in range(max(2, int(n_buffers)))]  # pinned words, device words, event
+        self._next = 0
+
+    def _upload(self, plan):
+        """-> (device words, slot): the plan in the next buffer of the ring, copied on the current stream"""
+        slot = self._ring[self._next % len(self._ring)]
+        self._next += 1
+        n = int(plan.words.size)
+        if slot[2] is not None:
+            slot[2].synchronize()  # the batch that read this buffer, n_buffers assembles ago
+        if slot[0] is None or slot[0].numel() < n:
+            slot[0] = torch.empty((max(2 * n, 1024),), dtype=torch.int32, pin_memory=True)
+            slot[1] = torch.empty((slot[0].numel(),), dtype=torch.int32, device=self.pool.device)
+        slot[0][:n].numpy()[...] = plan.words
+        slot[1][:n].copy_(slot[0][:n], non_blocking=True)
+        return slot[1], slot
+
+    @staticmethod
+    def _done(slot):
+        if slot[2] is None:
+            slot[2] = torch.cuda.Event()
+        slot[2].record()
+
+    def _supports(self, d_plan, plan, out):
+        p = self.pool
+        lib().call("dana_episode_supports", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p), _p(d_plan),
+                   int(plan.words.size), plan.s_off, plan.n_supports, self._means_p, self.support_size, _p(out), _stream())
+
+    def assemble(self, plan):
+        h, p = self.holders, self.pool
+        if h is None:
+            raise RuntimeError("EpisodeAssembler.assemble: built without holders")
+        B, H, W = h.im_data.size(0), h.im_data.size(2), h.im_data.size(3)
+        n_sup = B * h.support_ims.size(1)
+        if plan.batch != B or plan.n_supports != n_sup or plan.holder_hw != (H, W):
+            raise ValueError("EpisodeAssembler.assemble: the plan (%d queries, %d supports, holder %s) is not for these holders "
+                             "(%d, %d, %s)" % (plan.batch, plan.n_supports, plan.holder_hw, B, n_sup, (H, W)))
+        d_plan, slot = self._upload(plan)
+        n_words, stream = int(plan.words.size), _stream()
+        lib().call("dana_episode_queries", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p), _p(d_plan),
+                   n_words, plan.q_off, B, self._means_p, _p(h.im_data), H, W, _p(h.im_info), stream)
+        if n_sup:
+            self._supports(d_plan, plan, h.support_ims)
+        lib().call("dana_episode_boxes", _p(p.d_boxes), len(p.boxes), _p(p.d_meta), len(p), _p(d_plan), n_words, plan.q_off, B,
+                   h.gt_boxes.size(1), _p(h.gt_boxes), _p(h.num_boxes), _p(self.all_cls_gt_boxes),
+                   _p(self.all_cls_num_boxes), stream)
+        self._done(slot)
+        return h.tensors() + (self.all_cls_gt_boxes,)
+
+    def support_crops(self, records, out=None):
+        """records: a plan of supports only (`plan_episode(pool, (), supports)`) -> fp32 [N][3][S][S], what
+        `encode_support_bank` / `encode_supports` (reshaped to [C][shot]) take"""
+        if records.batch != 0 or records.n_supports < 1:
+            raise ValueError("EpisodeAssembler.support_crops: need a plan of supports only")
+        S = self.support_size
+        if out is None:
+            out = torch.empty((records.n_supports, 3, S, S), dtype=torch.float32, device=self.pool.device)
+        _chk(out, "out")
+        if out.numel() != records.n_supports * 3 * S * S:
+            raise ValueError("EpisodeAssembler.support_crops: out must hold [%d][3][%d][%d]" % (records.n_supports, S, S))
+        d_plan, slot = self._upload(records)
+        self._supports(d_plan, records, out)
+        self._done(slot)
+        return out

@@ -712,6 +712,33 @@ int dana_crop_resize_pad(const float* im_hwc, int height, int width, int x_min, 
 int dana_crop_pad_chw(const float* im_hwc, int height, int width, int y_start, int x_start, int crop_h, int crop_w,
                       float* out_chw, int out_h, int out_w, dana_stream_t stream);
 
+/* A batch of episodes from a resident image pool (csrc/episode.hip; dana_amd/pipeline.py builds the pool and the plan).
+ * pool: packed uint8 RGB frames in one DEVICE byte buffer; offsets[n_rows] = byte offset of each row's frame,
+ * meta[n_rows][5] = (h, w, flipped, first box, box count). plan: DEVICE int32 words: 16-word query records at q_off,
+ * 16-word support records at s_off, the queries' box orders behind them (word layout: the enums of episode.hip,
+ * written by pipeline.plan_episode). pixel_means_bgr: 3 HOST floats. A record that names no image of the pool writes
+ * zeros; nothing outside the pool is read. Results have the bits of the per-image entry points above. */
+
+/* minibatch.py:70-96 + blob.py:35-52 + fs_loader.py:186-280,318 for all `batch` queries: im_data [batch][3][height][width]
+ * = dana_prep_image's value at prepared pixel (y_s + y, x_s + x) inside each record's copy window, 0 elsewhere (no fp32
+ * intermediate image); im_info [batch][3] = (height, width, im_scale) (fs_loader.py:266-283,319) */
+int dana_episode_queries(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                         int n_rows, const int* plan, int plan_words, int q_off, int batch,
+                         const float* pixel_means_bgr, float* im_data, int height, int width, float* im_info,
+                         dana_stream_t stream);
+/* fs_loader.py:113-139,149-174 for all n_supports supports: whole image to im_scale, box crop resized to rw x rh, CHW,
+ * zero-padded -> out_chw [n_supports][3][target][target] (dana_prep_image then dana_crop_resize_pad, composed per pixel) */
+int dana_episode_supports(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                          int n_rows, const int* plan, int plan_words, int s_off, int n_supports,
+                          const float* pixel_means_bgr, int target, float* out_chw, dana_stream_t stream);
+/* minibatch.py:52-54 + fs_loader.py:183-315 for all `batch` queries: boxes [n_boxes_total][5] (x1, y1, x2, y2, class,
+ * unscaled) gathered in the plan's order, scaled (product in double, rounded to float), shifted by the crop start, clamped,
+ * degenerate boxes dropped, compacted, cut at max_num_box, zero-filled -> gt_boxes [batch][max_num_box][5] (the positive
+ * class only, label 1) with num_boxes [batch], and all_cls_gt_boxes / all_cls_num_boxes of the same shapes */
+int dana_episode_boxes(const float* boxes, long n_boxes_total, const int* meta, int n_rows, const int* plan,
+                       int plan_words, int q_off, int batch, int max_num_box, float* gt_boxes, long long* num_boxes,
+                       float* all_cls_gt_boxes, long long* all_cls_num_boxes, dana_stream_t stream);
+
 /* ---- counter-based device RNG for the training target layers (opt-in) ---------------------------
  * Philox-4x32-10 keyed by (seed, offset, image): the draws of anchor_target_layer.py:137-156 and
  * proposal_target_layer_cascade.py:143-175 without reading the fg / bg counts back to the host. */
