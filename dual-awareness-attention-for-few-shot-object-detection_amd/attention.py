@@ -116,6 +116,10 @@ def attention_maps(model, im_data, im_info, boxes, support, levels=ATTENTION_LEV
     the eval forward takes as its 5th argument (support images, a SupportCache selection, a ClassSweep)
     -> AttentionMaps(ba, rpn, roi) of float32 device tensors (module docstring); a level not in `levels` is None. `ba`
     needs support images and the BA block: without them it is None, or a ValueError when `levels` names it explicitly."""
+    from .dana import QueryBatch
+    if isinstance(im_data, QueryBatch):
+        raise TypeError("attention_maps takes the query images themselves (im_data [B, 3, H, W]), not a QueryBatch: the maps "
+                        "are an inspection tool and run the trunk")
     explicit = levels is not ATTENTION_LEVELS
     levels = check_levels(levels)
     if type(model)._forward_gen is not DAnARCNN._forward_gen:

@@ -152,7 +152,57 @@ bank_gather_episode_kernel(const float4* __restrict__ map_pe, const float4* __re
   }
 }
 
+// Query bank (dana.QueryBank): the trunk maps [N][rows][C] of a pool of query images are encoded once over a frozen trunk; a
+// forward names its B images by bank row and ONE launch copies them into the first C columns of corr [B*rows][ld_out] -- where
+// the query trunk writes its result -- and leaves columns C .. ld_out-1 (the attended half) alone.
+// grid (gx, B): workgroup row b walks the rows*C/4 16-byte units of image index[b]; a workgroup takes BANK_UNROLL * 256
+// consecutive units, each lane BANK_UNROLL of them 256 apart, every load in front of the first store (a unit past the image's
+// end reads the image's last unit again and stores nothing). Unit u = (r, c4) lands at row b*rows + r, 16-byte column c4.
+__global__ void __launch_bounds__(256)
+qbank_gather_kernel(const float4* __restrict__ maps, const int* __restrict__ index, int n_bank, unsigned units,
+                    unsigned c4s, int rows, float4* __restrict__ out, int ld4) {
+  const int b = blockIdx.y;
+  // (units < 2^31 - 1024, checked by the entry point: unit numbers and their row / column split stay in 32 bits)
+  const unsigned u0 = blockIdx.x * (BANK_UNROLL * 256) + threadIdx.x;
+  if (u0 - threadIdx.x >= units) return;
+  const int n = index[b];
+  if (n < 0 || n >= n_bank) return;  // (validated on the host; never read outside the bank)
+  const float4* src = maps + (long long)n * units;
+  float4* dst = out + (long long)b * rows * ld4;
+  float4 v[BANK_UNROLL];
+#pragma unroll
+  for (int k = 0; k < BANK_UNROLL; ++k) v[k] = src[min(u0 + (unsigned)k * 256, units - 1)];
+#pragma unroll
+  for (int k = 0; k < BANK_UNROLL; ++k) {
+    const unsigned u = u0 + (unsigned)k * 256;
+    if (u < units) {
+      const unsigned r = u / c4s;
+      dst[(long long)r * ld4 + (u - r * c4s)] = v[k];
+    }
+  }
+}
+
 extern "C" {
+
+int dana_qbank_gather(const float* maps, const int* index, int n_bank, int B, int rows, int channels, float* out, int ld_out,
+                      dana_stream_t stream) {
+  DANA_CHECK_ARG(n_bank >= 0 && B >= 0 && B <= 65535 && rows >= 0 && channels >= 4 && channels % 4 == 0 &&
+                     ld_out >= channels && ld_out % 4 == 0,
+                 "dana_qbank_gather: bad shape n_bank=%d B=%d rows=%d channels=%d ld_out=%d (channels and ld_out multiples "
+                 "of 4, ld_out >= channels, B <= 65535)", n_bank, B, rows, channels, ld_out);
+  const long long units = (long long)rows * (channels / 4);
+  if (B == 0 || units == 0) return DANA_OK;
+  DANA_CHECK_ARG(maps && index && out && n_bank > 0, "dana_qbank_gather: null pointer");
+  DANA_CHECK_ARG((((uintptr_t)maps | (uintptr_t)out) & 15) == 0, "dana_qbank_gather: maps and out must be 16-byte aligned");
+  const long long per_wg = (long long)BANK_UNROLL * 256;
+  DANA_CHECK_ARG(units < 0x7fffffffLL - per_wg, "dana_qbank_gather: %lld 16-byte units per image (fewer than 2^31 - %lld)",
+                 units, per_wg);
+  const long long gx = (units + per_wg - 1) / per_wg;
+  qbank_gather_kernel<<<dim3((unsigned)gx, (unsigned)B), 256, 0, (hipStream_t)stream>>>(
+      (const float4*)maps, index, n_bank, (unsigned)units, (unsigned)(channels / 4), rows, (float4*)out, ld_out / 4);
+  DANA_CHECK_LAUNCH("dana_qbank_gather");
+  return DANA_OK;
+}
 
 int dana_bank_gather_episode(const float* map_pe, const float* pool_pe, const int* index, int n_bank, int B, int way,
                              int shot, int map_rows, int pool_rows, int channels, float* s_pe, float* sp_pe,

@@ -1043,6 +1043,48 @@ class DAnARCNN(nn.Module):
                 ops.add_pe(sp, plan["pe49"], c * P2, P2, 1024, out=pool_pe[n0:n0 + c])
         return SupportBank(self, map_pe, pool_pe, (sh_, sw_), pool, self._bank_state(dev), dev)
 
+    # ---- query bank: the query trunk's output over a frozen trunk, encoded once ----------------------------------
+    _no_query_bank = None  # a sibling detector says here why it has none (frcnn.py)
+
+    def encode_query_bank(self, images, chunk=None):
+        """images [N, 3, H, W] (the query images of a fine-tuning or validation set, prepared as im_data holders are -- what
+        pipeline.EpisodeAssembler or prep_im_for_blob + padding produce --, all of one H x W) -> QueryBank: per image the
+        trunk map [fh*fw][1024] the forward writes into the first half of corr, from the kernels the forward uses. The trunk
+        runs `chunk` images at a time (default min(N, 4)) through the launches of a forward that saves nothing, under no_grad,
+        in train or eval mode (the trunk's BatchNorms are frozen in both). `model(qbank.batch(index), im_info, gt_boxes,
+        num_boxes, support)` then gathers the batch's rows (one launch) and runs no query trunk: in train mode over a frozen
+        trunk (cfg.RESNET.FIXED_BLOCKS = 3), in eval mode under any freeze. One 600 x 1000 image costs 38*63*1024*4 B =
+        9.8 MB."""
+        if self._no_query_bank is not None:
+            raise NotImplementedError("encode_query_bank: " + self._no_query_bank)
+        if not torch.is_tensor(images) or images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
+            raise ValueError("encode_query_bank: images must be [N, 3, H, W] with N >= 1, got %s"
+                             % (tuple(images.shape) if torch.is_tensor(images) else type(images)))
+        if not images.is_cuda:
+            raise RuntimeError("images must be a CUDA (HIP) tensor: this build has no CPU path")
+        N, dev = images.size(0), images.device
+        chunk = min(N, 4) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("encode_query_bank: chunk must be >= 1, got %d" % chunk)
+        H, W = images.size(2), images.size(3)
+        fh, fw = self._feat_size(H, W)
+        with torch.no_grad():
+            plan = self._get_plan()
+            maps = torch.empty((N, fh * fw, 1024), dtype=torch.float32, device=dev)
+            for n0 in range(0, N, chunk):
+                ims = images[n0:n0 + chunk].float().contiguous()
+                c = ims.size(0)
+                self._rcnn_base(ims, plan, out_stride=1024, out_buf=maps[n0:n0 + c].view(c * fh * fw, 1024))
+        return QueryBank(self, maps, (H, W), (fh, fw), self._qbank_state(dev), dev)
+
+    def _qbank_state(self, dev):
+        """what a QueryBank's rows depend on: `_bank_state`, and -- while any trunk parameter trains (FIXED_BLOCKS < 3; a
+        QueryBank also serves eval-mode forwards of such a model) -- the weight epoch: the fused optimizers write the weights
+        through raw pointers and bump no tensor version, so every optimizer step (`_epoch += 1`, as for the packed / Winograd
+        weight copies) makes a bank over a training trunk stale"""
+        trains = any(p.requires_grad for p in self.RCNN_base.parameters())
+        return self._bank_state(dev) + ((self._epoch,) if trains else ())
+
     # ---- stages shared with the sibling detectors (frcnn.py, fgn.py, fsod.py) ------------------------------------
     def _saving_ctx(self, lists, align_only_for=None):
         """-> (bridge: loss.backward() will follow, ctx: a list per name in `lists` when the forward saves, else None)"""
@@ -1139,7 +1181,8 @@ class DAnARCNN(nn.Module):
     def forward(self, im_data, im_info, gt_boxes, num_boxes, support_ims, all_cls_gt_boxes=None):
         """dana.py:87-220. The body is `_forward_gen`, a generator that pauses at the ONE host round trip of the
         training forward (the fg / bg counts the reference's np.random draws need): eagerly that is a D2H read, the
-        draws and one pinned upload right here; `graphs.GraphedDAnA` captures the two halves as hipGraphs instead."""
+        draws and one pinned upload right here; `graphs.GraphedDAnA` captures the two halves as hipGraphs instead.
+        im_data may be a QueryBatch (encode_query_bank): the batch's trunk maps are gathered, no query trunk runs."""
         gen = self._forward_gen(im_data, im_info, gt_boxes, num_boxes, support_ims)
         try:
             req = next(gen)
@@ -1147,7 +1190,7 @@ class DAnARCNN(nn.Module):
                 req = next(gen)
         except StopIteration as done:
             return done.value
-        drawn = ops.draw_and_upload(req, im_data.device)
+        drawn = ops.draw_and_upload(req, im_data.bank.device if isinstance(im_data, QueryBatch) else im_data.device)
         try:
             gen.send(drawn)
         except StopIteration as done:
@@ -1208,8 +1251,18 @@ class DAnARCNN(nn.Module):
     def _forward_setup(self, im_data, im_info, gt_boxes, support_ims):
         """checks the inputs, opens the saving-forward ctx and the support stream -> the forward's constants"""
         plan = self._get_plan()
-        dev = im_data.device
+        # a QueryBatch (qbank.batch(index)) in place of im_data: the query images are named by row of a QueryBank
+        qbatch = im_data if isinstance(im_data, QueryBatch) else None
+        dev, B = (qbatch.bank.device, qbatch.B) if qbatch is not None else (im_data.device, im_data.size(0))
         training = self.training
+        if qbatch is not None:
+            if training:
+                from . import backward as BW
+                if BW.first_trainable_stage(self) != 3:
+                    raise ValueError("a QueryBank batch in train mode needs every trunk stage frozen (build the model under "
+                                     "cfg.RESNET.FIXED_BLOCKS = 3): a bank row is a constant of the run only while layer1-3 "
+                                     "do not train, and no gradient can flow into a bank")
+            qbatch._check(self, dev)
         # a ClassSweep (cache.sweep(classes)): every query image against each of C cached sets, B*C problems p = b*C + c
         sweep = support_ims if isinstance(support_ims, ClassSweep) else None
         cache = sweep.cache if sweep is not None else (support_ims if isinstance(support_ims, SupportCache) else None)
@@ -1229,14 +1282,14 @@ class DAnARCNN(nn.Module):
                 raise ValueError("a SupportBank episode needs every trunk stage frozen (build the model under "
                                  "cfg.RESNET.FIXED_BLOCKS = 3): a bank row is a constant of the run only while layer1-3 do "
                                  "not train, and no support-map gradient can flow into a bank")
-            episode._check(self, dev, im_data.size(0))
+            episode._check(self, dev, B)
         if sweep is not None and cfg.POOLING_MODE != "align":
             raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
                                       "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
-        B = im_data.size(0)
         Cs = len(sweep) if sweep is not None else 1
-        f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, episode=episode, B=B, Cs=Cs,
+        f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, episode=episode, qbatch=qbatch,
+                            B=B, Cs=Cs,
                             NP=B * Cs,  # problems: the RPN stage from the attention on and the RoI stage run over them
                             im_info=im_info.data.float().contiguous(), gt_boxes=gt_boxes.data, shot=self.n_shot,
                             way=self.n_way if training else 1,  # eval reshapes supports as [*, n_shot] (dana.py:111)
@@ -1298,7 +1351,7 @@ class DAnARCNN(nn.Module):
                 rng = (int(self.rng_seed), 0)
         tr_ = cfg.TRAIN
         num_fg = int(tr_.RPN_FG_FRACTION * tr_.RPN_BATCHSIZE)
-        afh, afw = self._feat_size(im_data.size(2), im_data.size(3))
+        afh, afw = f.qbatch.bank.map_hw if f.qbatch is not None else self._feat_size(im_data.size(2), im_data.size(3))
         # host-RNG capture: this block is its own little graph, replayed on the side stream (graphs.py)
         side = main if (capturing and rng is None) else self._stream("targets", dev)
         gt_f = f.gt_boxes.float().contiguous()
@@ -1332,7 +1385,7 @@ class DAnARCNN(nn.Module):
         # alternating block by block on its own stream / single-stream) and everything that depends only on the supports
         # run on the support stream, concurrently with the query side.
         plan, dev, B, shot, ctx, main, sup_stream = f.plan, f.dev, f.B, f.shot, f.ctx, f.main, f.sup_stream
-        fh, fw = self._feat_size(im_data.size(2), im_data.size(3))
+        fh, fw = f.qbatch.bank.map_hw if f.qbatch is not None else self._feat_size(im_data.size(2), im_data.size(3))
         if f.cache is not None:
             # cached supports (encode_supports): the query-independent support side was computed once per support set;
             # one launch gathers image b's set into this forward's B-batched buffers (a sweep gathers B*C sets, the
@@ -1347,7 +1400,10 @@ class DAnARCNN(nn.Module):
                 ctx.update(shot=f.shot)
             sup = dict(fields, map=f.cache.sup_map, rpn_done=None, roi_done=None)
             corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
-            self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
+            if f.qbatch is not None:  # (a query bank: the trunk maps of the batch's rows into corr's first half, one launch)
+                f.qbatch._gather(corr)
+            else:
+                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
             f.mark("trunk (query + support)")
             return corr, (fh, fw), sup
         if f.episode is not None:
@@ -1367,8 +1423,11 @@ class DAnARCNN(nn.Module):
                 if ctx is not None:
                     ctx.update(s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
             corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
-            self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None,
-                            save_from=ctx["t"] if ctx is not None else 3)
+            if f.qbatch is not None:  # (both banks: no trunk launch in the iteration)
+                f.qbatch._gather(corr)
+            else:
+                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None,
+                                save_from=ctx["t"] if ctx is not None else 3)
             f.mark("trunk (query + support)")
             return corr, (fh, fw), dict(feat=None, map=(sh_, sw_), kp=kp, unary=unary, s_t=s_t, rpn_done=rpn_done,
                                         sp_pe=sp_pe)
@@ -1376,7 +1435,15 @@ class DAnARCNN(nn.Module):
         save_q, save_s = (ctx["q_saved"], ctx["s_saved"]) if ctx is not None else (None, None)
         save_from = ctx["t"] if ctx is not None else 3
         sup_stream.wait_event(f.inputs_ready)
-        if f.merge[0]:
+        if f.qbatch is not None:
+            # a query bank: one gather fills corr's first half; the support trunk runs as its own one-segment walk on the
+            # support stream, whatever the merge settings say (there is no query batch to merge with). In train mode the trunk
+            # is frozen (ctx["t"] == 3), so neither side saves anything
+            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
+            with ops.on_stream(sup_stream):
+                sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s, save_from=save_from)
+            f.qbatch._gather(corr)
+        elif f.merge[0]:
             _, (q, s), ((corr, _), (sfeat, _)) = self._drain(self._trunk_gen(
                 [im_data, sup_ims], plan, outs=[(None, 2048), (None, 1024)], saves=[save_q, save_s], side=sup_stream,
                 merge_from=f.merge[1], save_m=ctx["m_saved"] if ctx is not None else None, save_from=save_from))
@@ -2212,3 +2279,116 @@ class BankEpisode:
         written by ONE launch"""
         bank = self.bank
         return ops.bank_gather_episode(bank.map_pe, bank.pool_pe, bank._index[self._host.shape], self.B, self.way, shot)
+
+
+def resolve_query_batch(index, n_bank, B=None):
+    """The query rows of one batch, host only (no device): index [B] integers, entry b the bank row of query image b -> a
+    C-contiguous int32 array of that shape. Repeats are fine. B None: any batch size >= 1. ValueError: a device tensor, a
+    non-integer dtype, a wrong shape; IndexError: an entry outside [0, n_bank)."""
+    if torch.is_tensor(index):
+        if index.is_cuda:
+            raise ValueError("a query batch takes a host index (a numpy array, a list or a CPU tensor), not a device tensor: "
+                             "it is validated on the host and uploaded once")
+        index = index.numpy()
+    arr = np.asarray(index)
+    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
+        raise ValueError("a query batch's index holds integers (bank rows), got dtype %s" % arr.dtype)
+    if arr.ndim != 1 or arr.shape[0] < 1 or (B is not None and arr.shape[0] != int(B)):
+        raise ValueError("a query batch's index must be [%s] (per query image its bank row), got %s"
+                         % ("B" if B is None else int(B), arr.shape))
+    bad = arr[(arr < 0) | (arr >= int(n_bank))]
+    if bad.size:
+        raise IndexError("query batch: rows %s outside [0, %d)" % (sorted(set(int(v) for v in bad))[:8], int(n_bank)))
+    return np.array(arr, dtype=np.int32, order="C")  # (always a copy: the caller may go on writing its array)
+
+
+class QueryBank:
+    """The trunk maps of a pool of N query images of one H x W (DAnARCNN.encode_query_bank): maps [N][fh*fw][1024], what the
+    query trunk writes into the first half of corr. Over a frozen trunk (cfg.RESNET.FIXED_BLOCKS = 3) they are constants of a
+    fine-tuning run, as a SupportBank's rows are. `qb = bank.batch(index)` names the B images of a forward by bank row;
+    `model(qb, im_info, gt_boxes, num_boxes, support)` gathers them (one launch, dana_qbank_gather, index read on the device)
+    and runs no query trunk -- in train mode with support images or a BankEpisode, in eval mode with support images, a
+    SupportCache or a ClassSweep; `qb.set(index)` names the next forward's -- a recorded replay (program.ProgramTrainer)
+    follows it. The bank records what it was built under (the trunk's parameters and buffers, the MFMA and Winograd
+    settings, the device); using it after any of that changed raises ("re-encode"). Layer4, the RPN and the heads may move.
+    A trunk with stages that train (FIXED_BLOCKS < 3: eval-mode use only) is written by the fused optimizers through raw
+    pointers, which no tensor version shows, so there the bank also records the model's weight epoch: it is stale after every
+    optimizer step (and after a ProgramTrainer recording), i.e. it serves the forwards between two steps only."""
+
+    def __init__(self, model, maps, image_hw, map_hw, state, dev):
+        self._model = weakref.ref(model)
+        self.maps = maps
+        self.image_hw, self.map_hw, self.device = tuple(image_hw), tuple(map_hw), torch.device(dev)
+        self._state = state
+        self._index = {}       # B -> device int32 [B]: what dana_qbank_gather reads
+        self._index_host = {}  # ... and what it holds
+
+    def __len__(self):
+        return self.maps.size(0)
+
+    def nbytes(self):
+        return self.maps.numel() * self.maps.element_size()
+
+    def _check(self, model, dev):
+        if self._model() is not model:
+            raise RuntimeError("this QueryBank was encoded by another model: re-encode the images with this one")
+        if torch.device(dev) != self.device:
+            raise RuntimeError("this QueryBank lives on %s, the forward runs on %s: re-encode the images there" % (self.device, dev))
+        if model._qbank_state(dev) != self._state:
+            raise RuntimeError("the model changed since encode_query_bank (the trunk's weights or buffers, the MFMA mode or "
+                               "the Winograd settings; over a trunk with stages that train, any optimizer step or "
+                               "re-recording): re-encode the images")
+
+    def batch(self, index):
+        """-> QueryBatch over index [B] (`resolve_query_batch`)"""
+        return QueryBatch(self, index)
+
+    def _write_index(self, arr):
+        """arr into the device index of its B (allocated once per B: a recording points at it); one small asynchronous
+        upload on the current stream, as SupportBank._write_index's"""
+        key = arr.shape[0]
+        host = self._index_host.get(key)
+        if host is not None and np.array_equal(host, arr):
+            return
+        if SupportCache._active_recording():
+            raise RuntimeError("QueryBank: the batch changed inside a recording / capture: batch.set(index) before it")
+        if key not in self._index:
+            self._index[key] = torch.zeros((key,), dtype=torch.int32, device=self.device)
+        staged = torch.empty((key,), dtype=torch.int32, pin_memory=True)
+        staged.copy_(torch.from_numpy(arr))
+        self._index[key].copy_(staged, non_blocking=True)
+        self._index_host[key] = arr.copy()
+
+
+class QueryBatch:
+    """QueryBank.batch(index): the 1st argument of a forward, in place of im_data [B, 3, H, W] -- query image b is bank row
+    index[b]. B, the device and H x W come from the batch. The index lives in a device buffer the bank owns (one per B, shared
+    by the bank's batches of that size: the forward uploads a batch's index when the buffer holds another); `set(index)`
+    rewrites it for the next forward."""
+
+    __slots__ = ("bank", "B", "_host")
+
+    def __init__(self, bank, index):
+        self.bank = bank
+        self._host = resolve_query_batch(index, len(bank))
+        self.B = self._host.shape[0]
+        bank._write_index(self._host)
+
+    def set(self, index):
+        """the query images of the next forwards (same B), validated on the host and written into the device index"""
+        self._host = resolve_query_batch(index, len(self.bank), self.B)
+        self.bank._write_index(self._host)
+
+    @property
+    def index(self):
+        """the batch's host index [B] (a copy)"""
+        return self._host.copy()
+
+    def _check(self, model, dev):
+        self.bank._check(model, dev)
+        self.bank._write_index(self._host)  # (a no-op unless another batch of this size used the buffer since)
+
+    def _gather(self, corr):
+        """the batch's trunk maps into the first 1024 columns of corr [B*fh*fw][2048], ONE launch on the current stream"""
+        bank = self.bank
+        return ops.qbank_gather(bank.maps, bank._index[self.B], self.B, out=corr, ld_out=corr.size(1))

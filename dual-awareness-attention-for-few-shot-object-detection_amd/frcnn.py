@@ -68,6 +68,11 @@ class FasterRCNN(DAnARCNN):
                         "trains; fsod and fgn pool their own kernels; the plain Faster R-CNN has no support branch), so "
                         "DAnA's bank rows are not what their forwards read: train them from support images")
 
+    # a QueryBank replaces the query trunk call of DAnA's `_trunks`, which writes into corr; the siblings' forwards own their
+    # trunk calls and their own query-map buffers
+    _no_query_bank = ("the sibling detectors run their own trunk calls into their own query-map buffers (DAnA's bank rows "
+                      "are gathered into corr, which they do not have): run them from query images")
+
     def encode_supports(self, support_ims, num_shots=None):
         """support_ims [C, shot, 3, 320, 320] -> SupportCache of the model's per-set support tensors (`_cache_layout`),
         each set built by `_support_set` with the launches an uncached B = 1 eval forward issues for it. The forward takes

@@ -38,6 +38,14 @@ def _refuse_bank_episode(who, inputs):
                                   "eagerly" % who)
 
 
+def _refuse_query_batch(who, inputs):
+    from .dana import QueryBatch
+    if any(isinstance(t, QueryBatch) for t in inputs):
+        raise NotImplementedError("%s does not capture a QueryBank batch (hipGraph capture of a forward from a query bank is "
+                                  "unverified): replay the training iteration with program.ProgramTrainer(trainer, batch, "
+                                  "...), or run it eagerly" % who)
+
+
 class GraphedDAnA:
     """model(*inputs) as hipGraph replays. Inputs are copied into static buffers (skipped when the caller passes the
     static buffers themselves: `runner.inputs`); outputs are static tensors, valid until the next call.
@@ -47,6 +55,7 @@ class GraphedDAnA:
     changing any of them; for training use `GraphedTrainer`, whose graphs re-derive them from the live weights."""
 
     def __init__(self, model, *example_inputs, warmup=2):
+        _refuse_query_batch("GraphedDAnA", example_inputs)
         dev = example_inputs[0].device
         if dev.type != "cuda":
             raise RuntimeError("GraphedDAnA needs HIP tensors")
@@ -153,6 +162,7 @@ class GraphedTrainer:
         if not hasattr(self.model, "_forward_gen"):
             raise RuntimeError("GraphedTrainer drives DAnARCNN (the siblings train eagerly)")
         _refuse_bank_episode("GraphedTrainer", example_inputs)
+        _refuse_query_batch("GraphedTrainer", example_inputs)
         dev = example_inputs[0].device
         self.inputs = [_static_like(t) for t in example_inputs]
         self.stream = torch.cuda.Stream(device=dev)

@@ -1351,6 +1351,28 @@ def bank_gather_episode(map_pe, pool_pe, index, B, way, shot, s_pe=None, sp_pe=N
     return s_pe, sp_pe
 
 
+def qbank_gather(maps, index, B, out=None, ld_out=None):
+    """dana_qbank_gather: maps [N][rows][C] float32, index [B] int32 on the device -> out [B*rows][ld_out] with
+    out[b*rows + r][:C] = maps[index[b]][r] (columns C .. ld_out-1 keep what they held; an image whose index is outside [0, N)
+    keeps all of its rows). out None: a fresh buffer of row stride ld_out (default C)."""
+    _chk(maps, "maps")
+    _chk(index, "index", torch.int32)
+    if maps.dim() != 3:
+        raise ValueError("qbank_gather: maps [N][rows][C], got %s" % (tuple(maps.shape),))
+    N, rows, C = maps.shape
+    ld_out = C if ld_out is None else int(ld_out)
+    if index.numel() != B:
+        raise ValueError("qbank_gather: %d indices for B = %d images" % (index.numel(), B))
+    if ld_out < C:
+        raise ValueError("qbank_gather: ld_out %d is less than the %d channels of a row" % (ld_out, C))
+    if out is None:
+        out = torch.empty((B * rows, ld_out), dtype=torch.float32, device=maps.device)
+    if _chk(out, "out").numel() < B * rows * ld_out:
+        raise ValueError("qbank_gather: out must hold [%d][%d] floats" % (B * rows, ld_out))
+    lib().call("dana_qbank_gather", _p(maps), _p(index), N, B, rows, C, _p(out), ld_out, _stream())
+    return out
+
+
 def attn_softmax_unary_sweep(scores, out, unary, B, C, hw, nseg, length, ld_in, ld_out, kpad, unary_gamma, out_scale,
                              unary_stride=0):
     """class sweep: attn_softmax_unary_ over rows (b, i, c) of scores [B][hw][C][ld_in], written out of place to row

@@ -18,8 +18,12 @@ def shard_bounds(total, rank, world):
 
 def shard_episode(inputs, rank, world):
     """inputs = (im_data, im_info, gt_boxes, num_boxes, support_ims): slice dim 0 of each for `rank`."""
-    from .dana import BankEpisode
+    from .dana import BankEpisode, QueryBatch
     for t in inputs:
+        if isinstance(t, QueryBatch):
+            raise TypeError("shard_episode slices tensors; a QueryBank batch names rows of ONE device's bank and has no slice: "
+                            "every rank encodes its own bank (model.encode_query_bank) and draws the indices of its own "
+                            "share of the batch")
         if isinstance(t, BankEpisode):
             raise TypeError("shard_episode slices tensors; a SupportBank episode names rows of ONE device's bank and has no "
                             "slice: every rank encodes its own bank (model.encode_support_bank) and draws the indices of "

@@ -368,6 +368,22 @@ def _bank_episode(inputs):
     return next((t for t in inputs if isinstance(t, BankEpisode)), None)
 
 
+def _query_batch(inputs):
+    """the QueryBatch (dana.encode_query_bank) standing in for im_data, else None"""
+    from .dana import QueryBatch
+    return inputs[0] if inputs and isinstance(inputs[0], QueryBatch) else None
+
+
+def _query_device(inputs):
+    qb = _query_batch(inputs)
+    return qb.bank.device if qb is not None else inputs[0].device
+
+
+def _query_B(inputs):
+    qb = _query_batch(inputs)
+    return qb.B if qb is not None else inputs[0].size(0)
+
+
 class ProgramDAnA:
     """model(*inputs) as launch-program replays (train or eval mode, host or device RNG): the eager forward's launches on
     the eager forward's streams, minus its Python. Inputs are copied into static buffers (skipped when the caller passes
@@ -375,6 +391,9 @@ class ProgramDAnA:
     (mode, shapes, cfg, the weight-derived tensors of this moment): re-record after changing any of them."""
 
     def __init__(self, model, *example_inputs, warmup=2):
+        if _query_batch(example_inputs) is not None:
+            raise NotImplementedError("ProgramDAnA does not record a forward from a QueryBank batch (unverified): replay the "
+                                      "training iteration with ProgramTrainer(trainer, batch, ...), or run the forward eagerly")
         dev = example_inputs[0].device
         if dev.type != "cuda":
             raise RuntimeError("ProgramDAnA needs HIP tensors")
@@ -513,8 +532,11 @@ class ProgramTrainer:
         self.trainer, self.model = trainer, trainer.model
         if not hasattr(self.model, "_forward_gen"):
             raise RuntimeError("ProgramTrainer drives DAnARCNN (the siblings train eagerly)")
-        dev = example_inputs[0].device
+        dev = _query_device(example_inputs)
         self.inputs = [_static_like(t) for t in example_inputs]
+        # a QueryBatch in place of im_data (dana.encode_query_bank): no im_data holder is kept; the programs point at the
+        # bank's maps and at the device index of this batch size, which `batch.set(index)` rewrites between replays
+        self.qbatch = _query_batch(example_inputs)
         # a BankEpisode in place of support_ims (dana.encode_support_bank): the programs point at the bank's tensors and at
         # the device index of this episode's shape, which `ep.set(index)` rewrites between replays
         self.episode = _bank_episode(example_inputs)
@@ -541,7 +563,7 @@ class ProgramTrainer:
 
     def _record(self):
         tr, model = self.trainer, self.model
-        dev = self.inputs[0].device
+        dev = _query_device(self.inputs)
         import numpy as _np
         # the recording IS an eager iteration (its launches really run): parameters, momentum / both Adam moments and the host
         # RNG are put back behind it, so that constructing the runner does not move the training trajectory
@@ -550,6 +572,12 @@ class ProgramTrainer:
                 _np.random.get_state())
         tr.upload_hyper()      # the recorded iteration's optimizer reads the control block as every replay will
         model._get_plan()      # frozen-weight packs / BN folds are made ONCE, outside the program ...
+        # the recorded batch's / episode's index into its bank's device buffer BEFORE the recording opens (another batch of
+        # that size may have used the buffer since): inside it the forward's own check then finds nothing to upload
+        if self.qbatch is not None:
+            self.qbatch._check(model, dev)
+        if self.episode is not None:
+            self.episode._check(model, dev, _query_B(self.inputs))
         model._epoch += 1      # ... every trainable conv's derived tensors are re-derived INSIDE it, from the live weights
         prev_save = getattr(model, "save_for_backward", False)
         model.save_for_backward = True
@@ -632,7 +660,22 @@ class ProgramTrainer:
 
     def _check_episode(self, inputs):
         """a replay reads the recorded bank through the recorded index buffer: the caller's 5th argument must be an episode
-        of that bank and shape (its index of the moment is uploaded here if the buffer holds another episode's)"""
+        of that bank and shape (its index of the moment is uploaded here if the buffer holds another episode's). The same
+        holds for a QueryBatch as the 1st argument: a batch of the recorded QueryBank and size, or images where images were
+        recorded"""
+        qb = _query_batch(inputs)
+        if qb is not None or self.qbatch is not None:
+            if qb is None or self.qbatch is None:
+                raise RuntimeError("ProgramTrainer was recorded with %s and called with %s: re-record a runner for it" % (
+                    "query images" if self.qbatch is None else "a QueryBank batch",
+                    "query images" if qb is None else "a QueryBank batch"))
+            if qb.bank is not self.qbatch.bank:
+                raise RuntimeError("ProgramTrainer was recorded on a batch of another QueryBank (the programs point at that "
+                                   "bank's maps): re-record a runner for this one")
+            if qb.B != self.qbatch.B:
+                raise RuntimeError("ProgramTrainer was recorded on a query batch of %d images and called with %d: re-record a "
+                                   "runner for it" % (self.qbatch.B, qb.B))
+            qb._check(self.model, qb.bank.device)  # (raises "re-encode" after a trunk change; uploads the index if needed)
         ep = _bank_episode(inputs)
         if ep is None and self.episode is None:
             return
@@ -646,7 +689,7 @@ class ProgramTrainer:
         if ep._host.shape != self.episode._host.shape:
             raise RuntimeError("ProgramTrainer was recorded on a bank episode of shape %s and called with %s: re-record a "
                                "runner for it" % (self.episode._host.shape, ep._host.shape))
-        ep._check(self.model, self.inputs[0].device, self.inputs[0].size(0))  # (raises "re-encode" after a trunk change)
+        ep._check(self.model, _query_device(self.inputs), _query_B(self.inputs))  # (raises "re-encode" after a trunk change)
 
     def step(self, *inputs):
         self._check_episode(inputs)

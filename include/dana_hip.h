@@ -217,6 +217,14 @@ int dana_gather_shot_blocks(const void* src_ptrs, const void* dst_ptrs, const lo
 int dana_bank_gather_episode(const float* map_pe, const float* pool_pe, const int* index, int n_bank, int B, int way,
                              int shot, int map_rows, int pool_rows, int channels, float* s_pe, float* sp_pe,
                              dana_stream_t stream);
+/* Query bank (dana.QueryBank): the trunk maps of a pool of query images, maps [n_bank][rows][channels], encoded once over a
+ * frozen trunk. For b < B, r < rows, c < channels: out[(b*rows + r)*ld_out + c] = maps[index[b]][r][c]; columns
+ * channels .. ld_out-1 of out are not touched (out is corr [B*rows][ld_out], whose second half holds the attended rows).
+ * index [B] is read on the device, so a recorded replay gathers the batch of the moment; an index outside [0, n_bank) leaves
+ * its image's rows alone. One launch of 16-byte copies: channels % 4 == 0, ld_out % 4 == 0, ld_out >= channels, maps and out
+ * 16-byte aligned; B <= 65 535; rows * channels / 4 < 2^31 - 1024 (32-bit unit numbers in the kernel). */
+int dana_qbank_gather(const float* maps, const int* index, int n_bank, int B, int rows, int channels, float* out, int ld_out,
+                      dana_stream_t stream);
 
 /* ---- class sweep (dana.SupportCache.sweep): B query images x C cached support sets as B*C problems p = b*C + c, the
  * per-class forward of dana.py:87-220 for every class of an image (inference.py:70-140 fills all_boxes[j][i] with it).

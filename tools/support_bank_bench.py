@@ -1,7 +1,7 @@
 """The replayed fine-tuning iteration over a frozen trunk (cfg.RESNET.FIXED_BLOCKS = 3) at the BASELINE configs[2] shape
 (res50, BA on, way 2, shot 3, bs 4, 600x1000, weights seed 11, inputs seed 1996), from support images or from a support bank.
 
-    python tools/support_bank_bench.py --supports images|bank [--pool 64] [--steps 100]
+    python tools/support_bank_bench.py --supports images|bank [--queries images|bank] [--pool 64] [--steps 100]
 
 One run per process (the role streams take their hardware queues once per process). Prints one JSON line: ms per iteration
 timed as bench.py's trial() (3 warm steps, then the median GPU-side interval between consecutive iteration ends; two rounds,
@@ -11,7 +11,10 @@ many launches the two programs hold.
 `--supports bank`: a pool of `--pool` images (seed 1997) is encoded once (time and bytes reported); every timed iteration
 draws its B x way*shot bank rows with np.random (a cycle of 16 draws made in advance, so the training forward's own
 np.random stream is not moved), `ep.set(draw)`, then the replayed step: the loop of INTEGRATION.md.
-profiles/support_bank.md was made with it."""
+`--queries bank`: a pool of `--qpool` query images (seed 1998) is encoded once as a QueryBank (time and bytes reported, the
+gather alone timed into a corr-shaped buffer); every timed iteration draws its B bank rows from a cycle of 16 draws,
+`batch.set(draw)`, then the step. `--queries images` (the default) is the behaviour before the query bank.
+profiles/support_bank.md and profiles/query_bank.md were made with it."""
 import argparse
 import json
 import os
@@ -31,7 +34,9 @@ from cached_inference import trial  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--supports", default="images", choices=["images", "bank"])
+    ap.add_argument("--queries", default="images", choices=["images", "bank"])
     ap.add_argument("--pool", type=int, default=64)
+    ap.add_argument("--qpool", type=int, default=64)
     ap.add_argument("--launch", default="program", choices=["program", "eager"])
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--batch", type=int, default=4)
@@ -77,6 +82,34 @@ def main():
         bank_info.update(gather_us=round(e0.elapsed_time(e1) * 1e3 / 200, 2), gather_bytes_copied=moved)
         inputs = inputs[:4] + [ep]
         del pool
+    qbank_info, qb, qdraws = None, None, None
+    if args.queries == "bank":
+        qpool = S.normal("query_pool", (args.qpool, 3, args.height, args.width), 64.0, 0.0, 1998).to(dev)
+        model.encode_query_bank(qpool[:4])  # (warm: the weight plan, the allocator)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        qbank = model.encode_query_bank(qpool)
+        torch.cuda.synchronize()
+        qbank_info = {"pool": len(qbank), "encode_ms": round((time.perf_counter() - t0) * 1e3, 2), "nbytes": qbank.nbytes()}
+        del qpool
+        rng = np.random.RandomState(1998)
+        qdraws = [rng.randint(0, len(qbank), size=(args.batch,)) for _ in range(16)]
+        qb = qbank.batch(qdraws[0])
+        # the gather alone, back to back on one stream, into one corr-shaped buffer
+        corr = torch.empty((args.batch * qbank.maps.size(1), 2048), dtype=torch.float32, device=dev)
+        qgather = lambda: ops.qbank_gather(qbank.maps, qbank._index[args.batch], args.batch, out=corr, ld_out=2048)  # noqa: E731
+        for _ in range(10):
+            qgather()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(200):
+            qgather()
+        e1.record()
+        torch.cuda.synchronize()
+        qbank_info.update(gather_us=round(e0.elapsed_time(e1) * 1e3 / 200, 2),
+                          gather_bytes_copied=args.batch * qbank.maps[0].numel() * 4)
+        del corr
+        inputs = [qb] + inputs[1:]
     trainer = Trainer(model, lr=1e-5)
     np.random.seed(1996)
     trainer.step(*inputs)
@@ -93,6 +126,9 @@ def main():
     def step():
         if ep is not None:
             ep.set(draws[count[0] % len(draws)])
+        if qb is not None:
+            qb.set(qdraws[count[0] % len(qdraws)])
+        if ep is not None or qb is not None:
             count[0] += 1
         return run()
 
@@ -106,12 +142,12 @@ def main():
         step()
     host = (time.perf_counter() - t0 - ops.HOST_WAIT[0]) / k * 1e3
     torch.cuda.synchronize()
-    print(json.dumps({"label": args.label, "supports": args.supports, "fixed_blocks": cfg.RESNET.FIXED_BLOCKS,
+    print(json.dumps({"label": args.label, "supports": args.supports, "queries": args.queries, "fixed_blocks": cfg.RESNET.FIXED_BLOCKS,
                       "launch": args.launch, "steps": args.steps,
                       "shape": "%dx%d, B %d, way %d, shot %d" % (args.height, args.width, args.batch, way, shot),
                       "trainable_tensors": sum(p.requires_grad for p in model.parameters()),
                       "ms_per_step": round(min(rounds), 3), "ms_per_step_rounds": [round(r, 3) for r in rounds],
-                      "host_enqueue_ms_per_step": round(host, 3), "program_launches": launches, "bank": bank_info}))
+                      "host_enqueue_ms_per_step": round(host, 3), "program_launches": launches, "bank": bank_info, "query_bank": qbank_info}))
 
 
 if __name__ == "__main__":
