@@ -1686,8 +1686,16 @@ std::atomic<int>& epilogue_mode_cell() {
   return cell;
 }
 
+// The kernel instantiation of the most recent contraction launch (dana_debug_last_igemm_form; the encoding is documented in
+// include/dana_hip_debug.h). 0 = none yet. One relaxed store per launch of a compile-time constant.
+std::atomic<int> g_last_form(0);
+constexpr int form_code(int family, int bm, int bn, int stem, int bpre, int fuse, int elds, int nst, int apre, int df) {
+  return family | (bm / 64) << 4 | (bn / 64) << 6 | stem << 8 | bpre << 9 | fuse << 10 | elds << 11 | nst << 12 | apre << 16 | df << 17;
+}
+
 template <int BM, int BN, int STEM>
 int launch(const IgemmParams& p0, int batch, hipStream_t s) {
+  g_last_form.store(form_code(DANA_IGEMM_FAMILY_F32, BM, BN, STEM, 0, 0, 0, 0, 0, 0), std::memory_order_relaxed);
   IgemmParams p = p0;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
@@ -1709,6 +1717,8 @@ int launch_split(const IgemmParams& p0, int batch, hipStream_t s) {
   if constexpr (ELDS == 0 && FUSE == 0) {
     if (epilogue_mode_cell().load(std::memory_order_relaxed)) return launch_split<BM, BN, STEM, BPRE, 0, 1>(p0, batch, s);
   }
+  g_last_form.store(form_code(BM * BN >= 128 * 128 ? DANA_IGEMM_FAMILY_SPLIT_128 : DANA_IGEMM_FAMILY_SPLIT, BM, BN, STEM, BPRE, FUSE,
+                              ELDS, 0, 0, 0), std::memory_order_relaxed);
   IgemmParams p = p0;
   p.tiles_m = (p.M + BM - 1) / BM;
   p.tiles_n = (p.N + BN - 1) / BN;
@@ -1732,6 +1742,7 @@ int launch_split(const IgemmParams& p0, int batch, hipStream_t s) {
 
 template <int BN, int NST, int APRE, int DF = 0>
 int launch_dma(const IgemmParams& p0, int batch, hipStream_t s) {
+  g_last_form.store(form_code(DANA_IGEMM_FAMILY_DMA, 128, BN, 0, 1, 0, 0, NST, APRE, DF), std::memory_order_relaxed);
   IgemmParams p = p0;
   p.tiles_m = (p.M + 127) / 128;
   p.tiles_n = (p.N + BN - 1) / BN;
@@ -1756,8 +1767,8 @@ std::atomic<int>& mfma_mode_cell() {
   static std::atomic<int> cell(getenv("DANA_MFMA_SPLIT") ? atoi(getenv("DANA_MFMA_SPLIT")) : 1);
   return cell;
 }
-// An A/B knob from the environment, read ONCE per process (function-local statics at the call sites) and validated: an
-// unknown value is reported and ignored instead of silently meaning something else. -1 = not set.
+// An A/B knob from the environment, read ONCE per process (function-local statics below) and validated: an unknown value
+// is reported and ignored instead of silently meaning something else. -1 = not set.
 int env_choice(const char* name, std::initializer_list<int> allowed) {
   const char* e = getenv(name);
   if (!e || !*e) return -1;
@@ -1766,6 +1777,25 @@ int env_choice(const char* name, std::initializer_list<int> allowed) {
     if (a == v) return v;
   fprintf(stderr, "libdana_hip: %s=%s is not one of the accepted values; ignored\n", name, e);
   return -1;
+}
+// DANA_DMA_KERNEL / DANA_PP_STAGES: process-wide atomics like mfma_mode_cell(), initialised ONCE from the environment and
+// changed in-process by dana_debug_set_dma_kernel / dana_debug_set_pp_stages (-1 there = back to the environment's value).
+// dispatch() reads them once per launch; -1 = the dispatcher's own rule.
+int dma_kernel_env() {
+  static const int v = env_choice("DANA_DMA_KERNEL", {0, 1, 2});
+  return v;
+}
+std::atomic<int>& dma_kernel_cell() {
+  static std::atomic<int> cell(dma_kernel_env());
+  return cell;
+}
+int pp_stages_env() {
+  static const int v = env_choice("DANA_PP_STAGES", {2, 3, 4, 6, 13, 14});
+  return v;
+}
+std::atomic<int>& pp_stages_cell() {
+  static std::atomic<int> cell(pp_stages_env());
+  return cell;
 }
 unsigned long long* g_trace = nullptr;  // debug: per-block timestamps of the next split launches (dana_set_igemm_trace)
 
@@ -1779,10 +1809,10 @@ int dispatch(const IgemmParams& p, int batch, int stem, hipStream_t s) {
   // launch that cannot give most CUs one of those falls back to 64x64 blocks (measured: tools/conv_sweep.py).
   const int mode = mfma_mode_cell().load(std::memory_order_relaxed);
   if (p.apre) {
-    // planes x planes. DANA_PP_STAGES forces a form (tools/pp_probe.py, tests): 2 / 3 / 4 / 6 stages, 13 / 14 = 3 / 4 stages
+    // planes x planes. DANA_PP_STAGES / dana_debug_set_pp_stages forces a form (tools/pp_probe.py, tests): 2 / 3 / 4 / 6 stages, 13 / 14 = 3 / 4 stages
     // with two fragment sets. Default (profiles/r5_dma_kernel_probe.md): many tiles and a short K walk -> two stages, three
     // workgroups per CU; tile-starved or long-K launches -> three stages, two fragment sets.
-    static const int pp_env = env_choice("DANA_PP_STAGES", {2, 3, 4, 6, 13, 14});
+    const int pp_env = pp_stages_cell().load(std::memory_order_relaxed);
     const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * batch;
     const int stages = pp_env >= 0 ? pp_env : ((t128 < 400 || p.K >= 1024) ? 13 : 2);
     if (p.N <= 64) return stages == 2 ? launch_dma<64, 2, 1>(p, batch, s) : launch_dma<64, 3, 1>(p, batch, s);
@@ -1796,7 +1826,7 @@ int dispatch(const IgemmParams& p, int batch, int stem, hipStream_t s) {
   // pre-split weights, no ReLU-adjoint mask: the three-workgroups-per-CU kernel for the launches that took 128 x 128 tiles
   // (DANA_DMA_KERNEL=0: the round-4 kernel, for A/Bs; 2: wherever it can run, 64-wide tiles for N <= 64 -- tests)
   if (mode == 1 && p.bpre && !p.mask && p.KH * p.KW <= 32) {
-    static const int dm_env = env_choice("DANA_DMA_KERNEL", {0, 1, 2});
+    const int dm_env = dma_kernel_cell().load(std::memory_order_relaxed);
     const int dm = dm_env >= 0 ? dm_env : 1;
     if (dm == 2) return p.N <= 64 ? launch_dma<64, 2, 0>(p, batch, s) : launch_dma<128, 2, 0>(p, batch, s);
     if (dm == 1 && p.N > 64) {
@@ -1868,6 +1898,23 @@ int dana_debug_force_tile(int tile) {
   mfma_mode_cell().store(tile ? tile : 1, std::memory_order_relaxed);
   return DANA_OK;
 }
+
+int dana_debug_set_dma_kernel(int v) {
+  DANA_CHECK_ARG(v >= -1 && v <= 2, "dana_debug_set_dma_kernel: -1 (environment / default), 0 (split kernel), 1 (measured rule) or 2 (wherever it runs)");
+  dma_kernel_cell().store(v < 0 ? dma_kernel_env() : v, std::memory_order_relaxed);
+  return DANA_OK;
+}
+int dana_debug_get_dma_kernel(void) { return dma_kernel_cell().load(std::memory_order_relaxed); }
+
+int dana_debug_set_pp_stages(int v) {
+  DANA_CHECK_ARG(v == -1 || v == 2 || v == 3 || v == 4 || v == 6 || v == 13 || v == 14,
+                 "dana_debug_set_pp_stages: -1 (environment / default), 2, 3, 4, 6, 13 or 14");
+  pp_stages_cell().store(v < 0 ? pp_stages_env() : v, std::memory_order_relaxed);
+  return DANA_OK;
+}
+int dana_debug_get_pp_stages(void) { return pp_stages_cell().load(std::memory_order_relaxed); }
+
+int dana_debug_last_igemm_form(void) { return g_last_form.load(std::memory_order_relaxed); }
 
 int dana_set_igemm_trace(unsigned long long* buffer) {
   g_trace = buffer;

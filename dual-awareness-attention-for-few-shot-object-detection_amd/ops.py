@@ -4,6 +4,8 @@ PyTorch is used here only for device memory and streams: every function hands ra
 and the current HIP stream to a hand-written gfx950 kernel. Non-CUDA tensors are rejected -- there
 is no CPU fallback on the product path.
 """
+import collections
+import contextlib
 import ctypes
 import time as _time
 
@@ -947,6 +949,66 @@ def set_epilogue_mode(mode):
     prev = lib().query("dana_get_epilogue_mode")
     lib().call("dana_set_epilogue_mode", int(mode))
     return prev
+
+
+def set_dma_kernel(v):
+    """debug (include/dana_hip_debug.h: dana_debug_set_dma_kernel): 0 = never the DMA kernel on fp32 activation rows, 1 = the
+    measured rule, 2 = wherever it can run, -1 = back to DANA_DMA_KERNEL / the default. Returns the previous value."""
+    prev = lib().query("dana_debug_get_dma_kernel")
+    lib().call("dana_debug_set_dma_kernel", int(v))
+    return prev
+
+
+def get_dma_kernel():
+    return lib().query("dana_debug_get_dma_kernel")
+
+
+def set_pp_stages(v):
+    """debug (dana_debug_set_pp_stages): the planes x planes form, 2 / 3 / 4 / 6 stages, 13 / 14 = 3 / 4 stages with two
+    fragment sets, -1 = back to DANA_PP_STAGES / the dispatcher's rule. Returns the previous value."""
+    prev = lib().query("dana_debug_get_pp_stages")
+    lib().call("dana_debug_set_pp_stages", int(v))
+    return prev
+
+
+def get_pp_stages():
+    return lib().query("dana_debug_get_pp_stages")
+
+
+IgemmForm = collections.namedtuple("IgemmForm", "family bm bn stem bpre fuse elds nst apre df")
+_IGEMM_FAMILIES = {0: None, 1: "f32", 2: "split", 3: "split_128", 4: "dma"}
+
+
+def decode_igemm_form(code):
+    """the int of dana_debug_last_igemm_form (bit layout: include/dana_hip_debug.h) -> IgemmForm"""
+    return IgemmForm(_IGEMM_FAMILIES[code & 15], (code >> 4 & 3) * 64, (code >> 6 & 3) * 64, code >> 8 & 1, code >> 9 & 1,
+                     code >> 10 & 1, code >> 11 & 1, code >> 12 & 15, code >> 16 & 1, code >> 17 & 1)
+
+
+def last_igemm_form():
+    """debug: which kernel instantiation the most recent conv / GEMM launch of this process took (family None: none yet)"""
+    return decode_igemm_form(lib().query("dana_debug_last_igemm_form"))
+
+
+@contextlib.contextmanager
+def igemm_forms(tile=0, dma=-1, pp=-1, epilogue=0):
+    """debug: force the contraction kernels' form inside the block (force_tile / set_dma_kernel / set_pp_stages /
+    set_epilogue_mode) and put all four back on exit. A forced tile needs the split kernel (set_mfma_mode(1)); it is not
+    readable back, so the block leaves the dispatcher's own tile choice behind."""
+    prev_dma, prev_pp, prev_epi = get_dma_kernel(), get_pp_stages(), lib().query("dana_get_epilogue_mode")
+    try:
+        if tile:
+            force_tile(tile)
+        set_dma_kernel(dma)
+        set_pp_stages(pp)
+        set_epilogue_mode(epilogue)
+        yield
+    finally:
+        if tile:
+            force_tile(0)
+        lib().call("dana_debug_set_dma_kernel", prev_dma)
+        lib().call("dana_debug_set_pp_stages", prev_pp)
+        set_epilogue_mode(prev_epi)
 
 
 SPLIT_K = True  # split-K for tile-starved GEMMs (few tiles, long K); tools flip it for A/Bs

@@ -21,6 +21,31 @@ int dana_debug_force_tile(int tile);
  * (tests/test_gpu_contractions.py uses mode 1 as the reference of test_register_epilogue_*). */
 int dana_set_epilogue_mode(int mode);
 int dana_get_epilogue_mode(void);
+/* Kernel choice of the contractions on pre-split weights, in-process (the environment's DANA_DMA_KERNEL / DANA_PP_STAGES
+ * only give these two process-wide atomics their initial value, once). Every launch reads them when it is issued.
+ *  dma kernel: 0 = never the DMA kernel on fp32 activation rows (the split kernel of round 4), 1 = the measured rule
+ *    (default), 2 = the DMA kernel wherever it can run (64-wide tiles for N <= 64).
+ *  pp stages (planes x planes launches, DANA_A_SPLIT3): 2 / 3 / 4 / 6 staging stages, 13 / 14 = 3 / 4 stages with two
+ *    fragment sets; launches with N <= 64 have two forms only (2 -> two stages, every other value -> three).
+ * v = -1 returns to the environment's value, or without one to the dispatcher's own rule (the getters then return -1).
+ * Any other value is refused. */
+int dana_debug_set_dma_kernel(int v);
+int dana_debug_get_dma_kernel(void);
+int dana_debug_set_pp_stages(int v);
+int dana_debug_get_pp_stages(void);
+/* Which kernel instantiation the most recent conv / GEMM launch of this process took (stored when the launch is issued;
+ * 0 = none yet; the skinny N <= 8 GEMM and the Winograd transforms are not contractions of this family and leave it):
+ *   bits  0..3  family (DANA_IGEMM_FAMILY_*: f32-MFMA kernel, igemm_split_kernel, igemm_split_kernel_128, igemm_dma_kernel)
+ *   bits  4..5  BM / 64        bits  6..7  BN / 64
+ *   bit   8     STEM           bit   9     BPRE (weights as split planes; always 1 for the dma family)
+ *   bit  10     FUSE           bit  11     ELDS (epilogue through an LDS C tile)
+ *   bits 12..15 NST (dma family: staging stages; 0 elsewhere)
+ *   bit  16     APRE (dma family: activation rows as split planes)      bit 17  DF (dma family: two fragment sets) */
+#define DANA_IGEMM_FAMILY_F32 1
+#define DANA_IGEMM_FAMILY_SPLIT 2
+#define DANA_IGEMM_FAMILY_SPLIT_128 3
+#define DANA_IGEMM_FAMILY_DMA 4
+int dana_debug_last_igemm_form(void);
 /* While `buffer` is non-null every split-kernel block writes eight 64-bit words {shader-clock at start, at the first
  * K-step, after the K loop, at the end, HW_ID, 100 MHz wall clock at the end, wall clock at the start, 0} at
  * buffer[(z * grid + block) * 8]. The pointer is read when a launch is ISSUED, so two launches issued with two buffers can

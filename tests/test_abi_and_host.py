@@ -37,7 +37,8 @@ def test_library_exports_every_declared_symbol():
     # is declared by the drop-in ABI
     dbg = _lib.parse_header(_lib.DEBUG_HEADER)
     assert {"dana_set_epilogue_mode", "dana_set_sort_mode", "dana_set_igemm_trace", "dana_debug_force_tile",
-            "dana_debug_stream_create_cumask"} <= set(dbg)
+            "dana_debug_stream_create_cumask", "dana_debug_set_dma_kernel", "dana_debug_get_dma_kernel",
+            "dana_debug_set_pp_stages", "dana_debug_get_pp_stages", "dana_debug_last_igemm_form"} <= set(dbg)
     assert not set(dbg) & set(protos)
     for name in dbg:
         assert hasattr(cdll, name), "libdana_hip.so does not export %s" % name
@@ -153,6 +154,57 @@ def test_mfma_mode_switch_roundtrip_and_errors():
                ctypes.cast(ctypes.byref(out), ctypes.c_void_p))
     assert ops.get_mfma_mode() == 1
     ops.set_mfma_mode(prev)
+
+
+def _selectors_in_a_child(**env):
+    """(dma kernel, pp stages, stderr) as a fresh process started with `env` reports them"""
+    import subprocess
+    code = ("import sys; sys.path.insert(0, %r); from dana_amd import ops; "
+            "print(ops.get_dma_kernel(), ops.get_pp_stages())" % ROOT)
+    clean = {k: v for k, v in os.environ.items() if k not in ("DANA_DMA_KERNEL", "DANA_PP_STAGES")}
+    pr = subprocess.run([sys.executable, "-c", code], env=dict(clean, **env), stdout=subprocess.PIPE, stderr=subprocess.PIPE,
+                        timeout=120)
+    assert pr.returncode == 0, pr.stderr.decode()
+    dm, pp = pr.stdout.split()
+    return int(dm), int(pp), pr.stderr.decode()
+
+
+def test_contraction_form_selectors_roundtrip_errors_and_environment():
+    """dana_debug_set_dma_kernel / dana_debug_set_pp_stages (host-side state only): the setters change what the getters
+    report, refuse values the environment variables would not accept either, -1 returns to the value the process started
+    with; DANA_DMA_KERNEL / DANA_PP_STAGES give a fresh process its initial values, an unknown one is reported and ignored"""
+    L = _lib.lib()
+    dm0, pp0 = ops.get_dma_kernel(), ops.get_pp_stages()
+    try:
+        for v in (0, 1, 2):
+            prev = ops.get_dma_kernel()
+            assert ops.set_dma_kernel(v) == prev and ops.get_dma_kernel() == v
+        for v in (2, 3, 4, 6, 13, 14):
+            prev = ops.get_pp_stages()
+            assert ops.set_pp_stages(v) == prev and ops.get_pp_stages() == v
+        for bad in (3, -2, 13):
+            with pytest.raises(_lib.DanaError, match="dana_debug_set_dma_kernel"):
+                L.call("dana_debug_set_dma_kernel", bad)
+        for bad in (5, 0, 1, -2, 7, 15):
+            with pytest.raises(_lib.DanaError, match="dana_debug_set_pp_stages"):
+                L.call("dana_debug_set_pp_stages", bad)
+        assert (ops.get_dma_kernel(), ops.get_pp_stages()) == (2, 14)  # a refused value changes nothing
+        ops.set_dma_kernel(-1)
+        ops.set_pp_stages(-1)
+        assert (ops.get_dma_kernel(), ops.get_pp_stages()) == (dm0, pp0)
+        with ops.igemm_forms(dma=0, pp=13, epilogue=1):
+            assert (ops.get_dma_kernel(), ops.get_pp_stages(), L.query("dana_get_epilogue_mode")) == (0, 13, 1)
+        assert (ops.get_dma_kernel(), ops.get_pp_stages(), L.query("dana_get_epilogue_mode")) == (dm0, pp0, 0)
+    finally:
+        ops.set_dma_kernel(-1)
+        ops.set_pp_stages(-1)
+    f = ops.decode_igemm_form(4 | 2 << 4 | 1 << 6 | 1 << 9 | 3 << 12 | 1 << 16 | 1 << 17)
+    assert f == ops.IgemmForm("dma", 128, 64, 0, 1, 0, 0, 3, 1, 1)
+    assert ops.decode_igemm_form(3 | 2 << 4 | 2 << 6 | 1 << 11).family == "split_128"
+    assert _selectors_in_a_child()[:2] == (-1, -1)
+    assert _selectors_in_a_child(DANA_DMA_KERNEL="2", DANA_PP_STAGES="13")[:2] == (2, 13)
+    dm, pp, err = _selectors_in_a_child(DANA_PP_STAGES="5")
+    assert (dm, pp) == (-1, -1) and "DANA_PP_STAGES=5 is not one of the accepted values; ignored" in err
 
 
 def test_ops_refuse_cpu_tensors():

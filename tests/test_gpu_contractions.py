@@ -468,17 +468,23 @@ def test_register_epilogue_gives_the_lds_epilogues_bits(dev, shape):
     assert torch.isfinite(outs[1]).all() and torch.equal(outs[0], outs[1])
 
 
-def _with_env(name, value, fn):
-    import os
-    prev = os.environ.get(name)
-    os.environ[name] = value
-    try:
-        return fn()
-    finally:
-        if prev is None:
-            os.environ.pop(name, None)
-        else:
-            os.environ[name] = prev
+def _forced(fn, dma=-1, pp=-1):
+    """fn() under ops.igemm_forms(dma=, pp=) -> (its result, the form its LAST launch recorded)"""
+    from dana_amd import ops
+    with ops.igemm_forms(dma=dma, pp=pp):
+        got = fn()
+        return got, ops.last_igemm_form()
+
+
+# dispatch()'s map of a planes x planes stage value to igemm_dma_kernel<BN, NST, 1, DF>: N > 64 has a form per value, N <= 64
+# two stages or three
+_PP_FORMS = {2: (2, 0), 3: (3, 0), 4: (4, 0), 6: (6, 0), 13: (3, 1), 14: (4, 1)}
+
+
+def _pp_form(n, stages):
+    if n <= 64:
+        return (64, 2 if stages == 2 else 3, 0)
+    return (128,) + _PP_FORMS[stages]
 
 
 @pytest.mark.parametrize("case", CONV_CASES + [(1, 40, 50, 64, 64, 3, 1, 1, True, False), (2, 31, 33, 128, 160, 3, 2, 1, True, True)])
@@ -506,8 +512,10 @@ def test_dma_kernel_gives_the_split_kernels_bits_on_convs(dev, case):
         torch.cuda.synchronize()
         return o1, wide
 
-    old = _with_env("DANA_DMA_KERNEL", "0", run)
-    new = _with_env("DANA_DMA_KERNEL", "2", run)
+    old, f_old = _forced(run, dma=0)
+    new, f_new = _forced(run, dma=2)
+    assert f_old.family in ("split", "split_128") and f_old.bpre == 1, f_old
+    assert (f_new.family, f_new.apre, f_new.bn, f_new.nst) == ("dma", 0, 64 if Cout <= 64 else 128, 2), f_new
     assert torch.isfinite(new[0]).all()
     assert torch.equal(old[0], new[0]) and torch.equal(old[1], new[1])
 
@@ -518,7 +526,6 @@ def test_dma_kernel_gives_the_split_kernels_bits_on_convs(dev, case):
 def test_dma_kernel_gives_the_split_kernels_bits_on_gemms(dev, shape):
     """... and on GEMM-type launches: fp32 activation rows (APRE = 0) AND the activation rows as split planes (APRE = 1, two /
     three / four / six stages), batched and ragged"""
-    import os
     from dana_amd import ops
     if ops.get_mfma_mode() == 0:
         pytest.skip("split kernel only")
@@ -546,12 +553,15 @@ def test_dma_kernel_gives_the_split_kernels_bits_on_gemms(dev, shape):
         torch.cuda.synchronize()
         return out
 
-    old = _with_env("DANA_DMA_KERNEL", "0", run)
-    new = _with_env("DANA_DMA_KERNEL", "2", run)
+    old, f_old = _forced(run, dma=0)
+    new, f_new = _forced(run, dma=2)
+    assert f_old.family in ("split", "split_128") and f_old.bpre == 1, f_old
+    assert (f_new.family, f_new.apre, f_new.bn, f_new.nst) == ("dma", 0, 64 if n <= 64 else 128, 2), f_new
     assert torch.isfinite(new).all() and torch.equal(old, new)
-    for st in ("2", "3", "4", "6", "13", "14"):  # (1x: two fragment sets)
-        pp = _with_env("DANA_PP_STAGES", st, lambda: run(True))
-        assert torch.equal(old, pp), "planes x planes, %s stages" % st
+    for st in (2, 3, 4, 6, 13, 14):  # (1x: two fragment sets)
+        pp, f_pp = _forced(lambda: run(True), pp=st)
+        assert (f_pp.family, f_pp.apre) == ("dma", 1) and (f_pp.bn, f_pp.nst, f_pp.df) == _pp_form(n, st), (st, f_pp)
+        assert torch.equal(old, pp), "planes x planes, %d stages" % st
 
 
 @pytest.mark.parametrize("case", CONV_CASES)

@@ -16,6 +16,16 @@ pytestmark = pytest.mark.gpu
 HW = 8 * 10  # rows of one 128x160 image's trunk map
 
 
+@pytest.fixture
+def split_default():
+    """the launch counts and the refusal after a mode change are stated for a process whose default kernel is the bf16x6
+    split kernel: pin it, whatever DANA_MFMA_SPLIT says"""
+    from dana_amd import ops
+    prev = ops.set_mfma_mode(1)
+    yield
+    ops.set_mfma_mode(prev)
+
+
 # ---- 1. the gather alone ------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shape", [(1, 3, 3, 8, 16), (3, 4, 7, 12, 12), (2, 5, 80, 1024, 2048), (1, 2, 2394, 1024, 2048)],
                          ids=lambda v: "B%d-N%d-rows%d-C%d-ld%d" % v)
@@ -112,6 +122,7 @@ def test_bank_rows_are_what_the_forward_computes(dev, shot):
     _losses_agree(out_p, ref_p)
 
 
+@pytest.mark.usefixtures("split_default")
 # ---- 3. launch lists --------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("shot", [1, 2])
 def test_query_batch_forward_issues_one_gather_and_no_query_trunk(dev, shot):
@@ -251,6 +262,7 @@ def test_eval_forwards_from_a_query_batch(dev, shot):
     _close_eval(out, ref)
 
 
+@pytest.mark.usefixtures("split_default")
 # ---- 6. refusals and staleness ----------------------------------------------------------------------------------------------
 def test_refusals(dev):
     import dana_amd

@@ -1,6 +1,8 @@
 """planes x planes kernel (igemm_pp_kernel: both operands pre-split, LDS-DMA staging, 2 or 3 stages) against the split kernel
 (fp32 activation rows split in the K loop, pre-split weights) on the step's GEMM-type shapes: bit equality and duration
-(median of event-bracketed launches, interleaved, each launch alone on the chip).
+(median of event-bracketed launches, interleaved, each launch alone on the chip). The forms are selected in-process
+(ops.set_dma_kernel / ops.set_pp_stages: the environment variables are read once per process) and checked through
+ops.last_igemm_form().
 usage: python tools/pp_probe.py [out.md]"""
 import os, sys, torch
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -55,38 +57,38 @@ for name, m, n, k, b, res in SHAPES:
         else:
             ops.gemm_nt(a3, w3, m, n, k, out=o_pp, ldc=n, scale=sc, shift=sh, residual=r, relu=True)
 
-    STAGES = ("2", "3", "4", "6", "13", "14")
+    STAGES = (2, 3, 4, 6, 13, 14)
     t = {"split": [], "dma": []}
-    t.update({"pp" + st: [] for st in STAGES})
+    t.update({"pp%d" % st: [] for st in STAGES})
     same = {}
-    os.environ["DANA_DMA_KERNEL"] = "0"
+    ops.set_dma_kernel(0)
     run_split()
     torch.cuda.synchronize()
     o_old = o_ref.clone()
-    os.environ["DANA_DMA_KERNEL"] = "2"
+    ops.set_dma_kernel(2)
     o_ref.fill_(float("nan"))
     run_split()
     torch.cuda.synchronize()
-    same["dma"] = bool(torch.equal(o_ref, o_old))
+    same["dma"] = bool(torch.equal(o_ref, o_old)) and ops.last_igemm_form().family == "dma"
     for st in STAGES:
-        os.environ["DANA_PP_STAGES"] = st
+        ops.set_pp_stages(st)
         o_pp.fill_(float("nan"))
         run_pp()
         torch.cuda.synchronize()
-        same[st] = bool(torch.equal(o_old, o_pp))
+        same[st] = bool(torch.equal(o_old, o_pp)) and ops.last_igemm_form().apre == 1
     for _ in range(ROUNDS):
-        os.environ["DANA_DMA_KERNEL"] = "0"
+        ops.set_dma_kernel(0)
         t["split"].append(bracket(run_split))
-        os.environ["DANA_DMA_KERNEL"] = "2"
+        ops.set_dma_kernel(2)
         t["dma"].append(bracket(run_split))
         for st in STAGES:
-            os.environ["DANA_PP_STAGES"] = st
-            t["pp" + st].append(bracket(run_pp))
+            ops.set_pp_stages(st)
+            t["pp%d" % st].append(bracket(run_pp))
     med = {k_: sorted(v)[len(v) // 2] for k_, v in t.items()}
     rows.append((name, m, n, k, b, 2.0 * b * m * n * k / 1e9, med, same))
 L = ["| shape | GF | round-4 split kernel (2/CU) us | dma kernel, fp32 rows (3/CU) us | planes x planes 2 stages (3/CU) | 3 stages (2/CU) | 4 stages (1/CU) | 6 stages (1/CU) | 3 stages + 2 fragment sets | 4 stages + 2 fragment sets | dma / split | best planes / split | same bits |", "|---|---|---|---|---|---|---|---|---|---|---|---|---|"]
 for name, m, n, k, b, gf, med, same in rows:
-    best = min(med["pp" + st_] for st_ in STAGES)
+    best = min(med["pp%d" % st_] for st_ in STAGES)
     L.append("| %s M=%d N=%d K=%d b%d | %.2f | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f | %.1f | %.2f | %.2f | %s |" % (
         name, m, n, k, b, gf, med["split"], med["dma"], med["pp2"], med["pp3"], med["pp4"], med["pp6"], med["pp13"], med["pp14"], med["dma"] / med["split"],
         best / med["split"], "yes" if all(same.values()) else "NO %s" % same))
