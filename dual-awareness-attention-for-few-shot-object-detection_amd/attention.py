@@ -24,8 +24,9 @@ from collections import namedtuple
 import torch
 
 from . import ops
+from .cached_inputs import read_inputs
 from .config import cfg
-from .dana import ATTENTION_LEVELS, ClassSweep, DAnARCNN, SupportCache
+from .dana import ATTENTION_LEVELS, DAnARCNN
 
 AttentionMaps = namedtuple("AttentionMaps", ATTENTION_LEVELS)
 
@@ -116,8 +117,8 @@ def attention_maps(model, im_data, im_info, boxes, support, levels=ATTENTION_LEV
     the eval forward takes as its 5th argument (support images, a SupportCache selection, a ClassSweep)
     -> AttentionMaps(ba, rpn, roi) of float32 device tensors (module docstring); a level not in `levels` is None. `ba`
     needs support images and the BA block: without them it is None, or a ValueError when `levels` names it explicitly."""
-    from .dana import QueryBatch
-    if isinstance(im_data, QueryBatch):
+    qbatch, cache, _, _ = read_inputs(im_data, support)
+    if qbatch is not None:
         raise TypeError("attention_maps takes the query images themselves (im_data [B, 3, H, W]), not a QueryBatch: the maps "
                         "are an inspection tool and run the trunk")
     explicit = levels is not ATTENTION_LEVELS
@@ -127,7 +128,7 @@ def attention_maps(model, im_data, im_info, boxes, support, levels=ATTENTION_LEV
     if model.training:
         raise RuntimeError("attention_maps runs in eval mode (model.eval()): it reads the weights of an eval forward")
     want_ba = "ba" in levels
-    if want_ba and (isinstance(support, (SupportCache, ClassSweep)) or not model.semantic_enhance):
+    if want_ba and (cache is not None or not model.semantic_enhance):
         if explicit:
             raise ValueError("attention_maps: level 'ba' needs support images and a model with the BA block "
                              "(semantic_enhance): a SupportCache stores the BA-enhanced rows, not the weights")

@@ -18,7 +18,6 @@ Data layout in HBM (all fp32):
 import contextlib
 import math
 import time
-import weakref
 from types import SimpleNamespace
 
 import numpy as np
@@ -29,6 +28,9 @@ import torch.nn.functional as F
 from . import ops
 from .config import cfg
 from . import targets as T
+from .cached_inputs import (BankEpisode, ClassSweep, QueryBank, QueryBatch, SupportBank, SupportCache,  # noqa: F401
+                            check_cached_forward, query_batch_size, query_device, read_inputs, resolve_bank_episode,
+                            resolve_query_batch, resolve_shot_views)  # (the handles live there; importable from here as before)
 
 
 # ------------------------------------------------------------------------------------------------
@@ -1006,6 +1008,20 @@ class DAnARCNN(nn.Module):
         return (str(dev), self.use_winograd, self.winograd_min_cin, self.winograd_tile, ops.get_mfma_mode(),
                 self.presplit_weights) + tuple(t._version for t in cached[1])
 
+    @staticmethod
+    def _check_bank_images(who, layout, images, chunk, default_chunk):
+        """the argument checks of the two bank encoders -> (N, device, images per trunk run)"""
+        if not torch.is_tensor(images) or images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
+            raise ValueError("%s: images must be %s with N >= 1, got %s"
+                             % (who, layout, tuple(images.shape) if torch.is_tensor(images) else type(images)))
+        if not images.is_cuda:
+            raise RuntimeError("images must be a CUDA (HIP) tensor: this build has no CPU path")
+        N = images.size(0)
+        chunk = min(N, default_chunk) if chunk is None else int(chunk)
+        if chunk < 1:
+            raise ValueError("%s: chunk must be >= 1, got %d" % (who, chunk))
+        return N, images.device, chunk
+
     def encode_support_bank(self, images, chunk=None):
         """images [N, 3, 320, 320] (the support pool of a fine-tuning run: finetune_loader.py:59-74 keeps K exemplars per
         novel class and samples from them) -> SupportBank: per pool image the two support-side tensors that depend on
@@ -1017,15 +1033,7 @@ class DAnARCNN(nn.Module):
         only."""
         if self._no_support_bank is not None:
             raise NotImplementedError("encode_support_bank: " + self._no_support_bank)
-        if not torch.is_tensor(images) or images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
-            raise ValueError("encode_support_bank: images must be [N, 3, S, S] with N >= 1, got %s"
-                             % (tuple(images.shape) if torch.is_tensor(images) else type(images)))
-        if not images.is_cuda:
-            raise RuntimeError("images must be a CUDA (HIP) tensor: this build has no CPU path")
-        N, dev = images.size(0), images.device
-        chunk = min(N, 16) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError("encode_support_bank: chunk must be >= 1, got %d" % chunk)
+        N, dev, chunk = self._check_bank_images("encode_support_bank", "[N, 3, S, S]", images, chunk, 16)
         P2 = cfg.POOLING_SIZE * cfg.POOLING_SIZE
         sh_, sw_ = self._feat_size(images.size(2), images.size(3))
         self._check_support_map(sh_, sw_)
@@ -1057,15 +1065,7 @@ class DAnARCNN(nn.Module):
         9.8 MB."""
         if self._no_query_bank is not None:
             raise NotImplementedError("encode_query_bank: " + self._no_query_bank)
-        if not torch.is_tensor(images) or images.dim() != 4 or images.size(1) != 3 or images.size(0) < 1:
-            raise ValueError("encode_query_bank: images must be [N, 3, H, W] with N >= 1, got %s"
-                             % (tuple(images.shape) if torch.is_tensor(images) else type(images)))
-        if not images.is_cuda:
-            raise RuntimeError("images must be a CUDA (HIP) tensor: this build has no CPU path")
-        N, dev = images.size(0), images.device
-        chunk = min(N, 4) if chunk is None else int(chunk)
-        if chunk < 1:
-            raise ValueError("encode_query_bank: chunk must be >= 1, got %d" % chunk)
+        N, dev, chunk = self._check_bank_images("encode_query_bank", "[N, 3, H, W]", images, chunk, 4)
         H, W = images.size(2), images.size(3)
         fh, fw = self._feat_size(H, W)
         with torch.no_grad():
@@ -1190,7 +1190,7 @@ class DAnARCNN(nn.Module):
                 req = next(gen)
         except StopIteration as done:
             return done.value
-        drawn = ops.draw_and_upload(req, im_data.bank.device if isinstance(im_data, QueryBatch) else im_data.device)
+        drawn = ops.draw_and_upload(req, query_device(im_data))
         try:
             gen.send(drawn)
         except StopIteration as done:
@@ -1252,8 +1252,8 @@ class DAnARCNN(nn.Module):
         """checks the inputs, opens the saving-forward ctx and the support stream -> the forward's constants"""
         plan = self._get_plan()
         # a QueryBatch (qbank.batch(index)) in place of im_data: the query images are named by row of a QueryBank
-        qbatch = im_data if isinstance(im_data, QueryBatch) else None
-        dev, B = (qbatch.bank.device, qbatch.B) if qbatch is not None else (im_data.device, im_data.size(0))
+        qbatch, cache, sweep, episode = read_inputs(im_data, support_ims)
+        dev, B = query_device(im_data), query_batch_size(im_data)
         training = self.training
         if qbatch is not None:
             if training:
@@ -1263,16 +1263,11 @@ class DAnARCNN(nn.Module):
                                      "cfg.RESNET.FIXED_BLOCKS = 3): a bank row is a constant of the run only while layer1-3 "
                                      "do not train, and no gradient can flow into a bank")
             qbatch._check(self, dev)
-        # a ClassSweep (cache.sweep(classes)): every query image against each of C cached sets, B*C problems p = b*C + c
-        sweep = support_ims if isinstance(support_ims, ClassSweep) else None
-        cache = sweep.cache if sweep is not None else (support_ims if isinstance(support_ims, SupportCache) else None)
+        # a SupportCache, or a ClassSweep of one (cache.sweep(classes)): every query image against each of C cached sets,
+        # B*C problems p = b*C + c
         if cache is not None:
-            if training:
-                raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
-                                   "support side from support images")
-            cache._check(self, dev)
+            check_cached_forward(self, dev, cache, sweep)
         # a BankEpisode (bank.episode(index)): a training iteration over a frozen trunk names its supports by bank row
-        episode = support_ims if isinstance(support_ims, BankEpisode) else None
         if episode is not None:
             if not training:
                 raise RuntimeError("a SupportBank episode serves train-mode forwards over a frozen trunk; for inference "
@@ -1283,9 +1278,6 @@ class DAnARCNN(nn.Module):
                                  "cfg.RESNET.FIXED_BLOCKS = 3): a bank row is a constant of the run only while layer1-3 do "
                                  "not train, and no support-map gradient can flow into a bank")
             episode._check(self, dev, B)
-        if sweep is not None and cfg.POOLING_MODE != "align":
-            raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
-                                      "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
         self.num_of_rois = cfg.TRAIN.BATCH_SIZE if training else cfg.TEST.RPN_POST_NMS_TOP_N
         Cs = len(sweep) if sweep is not None else 1
         f = SimpleNamespace(plan=plan, dev=dev, training=training, sweep=sweep, cache=cache, episode=episode, qbatch=qbatch,
@@ -1379,6 +1371,16 @@ class DAnARCNN(nn.Module):
             f.inputs_ready.record()
         return SimpleNamespace(at=at, rng=rng, ctr=ctr, side=side, gt_f=gt_f, capturing=capturing, num_fg=num_fg)
 
+    def _query_side(self, f, im_data, fh, fw, save=None, save_from=3):
+        """-> corr [B*fh*fw][2048] with the query trunk maps in its first half: the batch's bank rows (a QueryBatch: one
+        gather launch, nothing to save) or the query trunk on the caller's stream"""
+        corr = torch.empty((f.B * fh * fw, 2048), dtype=torch.float32, device=f.dev)
+        if f.qbatch is not None:
+            f.qbatch._gather(corr)
+        else:
+            self._rcnn_base(im_data, f.plan, out_stride=2048, out_buf=corr, save=save, save_from=save_from)
+        return corr
+
     def _trunks(self, f, im_data, support_ims):
         """feature extraction (dana.py:98-115) + RPN-level support side -> (corr [B*h*w][base_feat | attended], (h, w), sup)"""
         # The query trunk runs on the caller's stream; the support trunk (cached / merged into the query's launches /
@@ -1399,11 +1401,7 @@ class DAnARCNN(nn.Module):
             if ctx is not None:
                 ctx.update(shot=f.shot)
             sup = dict(fields, map=f.cache.sup_map, rpn_done=None, roi_done=None)
-            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
-            if f.qbatch is not None:  # (a query bank: the trunk maps of the batch's rows into corr's first half, one launch)
-                f.qbatch._gather(corr)
-            else:
-                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr)
+            corr = self._query_side(f, im_data, fh, fw)
             f.mark("trunk (query + support)")
             return corr, (fh, fw), sup
         if f.episode is not None:
@@ -1422,12 +1420,8 @@ class DAnARCNN(nn.Module):
                 rpn_done = ops.record_event()
                 if ctx is not None:
                     ctx.update(s_pe=s_pe, kp=kp, unary=unary, Ns=Ns)
-            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
-            if f.qbatch is not None:  # (both banks: no trunk launch in the iteration)
-                f.qbatch._gather(corr)
-            else:
-                self._rcnn_base(im_data, plan, out_stride=2048, out_buf=corr, save=ctx["q_saved"] if ctx is not None else None,
-                                save_from=ctx["t"] if ctx is not None else 3)
+            corr = self._query_side(f, im_data, fh, fw, save=ctx["q_saved"] if ctx is not None else None,
+                                    save_from=ctx["t"] if ctx is not None else 3)  # (both banks: no trunk launch at all)
             f.mark("trunk (query + support)")
             return corr, (fh, fw), dict(feat=None, map=(sh_, sw_), kp=kp, unary=unary, s_t=s_t, rpn_done=rpn_done,
                                         sp_pe=sp_pe)
@@ -1439,10 +1433,9 @@ class DAnARCNN(nn.Module):
             # a query bank: one gather fills corr's first half; the support trunk runs as its own one-segment walk on the
             # support stream, whatever the merge settings say (there is no query batch to merge with). In train mode the trunk
             # is frozen (ctx["t"] == 3), so neither side saves anything
-            corr = torch.empty((B * fh * fw, 2048), dtype=torch.float32, device=dev)
             with ops.on_stream(sup_stream):
                 sfeat, sh_, sw_ = self._rcnn_base(sup_ims, plan, save=save_s, save_from=save_from)
-            f.qbatch._gather(corr)
+            corr = self._query_side(f, im_data, fh, fw)
         elif f.merge[0]:
             _, (q, s), ((corr, _), (sfeat, _)) = self._drain(self._trunk_gen(
                 [im_data, sup_ims], plan, outs=[(None, 2048), (None, 1024)], saves=[save_q, save_s], side=sup_stream,
@@ -1827,568 +1820,3 @@ class DAnARCNN(nn.Module):
         f.mark("join layer4 / neg head")
         f.tick("enqueued roialign..head")
         return prob_all, cls_prob, cls_score, neg_score
-
-
-def _is_shot_spec_leaf(x):
-    return x is None or isinstance(x, (int, np.integer)) and not isinstance(x, bool)
-
-
-def resolve_shot_views(shots, sets, counts, each=False):
-    """The shot views of a call, host only (no device): -> (sets, views), views[p] an ordered tuple of distinct shot
-    indices of set sets[p], each < counts[sets[p]] (the set's real shots).
-    shots: ONE spec for every problem -- None (all real shots of the set), an int k (shots 0..k-1: the nested K-shot
-    subsets) or a flat sequence of shot indices -- or a sequence of len(sets) specs, one per problem (recognised by an
-    element that is itself None or a sequence; per-problem ints k go as range(k)). "each" (each=True callers: a sweep)
-    expands every listed set into its S one-shot views, problem c*S + s = shot s of sets[c]; the listed sets must have
-    equal counts. ValueError: empty view, duplicates, device tensors, a bad spec; IndexError: a shot >= counts[set]."""
-    sets = [int(c) for c in sets]
-
-    def host_list(x):
-        if torch.is_tensor(x):
-            if x.is_cuda:
-                raise ValueError("shots= takes host values (ints, sequences or CPU tensors), not device tensors")
-            return x.reshape(-1).tolist()
-        return x
-
-    def one(spec, c):
-        n = int(counts[c])
-        spec = host_list(spec)
-        if spec is None:
-            return tuple(range(n))
-        if _is_shot_spec_leaf(spec):
-            k = int(spec)
-            if k < 1:
-                raise ValueError("shots=%d: a view needs at least one shot" % k)
-            if k > n:
-                raise IndexError("shots=%d: set %d has %d shots" % (k, c, n))
-            return tuple(range(k))
-        if isinstance(spec, str) or not hasattr(spec, "__iter__"):
-            raise ValueError("shots: %r is not a view (None, an int or a sequence of shot indices)" % (spec,))
-        view = []
-        for v in spec:
-            if v is None or not _is_shot_spec_leaf(v):
-                raise ValueError("shots: %r is not a shot index" % (v,))
-            view.append(int(v))
-        if not view:
-            raise ValueError("shots: empty view for set %d" % c)
-        if len(set(view)) != len(view):
-            raise ValueError("shots: view %s of set %d names a shot twice" % (view, c))
-        bad = [v for v in view if v < 0 or v >= n]
-        if bad:
-            raise IndexError("shots: %s outside the %d shots of set %d" % (bad, n, c))
-        return tuple(view)
-
-    shots = host_list(shots)
-    if isinstance(shots, str):
-        if shots != "each" or not each:
-            raise ValueError("shots=%r: %s" % (shots, "only a sweep takes shots='each'" if shots == "each" else
-                                               "the only string spec is 'each'"))
-        ns = sorted({int(counts[c]) for c in sets})
-        if len(ns) != 1:
-            raise ValueError("shots='each': the listed sets have different shot counts %s; sweep them by count" % ns)
-        return [c for c in sets for _ in range(ns[0])], [(s_,) for _ in sets for s_ in range(ns[0])]
-    per_problem = (not _is_shot_spec_leaf(shots) and hasattr(shots, "__iter__")
-                   and any(v is None or (hasattr(v, "__iter__") and not isinstance(v, str)) for v in shots))
-    if per_problem:
-        shots = list(shots)
-        if len(shots) != len(sets):
-            raise ValueError("shots: %d per-problem specs for %d problems" % (len(shots), len(sets)))
-        return sets, [one(sp, c) for sp, c in zip(shots, sets)]
-    return sets, [one(shots, c) for c in sets]
-
-
-class SupportCache:
-    """The query-independent support tensors of C support sets (encode_supports), per set as the model's
-    `_cache_layout` names them. DAnA:
-    RPN level  kp [shot*L][d] (column mean subtracted), unary [shot][L] (softmaxed), s_t [1024][shot*L];
-    RoI level  k2 [shot*49][dq], un2 [shot][49], and sw [shot*49][64] (folded S.Wt^T) or sp_pe [shot*49][1024]
-               (product attention or fold_roi_attn off).
-    The sibling detectors' layouts are in frcnn.py (meta), fsod.py and fgn.py.
-    `model(im_data, im_info, gt_boxes, num_boxes, cache)`: query image b uses set index[b] -- `select(indices)`, else the
-    identity when C == B and a broadcast when C == 1. The forward gathers the selected sets into B-batched buffers the cache
-    owns (one launch, dana_gather_blocks, index read on the device: a recorded replay follows later `select` calls).
-    Every tensor is `shot` independent blocks, so `select(indices, shots=)` / `sweep(classes, shots=)` serve shot VIEWS of a
-    set (`resolve_shot_views`: K-shot subsets, single shots, ragged sets encoded with `num_shots=`): problems whose view is
-    not range(shot) are gathered by dana_gather_shot_blocks into m-shot buffers (m = the longest view of the call; padding
-    slots zeroed, w [P][m] = 1/len(view) or 0) and the query side runs with shot = m; views of unequal length scale the
-    attention per segment by w (dana_attn_softmax_unary_w / _sweep_w). Needs the model's `_cache_shot_blocks`.
-    The cache records what it was built under; a forward after any of it changed raises ("re-encode")."""
-
-    def __init__(self, model, tensors, shot, sup_map, pool, state, dev, counts=None):
-        self._model = weakref.ref(model)
-        self._t = {k: v for k, v in tensors.items() if v is not None}
-        self.shot, self.sup_map, self.pool, self.device = shot, tuple(sup_map), pool, torch.device(dev)
-        self._state = state
-        self._C = next(iter(self._t.values())).size(0)
-        # the shapes the forward's consumers expect, per image (B of them stacked on the first axis)
-        self._shapes = model._cache_layout(shot, sup_map)
-        self.FIELDS = tuple(self._shapes)
-        self._sel = None        # host list of the last select(), or None
-        self._index = None      # device int32 [capacity]: what dana_gather_blocks reads
-        self._index_host = None  # what the device index holds
-        self._bufs = {}         # B -> (gathered tensors, device tables)
-        # shot views. _blocks: name -> (rows, floats per shot block) of a set's [rows][shot][block] tensor, or None when
-        # the model's cached tensors are not per-shot blocks (_no_shot_views says why)
-        self._blocks = model._cache_shot_blocks(sup_map)
-        self._no_shot_views = getattr(model, "_no_shot_views", None)
-        self._counts = tuple(int(n) for n in counts) if counts is not None else (shot,) * self._C
-        if len(self._counts) != self._C or any(n < 1 or n > shot for n in self._counts):
-            raise ValueError("SupportCache: shot counts %s for %d sets of %d shots" % (list(self._counts), self._C, shot))
-        self._sel_views = None   # the views of the last select(), or None: every selected set's real shots
-        self._view = None        # device int32 [capacity][shot], -1 padded: what dana_gather_shot_blocks reads
-        self._view_host = None   # what the device view table holds
-        self._vbufs = {}         # (P, m) -> (gathered m-shot tensors, device tables, n tensors, w [P][m])
-        self._mode = None        # the last prepared forward: None (identity views) or (m, weighted)
-
-    def __len__(self):
-        return self._C
-
-    @property
-    def shot_counts(self):
-        """the number of real shots of every set (encode_supports' num_shots; `shot` each without it)"""
-        return self._counts
-
-    def _views(self, shots, sets, each=False):
-        """-> (sets, views or None): `resolve_shot_views`, None when every view is the identity range(shot)"""
-        if self._blocks is None and (shots is not None or self._counts != (self.shot,) * self._C):
-            raise NotImplementedError("shot views (shots=, num_shots=): " + (self._no_shot_views or "not declared by the model"))
-        if shots is None and all(self._counts[c] == self.shot for c in sets):
-            return list(sets), None
-        sets, views = resolve_shot_views(shots, sets, self._counts, each=each)
-        ident = tuple(range(self.shot))
-        return sets, (None if all(v == ident for v in views) else views)
-
-    @property
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in self._t.values())
-
-    def _check(self, model, dev):
-        if self._model() is not model:
-            raise RuntimeError("this SupportCache was encoded by another model: re-encode the supports with this one")
-        if torch.device(dev) != self.device:
-            raise RuntimeError("this SupportCache lives on %s, the query on %s: re-encode the supports there" % (self.device, dev))
-        if model._cache_state(dev) != self._state:
-            raise RuntimeError("the model changed since encode_supports (weights, MFMA mode, Winograd settings, "
-                               "attention_type, semantic_enhance, fold_roi_attn or num_shot): re-encode the supports")
-
-    @staticmethod
-    def _active_recording():
-        from . import _lib
-        return _lib.RECORDER is not None or torch.cuda.is_current_stream_capturing()
-
-    def select(self, indices, shots=None):
-        """query image b of the next forwards uses support set indices[b] (a host sequence or a CPU tensor of length B),
-        and of it the shots `shots` names (`resolve_shot_views`; default: all real shots). Validated on the host, written
-        into the device index (and view table) the gather reads."""
-        if torch.is_tensor(indices):
-            if indices.is_cuda:
-                raise ValueError("SupportCache.select takes host indices (a sequence or a CPU tensor)")
-            indices = indices.reshape(-1).tolist()
-        idx = [int(i) for i in indices]
-        if not idx:
-            raise ValueError("SupportCache.select: empty selection")
-        bad = [i for i in idx if i < 0 or i >= self._C]
-        if bad:
-            raise IndexError("SupportCache.select: indices %s outside [0, %d)" % (bad, self._C))
-        _, views = self._views(shots, idx)
-        self._sel, self._sel_views = idx, views
-        self._write_index(idx)
-        if views is not None:
-            self._write_views(views)
-
-    def sweep(self, classes=None, shots=None):
-        """-> ClassSweep: `model(im_data, im_info, gt_boxes, num_boxes, cache.sweep(classes))` runs every query image
-        against each listed set (default: all C, in order). classes: a host sequence or a CPU tensor of set indices.
-        shots: the view of every class, or one per class (`resolve_shot_views`); "each" expands every class into its S
-        one-shot views, problem c*S + s of an image = shot s of class c (postprocess.ensemble_shots' layout)."""
-        if classes is None:
-            idx = list(range(self._C))
-        else:
-            if torch.is_tensor(classes):
-                if classes.is_cuda:
-                    raise ValueError("SupportCache.sweep takes host indices (a sequence or a CPU tensor)")
-                classes = classes.reshape(-1).tolist()
-            idx = [int(i) for i in classes]
-        if not idx:
-            raise ValueError("SupportCache.sweep: empty class list")
-        bad = [i for i in idx if i < 0 or i >= self._C]
-        if bad:
-            raise IndexError("SupportCache.sweep: indices %s outside [0, %d)" % (bad, self._C))
-        idx, views = self._views(shots, idx, each=True)
-        return ClassSweep(self, idx, views)
-
-    def _resolve(self, B):
-        if self._sel is not None:
-            if len(self._sel) != B:
-                raise RuntimeError("SupportCache: %d selected sets for a batch of %d query images" % (len(self._sel), B))
-            return self._sel
-        if self._C == B:
-            return list(range(B))
-        if self._C == 1:
-            return [0] * B
-        raise RuntimeError("SupportCache of %d sets for a batch of %d query images: call cache.select(indices) "
-                           "(without it C == B means set b for image b, C == 1 one set for every image)" % (self._C, B))
-
-    def _write_index(self, idx):
-        if idx == self._index_host:
-            return
-        if self._active_recording():
-            raise RuntimeError("SupportCache: the selection changed inside a recording / capture: select before it")
-        if self._index is None or self._index.numel() < len(idx):
-            self._index = torch.zeros((max(len(idx), self._C, 16),), dtype=torch.int32, device=self.device)
-        self._index[:len(idx)].copy_(torch.tensor(idx, dtype=torch.int32))
-        self._index_host = list(idx)
-
-    def _write_views(self, views):
-        """the view table of the next gather: row p = views[p], -1 padded to `shot`"""
-        rows = [list(v) + [-1] * (self.shot - len(v)) for v in views]
-        if rows == self._view_host:
-            return
-        if self._active_recording():
-            raise RuntimeError("SupportCache: the shot views changed inside a recording / capture: select before it")
-        if self._view is None or self._view.size(0) < len(rows):
-            self._view = torch.full((max(len(rows), self._C, 16), self.shot), -1, dtype=torch.int32, device=self.device)
-        self._view[:len(rows)].copy_(torch.tensor(rows, dtype=torch.int32))
-        self._view_host = rows
-
-    def _prepare(self, B, idx=None, views=None):
-        """host-side set-up of a forward that gathers B sets (selection written, gathered buffers + pointer tables
-        allocated): what a recording or capture must find done. idx, views: the B set indices and their shot views (a
-        class sweep's), else the selection / default for B images. Sets self._mode: None (identity views: the whole-set
-        buffers) or (m, weighted)"""
-        if idx is None:
-            idx = self._resolve(B)
-            views = self._sel_views if self._sel is not None else self._views(None, idx)[1]
-        self._write_index(idx)
-        if views is not None:
-            return self._prepare_views(B, views)
-        self._mode = None
-        if (self._C == 1 and B == 1) or B in self._bufs:
-            return
-        if self._active_recording():
-            raise RuntimeError("SupportCache: first B = %d forward inside a recording / capture: run one eagerly first" % B)
-        names = [k for k in self.FIELDS if k in self._t]
-        dst = {k: torch.empty((B,) + self._shapes[k], dtype=torch.float32, device=self.device) for k in names}
-        for k in names:
-            if self._t[k][0].numel() != dst[k][0].numel():
-                raise RuntimeError("SupportCache: tensor %s has %d elements per set, expected %d"
-                                   % (k, self._t[k][0].numel(), dst[k][0].numel()))
-        tab = torch.tensor([[self._t[k].data_ptr() for k in names], [dst[k].data_ptr() for k in names],
-                            [self._t[k][0].numel() * 4 for k in names]], dtype=torch.int64).to(self.device)
-        self._bufs[B] = (dst, tab, len(names))
-
-    def _prepare_views(self, P, views):
-        if len(views) != P:
-            raise RuntimeError("SupportCache: %d shot views for %d problems" % (len(views), P))
-        self._write_views(views)
-        m = max(len(v) for v in views)
-        self._mode = (m, any(len(v) != m for v in views))
-        if (P, m) in self._vbufs:
-            return
-        if self._active_recording():
-            raise RuntimeError("SupportCache: first (P, m) = (%d, %d) view forward inside a recording / capture: run one "
-                               "eagerly first" % (P, m))
-        names = [k for k in self.FIELDS if k in self._t]
-        shapes = self._model()._cache_layout(m, self.sup_map)
-        dst = {k: torch.empty((P,) + shapes[k], dtype=torch.float32, device=self.device) for k in names}
-        for k in names:
-            rows, block = self._blocks[k]
-            if self._t[k][0].numel() != rows * self.shot * block or dst[k][0].numel() != rows * m * block:
-                raise RuntimeError("SupportCache: tensor %s is not [%d][shot][%d] per set" % (k, rows, block))
-        tab = torch.tensor([[self._t[k].data_ptr() for k in names], [dst[k].data_ptr() for k in names],
-                            [self._blocks[k][0] for k in names], [self._blocks[k][1] * 4 for k in names]],
-                           dtype=torch.int64).to(self.device)
-        self._vbufs[(P, m)] = (dst, tab, len(names), torch.zeros((P, m), dtype=torch.float32, device=self.device))
-
-    def _gather_views(self, P, idx=None, views=None):
-        """-> ({name: the P problems' tensors}, m, w): `_gather` when every view is the identity (m = shot, w None), else
-        one dana_gather_shot_blocks launch into the (P, m) buffers; w [P][m] when the views' lengths differ, else None"""
-        self._prepare(P, idx, views)
-        if self._mode is None:
-            return self._gather(P, idx, prepared=True), self.shot, None
-        m, weighted = self._mode
-        dst, tab, n, w = self._vbufs[(P, m)]
-        from ._lib import lib
-        lib().call("dana_gather_shot_blocks", tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(), tab[3].data_ptr(), n,
-                   self._index.data_ptr(), self._view.data_ptr(), w.data_ptr(), self._C, self.shot, m, P, ops._stream())
-        return {k: dst.get(k) for k in self.FIELDS}, m, (w if weighted else None)
-
-    def _gather(self, B, idx=None, prepared=False):
-        """-> {name: the B selected sets in the forward's layout}, gathered by one launch (none for one set, one image)"""
-        if not prepared:
-            self._prepare(B, idx)
-            if self._mode is not None:
-                raise NotImplementedError("shot views: " + (self._no_shot_views or "this forward does not take them"))
-        if self._C == 1 and B == 1:
-            return {k: (self._t[k].view(self._shapes[k]) if k in self._t else None) for k in self.FIELDS}
-        dst, tab, n = self._bufs[B]
-        from ._lib import lib
-        lib().call("dana_gather_blocks", tab[0].data_ptr(), tab[1].data_ptr(), tab[2].data_ptr(), n, self._index.data_ptr(),
-                   self._C, B, ops._stream())
-        return {k: dst.get(k) for k in self.FIELDS}
-
-
-class ClassSweep:
-    """SupportCache.sweep(classes): as the 5th argument of an eval-mode forward, each of the B query images runs against
-    each of the C listed sets -- B*C problems p = b*C + c, each the cached forward of image b with set classes[c]
-    (dana.py:87-220 per class, as inference.py:70-140 fills all_boxes[j][i]). The query trunk runs once per image; the
-    outputs are laid out as the replicated call `model(im.repeat_interleave(C, 0), ..., cache)` after
-    `cache.select(classes * B)` lays them out: rois [B*C, R, 5] (column 0 = p), cls_prob [B*C*R, 2], bbox_pred [B*C*R, 4]."""
-
-    __slots__ = ("cache", "classes", "views")
-
-    def __init__(self, cache, classes, views=None):
-        # views: the shot view of every listed problem (SupportCache.sweep's shots=), None: every set whole
-        self.cache, self.classes, self.views = cache, tuple(classes), (None if views is None else tuple(views))
-
-    def __len__(self):
-        return len(self.classes)
-
-    def _index(self, B):
-        """the gather index of a B-image forward: the class list repeated for every image"""
-        return list(self.classes) * B
-
-    def _views(self, B):
-        """the shot views of a B-image forward, or None"""
-        return None if self.views is None else list(self.views) * B
-
-    def __repr__(self):
-        return "ClassSweep(%d sets: %s)" % (len(self.classes), list(self.classes))
-
-
-def resolve_bank_episode(index, n_bank, B, way, shot):
-    """The support rows of one training episode, host only (no device): index [B, way*shot] integers, row b the bank rows of
-    query image b's supports with its `shot` positives first (dana.py:103-104: the layout of support_ims) -> a C-contiguous
-    int32 array of that shape. Repeats are fine: one exemplar may be positive for one image and negative for another.
-    B None: any batch size >= 1. ValueError: a device tensor, a non-integer dtype, a wrong shape; IndexError: an entry
-    outside [0, n_bank)."""
-    if torch.is_tensor(index):
-        if index.is_cuda:
-            raise ValueError("a bank episode takes a host index (a numpy array, nested lists or a CPU tensor), not a device "
-                             "tensor: it is validated on the host and uploaded once")
-        index = index.numpy()
-    arr = np.asarray(index)
-    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise ValueError("a bank episode's index holds integers (bank rows), got dtype %s" % arr.dtype)
-    ws = int(way) * int(shot)
-    if arr.ndim != 2 or arr.shape[1] != ws or arr.shape[0] < 1 or (B is not None and arr.shape[0] != int(B)):
-        raise ValueError("a bank episode's index must be [%s, way*shot = %d] (per query image its %d positive supports, then "
-                         "the negatives), got %s" % ("B" if B is None else int(B), ws, int(shot), arr.shape))
-    bad = arr[(arr < 0) | (arr >= int(n_bank))]
-    if bad.size:
-        raise IndexError("bank episode: rows %s outside [0, %d)" % (sorted(set(int(v) for v in bad.reshape(-1)))[:8], int(n_bank)))
-    return np.array(arr, dtype=np.int32, order="C")  # (always a copy: the caller may go on writing its array)
-
-
-class SupportBank:
-    """The weight-independent support tensors of a pool of N images (DAnARCNN.encode_support_bank), for fine-tuning over a
-    frozen trunk (cfg.RESNET.FIXED_BLOCKS = 3): map_pe [N][L][1024], the trunk map + PE, and pool_pe [N][49][1024], its
-    average pool + PE -- everything on the support side in front of the first trained weight. (A SupportCache stores the
-    K / unary / S.Wt^T chain behind those weights, which is why it serves inference only.)
-    `ep = bank.episode(index)` names the B*way*shot supports of an iteration by bank row; `model(im_data, im_info, gt_boxes,
-    num_boxes, ep)` in train mode gathers them (one launch, dana_bank_gather_episode, index read on the device) and runs the
-    query trunk only; `ep.set(index)` names the next iteration's -- a recorded replay (program.ProgramTrainer) follows it.
-    The bank records what it was built under (the trunk's parameters and buffers, the MFMA and Winograd settings, the
-    device); using it after any of that changed raises ("re-encode")."""
-
-    def __init__(self, model, map_pe, pool_pe, sup_map, pool, state, dev):
-        self._model = weakref.ref(model)
-        self.map_pe, self.pool_pe = map_pe, pool_pe
-        self.sup_map, self.pool, self.device = tuple(sup_map), pool, torch.device(dev)
-        self._state = state
-        self._index = {}       # (B, way*shot) -> device int32 [B*way*shot]: what dana_bank_gather_episode reads
-        self._index_host = {}  # ... and what it holds
-
-    def __len__(self):
-        return self.map_pe.size(0)
-
-    def nbytes(self):
-        return sum(t.numel() * t.element_size() for t in (self.map_pe, self.pool_pe))
-
-    def _check(self, model, dev):
-        if self._model() is not model:
-            raise RuntimeError("this SupportBank was encoded by another model: re-encode the pool with this one")
-        if torch.device(dev) != self.device:
-            raise RuntimeError("this SupportBank lives on %s, the query on %s: re-encode the pool there" % (self.device, dev))
-        if model._bank_state(dev) != self._state:
-            raise RuntimeError("the model changed since encode_support_bank (the trunk's weights or buffers, the MFMA mode "
-                               "or the Winograd settings): re-encode the pool")
-
-    def episode(self, index):
-        """-> BankEpisode over index [B, way*shot] (`resolve_bank_episode`; way and shot are the model's)"""
-        return BankEpisode(self, index)
-
-    def _write_index(self, arr):
-        """arr into the device index of its shape (allocated once per shape: a recording points at it)"""
-        key = arr.shape
-        host = self._index_host.get(key)
-        if host is not None and np.array_equal(host, arr):
-            return
-        if SupportCache._active_recording():
-            raise RuntimeError("SupportBank: the episode changed inside a recording / capture: ep.set(index) before it")
-        if key not in self._index:
-            self._index[key] = torch.zeros((arr.size,), dtype=torch.int32, device=self.device)
-        # one asynchronous copy on the current stream, as Trainer.upload_hyper's: a pageable source would hold the host
-        # until the stream has drained, once per iteration. The pinned block comes from torch's host allocator, which
-        # does not hand it out again before the copy that read it has finished. The gather runs behind an event of this
-        # stream (the forward's inputs_ready), and every side stream of a step is joined before the next set()
-        staged = torch.empty((arr.size,), dtype=torch.int32, pin_memory=True)
-        staged.copy_(torch.from_numpy(arr).reshape(-1))
-        self._index[key].copy_(staged, non_blocking=True)
-        self._index_host[key] = arr.copy()
-
-
-class BankEpisode:
-    """SupportBank.episode(index): the 5th argument of a train-mode forward over a frozen trunk, in place of support_ims
-    [B, way*shot, 3, S, S] -- image b's supports are the bank rows index[b], positives first. The index lives in a device
-    buffer the bank owns (one per episode shape, shared by the bank's episodes of that shape: the forward uploads an
-    episode's index when the buffer holds another); `set(index)` rewrites it for the next iteration."""
-
-    __slots__ = ("bank", "B", "way", "shot", "_host")
-
-    def __init__(self, bank, index):
-        model = bank._model()
-        if model is None:
-            raise RuntimeError("the model of this SupportBank is gone")
-        self.bank, self.way, self.shot = bank, int(model.n_way), int(model.n_shot)
-        self._host = resolve_bank_episode(index, len(bank), None, self.way, self.shot)
-        self.B = self._host.shape[0]
-        bank._write_index(self._host)
-
-    def set(self, index):
-        """the supports of the next forwards (same shape), validated on the host and written into the device index"""
-        self._host = resolve_bank_episode(index, len(self.bank), self.B, self.way, self.shot)
-        self.bank._write_index(self._host)
-
-    @property
-    def index(self):
-        """the episode's host index [B, way*shot] (a copy)"""
-        return self._host.copy()
-
-    def _check(self, model, dev, B):
-        self.bank._check(model, dev)
-        if (self.way, self.shot) != (int(model.n_way), int(model.n_shot)):
-            raise RuntimeError("this episode was laid out for way %d, shot %d; the model now has way %d, shot %d: make a new "
-                               "one (bank.episode)" % (self.way, self.shot, model.n_way, model.n_shot))
-        if B != self.B:
-            raise RuntimeError("a bank episode of %d query images for a batch of %d" % (self.B, B))
-        self.bank._write_index(self._host)  # (a no-op unless another episode of this shape used the buffer since)
-
-    def _gather(self, shot):
-        """-> (s_pe [B][shot*L][1024], sp_pe [B*way*shot*49][1024]) of the episode, fresh buffers on the current stream,
-        written by ONE launch"""
-        bank = self.bank
-        return ops.bank_gather_episode(bank.map_pe, bank.pool_pe, bank._index[self._host.shape], self.B, self.way, shot)
-
-
-def resolve_query_batch(index, n_bank, B=None):
-    """The query rows of one batch, host only (no device): index [B] integers, entry b the bank row of query image b -> a
-    C-contiguous int32 array of that shape. Repeats are fine. B None: any batch size >= 1. ValueError: a device tensor, a
-    non-integer dtype, a wrong shape; IndexError: an entry outside [0, n_bank)."""
-    if torch.is_tensor(index):
-        if index.is_cuda:
-            raise ValueError("a query batch takes a host index (a numpy array, a list or a CPU tensor), not a device tensor: "
-                             "it is validated on the host and uploaded once")
-        index = index.numpy()
-    arr = np.asarray(index)
-    if arr.dtype == np.bool_ or not np.issubdtype(arr.dtype, np.integer):
-        raise ValueError("a query batch's index holds integers (bank rows), got dtype %s" % arr.dtype)
-    if arr.ndim != 1 or arr.shape[0] < 1 or (B is not None and arr.shape[0] != int(B)):
-        raise ValueError("a query batch's index must be [%s] (per query image its bank row), got %s"
-                         % ("B" if B is None else int(B), arr.shape))
-    bad = arr[(arr < 0) | (arr >= int(n_bank))]
-    if bad.size:
-        raise IndexError("query batch: rows %s outside [0, %d)" % (sorted(set(int(v) for v in bad))[:8], int(n_bank)))
-    return np.array(arr, dtype=np.int32, order="C")  # (always a copy: the caller may go on writing its array)
-
-
-class QueryBank:
-    """The trunk maps of a pool of N query images of one H x W (DAnARCNN.encode_query_bank): maps [N][fh*fw][1024], what the
-    query trunk writes into the first half of corr. Over a frozen trunk (cfg.RESNET.FIXED_BLOCKS = 3) they are constants of a
-    fine-tuning run, as a SupportBank's rows are. `qb = bank.batch(index)` names the B images of a forward by bank row;
-    `model(qb, im_info, gt_boxes, num_boxes, support)` gathers them (one launch, dana_qbank_gather, index read on the device)
-    and runs no query trunk -- in train mode with support images or a BankEpisode, in eval mode with support images, a
-    SupportCache or a ClassSweep; `qb.set(index)` names the next forward's -- a recorded replay (program.ProgramTrainer)
-    follows it. The bank records what it was built under (the trunk's parameters and buffers, the MFMA and Winograd
-    settings, the device); using it after any of that changed raises ("re-encode"). Layer4, the RPN and the heads may move.
-    A trunk with stages that train (FIXED_BLOCKS < 3: eval-mode use only) is written by the fused optimizers through raw
-    pointers, which no tensor version shows, so there the bank also records the model's weight epoch: it is stale after every
-    optimizer step (and after a ProgramTrainer recording), i.e. it serves the forwards between two steps only."""
-
-    def __init__(self, model, maps, image_hw, map_hw, state, dev):
-        self._model = weakref.ref(model)
-        self.maps = maps
-        self.image_hw, self.map_hw, self.device = tuple(image_hw), tuple(map_hw), torch.device(dev)
-        self._state = state
-        self._index = {}       # B -> device int32 [B]: what dana_qbank_gather reads
-        self._index_host = {}  # ... and what it holds
-
-    def __len__(self):
-        return self.maps.size(0)
-
-    def nbytes(self):
-        return self.maps.numel() * self.maps.element_size()
-
-    def _check(self, model, dev):
-        if self._model() is not model:
-            raise RuntimeError("this QueryBank was encoded by another model: re-encode the images with this one")
-        if torch.device(dev) != self.device:
-            raise RuntimeError("this QueryBank lives on %s, the forward runs on %s: re-encode the images there" % (self.device, dev))
-        if model._qbank_state(dev) != self._state:
-            raise RuntimeError("the model changed since encode_query_bank (the trunk's weights or buffers, the MFMA mode or "
-                               "the Winograd settings; over a trunk with stages that train, any optimizer step or "
-                               "re-recording): re-encode the images")
-
-    def batch(self, index):
-        """-> QueryBatch over index [B] (`resolve_query_batch`)"""
-        return QueryBatch(self, index)
-
-    def _write_index(self, arr):
-        """arr into the device index of its B (allocated once per B: a recording points at it); one small asynchronous
-        upload on the current stream, as SupportBank._write_index's"""
-        key = arr.shape[0]
-        host = self._index_host.get(key)
-        if host is not None and np.array_equal(host, arr):
-            return
-        if SupportCache._active_recording():
-            raise RuntimeError("QueryBank: the batch changed inside a recording / capture: batch.set(index) before it")
-        if key not in self._index:
-            self._index[key] = torch.zeros((key,), dtype=torch.int32, device=self.device)
-        staged = torch.empty((key,), dtype=torch.int32, pin_memory=True)
-        staged.copy_(torch.from_numpy(arr))
-        self._index[key].copy_(staged, non_blocking=True)
-        self._index_host[key] = arr.copy()
-
-
-class QueryBatch:
-    """QueryBank.batch(index): the 1st argument of a forward, in place of im_data [B, 3, H, W] -- query image b is bank row
-    index[b]. B, the device and H x W come from the batch. The index lives in a device buffer the bank owns (one per B, shared
-    by the bank's batches of that size: the forward uploads a batch's index when the buffer holds another); `set(index)`
-    rewrites it for the next forward."""
-
-    __slots__ = ("bank", "B", "_host")
-
-    def __init__(self, bank, index):
-        self.bank = bank
-        self._host = resolve_query_batch(index, len(bank))
-        self.B = self._host.shape[0]
-        bank._write_index(self._host)
-
-    def set(self, index):
-        """the query images of the next forwards (same B), validated on the host and written into the device index"""
-        self._host = resolve_query_batch(index, len(self.bank), self.B)
-        self.bank._write_index(self._host)
-
-    @property
-    def index(self):
-        """the batch's host index [B] (a copy)"""
-        return self._host.copy()
-
-    def _check(self, model, dev):
-        self.bank._check(model, dev)
-        self.bank._write_index(self._host)  # (a no-op unless another batch of this size used the buffer since)
-
-    def _gather(self, corr):
-        """the batch's trunk maps into the first 1024 columns of corr [B*fh*fw][2048], ONE launch on the current stream"""
-        bank = self.bank
-        return ops.qbank_gather(bank.maps, bank._index[self.B], self.B, out=corr, ld_out=corr.size(1))

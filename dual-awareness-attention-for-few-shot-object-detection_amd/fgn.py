@@ -14,7 +14,8 @@ import torch.nn as nn
 
 from . import backward as BW
 from . import ops
-from .dana import ClassSweep
+from .cached_inputs import ClassSweep
+from .dana import DAnARCNN
 from .frcnn import FasterRCNN
 
 
@@ -36,7 +37,6 @@ class FGN(FasterRCNN):
             mods[k] = mods.pop(k)
 
     def _init_weights(self):  # fgn.py:167-183: RCNN_cls_score keeps its default init
-        from .dana import DAnARCNN
         DAnARCNN._init_weights(self)
 
     def _bn(self, x, rows, bn, save=None):

@@ -11,8 +11,9 @@ import torch.nn as nn
 
 from . import backward as BW
 from . import ops
+from .cached_inputs import ClassSweep, SupportCache, check_cached_forward, read_inputs
 from .config import cfg
-from .dana import ClassSweep, DAnARCNN, SupportCache, _RPNParams
+from .dana import DAnARCNN, _RPNParams
 
 
 class FasterRCNN(DAnARCNN):
@@ -95,19 +96,12 @@ class FasterRCNN(DAnARCNN):
     def _cached_supports(self, support_ims, B, dev):
         """-> (the gathered per-problem support tensors, problems per image) when support_ims is a SupportCache or a
         ClassSweep (problems p = b*C + c), else (None, 1). One dana_gather_blocks launch, none for one set and one image"""
-        sweep = support_ims if isinstance(support_ims, ClassSweep) else None
-        cache = sweep.cache if sweep is not None else (support_ims if isinstance(support_ims, SupportCache) else None)
+        _, cache, sweep, _ = read_inputs(None, support_ims)
         if cache is None:
             return None, 1
-        if self.training:
-            raise RuntimeError("a SupportCache serves eval-mode forwards only (model.eval()); training recomputes the "
-                               "support side from support images")
-        cache._check(self, dev)
+        check_cached_forward(self, dev, cache, sweep)
         if sweep is None:
             return cache._gather(B), 1
-        if cfg.POOLING_MODE != "align":
-            raise NotImplementedError("a ClassSweep forward pools with RoIAlign (the grouped NHWC kernel); POOLING_MODE "
-                                      "'%s' is not supported there: sweep with cache.select per class instead" % cfg.POOLING_MODE)
         return cache._gather(B * len(sweep), sweep._index(B)), len(sweep)
 
     # ---- shared stages of the sibling detectors (frcnn, meta): trunk -> RPN -> targets -> RoI features -> layer4 ----
@@ -267,7 +261,6 @@ class MetaRCNN(FasterRCNN):
         self.RCNN_cls_score = nn.Sequential(nn.Linear(2048, 2))  # meta.py:199-201 (state_dict key RCNN_cls_score.0.*)
 
     def _init_weights(self):  # meta.py:144-159: RCNN_cls_score keeps its default init
-        from .dana import DAnARCNN
         DAnARCNN._init_weights(self)
 
     def _cache_layout(self, shot, sup_map):

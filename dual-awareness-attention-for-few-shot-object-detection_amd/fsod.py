@@ -15,7 +15,8 @@ import torch.nn as nn
 
 from . import backward as BW
 from . import ops
-from .dana import ClassSweep
+from .cached_inputs import ClassSweep
+from .dana import DAnARCNN
 from .frcnn import FasterRCNN
 
 
@@ -49,7 +50,6 @@ class FSOD(FasterRCNN):
             mods[k] = mods.pop(k)
 
     def _init_weights(self):
-        from .dana import DAnARCNN
         DAnARCNN._init_weights(self)
 
     # ---- cached support sets (encode_supports): per set, the pooled positive map and the support halves of the heads ----

@@ -24,6 +24,7 @@ import torch
 
 from . import ops
 from . import backward as BW
+from .cached_inputs import read_inputs
 
 
 def _static_like(t):
@@ -31,16 +32,14 @@ def _static_like(t):
 
 
 def _refuse_bank_episode(who, inputs):
-    from .dana import BankEpisode
-    if any(isinstance(t, BankEpisode) for t in inputs):
+    if read_inputs(inputs[0], *inputs[4:5]).episode is not None:
         raise NotImplementedError("%s does not capture a SupportBank episode (hipGraph capture of the frozen-trunk iteration "
                                   "is unverified): replay it with program.ProgramTrainer(trainer, ..., ep), or run it "
                                   "eagerly" % who)
 
 
 def _refuse_query_batch(who, inputs):
-    from .dana import QueryBatch
-    if any(isinstance(t, QueryBatch) for t in inputs):
+    if read_inputs(inputs[0]).qbatch is not None:
         raise NotImplementedError("%s does not capture a QueryBank batch (hipGraph capture of a forward from a query bank is "
                                   "unverified): replay the training iteration with program.ProgramTrainer(trainer, batch, "
                                   "...), or run it eagerly" % who)
@@ -61,8 +60,7 @@ class GraphedDAnA:
             raise RuntimeError("GraphedDAnA needs HIP tensors")
         if not hasattr(model, "_forward_gen"):
             raise RuntimeError("GraphedDAnA drives DAnARCNN (the siblings run eagerly)")
-        from .dana import SupportCache, ClassSweep
-        if any(isinstance(t, (SupportCache, ClassSweep)) for t in example_inputs):
+        if read_inputs(example_inputs[0], *example_inputs[4:5]).cache is not None:
             raise NotImplementedError("GraphedDAnA does not capture the cached-support forward (nor a class sweep): replay it with "
                                       "program.ProgramDAnA(model, ..., cache), or run it eagerly")
         _refuse_bank_episode("GraphedDAnA", example_inputs)
@@ -115,8 +113,7 @@ class GraphedDAnA:
         cur.wait_stream(self.stream)
 
     def __call__(self, *inputs):
-        from .dana import SupportCache, ClassSweep
-        if any(isinstance(t, (SupportCache, ClassSweep)) for t in inputs):
+        if read_inputs(inputs[0], *inputs[4:5]).cache is not None:
             raise NotImplementedError("GraphedDAnA replays the forward it captured (support images): a SupportCache "
                                       "forward replays through program.ProgramDAnA")
         for s, t in zip(self.inputs, inputs):

@@ -7,6 +7,8 @@ Backend "nccl" is RCCL on ROCm; the CPU tests run the same code over "gloo"."""
 import torch
 import torch.distributed as dist
 
+from .cached_inputs import read_inputs
+
 
 def shard_bounds(total, rank, world):
     """Contiguous, balanced [begin, end) of `total` episodes for `rank` (the first total % world ranks
@@ -18,16 +20,15 @@ def shard_bounds(total, rank, world):
 
 def shard_episode(inputs, rank, world):
     """inputs = (im_data, im_info, gt_boxes, num_boxes, support_ims): slice dim 0 of each for `rank`."""
-    from .dana import BankEpisode, QueryBatch
-    for t in inputs:
-        if isinstance(t, QueryBatch):
-            raise TypeError("shard_episode slices tensors; a QueryBank batch names rows of ONE device's bank and has no slice: "
-                            "every rank encodes its own bank (model.encode_query_bank) and draws the indices of its own "
-                            "share of the batch")
-        if isinstance(t, BankEpisode):
-            raise TypeError("shard_episode slices tensors; a SupportBank episode names rows of ONE device's bank and has no "
-                            "slice: every rank encodes its own bank (model.encode_support_bank) and draws the indices of "
-                            "its own share of the batch")
+    qbatch, _, _, episode = read_inputs(inputs[0], *inputs[4:5])
+    if qbatch is not None:
+        raise TypeError("shard_episode slices tensors; a QueryBank batch names rows of ONE device's bank and has no slice: "
+                        "every rank encodes its own bank (model.encode_query_bank) and draws the indices of its own "
+                        "share of the batch")
+    if episode is not None:
+        raise TypeError("shard_episode slices tensors; a SupportBank episode names rows of ONE device's bank and has no "
+                        "slice: every rank encodes its own bank (model.encode_support_bank) and draws the indices of "
+                        "its own share of the batch")
     b0, b1 = shard_bounds(inputs[0].size(0), rank, world)
     return tuple(t[b0:b1] for t in inputs)
 

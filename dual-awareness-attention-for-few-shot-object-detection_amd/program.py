@@ -37,6 +37,7 @@ from torch.utils._python_dispatch import TorchDispatchMode
 
 from . import _lib, ops
 from . import backward as BW
+from .cached_inputs import query_batch_size, query_device, read_inputs
 
 _EV_RECORD = torch._C._CudaEventBase.record
 _EV_WAIT = torch._C._CudaEventBase.wait
@@ -353,37 +354,6 @@ def _static_like(t):
     return t.detach().clone() if torch.is_tensor(t) else t
 
 
-def _support_cache(inputs):
-    from .dana import SupportCache
-    return next((t for t in inputs if isinstance(t, SupportCache)), None)
-
-
-def _class_sweep(inputs):
-    from .dana import ClassSweep
-    return next((t for t in inputs if isinstance(t, ClassSweep)), None)
-
-
-def _bank_episode(inputs):
-    from .dana import BankEpisode
-    return next((t for t in inputs if isinstance(t, BankEpisode)), None)
-
-
-def _query_batch(inputs):
-    """the QueryBatch (dana.encode_query_bank) standing in for im_data, else None"""
-    from .dana import QueryBatch
-    return inputs[0] if inputs and isinstance(inputs[0], QueryBatch) else None
-
-
-def _query_device(inputs):
-    qb = _query_batch(inputs)
-    return qb.bank.device if qb is not None else inputs[0].device
-
-
-def _query_B(inputs):
-    qb = _query_batch(inputs)
-    return qb.B if qb is not None else inputs[0].size(0)
-
-
 class ProgramDAnA:
     """model(*inputs) as launch-program replays (train or eval mode, host or device RNG): the eager forward's launches on
     the eager forward's streams, minus its Python. Inputs are copied into static buffers (skipped when the caller passes
@@ -391,7 +361,8 @@ class ProgramDAnA:
     (mode, shapes, cfg, the weight-derived tensors of this moment): re-record after changing any of them."""
 
     def __init__(self, model, *example_inputs, warmup=2):
-        if _query_batch(example_inputs) is not None:
+        qbatch, cache, sw, _ = read_inputs(example_inputs[0], *example_inputs[4:5])
+        if qbatch is not None:
             raise NotImplementedError("ProgramDAnA does not record a forward from a QueryBank batch (unverified): replay the "
                                       "training iteration with ProgramTrainer(trainer, batch, ...), or run the forward eagerly")
         dev = example_inputs[0].device
@@ -403,13 +374,10 @@ class ProgramDAnA:
         self.inputs = [_static_like(t) for t in example_inputs]
         # a SupportCache in place of support_ims (dana.encode_supports): the program keeps it (its tensors and the gathered
         # buffers are what the recording points at) and refuses another cache or a stale one
-        self.cache = _support_cache(example_inputs)
+        self.cache = cache
         # ... or a ClassSweep of one (cache.sweep(classes)): a later sweep of the same cache with the same number of sets
         # replays through the recorded gather, whose index is read on the device
-        sw = _class_sweep(example_inputs)
-        self.sweep_n = None
-        if sw is not None:
-            self.cache, self.sweep_n = sw.cache, len(sw)
+        self.sweep_n = len(sw) if sw is not None else None
         with torch.no_grad():
             for _ in range(warmup):  # eager: fills the plan / constant caches, creates the role streams
                 model(*self.inputs)
@@ -478,7 +446,7 @@ class ProgramDAnA:
             raise RuntimeError("the SupportCache's view table was reallocated after the recording: record a new runner")
 
     def __call__(self, *inputs):
-        sw = _class_sweep(inputs)
+        _, cache, sw, _ = read_inputs(inputs[0], *inputs[4:5])
         if (sw is None) != (self.sweep_n is None) or (sw is not None and (sw.cache is not self.cache or len(sw) != self.sweep_n)):
             raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: re-record a runner for it" % (
                 "a sweep of %s sets" % self.sweep_n if self.sweep_n is not None else "no class sweep",
@@ -489,7 +457,6 @@ class ProgramDAnA:
             sw.cache._check(self.model, self.inputs[0].device)  # (raises "re-encode" after a weight / mode change)
             sw.cache._prepare(B * self.sweep_n, sw._index(B), sw._views(B))  # the sweep's classes into the index the replay reads
             self._check_cache_buffers(sw.cache)
-        cache = _support_cache(inputs)
         if sw is None and cache is not self.cache:
             raise RuntimeError("ProgramDAnA was recorded with %s and called with %s: record a new runner for it" % (
                 "support images" if self.cache is None else "another SupportCache",
@@ -532,14 +499,13 @@ class ProgramTrainer:
         self.trainer, self.model = trainer, trainer.model
         if not hasattr(self.model, "_forward_gen"):
             raise RuntimeError("ProgramTrainer drives DAnARCNN (the siblings train eagerly)")
-        dev = _query_device(example_inputs)
+        dev = query_device(example_inputs[0])
         self.inputs = [_static_like(t) for t in example_inputs]
         # a QueryBatch in place of im_data (dana.encode_query_bank): no im_data holder is kept; the programs point at the
         # bank's maps and at the device index of this batch size, which `batch.set(index)` rewrites between replays
-        self.qbatch = _query_batch(example_inputs)
         # a BankEpisode in place of support_ims (dana.encode_support_bank): the programs point at the bank's tensors and at
         # the device index of this episode's shape, which `ep.set(index)` rewrites between replays
-        self.episode = _bank_episode(example_inputs)
+        self.qbatch, _, _, self.episode = read_inputs(example_inputs[0], *example_inputs[4:5])
         snap = None
         if warmup > 0:  # eager warm-up iterations must not move the training trajectory (as in GraphedTrainer)
             import numpy as _np
@@ -563,7 +529,7 @@ class ProgramTrainer:
 
     def _record(self):
         tr, model = self.trainer, self.model
-        dev = _query_device(self.inputs)
+        dev = query_device(self.inputs[0])
         import numpy as _np
         # the recording IS an eager iteration (its launches really run): parameters, momentum / both Adam moments and the host
         # RNG are put back behind it, so that constructing the runner does not move the training trajectory
@@ -577,7 +543,7 @@ class ProgramTrainer:
         if self.qbatch is not None:
             self.qbatch._check(model, dev)
         if self.episode is not None:
-            self.episode._check(model, dev, _query_B(self.inputs))
+            self.episode._check(model, dev, query_batch_size(self.inputs[0]))
         model._epoch += 1      # ... every trainable conv's derived tensors are re-derived INSIDE it, from the live weights
         prev_save = getattr(model, "save_for_backward", False)
         model.save_for_backward = True
@@ -663,7 +629,7 @@ class ProgramTrainer:
         of that bank and shape (its index of the moment is uploaded here if the buffer holds another episode's). The same
         holds for a QueryBatch as the 1st argument: a batch of the recorded QueryBank and size, or images where images were
         recorded"""
-        qb = _query_batch(inputs)
+        qb, _, _, ep = read_inputs(inputs[0], *inputs[4:5])
         if qb is not None or self.qbatch is not None:
             if qb is None or self.qbatch is None:
                 raise RuntimeError("ProgramTrainer was recorded with %s and called with %s: re-record a runner for it" % (
@@ -676,7 +642,6 @@ class ProgramTrainer:
                 raise RuntimeError("ProgramTrainer was recorded on a query batch of %d images and called with %d: re-record a "
                                    "runner for it" % (self.qbatch.B, qb.B))
             qb._check(self.model, qb.bank.device)  # (raises "re-encode" after a trunk change; uploads the index if needed)
-        ep = _bank_episode(inputs)
         if ep is None and self.episode is None:
             return
         if ep is None or self.episode is None:
@@ -689,7 +654,7 @@ class ProgramTrainer:
         if ep._host.shape != self.episode._host.shape:
             raise RuntimeError("ProgramTrainer was recorded on a bank episode of shape %s and called with %s: re-record a "
                                "runner for it" % (self.episode._host.shape, ep._host.shape))
-        ep._check(self.model, _query_device(self.inputs), _query_B(self.inputs))  # (raises "re-encode" after a trunk change)
+        ep._check(self.model, query_device(self.inputs[0]), query_batch_size(self.inputs[0]))  # (raises "re-encode" after a trunk change)
 
     def step(self, *inputs):
         self._check_episode(inputs)

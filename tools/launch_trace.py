@@ -3,11 +3,14 @@
 operation (rec / wait, event ordinal, stream ordinal). A host-side refactor must leave every line as it was.
 
 usage: launch_trace.py OUT.txt CASE [--mfma 0|1] [--shape B,way,shot,H,W]
-CASE = model[,train][,attr=value ...][,+bwd | +trainer | +cached | +sweep], e.g.
+CASE = model[,train][,attr=value ...][,+bwd | +trainer | +cached | +sweep | +bank | +qbank], e.g.
   DAnA                                            eval forward (eval cases run way 1, as the reference's eval)
   DAnA,train,merge_trunk=True,merge_from=1,+bwd   saving forward + model_backward
   DAnA,train,+trainer                             one Trainer.step
   DAnA,+cached  /  DAnA,+sweep                    encode_supports + one cached forward / one class sweep
+  DAnA,train,+bank  /  DAnA,train,+qbank          one forward from a SupportBank episode / a QueryBank batch: the model is
+                                                  built under cfg.RESNET.FIXED_BLOCKS = 3; the bank and its episode / batch
+                                                  are made once, untraced (an index write under a recorder is refused)
   fsod,train,+bwd                                 a sibling (frcnn, meta, fgn, fsod)
 The case runs once untraced (weight plan, allocator) and once traced. The other commit's package is traced by this same
 file: put its directory in front on PYTHONPATH (and DANA_LIB_PATH on the library to use)."""
@@ -60,7 +63,12 @@ def main(out_path, case, mfma=1, shape=(2, 2, 2, 160, 224)):
         dana_amd.DAnARCNN.trunk_layers = attrs.pop("trunk_layers")
     dev = torch.device("cuda:0")
     ops.set_mfma_mode(mfma)
+    cfg = dana_amd.cfg
+    prev_fixed = cfg.RESNET.FIXED_BLOCKS
+    if kind in ("+bank", "+qbank"):
+        cfg.RESNET.FIXED_BLOCKS = 3  # (read by the constructor: a bank row is a constant only over a frozen trunk)
     m = dana_amd.get_model(name, pretrained=False, way=way, shot=shot, classes=["fg", "bg"])
+    cfg.RESNET.FIXED_BLOCKS = prev_fixed
     sd = S.fill_state_dict(m.state_dict(), seed=21, profile="test")
     m.load_state_dict(S.tame_fsod_weights(sd) if name == "fsod" else sd)
     m.to(dev).train("train" in opts)
@@ -72,6 +80,11 @@ def main(out_path, case, mfma=1, shape=(2, 2, 2, 160, 224)):
     if kind == "+trainer":
         from dana_amd.trainer import Trainer
         tr = Trainer(m, lr=1e-3)
+    if kind == "+bank":  # (every support image of the episode is a bank row, in episode order)
+        bank = m.encode_support_bank(e[4].reshape(-1, 3, e[4].size(-2), e[4].size(-1)))
+        inputs = e[:4] + [bank.episode(np.arange(len(bank)).reshape(B, -1))]
+    if kind == "+qbank":
+        inputs = [m.encode_query_bank(e[0]).batch(np.arange(B))] + e[1:]
 
     def run():
         np.random.seed(7)
@@ -82,9 +95,9 @@ def main(out_path, case, mfma=1, shape=(2, 2, 2, 160, 224)):
                 cache = m.encode_supports(e[4].reshape(B, -1, 3, e[4].size(-2), e[4].size(-1)))
                 sup = cache.sweep() if kind == "+sweep" else cache
                 on, _lib.RECORDER = _lib.RECORDER, None  # (a cache's first forward of a batch size runs outside a recording)
-                m(*e[:4], sup)
+                m(*e[:4], sup, *inputs[5:])  # (meta's 6th argument, all_cls_gt_boxes, goes along)
                 _lib.RECORDER = on
-                return m(*e[:4], sup)
+                return m(*e[:4], sup, *inputs[5:])
             m(*inputs)
         if kind == "+bwd":
             BW.model_backward(m, (1.0, 1.0, 1.0, 1.0))
