@@ -84,6 +84,11 @@ struct IgemmParams {
   // A as pre-split planes (igemm_pp_kernel): A = bf16 planes [Kp / 16][3][a_rows][16] of the activation rows (the layout of
   // dana_split_weight with n = a_rows), written by the producing kernel's epilogue or by dana_split_weight; GEMM geometry only
   int apre, a_rows;
+  // sampled residual (res_sample = s > 0): output row m = (img, oh, ow) of a dense OH x OW map adds the residual row of pixel
+  // (s * oh, s * ow) of a res_h x res_w map (row stride ldr, res_bytes in all) -- the consumer of a stride-s 1x1 conv's
+  // input only reads those pixels, so the block in front of it computes only them. res_oh x res_ow = the dense map.
+  int res_sample, res_h, res_w, res_oh, res_ow;
+  unsigned res_bytes;
   unsigned long long* trace;  // debug (dana_set_igemm_trace): per block {start, first MFMA, loop end, end} in 100 MHz ticks + HW id
 };
 
@@ -433,6 +438,26 @@ constexpr StepSched<NM, NL, NR, NCVF, NBW> make_step_sched() {
 template <int NM, int NL, int NR, int NCVF, int NBW>
 inline constexpr StepSched<NM, NL, NR, NCVF, NBW> kStepSched = make_step_sched<NM, NL, NR, NCVF, NBW>();
 
+// Sampled residual: the byte offset of each of the tile's BM residual rows inside the res_h x res_w map, one entry per row,
+// built once per tile in LDS (one div / mod chain per row) and read just before each residual load -- no per-lane row
+// state in registers. Rows past M get an out-of-range offset (the load returns zeros). Ends with a barrier.
+template <int BM>
+__device__ __forceinline__ void build_res_row_table(const IgemmParams& p, int m0, unsigned* rtab) {
+  const int t = threadIdx.x;
+  if (t < BM) {
+    const int m = m0 + t;
+    unsigned off = OOB;
+    if (m < p.M) {
+      const int ohw = p.res_oh * p.res_ow;
+      const int img = m / ohw, rem = m - img * ohw;
+      const int oh = rem / p.res_ow, ow = rem - oh * p.res_ow;
+      off = (unsigned)((((long)img * p.res_h + oh * p.res_sample) * p.res_w + ow * p.res_sample) * p.ldr * 4);
+    }
+    rtab[t] = off;
+  }
+  __syncthreads();
+}
+
 // ---- epilogue on the accumulator registers (C/D map of the 32x32 MFMA: col = lane&31, row = (r&3) + 8*(r>>2) + 4*(lane>>5)).
 // With the output channel on the lane axis one accumulator register across a half-wave is 32 consecutive floats of one
 // output row = one 128-byte segment, so scale / shift / residual / ReLU / mask run where the values are and every access is
@@ -440,10 +465,13 @@ inline constexpr StepSched<NM, NL, NR, NCVF, NBW> kStepSched = make_step_sched<N
 // 128 x 128 tile), no barrier, no alignment condition on the rows. Rows past M fall outside the descriptors' ranges (loads
 // return zeros, stores are dropped); lanes whose channel is past N carry an out-of-range offset. Same arithmetic, in the
 // same order, as the LDS form of igemm_split_body (ELDS: dana_set_epilogue_mode(1)) -> the same bits.
-template <int BM, int BN, int HALVES = 0, int WITH_MASK = 1>
+// RSMP: the residual rows are SAMPLED (IgemmParams::res_sample; single geometry segment): one descriptor over the whole
+// residual map, the rows' offsets from the LDS table `rtab` (build_res_row_table) instead of compile-time multiples of ldr.
+template <int BM, int BN, int HALVES = 0, int WITH_MASK = 1, int RSMP = 0>
 __device__ __forceinline__ void epilogue_regs(const IgemmParams& p, f32x16 (&acc)[BM / 64][BN / 64], int m0, int n0, float* Cb,
-                                              int wm, int wn, int li, int lh) {
+                                              int wm, int wn, int li, int lh, unsigned* rtab = nullptr) {
   constexpr int TM = BM / 64, TN = BN / 64;
+  if constexpr (RSMP) build_res_row_table<BM>(p, m0, rtab);
   // (uniform) the tile lies in ONE geometry segment -- rows past M are not a segment: the descriptors' ranges drop them
   const bool one_seg = m0 + BM <= p.M0 || m0 >= p.M0 || p.M0 >= p.M;
   float scv[TN], shv[TN];
@@ -463,8 +491,10 @@ __device__ __forceinline__ void epilogue_regs(const IgemmParams& p, f32x16 (&acc
     const int ldc4 = (int)ld_c * 4, ldr4 = (int)ld_r * 4, ldm4 = (int)p.ldm * 4;
     const __amdgpu_buffer_rsrc_t rc_dst = __builtin_amdgcn_make_buffer_rsrc(
         (void*)((seg1 ? p.C1 : Cb) + mrel * ld_c), 0, rows_valid * ldc4, 0x00020000);
-    const __amdgpu_buffer_rsrc_t rc_res = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.residual ? (seg1 ? p.residual1 : p.residual) + mrel * ld_r : p.A), 0, p.residual ? rows_valid * ldr4 : 0, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rc_res =
+        RSMP ? __builtin_amdgcn_make_buffer_rsrc((void*)p.residual, 0, (int)p.res_bytes, 0x00020000)
+             : __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? (seg1 ? p.residual1 : p.residual) + mrel * ld_r : p.A), 0,
+                                                 p.residual ? rows_valid * ldr4 : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rc_msk = __builtin_amdgcn_make_buffer_rsrc(
         (void*)(p.mask ? p.mask + (long)m0 * p.ldm : p.A), 0, p.mask ? rows_valid * ldm4 : 0, 0x00020000);
     const int lrow = wm * (BM / 2) + 4 * lh;  // the lane's first row of the tile
@@ -473,7 +503,7 @@ __device__ __forceinline__ void epilogue_regs(const IgemmParams& p, f32x16 (&acc
     for (int j = 0; j < TN; ++j) {
       const bool nok = ncol[j] < p.N;
       vo_c[j] = nok ? (unsigned)(lrow * ldc4 + ncol[j] * 4) : OOB;
-      vo_r[j] = nok ? (unsigned)(lrow * ldr4 + ncol[j] * 4) : OOB;
+      vo_r[j] = nok ? (unsigned)((RSMP ? 0 : lrow * ldr4) + ncol[j] * 4) : OOB;
       vo_m[j] = nok ? (unsigned)(lrow * ldm4 + ncol[j] * 4) : OOB;
     }
     auto run = [&](auto res_c, auto relu_c, auto mask_c) {
@@ -493,7 +523,9 @@ __device__ __forceinline__ void epilogue_regs(const IgemmParams& p, f32x16 (&acc
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
               const int rt = (i0 + ii) * 32 + (r & 3) + 8 * (r >> 2);
-              if constexpr (RES)
+              if constexpr (RES && RSMP)
+                res[ii][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc_res, (int)(vo_r[j] + rtab[lrow + rt]), 0, 0));
+              else if constexpr (RES)
                 res[ii][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc_res, (int)(vo_r[j] + (unsigned)(rt * ldr4)), 0, 0));
               if constexpr (MASK)
                 msk[ii][j][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc_msk, (int)(vo_m[j] + (unsigned)(rt * ldm4)), 0, 0));
@@ -552,8 +584,10 @@ __device__ __forceinline__ void epilogue_regs(const IgemmParams& p, f32x16 (&acc
 // BPRE: the B operand is a WEIGHT that was split once per weight version (dana_split_weight: three bf16 planes per
 // K-step, [Kp / 16][3][N][16], Kp = K rounded up to 16, zero padded): its chunks of 8 bf16 go from HBM to the LDS planes as loaded, and
 // the K loop splits the activation rows only -- half the VALU work of the step.
-template <int BM, int BN, int STEM, int BPRE = 0, int FUSE = 0, int ELDS = 0>
+// FUSE = 2: the fused tail with a SAMPLED residual (strided tail); RSMP: sampled residual in the register epilogue.
+template <int BM, int BN, int STEM, int BPRE = 0, int FUSE = 0, int ELDS = 0, int RSMP = 0>
 __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
+  static_assert(!RSMP || (!STEM && !FUSE && !ELDS), "sampled residual: register epilogue of the plain conv / GEMM forms");
   constexpr int TM = BM / 64, TN = BN / 64;  // 32x32 MFMA tiles per wave in m / n
   constexpr int RA = BM / 64;                // float4 loads of A per thread per K-step (64 rows per pass)
   // B: fp32 rows like A (64 rows per pass), or 16-byte chunks of the pre-split planes (3 planes x BN rows x 2 halves)
@@ -947,6 +981,21 @@ __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
     // epilogue (bn3, + residual, ReLU) works on the accumulator layout directly: 32 lanes = 128 contiguous bytes of a row.
     static_assert(BM == 128 && BN == 64 && !STEM && BPRE, "fused tail: 128 x 64 tile over pre-split weights");
     unsigned short* A2 = (unsigned short*)smem;  // [4 K-steps][3 planes][BM rows][16] bf16
+    // (FUSE == 2) the residual rows' offsets, behind the A2 planes; published by the barrier below
+    unsigned* rtab = (unsigned*)smem + 4 * 3 * BM * 16 * 2 / 4;
+    if constexpr (FUSE == 2) {
+      if (tid < BM) {
+        const int m = m0 + tid;
+        unsigned off = OOB;
+        if (m < p.M) {
+          const int ohw = p.OH * p.OW;
+          const int img = m / ohw, rem = m - img * ohw;
+          const int oh = rem / p.OW, ow = rem - oh * p.OW;
+          off = (unsigned)((((long)img * p.IH + oh * p.stride) * p.IW + ow * p.stride) * p.ldr * 4);
+        }
+        rtab[tid] = off;
+      }
+    }
     {
       const int nn = wn * 32 + li;  // this lane's column of the 64 (N == BN)
       const float sc1 = p.scale ? p.scale[nn] : 1.f, sh1 = p.shift ? p.shift[nn] : 0.f;
@@ -978,12 +1027,15 @@ __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
     const int rows_valid = (p.M - m0) < BM ? (p.M - m0) : BM;
     const __amdgpu_buffer_rsrc_t rc_dst =
         __builtin_amdgcn_make_buffer_rsrc((void*)(Cb + (long)m0 * p.ldc), 0, (int)(rows_valid * p.ldc * 4), 0x00020000);
-    const __amdgpu_buffer_rsrc_t rc_res = __builtin_amdgcn_make_buffer_rsrc(
-        (void*)(p.residual ? p.residual + (long)m0 * p.ldr : p.A), 0, p.residual ? (int)(rows_valid * p.ldr * 4) : 0, 0x00020000);
+    // (FUSE == 2: one descriptor over the whole h x w residual map, row offsets from rtab)
+    const __amdgpu_buffer_rsrc_t rc_res =
+        FUSE == 2 ? __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? p.residual : p.A), 0, p.residual ? (int)p.res_bytes : 0, 0x00020000)
+                  : __builtin_amdgcn_make_buffer_rsrc((void*)(p.residual ? p.residual + (long)m0 * p.ldr : p.A), 0,
+                                                      p.residual ? (int)(rows_valid * p.ldr * 4) : 0, 0x00020000);
     const __amdgpu_buffer_rsrc_t rc_b2 = __builtin_amdgcn_make_buffer_rsrc((void*)p.Bw2, 0, 12 * N2 * 32, 0x00020000);
     const int ldc4 = (int)p.ldc * 4, ldr4 = (int)p.ldr * 4;
     const int lrow = wm * (BM / 2) + 4 * lh, lcol4 = (wn * 32 + li) * 4;
-    const int vo_c = lrow * ldc4 + lcol4, vo_r = lrow * ldr4 + lcol4;
+    const int vo_c = lrow * ldc4 + lcol4, vo_r = (FUSE == 2 ? 0 : lrow * ldr4) + lcol4;
     const int vo_b = (wn * 32 + li) * 32 + lh * 16;
     u32x4 bfr[4][3];
 #pragma unroll
@@ -998,12 +1050,26 @@ __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
       float res[TM][16];
       int vr = vo_r + c * 256, vc = vo_c + c * 256;  // (opaque per chunk: 64 loop-invariant row addresses would otherwise
       asm volatile("" : "+v"(vr), "+v"(vc));         //  be kept in registers across the loop -- one workgroup less per CU)
+      if constexpr (FUSE == 2) {
+        int tr = lrow;  // (opaque per chunk like vr: the table is re-read, four rows per ds_read_b128, not kept)
+        asm volatile("" : "+v"(tr));
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+          for (int r4 = 0; r4 < 4; ++r4) {
+            const u32x4 ro = *(const u32x4*)(rtab + tr + i * 32 + 8 * r4);
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+              res[i][4 * r4 + q] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rc_res, (int)((unsigned)vr + ro[q]), 0, 0));
+          }
+      } else {
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
         for (int r = 0; r < 16; ++r)
           res[i][r] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(
                                                     rc_res, vr + (i * 32 + (r & 3) + 8 * (r >> 2)) * ldr4, 0, 0));
+      }
       f32x16 acc2[TM];
 #pragma unroll
       for (int i = 0; i < TM; ++i)
@@ -1045,7 +1111,8 @@ __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
 
   // ---- epilogue on the accumulator registers (default): epilogue_regs above
   if constexpr (!ELDS) {
-    epilogue_regs<BM, BN>(p, acc, m0, n0, Cb, wm, wn, li, lh);
+    // (RSMP: the row table lies BEHIND the staging buffers -- other waves may still be in their last K-step's fragment reads)
+    epilogue_regs<BM, BN, 0, 1, RSMP>(p, acc, m0, n0, Cb, wm, wn, li, lh, (unsigned*)smem + 2 * 3 * (BM + BN) * SLD);
     if (p.trace && tid == 0) {
       unsigned long long* tr = p.trace + ((long)blockIdx.z * gridDim.x + blockIdx.x) * 8;
       tr[0] = t_start;
@@ -1266,13 +1333,13 @@ __device__ __forceinline__ void igemm_split_body(const IgemmParams& p) {
 // The kernels proper. The 128 x 128 tile is compiled for TWO workgroups per CU: 192 arch VGPRs beside its 64 accumulator
 // registers (the compiler, left alone with the one-block bound, spends 200+ on the epilogue's prefetches and halves the
 // occupancy of the whole K loop).
-template <int BM, int BN, int STEM, int BPRE = 0, int FUSE = 0, int ELDS = 0>
+template <int BM, int BN, int STEM, int BPRE = 0, int FUSE = 0, int ELDS = 0, int RSMP = 0>
 __global__ void __launch_bounds__(256, 2) igemm_split_kernel(IgemmParams p) {
-  igemm_split_body<BM, BN, STEM, BPRE, FUSE, ELDS>(p);
+  igemm_split_body<BM, BN, STEM, BPRE, FUSE, ELDS, RSMP>(p);
 }
-template <int STEM, int BPRE, int ELDS>
+template <int STEM, int BPRE, int ELDS, int RSMP = 0>
 __global__ void __launch_bounds__(256, 1) __attribute__((amdgpu_num_vgpr(192))) igemm_split_kernel_128(IgemmParams p) {
-  igemm_split_body<128, 128, STEM, BPRE, 0, ELDS>(p);
+  igemm_split_body<128, 128, STEM, BPRE, 0, ELDS, RSMP>(p);
 }
 
 // ---- the three-workgroups-per-CU contraction kernel (igemm_dma_kernel): weights by LDS-DMA, single fragment set --------------
@@ -1709,15 +1776,15 @@ int launch(const IgemmParams& p0, int batch, hipStream_t s) {
   return 0;
 }
 
-template <int BM, int BN, int STEM = 0, int BPRE = 0, int FUSE = 0, int ELDS = 0>
+template <int BM, int BN, int STEM = 0, int BPRE = 0, int FUSE = 0, int ELDS = 0, int RSMP = 0>
 int launch_split(const IgemmParams& p0, int batch, hipStream_t s) {
   if constexpr (BPRE == 0 && FUSE == 0) {
-    if (p0.bpre) return launch_split<BM, BN, STEM, 1, 0, ELDS>(p0, batch, s);
+    if (p0.bpre) return launch_split<BM, BN, STEM, 1, 0, ELDS, RSMP>(p0, batch, s);
   }
-  if constexpr (ELDS == 0 && FUSE == 0) {
+  if constexpr (ELDS == 0 && FUSE == 0 && RSMP == 0) {
     if (epilogue_mode_cell().load(std::memory_order_relaxed)) return launch_split<BM, BN, STEM, BPRE, 0, 1>(p0, batch, s);
   }
-  g_last_form.store(form_code(BM * BN >= 128 * 128 ? DANA_IGEMM_FAMILY_SPLIT_128 : DANA_IGEMM_FAMILY_SPLIT, BM, BN, STEM, BPRE, FUSE,
+  g_last_form.store(form_code(BM * BN >= 128 * 128 ? DANA_IGEMM_FAMILY_SPLIT_128 : DANA_IGEMM_FAMILY_SPLIT, BM, BN, STEM, BPRE, FUSE ? 1 : 0,
                               ELDS, 0, 0, 0), std::memory_order_relaxed);
   IgemmParams p = p0;
   p.tiles_m = (p.M + BM - 1) / BM;
@@ -1726,16 +1793,17 @@ int launch_split(const IgemmParams& p0, int batch, hipStream_t s) {
   const size_t lds_c = (size_t)BM * (BN + 4) * sizeof(float);
   if (lds_c > lds && ELDS) lds = lds_c;
   if (FUSE && lds < (size_t)4 * 3 * BM * 16 * 2) lds = (size_t)4 * 3 * BM * 16 * 2;  // the tile as four K-steps of A
+  if (FUSE == 2 || RSMP) lds += (size_t)BM * 4;  // the residual rows' offset table, behind everything else
   dim3 grid(p.tiles_m * p.tiles_n, 1, batch);
   static DeviceOnce attr;
   if constexpr (BM * BN >= 128 * 128) {
-    attr.once([&] { return hipFuncSetAttribute((const void*)igemm_split_kernel_128<STEM, BPRE, ELDS>, hipFuncAttributeMaxDynamicSharedMemorySize,
+    attr.once([&] { return hipFuncSetAttribute((const void*)igemm_split_kernel_128<STEM, BPRE, ELDS, RSMP>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds); });
-    igemm_split_kernel_128<STEM, BPRE, ELDS><<<grid, 256, lds, s>>>(p);
+    igemm_split_kernel_128<STEM, BPRE, ELDS, RSMP><<<grid, 256, lds, s>>>(p);
   } else {
-    attr.once([&] { return hipFuncSetAttribute((const void*)igemm_split_kernel<BM, BN, STEM, BPRE, FUSE, ELDS>,
+    attr.once([&] { return hipFuncSetAttribute((const void*)igemm_split_kernel<BM, BN, STEM, BPRE, FUSE, ELDS, RSMP>,
                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); });
-    igemm_split_kernel<BM, BN, STEM, BPRE, FUSE, ELDS><<<grid, 256, lds, s>>>(p);
+    igemm_split_kernel<BM, BN, STEM, BPRE, FUSE, ELDS, RSMP><<<grid, 256, lds, s>>>(p);
   }
   return 0;
 }
@@ -1799,7 +1867,24 @@ std::atomic<int>& pp_stages_cell() {
 }
 unsigned long long* g_trace = nullptr;  // debug: per-block timestamps of the next split launches (dana_set_igemm_trace)
 
+// A launch with a sampled residual goes only to the kernels whose register epilogue implements it: igemm_split_kernel at
+// 64 x 64 and igemm_split_kernel_128. The tile-shape rules are dispatch()'s own; a launch those rules would give to another
+// form (f32-MFMA mode, the LDS epilogue, N <= 64, a mask, planes x planes) is refused (-1), and one
+// they would give to igemm_dma_kernel (>= 600 tiles, K <= 192) takes the 128 x 128 tile it had before that kernel existed.
+int dispatch_sampled(const IgemmParams& p, int batch, hipStream_t s) {
+  const int mode = mfma_mode_cell().load(std::memory_order_relaxed);
+  if (!mode || p.apre || p.mask || p.KH * p.KW > 32 || p.M0 != p.M || epilogue_mode_cell().load(std::memory_order_relaxed)) return -1;
+  if (p.N <= 64) return -1;  // (a forced 128 x 64 / 64 x 128 tile -- debug modes 2 / 5 -- is a tile this launch cannot take: the rules below)
+  if (mode == 3) return launch_split<64, 64, 0, 0, 0, 0, 1>(p, batch, s);
+  if (mode == 4) return launch_split<128, 128, 0, 0, 0, 0, 1>(p, batch, s);
+  if (p.N <= 256 && p.N % 128 != 0 && p.N % 128 <= 32) return launch_split<64, 64, 0, 0, 0, 0, 1>(p, batch, s);
+  const long t128 = (long)((p.M + 127) / 128) * ((p.N + 127) / 128) * batch;
+  if (t128 < 100) return launch_split<64, 64, 0, 0, 0, 0, 1>(p, batch, s);
+  return launch_split<128, 128, 0, 0, 0, 0, 1>(p, batch, s);
+}
+
 int dispatch(const IgemmParams& p, int batch, int stem, hipStream_t s) {
+  if (p.res_sample) return stem ? -1 : dispatch_sampled(p, batch, s);
   if (stem) {
     const int smode = mfma_mode_cell().load(std::memory_order_relaxed);
     return smode ? launch_split<128, 64, 1>(p, batch, s) : launch<128, 64, 1>(p, batch, s);
@@ -1930,7 +2015,7 @@ static int conv2d_impl(const char* who, const float* input, const float* weight,
                        int h0, int w0, int batch1, int h1, int w1, int cin, int cout, int kh, int kw, int stride,
                        int pad, long in_pix_stride, long out0_stride, long out1_stride, long res0_stride,
                        long res1_stride, int flags, dana_stream_t stream, const float* mask = nullptr,
-                       long mask_stride = 0) {
+                       long mask_stride = 0, int res_h = 0, int res_w = 0, int res_sample = 0) {
   DANA_CHECK_ARG(batch0 >= 0 && batch1 >= 0 && cin > 0 && cout > 0 && kh > 0 && kw > 0 && stride > 0 && pad >= 0,
                  "%s: bad shape", who);
   DANA_CHECK_ARG((batch0 == 0 || (h0 > 0 && w0 > 0)) && (batch1 == 0 || (h1 > 0 && w1 > 0)), "%s: bad image size", who);
@@ -2012,7 +2097,22 @@ static int conv2d_impl(const char* who, const float* input, const float* weight,
   p.ldr1 = res1_stride > 0 ? res1_stride : cout;
   DANA_CHECK_ARG(((uintptr_t)input & 15) == 0 && ((uintptr_t)weight & 15) == 0,
                  "%s: input/weight must be 16-byte aligned", who);
-  run(p, 1, stem, (hipStream_t)stream);
+  if (res_sample > 0 && res0) {
+    DANA_CHECK_ARG(batch1 == 0 && !mask && res_h > 0 && res_w > 0 && (res_h - 1) / res_sample + 1 == p.OH &&
+                       (res_w - 1) / res_sample + 1 == p.OW,
+                   "%s: sampled residual: one segment, no mask, and (res_h - 1) / res_sample + 1 x (res_w - 1) / res_sample + 1 must be the output map", who);
+    const long res_bytes = (long)batch0 * res_h * res_w * p.ldr * 4;
+    DANA_CHECK_ARG(res_bytes < (long)OOB, "%s: residual span >= 2 GiB; split the batch", who);
+    p.res_sample = res_sample;
+    p.res_h = res_h;
+    p.res_w = res_w;
+    p.res_oh = p.OH;
+    p.res_ow = p.OW;
+    p.res_bytes = (unsigned)res_bytes;
+  }
+  const int rc = run(p, 1, stem, (hipStream_t)stream);
+  DANA_CHECK_ARG(rc == 0, "%s: a sampled residual needs the split kernel's register epilogue at a 64 x 64 or 128 x 128 tile "
+                          "(dana_set_mfma_mode(1), dana_set_epilogue_mode(0), cout > 64, at most 32 taps)", who);
   DANA_CHECK_LAUNCH(who);
   return DANA_OK;
 }
@@ -2026,6 +2126,17 @@ int dana_conv2d_nhwc(const float* input, const float* weight, float* output, con
                      0, flags, stream);
 }
 
+int dana_conv2d_nhwc_sampled_res(const float* input, const float* weight, float* output, const float* scale,
+                                 const float* shift, const float* residual, int batch, int in_h, int in_w, int cin,
+                                 int cout, int kh, int kw, int stride, int pad, long in_pix_stride, long out_pix_stride,
+                                 long res_pix_stride, int res_h, int res_w, int res_sample, int flags, dana_stream_t stream) {
+  const char* who = "dana_conv2d_nhwc_sampled_res";
+  DANA_CHECK_ARG(residual && res_sample >= 1 && res_sample <= 2, "%s: needs a residual and res_sample 1 or 2", who);
+  return conv2d_impl(who, input, weight, output, nullptr, scale, shift, residual, nullptr, batch, in_h, in_w, 0, 0, 0, cin,
+                     cout, kh, kw, stride, pad, in_pix_stride, out_pix_stride, 0, res_pix_stride, 0, flags, stream, nullptr, 0,
+                     res_h, res_w, res_sample);
+}
+
 int dana_conv2d_nhwc_masked(const float* input, const float* weight, float* output, const float* scale,
                             const float* shift, const float* residual, const float* mask_act, int batch, int in_h,
                             int in_w, int cin, int cout, int kh, int kw, int stride, int pad, long in_pix_stride,
@@ -2036,12 +2147,11 @@ int dana_conv2d_nhwc_masked(const float* input, const float* weight, float* outp
                      res_pix_stride, 0, flags, stream, mask_act, mask_pix_stride);
 }
 
-int dana_bottleneck_tail_nhwc(const float* input, const float* w2_split, const float* scale2, const float* shift2,
-                              const float* w3_split, const float* scale3, const float* shift3, const float* residual,
-                              float* output, int batch, int h, int w, int cin, int cmid, int cout, long in_pix_stride,
-                              long out_pix_stride, long res_pix_stride, int flags, dana_stream_t stream) {
-  const char* who = "dana_bottleneck_tail_nhwc";
-  DANA_CHECK_ARG(batch >= 0 && h > 0 && w > 0, "%s: bad shape", who);
+static int tail_impl(const char* who, const float* input, const float* w2_split, const float* scale2, const float* shift2,
+                     const float* w3_split, const float* scale3, const float* shift3, const float* residual,
+                     float* output, int batch, int h, int w, int cin, int cmid, int cout, long in_pix_stride,
+                     long out_pix_stride, long res_pix_stride, int stride, int flags, dana_stream_t stream) {
+  DANA_CHECK_ARG(batch >= 0 && h > 0 && w > 0 && (stride == 1 || stride == 2), "%s: bad shape (stride 1 or 2)", who);
   if (batch == 0) return DANA_OK;
   DANA_CHECK_ARG(input && w2_split && w3_split && output, "%s: null pointer", who);
   DANA_CHECK_ARG(cmid == 64 && cin % SBK == 0 && cin > 0 && cout % 64 == 0 && cout > 0,
@@ -2057,12 +2167,12 @@ int dana_bottleneck_tail_nhwc(const float* input, const float* w2_split, const f
   p.residual = residual;
   p.IH = p.IH1 = h;
   p.IW = p.IW1 = w;
-  p.OH = p.OH1 = h;
-  p.OW = p.OW1 = w;
-  p.M = p.M0 = batch * h * w;
+  p.OH = p.OH1 = (h - 1) / stride + 1;
+  p.OW = p.OW1 = (w - 1) / stride + 1;
+  p.M = p.M0 = batch * p.OH * p.OW;
   p.N = cmid;
   p.KH = p.KW = 3;
-  p.stride = 1;
+  p.stride = stride;
   p.pad = 1;
   p.Cin = cin;
   p.K = 9 * cin;
@@ -2091,9 +2201,34 @@ int dana_bottleneck_tail_nhwc(const float* input, const float* w2_split, const f
   DANA_CHECK_ARG(((uintptr_t)input & 15) == 0 && ((uintptr_t)w2_split & 15) == 0 && ((uintptr_t)w3_split & 15) == 0,
                  "%s: input / weights must be 16-byte aligned", who);
   p.trace = nullptr;
-  launch_split<128, 64, 0, 1, 1>(p, 1, (hipStream_t)stream);
+  if (stride == 1) {
+    launch_split<128, 64, 0, 1, 1>(p, 1, (hipStream_t)stream);
+  } else {
+    // the residual is read at pixel (stride * oh, stride * ow) of its h x w map: one descriptor over the whole map
+    const long res_bytes = (long)batch * h * w * p.ldr * 4;
+    DANA_CHECK_ARG(res_bytes < (long)OOB, "%s: residual span >= 2 GiB; split the batch", who);
+    p.res_bytes = (unsigned)res_bytes;
+    launch_split<128, 64, 0, 1, 2>(p, 1, (hipStream_t)stream);
+  }
   DANA_CHECK_LAUNCH(who);
   return DANA_OK;
+}
+
+int dana_bottleneck_tail_nhwc(const float* input, const float* w2_split, const float* scale2, const float* shift2,
+                              const float* w3_split, const float* scale3, const float* shift3, const float* residual,
+                              float* output, int batch, int h, int w, int cin, int cmid, int cout, long in_pix_stride,
+                              long out_pix_stride, long res_pix_stride, int flags, dana_stream_t stream) {
+  return tail_impl("dana_bottleneck_tail_nhwc", input, w2_split, scale2, shift2, w3_split, scale3, shift3, residual, output,
+                   batch, h, w, cin, cmid, cout, in_pix_stride, out_pix_stride, res_pix_stride, 1, flags, stream);
+}
+
+int dana_bottleneck_tail_strided_nhwc(const float* input, const float* w2_split, const float* scale2, const float* shift2,
+                                      const float* w3_split, const float* scale3, const float* shift3,
+                                      const float* residual, float* output, int batch, int h, int w, int cin, int cmid,
+                                      int cout, long in_pix_stride, long out_pix_stride, long res_pix_stride, int stride,
+                                      int flags, dana_stream_t stream) {
+  return tail_impl("dana_bottleneck_tail_strided_nhwc", input, w2_split, scale2, shift2, w3_split, scale3, shift3, residual,
+                   output, batch, h, w, cin, cmid, cout, in_pix_stride, out_pix_stride, res_pix_stride, stride, flags, stream);
 }
 
 int dana_conv2d_nhwc_dual(const float* input, const float* weight, float* out0, float* out1, const float* scale,

@@ -263,7 +263,10 @@ __device__ __forceinline__ void at6(const float4 (&m)[6], float4 (&o)[4]) {
   o[3] = f4add(f4ma(s, 8.f, q), m[5]);
 }
 
-// one lane = (tile, 4 output channels)
+// one lane = (tile, 4 output channels). SUB = 2: only rows / columns 0 and 2 of each 4 x 4 tile are finished and written,
+// into a dense ((H-1)/2+1) x ((W-1)/2+1) map -- the pixels a stride-2 1x1 consumer reads (tile origins are multiples of 4,
+// so these are the even pixels of the image); per written element the same expression as SUB = 1 -> the same bits.
+template <int SUB = 1>
 __global__ void __launch_bounds__(256)
 wino4_output_kernel(const float* __restrict__ M, float* __restrict__ out, const float* __restrict__ scale,
                     const float* __restrict__ shift, const float* __restrict__ mask, long ldm, int H, int W, int N4,
@@ -293,16 +296,21 @@ wino4_output_kernel(const float* __restrict__ M, float* __restrict__ out, const 
   const float4 sc = scale ? ((const float4*)scale)[n4] : make_float4(1, 1, 1, 1);
   const float4 sh = shift ? ((const float4*)shift)[n4] : make_float4(0, 0, 0, 0);
 #pragma unroll
-  for (int r = 0; r < 4; ++r) {
+  for (int r = 0; r < 4; r += SUB) {
     const int y = 4 * i + r;
     if (y >= H) break;
     float4 o[4];
     at6(s[r], o);
 #pragma unroll
-    for (int c = 0; c < 4; ++c) {
+    for (int c = 0; c < 4; c += SUB) {
       const int x = 4 * j + c;
       if (x >= W) break;
       float4 v = make_float4(o[c].x * sc.x + sh.x, o[c].y * sc.y + sh.y, o[c].z * sc.z + sh.z, o[c].w * sc.w + sh.w);
+      if constexpr (SUB == 2) {  // (no residual / mask on the sampled form: checked by the host)
+        if (relu) v = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
+        *(float4*)(out + ((img * ((H + 1) / 2) + y / 2) * ((W + 1) / 2) + x / 2) * ldc + n4 * 4) = v;
+        continue;
+      }
       if (res) {  // grouped residual (class sweep): output image img reads residual image img / rgroup
         const float4 q = *(const float4*)(res + (((img / rgroup) * H + y) * W + x) * ldr + n4 * 4);
         v = f4add(v, q);
@@ -583,9 +591,10 @@ size_t dana_conv3x3_winograd4_workspace_bytes(int batch, int h, int w, int cin, 
 static int wino4_impl(const float* input, const float* u, float* output, const float* scale, const float* shift,
                       const float* mask_act, const float* res, long res_pix_stride, int res_group, int batch, int h,
                       int w, int cin, int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
-                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
+                      int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream, int sub = 1) {
   DANA_CHECK_ARG(batch >= 0 && h > 0 && w > 0 && cin > 0 && cout > 0 && cin % 4 == 0 && cout % 4 == 0,
                  "dana_conv3x3_winograd4_nhwc: bad shape");
+  DANA_CHECK_ARG(sub == 1 || (sub == 2 && !mask_act && !res), "dana_conv3x3_winograd4_nhwc: sub is 1 or 2 (2: no mask, no residual)");
   if (batch == 0) return DANA_OK;
   DANA_CHECK_ARG(input && u && output, "dana_conv3x3_winograd4_nhwc: null pointer");
   const long lda = in_pix_stride > 0 ? in_pix_stride : cin;
@@ -620,9 +629,14 @@ static int wino4_impl(const float* input, const float* u, float* output, const f
                         p.tiles * cin, w3 ? 3 * cout * kp : (long)cout * cin, p.tiles * cout, 1.f, w3 ? DANA_W_SPLIT3 : 0,
                         stream);
   if (rc) return rc;
-  wino4_output_kernel<<<dana_ceil_div(p.tiles * N4, 256), 256, 0, s>>>(M, output, scale, shift, mask_act, ldm, h, w, N4,
-                                                                      p.th, p.tw, p.tiles, ldc,
-                                                                      (flags & DANA_EPI_RELU) ? 1 : 0, 0, 0, res, ldr, res_group);
+  if (sub == 2)
+    wino4_output_kernel<2><<<dana_ceil_div(p.tiles * N4, 256), 256, 0, s>>>(M, output, scale, shift, nullptr, ldm, h, w, N4,
+                                                                           p.th, p.tw, p.tiles, ldc,
+                                                                           (flags & DANA_EPI_RELU) ? 1 : 0);
+  else
+    wino4_output_kernel<<<dana_ceil_div(p.tiles * N4, 256), 256, 0, s>>>(M, output, scale, shift, mask_act, ldm, h, w, N4,
+                                                                        p.th, p.tw, p.tiles, ldc,
+                                                                        (flags & DANA_EPI_RELU) ? 1 : 0, 0, 0, res, ldr, res_group);
   DANA_CHECK_LAUNCH("dana_conv3x3_winograd4_nhwc(output transform)");
   return DANA_OK;
 }
@@ -633,6 +647,17 @@ int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float
                                        int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream) {
   return wino4_impl(input, u, output, scale, shift, mask_act, nullptr, 0, 1, batch, h, w, cin, cout, in_pix_stride,
                     out_pix_stride, mask_pix_stride, flags, workspace, workspace_bytes, stream);
+}
+
+/* F(4x4, 3x3) forward whose output transform writes the even pixels only (sub = 2): output is the dense
+ * [batch][(h-1)/2+1][(w-1)/2+1][out_pix_stride] map a stride-2 1x1 consumer reads; sub = 1 writes the full map.
+ * The input transform and the plane GEMM are the full-size ones; workspace as dana_conv3x3_winograd4_workspace_bytes. */
+int dana_conv3x3_winograd4_nhwc_sub(const float* input, const float* u, float* output, const float* scale,
+                                    const float* shift, int batch, int h, int w, int cin, int cout, long in_pix_stride,
+                                    long out_pix_stride, int sub, int flags, void* workspace, size_t workspace_bytes,
+                                    dana_stream_t stream) {
+  return wino4_impl(input, u, output, scale, shift, nullptr, nullptr, 0, 1, batch, h, w, cin, cout, in_pix_stride,
+                    out_pix_stride, 0, flags, workspace, workspace_bytes, stream, sub);
 }
 
 size_t dana_conv3x3_winograd4_dual_workspace_bytes(int n0, int h0, int w0, int n1, int h1, int w1, int cin, int cout) {

@@ -165,6 +165,9 @@ def _rows(t, row):
 
 class DAnARCNN(nn.Module):
     """Dual-Awareness-Attention Faster R-CNN (dana.py:19,327)."""
+    # a stage's last block computes only the pixels the next stage's stride-2 1x1 convs read (_trunk_gen; DESIGN.md 3).
+    # A class attribute: the siblings share the block walker, not this class's __init__
+    trim_strided_seams = True
 
     def __init__(self, classes, attention_type="concat", rpn_reduce_dim=256, rcnn_reduce_dim=256, gamma=0.1,
                  semantic_enhance=False, num_layers=50, pretrained=False, num_way=2, num_shot=5, pos_encoding=True):
@@ -588,8 +591,29 @@ class DAnARCNN(nn.Module):
                     ops.maxpool3x3s2_ceil(_rows(xs[0][0], row), n, h, w, 64, out=o)
         return xp[0][0], psegs
 
-    def _block(self, segs, x, bp, merged=False, outs=None, in_stride=0, saves=None, key=None, alloc=None, save_m=None):
+    def _can_trim(self, bp, nbp):
+        """block `bp` may compute only the even pixels of its output: the next block `nbp` reads nothing else (its 1x1 conv1
+        and 1x1 downsample conv both carry stride 2, resnet.py:71,136) and `bp` is an identity block whose tail has a
+        sampled form -- the fused conv2 + conv3 launch, or an F(4x4,3x3) conv2 followed by a conv3 that runs on the split
+        kernel's register epilogue (ops.conv2d_nhwc's res_sample)."""
+        n1, nds = nbp["c1"], nbp["ds"]
+        if nds is None or any((c["k"], c["stride"], c["pad"]) != (1, 2, 0) for c in (n1, nds)):
+            return False
+        c1, c2, c3 = bp["c1"], bp["c2"], bp["c3"]
+        if bp["ds"] is not None or c1["stride"] != 1 or (c2["k"], c2["stride"], c2["pad"]) != (3, 1, 1) or ops.get_mfma_mode() != 1:
+            return False
+        if c2["cout"] == 64 and c2.get("u") is None and c2["ws"] is not None and c3["ws"] is not None:
+            return True  # (the fused tail)
+        u = c2.get("u")
+        return (u is not None and u.size(0) == 36 and c3["cout"] > 64 and c3["cout"] % 128 == 0
+                and ops.get_epilogue_mode() == 0)
+
+    def _block(self, segs, x, bp, merged=False, outs=None, in_stride=0, saves=None, key=None, alloc=None, save_m=None,
+               trim=False, pre=False):
         """one Bottleneck (resnet.py:66-108) over the batch segments of x -> (o3, segs on the block's output grid, outs).
+        trim (per-segment launches that save nothing, _can_trim): the block's tail computes only the even pixels of its
+        output -> a dense map on the sampled grid; pre: x IS such a sampled map, so the block's strided 1x1 convs (conv1,
+        downsample) walk it with stride 1. Every value has the bits of the untrimmed walk.
         outs: per segment (buffer, or None for a fresh one; row stride) that the block's result goes to instead of a dense
         [all rows][cout] buffer. saves: per segment a list (None: nothing is saved) that receives dict(x, o1, o2, o3, h1, w1, ...) for
         backward.bottleneck_backward (row views of the segments' buffers); save_m: a list that receives the [query | support]
@@ -599,7 +623,11 @@ class DAnARCNN(nn.Module):
         if saves is not None and saves[0] is None:
             saves = None
         c1, c2, c3, ds = bp["c1"], bp["c2"], bp["c3"], bp["ds"]
-        dev, cout, sd = x.device, c3["cout"], c1["stride"]
+        dev, cout, sd = x.device, c3["cout"], 1 if pre else c1["stride"]
+        if pre:  # (a copy of the plan's entries: the geometry changes, the weights do not)
+            c1, ds = dict(c1, stride=1), dict(ds, stride=1)
+        if (trim or pre) and (merged or saves is not None or outs is not None):
+            raise ValueError("a trimmed seam: per-segment launches that save nothing and write a fresh buffer")
         osegs = self._grid(segs, lambda h, w: ((h - 1) // sd + 1, (w - 1) // sd + 1))  # (the 1x1 conv1 carries the stride)
         calloc = None if merged else alloc  # (a merged launch's output is written and read on the caller's stream alone)
         o1 = self._conv(segs, osegs, x, c1, True, merged, in_stride=in_stride, alloc=calloc)
@@ -617,13 +645,26 @@ class DAnARCNN(nn.Module):
                 and c2.get("u") is None and c2["ws"] is not None and c3["ws"] is not None):
             # conv2 -> conv3 in one launch (layer1's identity blocks; nothing of a frozen layer is saved for the backward)
             outs = given()
-            dest = self._dest(osegs, cout, outs, calloc, dev)
+            tsegs = self._grid(osegs, lambda h, w: ((h - 1) // 2 + 1, (w - 1) // 2 + 1)) if trim else osegs
+            dest = self._dest(tsegs, cout, outs, calloc, dev)
             for (n, _, row, st), (_, (h1, w1), orow, _), (o, ld) in zip(segs, osegs, dest):
                 with _on(st):
                     ops.bottleneck_tail(_rows(o1, orow), n, h1, w1, c2["cin"], c2["ws"], c2["scale"], c2["shift"], c3["ws"],
                                         c3["scale"], c3["shift"], cout, residual=_rows(x, row), res_stride=in_stride, out=o,
-                                        out_stride=ld)
-            return dest[0][0], osegs, outs
+                                        out_stride=ld, stride=2 if trim else 1)
+            return dest[0][0], tsegs, outs
+        if trim:
+            # conv2's output transform writes the even pixels only; conv3 runs on those rows and adds x at those pixels
+            tsegs = self._grid(osegs, lambda h, w: ((h - 1) // 2 + 1, (w - 1) // 2 + 1))
+            d2, d3 = self._dest(tsegs, c2["cout"], None, calloc, dev), self._dest(tsegs, cout, None, calloc, dev)
+            for (n, _, row, st), (_, (h1, w1), orow, _), (_, (h2, w2), _, _), (o2, _), (o, ld) in zip(segs, osegs, tsegs, d2, d3):
+                with _on(st):
+                    ops.conv3x3_winograd(_rows(o1, orow), n, h1, w1, c2["cin"], c2.get("us") or c2["u"], c2["cout"],
+                                         scale=c2["scale"], shift=c2["shift"], relu=True, out=o2, out_stride=c2["cout"], sub=2)
+                    ops.conv2d_nhwc(o2, n, h2, w2, c3["cin"], self._b(c3), cout, 1, 1, 1, 0, scale=c3["scale"],
+                                    shift=c3["shift"], residual=_rows(x, row), relu=True, out=o, out_stride=ld,
+                                    res_stride=in_stride, res_hw=(h1, w1), res_sample=2)
+            return d3[0][0], tsegs, None
         keep = [[] for _ in segs] if saves is not None else None  # conv2's Winograd-domain input (V planes), per segment, for
         o2 = self._conv(osegs, osegs, o1, c2, True, merged, keep=keep, alloc=calloc)  # its weight gradient
         outs = given()
@@ -736,6 +777,7 @@ class DAnARCNN(nn.Module):
         x, segs = self._stem(segs, ims, plan["stem"], merged, alloc)
         yield
         nl = len(plan["layers"])
+        nosave, pre = saves is None or all(s is None for s in saves), False
         stall = getattr(self, "_debug_stall", None) if two else None  # tests: (layer, spin cycles) -- hold the caller's
         for li, layer in enumerate(plan["layers"]):                  # stream back in front of every two-launch block there
             if two and not merged and li >= merge_from:
@@ -744,9 +786,15 @@ class DAnARCNN(nn.Module):
                 last = (li == nl - 1) and (bi == len(layer) - 1)
                 if stall is not None and not merged and li == stall[0]:
                     torch.cuda._sleep(int(stall[1]))
+                # a stage's last block computes only the pixels the next stage's stride-2 1x1 convs read:
+                # both blocks per segment (not merged, here and in the next stage), neither saving, no caller-given buffer
+                trim = (self.trim_strided_seams and not last and bi == len(layer) - 1 and li + 1 < nl and not merged
+                        and not (two and li + 1 >= merge_from) and (nosave or li + 1 < save_from)
+                        and self._can_trim(bp, plan["layers"][li + 1][0]))
                 x, segs, dest = self._block(segs, x, bp, merged, outs=outs if last and outs[0][1] else None,
                                             saves=saves if li >= save_from else None, key="RCNN_base.%d.%d" % (4 + li, bi), alloc=alloc,
-                                            save_m=save_m)
+                                            save_m=save_m, trim=trim, pre=pre)
+                pre = trim
                 if not last:
                     yield
         if two and not merged:

@@ -708,8 +708,11 @@ def plain_rcnn_losses(scores, labels, bbox_pred, bbox_targets, inside_ws, outsid
 # dense contractions
 # ------------------------------------------------------------------------------------------------
 def conv2d_nhwc(x, batch, in_h, in_w, cin, weight, cout, kh, kw, stride, pad, scale=None, shift=None,
-                residual=None, relu=False, in_stride=0, out=None, out_stride=0, res_stride=0, stem=False):
-    """x: flat NHWC buffer; weight packed [cout][kh][kw][cin]. Returns (out, OH, OW)."""
+                residual=None, relu=False, in_stride=0, out=None, out_stride=0, res_stride=0, stem=False, res_hw=None,
+                res_sample=0):
+    """x: flat NHWC buffer; weight packed [cout][kh][kw][cin]. Returns (out, OH, OW).
+    res_hw / res_sample: the residual is a [batch][res_hw[0]][res_hw[1]] map read at pixel (res_sample * oh, res_sample * ow)
+    (dana_conv2d_nhwc_sampled_res: the split kernel's register epilogue only -- any other path raises)."""
     _chk(x, "x")
     wp, wfl = _wf(weight)
     oh = (in_h + 2 * pad - kh) // stride + 1
@@ -719,8 +722,13 @@ def conv2d_nhwc(x, batch, in_h, in_w, cin, weight, cout, kh, kw, stride, pad, sc
         out_stride = cout
     flags = (EPI_RELU if relu else 0) | (CONV_STEM7 if stem else 0) | wfl
     e0 = _prof_begin()
-    lib().call("dana_conv2d_nhwc", _p(x), wp, _p(out), _p(scale), _p(shift), _p(residual), batch, in_h,
-               in_w, cin, cout, kh, kw, stride, pad, in_stride, out_stride, res_stride, flags, _stream())
+    if res_sample:
+        lib().call("dana_conv2d_nhwc_sampled_res", _p(x), wp, _p(out), _p(scale), _p(shift), _p(_chk(residual, "residual")),
+                   batch, in_h, in_w, cin, cout, kh, kw, stride, pad, in_stride, out_stride, res_stride, res_hw[0], res_hw[1],
+                   int(res_sample), flags, _stream())
+    else:
+        lib().call("dana_conv2d_nhwc", _p(x), wp, _p(out), _p(scale), _p(shift), _p(residual), batch, in_h,
+                   in_w, cin, cout, kh, kw, stride, pad, in_stride, out_stride, res_stride, flags, _stream())
     # algorithmic flops: the stem counts its 3 real channels x 49 real taps, not the padded K=224
     _prof_end(e0, ("conv%dx%d M=%d N=%d K=%d s%d", (kh, kw, batch * oh * ow, cout, kh * kw * cin, stride)),
               2.0 * batch * oh * ow * cout * kh * kw * (3 if stem else cin),
@@ -730,23 +738,31 @@ def conv2d_nhwc(x, batch, in_h, in_w, cin, weight, cout, kh, kw, stride, pad, sc
 
 
 def bottleneck_tail(x, batch, h, w, cin, w2, scale2, shift2, w3, scale3, shift3, cout, residual=None, relu=True, in_stride=0,
-                    out=None, out_stride=0, res_stride=0):
+                    out=None, out_stride=0, res_stride=0, stride=1):
     """conv2 (3x3 / 1 / pad 1, cin -> 64) + bn2 + ReLU + conv3 (1x1, 64 -> cout) + bn3 + residual + ReLU of a Bottleneck
-    (resnet.py:92-100) as ONE launch; w2 / w3 are W3 split planes. Returns (out, h, w)."""
+    (resnet.py:92-100) as ONE launch; w2 / w3 are W3 split planes. Returns (out, oh, ow).
+    stride = 2: only the pixels (2 * oh, 2 * ow) are computed, into a dense (h - 1) // 2 + 1 x (w - 1) // 2 + 1 map; the
+    residual stays the h x w map and is read at those pixels (dana_bottleneck_tail_strided_nhwc)."""
     _chk(x, "x")
     if not (isinstance(w2, W3) and isinstance(w3, W3)):
         raise TypeError("bottleneck_tail: both weights must be split planes (ops.split_weight)")
+    oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
     if out is None:
-        out = torch.empty((batch * h * w, cout), dtype=torch.float32, device=x.device)
+        out = torch.empty((batch * oh * ow, cout), dtype=torch.float32, device=x.device)
         out_stride = cout
     e0 = _prof_begin()
-    lib().call("dana_bottleneck_tail_nhwc", _p(x), _p(w2.t), _p(scale2), _p(shift2), _p(w3.t), _p(scale3), _p(shift3),
-               _p(residual), _p(out), batch, h, w, cin, 64, cout, in_stride, out_stride, res_stride, EPI_RELU if relu else 0,
-               _stream())
-    m = batch * h * w
-    _prof_end(e0, ("conv3x3+1x1 M=%d N=%d K=%d+64 s1", (m, cout, 9 * cin)), 2.0 * m * 64 * (9 * cin + cout),
-              4.0 * (m * cin + 64 * 9 * cin + 64 * cout + m * cout * (2 if residual is not None else 1)))
-    return out, h, w
+    if stride == 1:
+        lib().call("dana_bottleneck_tail_nhwc", _p(x), _p(w2.t), _p(scale2), _p(shift2), _p(w3.t), _p(scale3), _p(shift3),
+                   _p(residual), _p(out), batch, h, w, cin, 64, cout, in_stride, out_stride, res_stride,
+                   EPI_RELU if relu else 0, _stream())
+    else:
+        lib().call("dana_bottleneck_tail_strided_nhwc", _p(x), _p(w2.t), _p(scale2), _p(shift2), _p(w3.t), _p(scale3),
+                   _p(shift3), _p(residual), _p(out), batch, h, w, cin, 64, cout, in_stride, out_stride, res_stride,
+                   int(stride), EPI_RELU if relu else 0, _stream())
+    m = batch * oh * ow
+    _prof_end(e0, ("conv3x3+1x1 M=%d N=%d K=%d+64 s%d", (m, cout, 9 * cin, stride)), 2.0 * m * 64 * (9 * cin + cout),
+              4.0 * (batch * h * w * cin + 64 * 9 * cin + 64 * cout + m * cout * (2 if residual is not None else 1)))
+    return out, oh, ow
 
 
 def conv2d_nhwc_dual(x, n0, h0, w0, n1, h1, w1, cin, weight, cout, kh, kw, stride, pad, scale=None, shift=None,
@@ -873,18 +889,23 @@ def winograd_filter_transform(w_packed, cout, cin, tile=2):
 
 
 def conv3x3_winograd(x, batch, h, w, cin, u, cout, scale=None, shift=None, relu=False, in_stride=0, out=None,
-                     out_stride=0, mask=None, mask_stride=0, keep_v=None, residual=None, res_stride=0, res_group=1):
+                     out_stride=0, mask=None, mask_stride=0, keep_v=None, residual=None, res_stride=0, res_group=1, sub=1):
     """stride-1 pad-1 3x3 conv through Winograd F(2x2,3x3) or F(4x4,3x3), chosen by u (winograd_filter_transform).
     keep_v: a list that receives the launch's workspace (F(4x4) only): its first 36*tiles*cin floats are the input's
     transform V, which conv3x3_wgrad_winograd(v=...) takes instead of transforming the input again.
-    residual (class sweep): out = relu?(conv * scale + shift + residual[image // res_group]), row stride res_stride."""
+    residual (class sweep): out = relu?(conv * scale + shift + residual[image // res_group]), row stride res_stride.
+    sub = 2 (F(4x4) only, no mask / residual): the output transform writes the even pixels only, a dense
+    (h - 1) // 2 + 1 x (w - 1) // 2 + 1 map (dana_conv3x3_winograd4_nhwc_sub). Returns (out, oh, ow)."""
     _chk(x, "x")
     up, wfl = _wf(u)
     m = 2 if (u.batch if isinstance(u, W3) else u.size(0)) == 16 else 4
     if wfl and m != 4:
         raise ValueError("conv3x3_winograd: split filters with F(4x4,3x3) only")
+    if sub != 1 and (m != 4 or mask is not None or residual is not None):
+        raise ValueError("conv3x3_winograd: sub = 2 needs F(4x4,3x3) filters, no mask, no residual")
+    oh, ow = (h - 1) // sub + 1, (w - 1) // sub + 1
     if out is None:
-        out = torch.empty((batch * h * w, cout), dtype=torch.float32, device=x.device)
+        out = torch.empty((batch * oh * ow, cout), dtype=torch.float32, device=x.device)
         out_stride = cout
     sfx = "" if m == 2 else "4"
     ws = _ws(lib().query("dana_conv3x3_winograd%s_workspace_bytes" % sfx, batch, h, w, cin, cout), x.device)
@@ -895,6 +916,9 @@ def conv3x3_winograd(x, batch, h, w, cin, u, cout, scale=None, shift=None, relu=
         lib().call("dana_conv3x3_winograd_nhwc_grouped_res", _p(x), up, _p(out), _p(scale), _p(shift),
                    _p(_chk(residual, "residual")), batch, h, w, cin, cout, in_stride, out_stride, res_stride,
                    int(res_group), m, (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(), _stream())
+    elif sub != 1:
+        lib().call("dana_conv3x3_winograd4_nhwc_sub", _p(x), up, _p(out), _p(scale), _p(shift), batch, h, w, cin, cout,
+                   in_stride, out_stride, int(sub), (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(), _stream())
     else:
         lib().call("dana_conv3x3_winograd%s_nhwc_masked" % sfx, _p(x), up, _p(out), _p(scale), _p(shift), _p(mask), batch,
                    h, w, cin, cout, in_stride, out_stride, mask_stride, (EPI_RELU if relu else 0) | wfl, _p(ws), ws.numel(),
@@ -906,7 +930,7 @@ def conv3x3_winograd(x, batch, h, w, cin, u, cout, scale=None, shift=None, relu=
               4.0 * (m + 2) * (m + 2) * (batch * ((h + m - 1) // m) * ((w + m - 1) // m) * (cin + cout) + cout * cin),
               # what the matrix cores execute: (m+2)^2 plane GEMMs of [tiles x cin] . [cin x cout]
               executed=2.0 * (m + 2) * (m + 2) * batch * ((h + m - 1) // m) * ((w + m - 1) // m) * cin * cout)
-    return out, h, w
+    return out, oh, ow
 
 
 def set_mfma_mode(mode):
@@ -941,6 +965,10 @@ def cumask_stream(cus_per_xcd, n_xcd=8, cus_in_xcd=32):
     lib().call("dana_debug_stream_create_cumask", ctypes.cast(mask, ctypes.c_void_p), words, n_xcd,
                ctypes.cast(ctypes.byref(out), ctypes.c_void_p))
     return torch.cuda.ExternalStream(out.value)
+
+
+def get_epilogue_mode():
+    return lib().query("dana_get_epilogue_mode")
 
 
 def set_epilogue_mode(mode):

@@ -293,6 +293,25 @@ int dana_bottleneck_tail_nhwc(const float* input, const float* w2_split, const f
                               const float* w3_split, const float* scale3, const float* shift3, const float* residual,
                               float* output, int batch, int h, int w, int cin, int cmid, int cout, long in_pix_stride,
                               long out_pix_stride, long res_pix_stride, int flags, dana_stream_t stream);
+/* ... computing only the pixels a stride-`stride` 1x1 consumer reads (stride 1 or 2; resnet.py:71,136 put a layer's stride
+ * on the next block's 1x1 conv1 / downsample): conv2 runs 3x3 / stride `stride` / pad 1 over the h x w input, OH = (h-1)/stride+1,
+ * conv3 + bn3 (+ ReLU) on those rows only; output is the dense [batch*OH*OW][out_pix_stride] map, the residual row of output
+ * pixel (oh, ow) is pixel (stride*oh, stride*ow) of the [batch][h][w][res_pix_stride] map. Every written value has the bits
+ * dana_bottleneck_tail_nhwc writes at that pixel. stride = 1 is dana_bottleneck_tail_nhwc. */
+int dana_bottleneck_tail_strided_nhwc(const float* input, const float* w2_split, const float* scale2, const float* shift2,
+                                      const float* w3_split, const float* scale3, const float* shift3,
+                                      const float* residual, float* output, int batch, int h, int w, int cin, int cmid,
+                                      int cout, long in_pix_stride, long out_pix_stride, long res_pix_stride, int stride,
+                                      int flags, dana_stream_t stream);
+/* dana_conv2d_nhwc whose residual is SAMPLED: output pixel (oh, ow) adds pixel (res_sample*oh, res_sample*ow) of the
+ * [batch][res_h][res_w][res_pix_stride] map; (res_h-1)/res_sample+1 x (res_w-1)/res_sample+1 must be the conv's output map
+ * (the expand conv of a block whose consumer has stride 2: the rows are the even pixels, the residual is x at those pixels).
+ * Runs on the split kernel's register epilogue at a 64 x 64 or 128 x 128 tile (dana_set_mfma_mode(1), cout > 64); any
+ * other path returns DANA_ERR_ARG. res_sample 1 or 2; same bits as dana_conv2d_nhwc over a gathered residual. */
+int dana_conv2d_nhwc_sampled_res(const float* input, const float* weight, float* output, const float* scale,
+                                 const float* shift, const float* residual, int batch, int in_h, int in_w, int cin,
+                                 int cout, int kh, int kw, int stride, int pad, long in_pix_stride, long out_pix_stride,
+                                 long res_pix_stride, int res_h, int res_w, int res_sample, int flags, dana_stream_t stream);
 
 /* The same conv over TWO image groups in one launch: input rows = batch0 images of h0 x w0 followed by
  * batch1 images of h1 x w1 (same channels / pixel stride); outputs go to out0 / out1 with their own row
@@ -328,6 +347,14 @@ int dana_conv3x3_winograd4_nhwc_masked(const float* input, const float* u, float
                                        const float* shift, const float* mask_act, int batch, int h, int w, int cin,
                                        int cout, long in_pix_stride, long out_pix_stride, long mask_pix_stride,
                                        int flags, void* workspace, size_t workspace_bytes, dana_stream_t stream);
+/* The F(4x4,3x3) forward whose output transform finishes and writes only rows / columns 0 and 2 of each 4 x 4 tile
+ * (sub = 2), i.e. the even pixels, into the dense [batch][(h-1)/2+1][(w-1)/2+1][out_pix_stride] map a stride-2 1x1 consumer
+ * reads. Input transform and plane GEMM are the full-size ones (same workspace); every written value has the bits of the
+ * full output at that pixel. sub = 1: the full map (dana_conv3x3_winograd4_nhwc_masked without a mask). */
+int dana_conv3x3_winograd4_nhwc_sub(const float* input, const float* u, float* output, const float* scale,
+                                    const float* shift, int batch, int h, int w, int cin, int cout, long in_pix_stride,
+                                    long out_pix_stride, int sub, int flags, void* workspace, size_t workspace_bytes,
+                                    dana_stream_t stream);
 /* The RPN 3x3 conv of a class sweep (rpn.py:63 RPN_Conv on cat([base_feat, attended]) of dana.py:157), split by input
  * channels: W[:, :1024] * base_feat once per image (no shift, no ReLU) gives `residual`, then this launch runs
  * W[:, 1024:] * attended per problem with out = relu?(conv*scale + shift + residual[image / res_group]): output image n
