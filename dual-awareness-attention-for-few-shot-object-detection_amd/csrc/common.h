@@ -71,6 +71,34 @@ int dana_wgrad_tn_batched(const float* dY, const float* X, float* out, int plane
                           long batch_x, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __HIPCC__
+// One axis of cv2.resize(INTER_LINEAR) on fp32 (OpenCV resize.cpp, float path), shared by the input pipeline
+// (pipeline.hip), the episode assembler (episode.hip) and the sheets (render.hip) so that the three resize by one rule:
+// sample position (d + 0.5) * scale - 0.5 in double, rounded to float, s = floor, f = position - s; s < 0 -> (0, 0);
+// s >= n - 1 -> (n - 1, 0). s0 and s1 are always inside [0, n). Its users are compiled with -ffp-contract=off.
+struct DanaTap {
+  int s0, s1;
+  float a0, a1;
+};
+__device__ __forceinline__ DanaTap dana_linear_tap(int d, double scale, int n) {
+  float f = (float)(((double)d + 0.5) * scale - 0.5);
+  int s = (int)floorf(f);
+  f -= (float)s;
+  if (s < 0) {
+    s = 0;
+    f = 0.f;
+  }
+  if (s >= n - 1) {
+    s = n - 1;
+    f = 0.f;
+  }
+  DanaTap t;
+  t.s0 = s;
+  t.s1 = min(s + 1, n - 1);
+  t.a0 = 1.f - f;
+  t.a1 = f;
+  return t;
+}
+
 // The exact three-way bf16 split of four fp32 values (igemm.hip: x = h + m + l, each a bf16 taken by truncation), packed
 // as the planes store them: 4 bf16 = 8 bytes per plane. Shared by the contraction kernels' staging path, dana_split_weight
 // and the producers that write an activation as split planes (winograd.hip).

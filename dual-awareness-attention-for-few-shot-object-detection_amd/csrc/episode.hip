@@ -27,30 +27,6 @@ enum { Q_ROW = 0, Q_NORDER = 1, Q_SCALE = 2, Q_INV = 4, Q_YS = 6, Q_XS = 7, Q_CO
 enum { S_ROW = 0, S_INV = 2, S_SX = 4, S_SY = 6, S_X0 = 8, S_Y0 = 9, S_CW = 10, S_CH = 11, S_RW = 12, S_RH = 13,
        S_OH = 14, S_OW = 15 };
 
-struct Tap {
-  int s0, s1;
-  float a0, a1;
-};
-// pipeline.hip's linear_tap: s0 and s1 are always inside [0, n)
-__device__ __forceinline__ Tap linear_tap(int d, double scale, int n) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) {
-    s = 0;
-    f = 0.f;
-  }
-  if (s >= n - 1) {
-    s = n - 1;
-    f = 0.f;
-  }
-  Tap t;
-  t.s0 = s;
-  t.s1 = min(s + 1, n - 1);
-  t.a0 = 1.f - f;
-  t.a1 = f;
-  return t;
-}
 
 __device__ __forceinline__ double plan_double(const int* rec, int word) {
   return *reinterpret_cast<const double*>(rec + word);
@@ -75,7 +51,7 @@ __device__ __forceinline__ bool source_of(const unsigned char* pool, const long 
 }
 
 // prep_image_kernel's value of channel c (BGR) at the prepared pixel whose taps are (tx, ty)
-__device__ __forceinline__ float prep_value(const Source& s, const Tap& tx, const Tap& ty, int c, float mean) {
+__device__ __forceinline__ float prep_value(const Source& s, const DanaTap& tx, const DanaTap& ty, int c, float mean) {
   const int x0 = s.flipped ? s.w - 1 - tx.s0 : tx.s0, x1 = s.flipped ? s.w - 1 - tx.s1 : tx.s1;
   const unsigned char* r0 = s.im + (long)ty.s0 * s.w * 3;
   const unsigned char* r1 = s.im + (long)ty.s1 * s.w * 3;
@@ -109,7 +85,7 @@ episode_queries_kernel(const unsigned char* __restrict__ pool, const long long* 
   if (y < rec[Q_COPY_H] && x < rec[Q_COPY_W] &&
       source_of(pool, offsets, meta, n_rows, pool_bytes, rec[Q_ROW], s)) {
     const double inv = plan_double(rec, Q_INV);
-    const Tap tx = linear_tap(rec[Q_XS] + x, inv, s.w), ty = linear_tap(rec[Q_YS] + y, inv, s.h);
+    const DanaTap tx = dana_linear_tap(rec[Q_XS] + x, inv, s.w), ty = dana_linear_tap(rec[Q_YS] + y, inv, s.h);
     const float mean[3] = {m0, m1, m2};
 #pragma unroll
     for (int c = 0; c < 3; ++c) v[c] = prep_value(s, tx, ty, c, mean[c]);
@@ -135,12 +111,12 @@ episode_supports_kernel(const unsigned char* __restrict__ pool, const long long*
   if (x < rec[S_RW] && y < rec[S_RH] && rec[S_CW] > 0 && rec[S_CH] > 0 &&
       source_of(pool, offsets, meta, n_rows, pool_bytes, rec[S_ROW], s)) {
     // the second resample (crop_resize_pad_kernel): taps into the crop, whose pixels are prepared-image pixels
-    const Tap tx = linear_tap(x, plan_double(rec, S_SX), rec[S_CW]), ty = linear_tap(y, plan_double(rec, S_SY), rec[S_CH]);
+    const DanaTap tx = dana_linear_tap(x, plan_double(rec, S_SX), rec[S_CW]), ty = dana_linear_tap(y, plan_double(rec, S_SY), rec[S_CH]);
     // the first resample (prep_image_kernel) at the two prepared columns and two prepared rows those taps name
     const double inv = plan_double(rec, S_INV);
     const int x0 = rec[S_X0], y0 = rec[S_Y0];
-    const Tap px0 = linear_tap(x0 + tx.s0, inv, s.w), px1 = linear_tap(x0 + tx.s1, inv, s.w);
-    const Tap py0 = linear_tap(y0 + ty.s0, inv, s.h), py1 = linear_tap(y0 + ty.s1, inv, s.h);
+    const DanaTap px0 = dana_linear_tap(x0 + tx.s0, inv, s.w), px1 = dana_linear_tap(x0 + tx.s1, inv, s.w);
+    const DanaTap py0 = dana_linear_tap(y0 + ty.s0, inv, s.h), py1 = dana_linear_tap(y0 + ty.s1, inv, s.h);
     const float mean[3] = {m0, m1, m2};
 #pragma unroll
     for (int c = 0; c < 3; ++c) {

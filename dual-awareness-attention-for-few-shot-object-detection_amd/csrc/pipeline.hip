@@ -17,29 +17,6 @@
 
 namespace {
 
-struct Tap {
-  int s0, s1;
-  float a0, a1;
-};
-__device__ __forceinline__ Tap linear_tap(int d, double scale, int n) {
-  float f = (float)(((double)d + 0.5) * scale - 0.5);
-  int s = (int)floorf(f);
-  f -= (float)s;
-  if (s < 0) {
-    s = 0;
-    f = 0.f;
-  }
-  if (s >= n - 1) {
-    s = n - 1;
-    f = 0.f;
-  }
-  Tap t;
-  t.s0 = s;
-  t.s1 = min(s + 1, n - 1);
-  t.a0 = 1.f - f;
-  t.a1 = f;
-  return t;
-}
 
 __global__ void __launch_bounds__(256)
 prep_image_kernel(const unsigned char* __restrict__ im, int h, int w, long row_stride, int flipped, float m0, float m1,
@@ -47,7 +24,7 @@ prep_image_kernel(const unsigned char* __restrict__ im, int h, int w, long row_s
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= (long)oh * ow) return;
   const int x = (int)(i % ow), y = (int)(i / ow);
-  const Tap tx = linear_tap(x, scale_x, w), ty = linear_tap(y, scale_y, h);
+  const DanaTap tx = dana_linear_tap(x, scale_x, w), ty = dana_linear_tap(y, scale_y, h);
   const int x0 = flipped ? w - 1 - tx.s0 : tx.s0, x1 = flipped ? w - 1 - tx.s1 : tx.s1;
   const unsigned char* r0 = im + (long)ty.s0 * row_stride;
   const unsigned char* r1 = im + (long)ty.s1 * row_stride;
@@ -71,7 +48,7 @@ crop_resize_pad_kernel(const float* __restrict__ im, int w, int x0, int y0, int 
   const int x = (int)(i % target), y = (int)(i / target);
   float v[3] = {0.f, 0.f, 0.f};
   if (x < rw && y < rh) {
-    const Tap tx = linear_tap(x, scale_x, cw), ty = linear_tap(y, scale_y, ch);
+    const DanaTap tx = dana_linear_tap(x, scale_x, cw), ty = dana_linear_tap(y, scale_y, ch);
     const float* r0 = im + ((long)(y0 + ty.s0) * w + x0) * 3;
     const float* r1 = im + ((long)(y0 + ty.s1) * w + x0) * 3;
 #pragma unroll

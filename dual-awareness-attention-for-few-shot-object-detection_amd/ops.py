@@ -1526,6 +1526,68 @@ def heatmap_render(maps, images, table, alpha, means_bgr):
     return out
 
 
+def render_to_rgb(images, means_bgr):
+    """dana_render_to_rgb: [..., 3, H, W] float32 (BGR planes minus means_bgr) -> [..., H, W, 3] uint8 RGB, one launch"""
+    _chk(images, "images")
+    if images.dim() < 3 or images.size(-3) != 3:
+        raise ValueError("render_to_rgb: images must be [..., 3, H, W], got %s" % (tuple(images.shape),))
+    H, W = images.shape[-2:]
+    out = torch.empty(tuple(images.shape[:-3]) + (H, W, 3), dtype=torch.uint8, device=images.device)
+    lib().call("dana_render_to_rgb", _p(images), _p(out), images.numel() // max(3 * H * W, 1), H, W, float(means_bgr[0]),
+               float(means_bgr[1]), float(means_bgr[2]), _stream())
+    return out
+
+
+def render_draw_boxes(canvas, boxes, counts_ptr, offsets_ptr, lists_per_image, num_boxes, per_image, scale, thickness,
+                      min_score, colors, color_index, font, labels, top_last):
+    """dana_render_draw_boxes: canvas [N, H, W, 3] uint8 drawn into in place (and returned), one launch. boxes [M, ld >= 5]
+    float32; counts_ptr / offsets_ptr device addresses of the int32 layout (or None with num_boxes int32 [N] and
+    per_image for the ground-truth form); scale a float32 [N] tensor or a number; min_score a number or None; color_index int32 of any length (rows at or beyond
+    its end take their class slot)."""
+    _chk(canvas, "canvas", torch.uint8)
+    _chk(boxes, "boxes")
+    _chk(colors, "colors", torch.uint8)
+    if canvas.dim() != 4 or canvas.size(3) != 3:
+        raise ValueError("render_draw_boxes: canvas must be [N, H, W, 3], got %s" % (tuple(canvas.shape),))
+    if boxes.dim() != 2 or boxes.size(1) < 5:
+        raise ValueError("render_draw_boxes: boxes must be [M, >=5], got %s" % (tuple(boxes.shape),))
+    N, H, W = canvas.shape[:3]
+    scale_dev = None
+    if isinstance(scale, torch.Tensor):
+        scale_dev = _chk(scale, "scale")
+        if scale_dev.numel() != N:
+            raise ValueError("render_draw_boxes: scale holds %d values for %d images" % (scale_dev.numel(), N))
+    if color_index is not None:
+        _chk(color_index, "color_index", torch.int32)
+    if num_boxes is not None and _chk(num_boxes, "num_boxes", torch.int32).numel() != N:
+        raise ValueError("render_draw_boxes: num_boxes holds %d values for %d images" % (num_boxes.numel(), N))
+    if labels:
+        _chk(font, "font", torch.uint8)
+    lib().call("dana_render_draw_boxes", _p(canvas), N, H, W, _p(boxes), boxes.size(1), boxes.size(0), counts_ptr, offsets_ptr,
+               int(lists_per_image), _p(num_boxes), int(per_image), _p(scale_dev), 1.0 if scale_dev is not None else float(scale),
+               int(thickness), 0 if min_score is None else 1, 0.0 if min_score is None else float(min_score), _p(colors),
+               colors.numel() // 3, _p(color_index), 0 if color_index is None else color_index.numel(), _p(font) if labels else None, 1 if labels else 0, 1 if top_last else 0,
+               _stream())
+    return canvas
+
+
+def render_sheet(query, supports, side, pad, pad_value):
+    """dana_render_sheet: query [N, H, W, 3] and supports [N, S, hs, ws, 3] uint8 -> [N, H, W + cols * (pad + side), 3],
+    one launch"""
+    _chk(query, "query_rgb", torch.uint8)
+    _chk(supports, "supports_rgb", torch.uint8)
+    if query.dim() != 4 or query.size(3) != 3 or supports.dim() != 5 or supports.size(4) != 3 or supports.size(0) != query.size(0):
+        raise ValueError("render_sheet: query [N, H, W, 3] and supports [N, S, hs, ws, 3], got %s and %s"
+                         % (tuple(query.shape), tuple(supports.shape)))
+    N, H, W = query.shape[:3]
+    S, hs, ws = supports.shape[1:4]
+    rpc = max(1, (H + pad) // (side + pad))
+    out = torch.empty((N, H, W + -(-S // rpc) * (pad + side), 3), dtype=torch.uint8, device=query.device)
+    lib().call("dana_render_sheet", _p(query), _p(supports), _p(out), N, H, W, S, hs, ws, int(side), int(pad), int(pad_value),
+               _stream())
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # backward building blocks (groundwork for the training step)
 # ------------------------------------------------------------------------------------------------

@@ -951,6 +951,42 @@ int dana_heatmap_render(const float* maps, const float* images, const unsigned c
                         int gh, int gw, int size, float alpha, float mean_b, float mean_g, float mean_r,
                         dana_stream_t stream);
 
+/* ---- the prediction figure: README images/prediction.jpg, fsod_logger.py:22-34,56-102, net_utils.py:50-60 -----------------
+ * Images, boxes and sheets as RGB bytes on the device (csrc/render.hip states the pixel rule; dana_amd/render.py restates
+ * it in numpy). Byte buffers are passed as void*.
+ *
+ * images [n_images][3][height][width] prepared as the model is fed (BGR planes minus the means) -> out
+ * [n_images][height][width][3] RGB: clamp(image + mean, 0, 255) rounded as dana_heatmap_render does at alpha = 0; NaN -> 0. */
+int dana_render_to_rgb(const float* images, void* out, long n_images, int height, int width, float mean_b, float mean_g,
+                       float mean_r, dana_stream_t stream);
+
+/* Outlines (and labels) of every box of every image into canvas [n_images][height][width][3], in place, in one launch.
+ * boxes: n_rows rows of row_ld >= 5 floats (x1, y1, x2, y2, v). Two forms:
+ *   counts != NULL: counts / offsets of n_images * lists_per_image lists (the layout dana_detect_postprocess_batched and
+ *     dana_detect_merge write); list p belongs to image p / lists_per_image and has class slot p % lists_per_image;
+ *   counts == NULL: image b owns rows b * per_image .. + min(num_boxes[b], per_image) (lists_per_image = 1); rows with
+ *     v == 0 are not drawn.
+ * Coordinates are multiplied by scale_dev[b] (or `scale` when scale_dev is NULL) in fp32; rows with a non-finite product,
+ * a NaN v, v < min_score (use_min_score != 0) or x2 < x1 / y2 < y1 after truncation are skipped, and so is a row outside
+ * the buffer. Colour: colors[n_colors][3] at color_index[row] modulo n_colors; a row at or beyond n_color_index (NULL: every
+ * row) takes its class slot, which is 0 in the ground-truth form. height <= 65535 * 16. labels != 0 prints
+ * "<slot> <v to hundredths>" (ground-truth form: "<v as integer>") with font[12][7] ("0123456789. ", 5 bits per row).
+ * top_last = 0: the first row of an image's order is painted on top; 1: the last. Pixels nothing covers are not written. */
+int dana_render_draw_boxes(void* canvas, int n_images, int height, int width, const float* boxes, int row_ld, long n_rows,
+                           const int* counts, const int* offsets, int lists_per_image, const int* num_boxes,
+                           int per_image, const float* scale_dev, float scale, int thickness, int use_min_score,
+                           float min_score, const unsigned char* colors, int n_colors, const int* color_index,
+                           long n_color_index, const unsigned char* font, int labels, int top_last,
+                           dana_stream_t stream);
+
+/* query [n_images][height][width][3] and supports [n_images][n_shots][shot_h][shot_w][3] -> out
+ * [n_images][height][width + cols * (pad + side)][3], rows_per_col = max(1, (height + pad) / (side + pad)), cols =
+ * ceil(n_shots / rows_per_col): the query at the left, shot s resized to side x side (cv2.resize(INTER_LINEAR), the
+ * convention of dana_prep_image) at x = width + pad + (s / rows_per_col) * (side + pad), y = (s % rows_per_col) *
+ * (side + pad), pad_value everywhere else. side <= height. */
+int dana_render_sheet(const void* query, const void* supports, void* out, int n_images, int height, int width, int n_shots,
+                      int shot_h, int shot_w, int side, int pad, int pad_value, dana_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
