@@ -14,6 +14,20 @@
 //
 // Rows are only ever copied (bit for bit); the one arithmetic line is the fp32 multiply of dets_to_gt_kernel, compiled with
 // -ffp-contract=off like the other byte-parity kernels.
+//
+// dana_detect_merge_soft puts two more steps beside the hard NMS (neither is in the reference; both are restated from
+// their papers, DESIGN.md "Soft-NMS and box voting"):
+//   merge_soft_kernel      Soft-NMS (Bodla et al. 2017), one workgroup per list: the concatenation's boxes, working scores
+//                          and live flags stay in LDS for the whole loop. A pass = workgroup argmax of the live working
+//                          scores (ties to the lowest concatenation index: shuffle reduction inside a wave, the four wave
+//                          winners through LDS), then every thread decays the rows it owns against the picked box. It
+//                          writes its emissions in the form merge_compact_kernel reads (sorted_* / order / keep / num_keep),
+//                          so the compaction is shared with the hard path.
+//   merge_vote_kernel      box voting (Gidaris & Komodakis 2015), one thread per emitted row: the list's concatenation goes
+//                          through LDS in 256-row chunks, in order, and the thread adds the voters to five double
+//                          accumulators sequentially -- the order is the definition, so the result is reproducible.
+// Their arithmetic is one IEEE operation per written operation (fp32 IoU with the exact division; the Gaussian decay and the
+// voting sums in double), which postprocess.merge_soft_numpy restates.
 #include "common.h"
 #include "../../include/dana_hip.h"
 
@@ -21,6 +35,10 @@ namespace {
 
 // dana_nms scans a problem with its column words resident in LDS: (n / 64) * 8 + 528 bytes <= 64 KiB
 constexpr int MERGE_MAX_CAPACITY = (64 * 1024 - 128 * 4 - 16) / 8 * 64;
+// merge_soft_kernel keeps 21 bytes of a row in LDS (box 16, working score 4, live flag 1), 64 KiB less its static words
+constexpr int SOFT_ROW_BYTES = 21;
+constexpr int SOFT_MAX_CAPACITY = (64 * 1024 - 64) / SOFT_ROW_BYTES / 64 * 64;  // 3072
+constexpr int VOTE_CHUNK = 256;
 
 __global__ void __launch_bounds__(256)
 merge_scatter_kernel(const float* __restrict__ dets_in, const int* __restrict__ counts_in,
@@ -122,6 +140,171 @@ merge_compact_kernel(const float4* __restrict__ sorted_boxes, const float* __res
   }
 }
 
+// iou(a, b) with the legacy +1 widths and the exact division (the last branch of nms.hip's iou_suppress): the soft path
+// needs the value, not only its side of a threshold
+__device__ __forceinline__ float area_p1(float4 a) { return (a.z - a.x + 1.f) * (a.w - a.y + 1.f); }
+__device__ __forceinline__ float iou_p1(float4 a, float4 b) {
+  const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x) + 1.f, 0.f);
+  const float h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y) + 1.f, 0.f);
+  const float inter = w * h;
+  return inter / ((area_p1(a) + area_p1(b)) - inter);
+}
+
+// does candidate (ta, ia) rank in front of (tb, ib)? Larger working score first, a NaN behind every number, then the lower
+// concatenation index: a total order, so the reduction tree gives what a sequential scan gives
+__device__ __forceinline__ bool soft_ranks_first(float ta, int ia, float tb, int ib) {
+  const bool na = ta != ta, nb = tb != tb;
+  if (na != nb) return nb;
+  if (!na && ta != tb) return ta > tb;
+  return ia < ib;
+}
+
+enum { SOFT_LINEAR = 1, SOFT_GAUSSIAN = 2 };
+
+__global__ void __launch_bounds__(256)
+merge_soft_kernel(const float4* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ n_total,
+                  int capacity, int method, float nms_thresh, int inclusive, float sigma, float min_score, int max_dets,
+                  float4* __restrict__ sorted_boxes, float* __restrict__ sorted_scores, int* __restrict__ order,
+                  int* __restrict__ keep, int* __restrict__ num_keep) {
+  extern __shared__ float4 s_rows[];  // box [capacity] | working score [capacity] | live [capacity]
+  __shared__ float s_wt[4];
+  __shared__ int s_wi[4];
+  float4* s_box = s_rows;
+  float* s_t = (float*)(s_box + capacity);
+  unsigned char* s_live = (unsigned char*)(s_t + capacity);
+  const int l = blockIdx.x;
+  const long frame = (long)l * capacity;
+  const int n = min(max(n_total[l], 0), capacity);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  for (int i = threadIdx.x; i < n; i += 256) {
+    s_box[i] = boxes[frame + i];
+    s_t[i] = scores[frame + i];
+    s_live[i] = 1;
+  }
+  __syncthreads();
+  const int limit = max_dets > 0 ? min(max_dets, n) : n;
+  const double dsigma = (double)sigma;
+  int emitted = 0;
+  while (emitted < limit) {
+    // the live row with the largest working score; rows of a thread come in ascending index
+    float bt = 0.f;
+    int bi = -1;
+    for (int i = threadIdx.x; i < n; i += 256) {
+      if (!s_live[i]) continue;
+      const float t = s_t[i];
+      if (bi < 0 || soft_ranks_first(t, i, bt, bi)) {
+        bt = t;
+        bi = i;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ot = __shfl_xor(bt, o);
+      const int oi = __shfl_xor(bi, o);
+      if (oi >= 0 && (bi < 0 || soft_ranks_first(ot, oi, bt, bi))) {
+        bt = ot;
+        bi = oi;
+      }
+    }
+    if (lane == 0) {
+      s_wt[wave] = bt;
+      s_wi[wave] = bi;
+    }
+    __syncthreads();
+    bt = s_wt[0];
+    bi = s_wi[0];
+#pragma unroll
+    for (int w = 1; w < 4; ++w) {
+      const float ot = s_wt[w];
+      const int oi = s_wi[w];
+      if (oi >= 0 && (bi < 0 || soft_ranks_first(ot, oi, bt, bi))) {
+        bt = ot;
+        bi = oi;
+      }
+    }
+    if (bi < 0) break;  // nothing is live (the same in every thread)
+    const float4 pick = s_box[bi];
+    if (threadIdx.x == 0) {
+      sorted_boxes[frame + emitted] = pick;
+      sorted_scores[frame + emitted] = bt;
+      order[frame + emitted] = bi;
+      keep[frame + emitted] = emitted;
+    }
+    for (int i = threadIdx.x; i < n; i += 256) {
+      if (!s_live[i]) continue;
+      if (i == bi) {
+        s_live[i] = 0;
+        continue;
+      }
+      const float o = iou_p1(pick, s_box[i]);
+      float t = s_t[i];
+      if (method == SOFT_LINEAR) {
+        if (inclusive ? (o >= nms_thresh) : (o > nms_thresh)) t = t * (1.f - o);
+      } else {
+        t = (float)((double)t * exp(-(double)(o * o) / dsigma));
+      }
+      s_t[i] = t;
+      if (t < min_score) s_live[i] = 0;
+    }
+    ++emitted;
+    __syncthreads();  // the updates are in LDS, and s_wt / s_wi are free again
+  }
+  if (threadIdx.x == 0) num_keep[l] = emitted;
+}
+
+// grid (n_lists, row blocks): thread k of block (l, y) owns emitted row y*256 + k of list l
+__global__ void __launch_bounds__(256)
+merge_vote_kernel(const float4* __restrict__ boxes, const float* __restrict__ scores, const int* __restrict__ n_total,
+                  int capacity, float vote_thresh, int vote_avg, const int* __restrict__ counts_out,
+                  const int* __restrict__ offsets_out, float* __restrict__ dets_out, int* __restrict__ votes_out) {
+  __shared__ float4 s_box[VOTE_CHUNK];
+  __shared__ float s_score[VOTE_CHUNK];
+  const int l = blockIdx.x;
+  const int cnt = counts_out[l];
+  const int k = blockIdx.y * 256 + threadIdx.x;
+  if ((int)(blockIdx.y * 256) >= cnt) return;  // (the whole workgroup)
+  const long frame = (long)l * capacity;
+  const int n = min(max(n_total[l], 0), capacity);
+  const bool mine = k < cnt;
+  const long at = (long)offsets_out[l] + k;
+  float* o = dets_out + at * 5;
+  const float4 me = mine ? make_float4(o[0], o[1], o[2], o[3]) : make_float4(0.f, 0.f, 0.f, 0.f);
+  double x1 = 0.0, y1 = 0.0, x2 = 0.0, y2 = 0.0, wsum = 0.0;
+  int votes = 0;
+  for (int c0 = 0; c0 < n; c0 += VOTE_CHUNK) {
+    const int m = min(VOTE_CHUNK, n - c0);
+    if ((int)threadIdx.x < m) {
+      s_box[threadIdx.x] = boxes[frame + c0 + threadIdx.x];
+      s_score[threadIdx.x] = scores[frame + c0 + threadIdx.x];
+    }
+    __syncthreads();
+    if (mine) {
+      for (int j = 0; j < m; ++j) {  // ascending concatenation index: the order is the definition
+        const float4 b = s_box[j];
+        if (iou_p1(me, b) >= vote_thresh) {
+          const double s = (double)s_score[j];
+          x1 += s * (double)b.x;
+          y1 += s * (double)b.y;
+          x2 += s * (double)b.z;
+          y2 += s * (double)b.w;
+          wsum += s;
+          ++votes;
+        }
+      }
+    }
+    __syncthreads();
+  }
+  if (!mine) return;
+  if (wsum > 0.0) {
+    o[0] = (float)(x1 / wsum);
+    o[1] = (float)(y1 / wsum);
+    o[2] = (float)(x2 / wsum);
+    o[3] = (float)(y2 / wsum);
+  }
+  if (vote_avg) o[4] = (float)(wsum / (double)votes);
+  votes_out[at] = votes;
+}
+
 __global__ void __launch_bounds__(256)
 dets_to_gt_kernel(const float* __restrict__ dets, const int* __restrict__ counts, const int* __restrict__ offsets,
                   const float* __restrict__ im_info, int im_info_stride, const float* __restrict__ labels,
@@ -191,37 +374,42 @@ bool merge_shape_ok(int n_lists, int groups, int capacity) {
   return n_lists >= 0 && n_lists <= 65535 && groups > 0 && capacity >= 0 && capacity <= MERGE_MAX_CAPACITY;
 }
 
-}  // namespace
+// what dana_detect_merge_soft adds to a merge (null: dana_detect_merge itself)
+struct SoftArgs {
+  int method;  // 0 hard, SOFT_LINEAR, SOFT_GAUSSIAN
+  float sigma, min_score, vote_thresh;
+  int vote_avg;
+  int* votes_out;
+};
 
-extern "C" {
-
-size_t dana_detect_merge_workspace_bytes(int n_lists, int groups, int capacity) {
-  if (!merge_shape_ok(n_lists, groups, capacity) || n_lists == 0 || capacity == 0) return 0;
-  return merge_plan(n_lists, capacity).total;
-}
-
-int dana_detect_merge(const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
-                      int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, float* dets_out,
-                      int* group_out, int* row_out, int* counts_out, int* offsets_out, void* workspace,
-                      size_t workspace_bytes, dana_stream_t stream) {
-  DANA_CHECK_ARG(n_lists >= 0 && n_lists <= 65535 && groups > 0 && capacity >= 0,
-                 "dana_detect_merge: bad shape n_lists=%d groups=%d capacity=%d", n_lists, groups, capacity);
-  DANA_CHECK_ARG(capacity <= MERGE_MAX_CAPACITY, "dana_detect_merge: capacity %d above the %d rows dana_nms takes per problem",
-                 capacity, MERGE_MAX_CAPACITY);
-  DANA_CHECK_ARG(offsets_out && (counts_out || n_lists == 0), "dana_detect_merge: null counts_out / offsets_out");
+int merge_run(const char* who, const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
+              int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, float* dets_out, int* group_out,
+              int* row_out, int* counts_out, int* offsets_out, void* workspace, size_t workspace_bytes, dana_stream_t stream,
+              const SoftArgs* soft) {
+  const bool soft_loop = soft && soft->method != 0;
+  const bool vote = soft && soft->vote_thresh >= 0.f;
+  DANA_CHECK_ARG(n_lists >= 0 && n_lists <= 65535 && groups > 0 && capacity >= 0, "%s: bad shape n_lists=%d groups=%d capacity=%d",
+                 who, n_lists, groups, capacity);
+  DANA_CHECK_ARG(capacity <= MERGE_MAX_CAPACITY, "%s: capacity %d above the %d rows dana_nms takes per problem", who, capacity,
+                 MERGE_MAX_CAPACITY);
+  DANA_CHECK_ARG(!soft_loop || capacity <= SOFT_MAX_CAPACITY,
+                 "%s: capacity %d above the %d rows the soft-NMS kernel holds in LDS (%d bytes per row)", who, capacity,
+                 SOFT_MAX_CAPACITY, SOFT_ROW_BYTES);
+  DANA_CHECK_ARG(offsets_out && (counts_out || n_lists == 0), "%s: null counts_out / offsets_out", who);
   hipStream_t s = (hipStream_t)stream;
   if (n_lists == 0 || capacity == 0) {
     if ((n_lists && hipMemsetAsync(counts_out, 0, (size_t)n_lists * sizeof(int), s) != hipSuccess) ||
         hipMemsetAsync(offsets_out, 0, (size_t)(n_lists + 1) * sizeof(int), s) != hipSuccess) {
-      dana_set_error("dana_detect_merge: memset failed");
+      dana_set_error("%s: memset failed", who);
       return DANA_ERR_HIP;
     }
     return DANA_OK;
   }
-  DANA_CHECK_ARG(dets_in && counts_in && offsets_in && dets_out && group_out && row_out, "dana_detect_merge: null pointer");
+  DANA_CHECK_ARG(dets_in && counts_in && offsets_in && dets_out && group_out && row_out && (!vote || soft->votes_out),
+                 "%s: null pointer", who);
   const MergePlan p = merge_plan(n_lists, capacity);
   if (!workspace || workspace_bytes < p.total) {
-    dana_set_error("dana_detect_merge: workspace %zu < %zu", workspace_bytes, p.total);
+    dana_set_error("%s: workspace %zu < %zu", who, workspace_bytes, p.total);
     return DANA_ERR_WORKSPACE;
   }
   char* ws = (char*)workspace;
@@ -237,21 +425,79 @@ int dana_detect_merge(const float* dets_in, const int* counts_in, const int* off
   int* n_total = (int*)(ws + p.n_total);
   merge_scatter_kernel<<<dim3(groups, n_lists), 256, 0, s>>>(dets_in, counts_in, offsets_in, groups, capacity, (float4*)boxes,
                                                              scores, src_group, src_row, n_total);
-  DANA_CHECK_LAUNCH("dana_detect_merge(scatter)");
-  int rc = dana_sort_desc(scores, n_lists, capacity, order, sorted_scores, ws + p.sort_ws, p.nms_ws - p.sort_ws, stream);
-  if (rc) return rc;
-  rc = dana_gather_boxes(boxes, order, n_lists, capacity, capacity, capacity, sorted_boxes, stream);
-  if (rc) return rc;
-  if (do_nms) {
-    rc = dana_nms(sorted_boxes, capacity, n_lists, nms_thresh, nms_inclusive, capacity, keep, capacity, num_keep,
-                  ws + p.nms_ws, p.total - p.nms_ws, stream);
+  DANA_CHECK_LAUNCH(who);
+  if (soft_loop) {
+    // the emissions in the form the compaction reads: emission i sits at sorted position i, and all of them are "kept"
+    const size_t lds = dana_align_up((size_t)capacity * SOFT_ROW_BYTES, 16);
+    merge_soft_kernel<<<n_lists, 256, lds, s>>>((const float4*)boxes, scores, n_total, capacity, soft->method, nms_thresh,
+                                                nms_inclusive, soft->sigma, soft->min_score, max_dets, (float4*)sorted_boxes,
+                                                sorted_scores, order, keep, num_keep);
+    DANA_CHECK_LAUNCH(who);
+    do_nms = 1;
+  } else {
+    int rc = dana_sort_desc(scores, n_lists, capacity, order, sorted_scores, ws + p.sort_ws, p.nms_ws - p.sort_ws, stream);
     if (rc) return rc;
+    rc = dana_gather_boxes(boxes, order, n_lists, capacity, capacity, capacity, sorted_boxes, stream);
+    if (rc) return rc;
+    if (do_nms) {
+      rc = dana_nms(sorted_boxes, capacity, n_lists, nms_thresh, nms_inclusive, capacity, keep, capacity, num_keep,
+                    ws + p.nms_ws, p.total - p.nms_ws, stream);
+      if (rc) return rc;
+    }
   }
   merge_compact_kernel<<<n_lists, 256, 0, s>>>((const float4*)sorted_boxes, sorted_scores, order, src_group, src_row, keep,
                                                num_keep, n_total, n_lists, capacity, do_nms, max_dets, dets_out, group_out,
                                                row_out, counts_out, offsets_out);
-  DANA_CHECK_LAUNCH("dana_detect_merge(compact)");
+  DANA_CHECK_LAUNCH(who);
+  if (vote) {
+    const int rows = max_dets > 0 ? min(max_dets, capacity) : capacity;  // the most rows a list can emit
+    merge_vote_kernel<<<dim3(n_lists, (rows + 255) / 256), 256, 0, s>>>((const float4*)boxes, scores, n_total, capacity,
+                                                                        soft->vote_thresh, soft->vote_avg, counts_out,
+                                                                        offsets_out, dets_out, soft->votes_out);
+    DANA_CHECK_LAUNCH(who);
+  }
   return DANA_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+size_t dana_detect_merge_workspace_bytes(int n_lists, int groups, int capacity) {
+  if (!merge_shape_ok(n_lists, groups, capacity) || n_lists == 0 || capacity == 0) return 0;
+  return merge_plan(n_lists, capacity).total;
+}
+
+int dana_detect_merge(const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
+                      int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, float* dets_out,
+                      int* group_out, int* row_out, int* counts_out, int* offsets_out, void* workspace,
+                      size_t workspace_bytes, dana_stream_t stream) {
+  return merge_run("dana_detect_merge", dets_in, counts_in, offsets_in, n_lists, groups, capacity, do_nms, nms_thresh,
+                   nms_inclusive, max_dets, dets_out, group_out, row_out, counts_out, offsets_out, workspace, workspace_bytes,
+                   stream, nullptr);
+}
+
+// (the frame, the sort's and the NMS's scratch of dana_detect_merge: method 0 runs that chain, and the soft loop writes its
+// emissions into the same frame rows)
+size_t dana_detect_merge_soft_workspace_bytes(int n_lists, int groups, int capacity) {
+  return dana_detect_merge_workspace_bytes(n_lists, groups, capacity);
+}
+
+int dana_detect_merge_soft(const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
+                           int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, int method,
+                           float sigma, float min_score, float vote_thresh, int vote_score, float* dets_out, int* group_out,
+                           int* row_out, int* votes_out, int* counts_out, int* offsets_out, void* workspace,
+                           size_t workspace_bytes, dana_stream_t stream) {
+  DANA_CHECK_ARG(method >= 0 && method <= SOFT_GAUSSIAN && (vote_score == 0 || vote_score == 1),
+                 "dana_detect_merge_soft: bad method %d (0 hard, 1 linear, 2 gaussian) or vote_score %d (0 id, 1 avg)", method,
+                 vote_score);
+  DANA_CHECK_ARG(method != SOFT_GAUSSIAN || sigma > 0.f, "dana_detect_merge_soft: sigma %g must be positive", (double)sigma);
+  DANA_CHECK_ARG(!(vote_thresh > 1.f) && vote_thresh == vote_thresh, "dana_detect_merge_soft: vote_thresh %g above 1",
+                 (double)vote_thresh);
+  const SoftArgs soft = {method, sigma, min_score, vote_thresh, vote_score, votes_out};
+  return merge_run("dana_detect_merge_soft", dets_in, counts_in, offsets_in, n_lists, groups, capacity, do_nms, nms_thresh,
+                   nms_inclusive, max_dets, dets_out, group_out, row_out, counts_out, offsets_out, workspace, workspace_bytes,
+                   stream, &soft);
 }
 
 int dana_dets_to_gt_boxes(const float* dets, const int* counts, const int* offsets, const float* im_info,

@@ -10,8 +10,11 @@ an image's class lists (inference.py:70), as one C call over all lists and one D
 `ensemble_shots` and `cap_per_image` are the two uses spelled out. `as_gt_boxes` turns merged lists into the
 gt_boxes / num_boxes tensors of a train-mode forward (pseudo-labels are trained on, utils.py:130-179) without leaving the
 device. `merge_numpy` is the merge restated in numpy float64 (host): the tests' yardstick, pinned to the reference's own
-chain by tests/golden/merge_dets.npz."""
+chain by tests/golden/merge_dets.npz. `merge_detections(method="linear" | "gaussian", vote_thresh=...)` runs Soft-NMS and box
+voting in the same call (dana_detect_merge_soft; restated from their papers, not from the reference), and
+`merge_soft_numpy` is their host restatement, operation for operation."""
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -47,7 +50,15 @@ def detections(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=Fa
     return dets[keep]
 
 
-def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive):
+def _decode_nms_thresh(nms_thresh):
+    """the `nms_thresh` keyword of the batched decoders -> the float handed to the C call: "cfg" is cfg.TEST.NMS; None is
+    2.0, above every IoU (with +1 widths iou <= 1), so nothing is suppressed and the lists come back thresholded and sorted"""
+    if nms_thresh is None:
+        return 2.0
+    return float(cfg.TEST.NMS if isinstance(nms_thresh, str) and nms_thresh == "cfg" else nms_thresh)
+
+
+def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive, nms_thresh="cfg"):
     """the batched call itself -> (dets [max(B*R,1),5] packed device buffer, host int32 counts [B], offsets [B+1], and the
     device int32 tensor counts | offsets [2B+1] the host pair was read from)"""
     if rois.dim() != 3 or rois.size(2) != 5:
@@ -67,19 +78,22 @@ def _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive
     lib().call("dana_detect_postprocess_batched", ops._p(rois), ops._p(cls_prob), ops._p(bbox_pred), ops._p(im_info), B,
                R, ctypes.cast(f4(*cfg.TRAIN.BBOX_NORMALIZE_STDS), ctypes.c_void_p),
                ctypes.cast(f4(*cfg.TRAIN.BBOX_NORMALIZE_MEANS), ctypes.c_void_p),
-               int(bool(cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED)), float(thresh), float(cfg.TEST.NMS),
+               int(bool(cfg.TRAIN.BBOX_NORMALIZE_TARGETS_PRECOMPUTED)), float(thresh), _decode_nms_thresh(nms_thresh),
                int(bool(nms_inclusive)), ops._p(dets), layout.data_ptr(), layout.data_ptr() + 4 * B, ops._p(ws),
                ws.numel(), ops._stream())
     host = layout.cpu()
     return dets, host[:B], host[B:], layout
 
 
-def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False):
+def detections_batched(rois, cls_prob, bbox_pred, im_info, thresh=0.05, nms_inclusive=False, with_layout=False, *,
+                       nms_thresh="cfg"):
     """rois [B,R,5], cls_prob [B*R,2], bbox_pred [B*R,4], im_info [B,3] (the eval forward's outputs for B images) ->
     list of B cls_dets [K_b,5], each equal to `detections()` on its image. One C call (decode over B*R rows, B-row sort,
     B NMS problems, packed compaction) and ONE D2H read of the per-image counts / offsets. with_layout=True also returns
-    the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]])."""
-    dets, counts, offsets, _ = _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive)
+    the host int32 tensors counts [B] and offsets [B+1] (image b's rows: dets[offsets[b]:offsets[b+1]]). `nms_thresh`
+    replaces cfg.TEST.NMS in the call; None leaves the lists unsuppressed (thresholded and sorted), which is what a
+    soft-NMS `merge_detections(..., 1, method="linear")` over them starts from."""
+    dets, counts, offsets, _ = _detections_packed(rois, cls_prob, bbox_pred, im_info, thresh, nms_inclusive, nms_thresh)
     out = [dets[int(offsets[b]):int(offsets[b]) + int(counts[b])] for b in range(counts.numel())]
     return (out, counts, offsets) if with_layout else out
 
@@ -94,12 +108,13 @@ class ClassDetections(list):
 
 
 def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=0.05, nms_inclusive=False,
-                        with_layout=False):
+                        with_layout=False, *, nms_thresh="cfg"):
     """A class sweep's outputs (model(..., cache.sweep(classes)): rois [B*C,R,5], cls_prob [B*C*R,2], bbox_pred [B*C*R,4])
     with im_info [B,3] per IMAGE -> dets[b][c], a [K,5] tensor equal to `detections()` on problem b*C + c with image b's
     im_info: the all_boxes[j][i] layout of inference.py:70-140 (j the class, i the image). One batched post-processing
     call over the B*C problems, one D2H read; the im_info row of problem p (image p // C) is repeated on the device.
-    with_layout=True returns the same nested list as a `ClassDetections`, which also carries the packed buffer."""
+    with_layout=True returns the same nested list as a `ClassDetections`, which also carries the packed buffer.
+    `nms_thresh` as in `detections_batched` (None: no per-class NMS, for soft-NMS in its place)."""
     if rois.dim() != 3 or rois.size(2) != 5:
         raise ValueError("detections_by_class: rois must be [B*C, R, 5], got %s" % (tuple(rois.shape),))
     C = int(num_classes)
@@ -108,7 +123,7 @@ def detections_by_class(rois, cls_prob, bbox_pred, im_info, num_classes, thresh=
     if C < 1 or rois.size(0) != B * C:
         raise ValueError("detections_by_class: %d problems for %d images x %d classes" % (rois.size(0), B, C))
     info_p = ops.repeat_rows_grouped(im_info, 1, 3, C, B * C, ld_src=im_info.size(1))
-    packed, counts, offsets, layout = _detections_packed(rois, cls_prob, bbox_pred, info_p, thresh, nms_inclusive)
+    packed, counts, offsets, layout = _detections_packed(rois, cls_prob, bbox_pred, info_p, thresh, nms_inclusive, nms_thresh)
     flat = [packed[int(offsets[p]):int(offsets[p]) + int(counts[p])] for p in range(B * C)]
     nested = [flat[b * C:(b + 1) * C] for b in range(B)]
     if not with_layout:
@@ -126,6 +141,11 @@ class MergedDetections(ClassDetections):
     `groups` inputs the row came from) and `row` (its row inside that input). `total` = rows in all lists."""
     group = row = None
     total = 0
+    votes = None  # device int32 [total]: the voters of every packed row, when the merge ran with box voting
+
+    def _take_layout(self, m):
+        self.packed, self.counts, self.offsets, self.layout_dev = m.packed, m.counts, m.offsets, m.layout_dev
+        self.total, self.group, self.row, self.votes = m.total, m.group, m.row, m.votes
 
     def list_index(self):
         """host int32 [total]: the output list of every packed row (what `add_packed` takes as image ids, mapped through
@@ -175,7 +195,29 @@ def _packed_layout(dets, who):
     return packed, P, hc, ho, layout.data_ptr(), layout.data_ptr() + 4 * P, (layout,)
 
 
-def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_dets=0, with_layout=False, capacity=None):
+SOFT_METHODS = {"hard": 0, "linear": 1, "gaussian": 2}
+VOTE_SCORES = {"id": 0, "avg": 1}
+
+
+def _soft_args(who, nms_thresh, method, sigma, min_score, vote_thresh, vote_score):
+    """the soft-NMS / voting keywords, checked before any C call -> (method id, sigma, min_score, vote_thresh or -1.0 when
+    voting is off, vote_score id)"""
+    if method not in SOFT_METHODS:
+        raise ValueError("%s: method must be one of %s, got %r" % (who, sorted(SOFT_METHODS), method))
+    if vote_score not in VOTE_SCORES:
+        raise ValueError("%s: vote_score must be one of %s, got %r" % (who, sorted(VOTE_SCORES), vote_score))
+    if method == "linear" and nms_thresh is None:
+        raise ValueError("%s: method=\"linear\" decays the rows above nms_thresh and needs one, got None" % who)
+    if not float(sigma) > 0.0:
+        raise ValueError("%s: sigma must be positive, got %r" % (who, sigma))
+    if vote_thresh is not None and not 0.0 < float(vote_thresh) <= 1.0:
+        raise ValueError("%s: vote_thresh must lie in (0, 1], got %r" % (who, vote_thresh))
+    return (SOFT_METHODS[method], float(sigma), float(min_score), -1.0 if vote_thresh is None else float(vote_thresh),
+            VOTE_SCORES[vote_score])
+
+
+def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_dets=0, with_layout=False, capacity=None, *,
+                     method="hard", sigma=0.5, min_score=0.001, vote_thresh=None, vote_score="id"):
     """Merge every `groups` consecutive detection lists into one, on the device: concatenate in group order, sort by score
     (descending, stable: equal scores keep concatenation order -- lower group first, then lower row), greedy NMS at
     `nms_thresh` ("cfg": cfg.TEST.NMS; None: no NMS, a pure merge), keep the first `max_dets` (0: all). The chain of
@@ -185,7 +227,19 @@ def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_de
     with host or device int32 layout. -> list of P // groups tensors [K_l,5]; with_layout=True a `MergedDetections`,
     which also carries `packed`, `counts`, `offsets`, `layout_dev`, `group`, `row`. One C call, one D2H read (the output
     layout). The frame a list is sorted in (`capacity` rows) is sized from the host counts; with a device-only layout
-    pass `capacity` (>= the longest concatenation), because nothing is read back to find it."""
+    pass `capacity` (>= the longest concatenation), because nothing is read back to find it.
+
+    `method` "linear" / "gaussian" put Soft-NMS (Bodla et al. 2017) in the place of the hard NMS: the best live row is
+    emitted with its working score, the live rows it overlaps are decayed -- by 1 - IoU above `nms_thresh`, or by
+    exp(-IoU^2 / sigma) -- and rows falling below `min_score` are dropped; the output rows then carry the decayed scores, in
+    descending order. `vote_thresh` in (0, 1] turns box voting on (Gidaris & Komodakis 2015) under any method: every emitted
+    box becomes the score-weighted mean of ALL the list's input boxes with IoU >= vote_thresh to it, and `votes` (device
+    int32 per packed row) counts them; `vote_score="avg"` also replaces the score by the voters' mean score. The definitions
+    are in include/dana_hip.h (dana_detect_merge_soft) and restated by `merge_soft_numpy`. With the defaults (method "hard",
+    no voting) the call and the result are dana_detect_merge's; otherwise a `MergedDetections` comes back, lists up to 3072
+    rows long under the soft methods."""
+    soft = _soft_args("merge_detections", nms_thresh, method, sigma, min_score, vote_thresh, vote_score)
+    use_soft = soft[0] != 0 or vote_thresh is not None
     groups = int(groups)
     if groups < 1:
         raise ValueError("merge_detections: groups must be >= 1, got %d" % groups)
@@ -208,39 +262,54 @@ def merge_detections(dets, groups, nms_thresh="cfg", nms_inclusive=False, max_de
     capacity = int(capacity)
     do_nms, thr = _nms_pair(nms_thresh)
     out = torch.empty((max(rows_cap, 1), 5), dtype=torch.float32, device=dev)
-    ibuf = torch.empty((2 * max(rows_cap, 1) + 2 * n_lists + 1,), dtype=torch.int32, device=dev)  # group | row | counts | offsets
     slot = max(rows_cap, 1)
-    group, row, layout = ibuf[:slot], ibuf[slot:2 * slot], ibuf[2 * slot:]
-    ws = ops._ws(lib().query("dana_detect_merge_workspace_bytes", n_lists, groups, capacity), dev)
-    lib().call("dana_detect_merge", ops._p(packed), p_counts, p_offsets, n_lists, groups, capacity, do_nms, thr,
-               int(bool(nms_inclusive)), int(max_dets), ops._p(out), group.data_ptr(), row.data_ptr(), layout.data_ptr(),
-               layout.data_ptr() + 4 * n_lists, ops._p(ws), ws.numel(), ops._stream())
+    votes = None
+    if not use_soft:
+        ibuf = torch.empty((2 * slot + 2 * n_lists + 1,), dtype=torch.int32, device=dev)  # group | row | counts | offsets
+        group, row, layout = ibuf[:slot], ibuf[slot:2 * slot], ibuf[2 * slot:]
+        ws = ops._ws(lib().query("dana_detect_merge_workspace_bytes", n_lists, groups, capacity), dev)
+        lib().call("dana_detect_merge", ops._p(packed), p_counts, p_offsets, n_lists, groups, capacity, do_nms, thr,
+                   int(bool(nms_inclusive)), int(max_dets), ops._p(out), group.data_ptr(), row.data_ptr(), layout.data_ptr(),
+                   layout.data_ptr() + 4 * n_lists, ops._p(ws), ws.numel(), ops._stream())
+    else:
+        ibuf = torch.empty((3 * slot + 2 * n_lists + 1,), dtype=torch.int32, device=dev)  # group | row | votes | counts | offsets
+        group, row, votes, layout = ibuf[:slot], ibuf[slot:2 * slot], ibuf[2 * slot:3 * slot], ibuf[3 * slot:]
+        ws = ops._ws(lib().query("dana_detect_merge_soft_workspace_bytes", n_lists, groups, capacity), dev)
+        lib().call("dana_detect_merge_soft", ops._p(packed), p_counts, p_offsets, n_lists, groups, capacity, do_nms, thr,
+                   int(bool(nms_inclusive)), int(max_dets), soft[0], soft[1], soft[2], soft[3], soft[4], ops._p(out),
+                   group.data_ptr(), row.data_ptr(), votes.data_ptr(), layout.data_ptr(), layout.data_ptr() + 4 * n_lists,
+                   ops._p(ws), ws.numel(), ops._stream())
     del alive
     host = layout.cpu()
     counts, offsets = host[:n_lists], host[n_lists:]
     lists = [out[int(offsets[i]):int(offsets[i]) + int(counts[i])] for i in range(n_lists)]
-    if not with_layout:
+    if not with_layout and not use_soft:
         return lists
     m = MergedDetections(lists)
     m.packed, m.counts, m.offsets, m.layout_dev, m.num_classes = out, counts, offsets, layout, 1
     m.total = int(offsets[n_lists])
     m.group, m.row = group[:m.total], row[:m.total]
+    m.votes = votes[:m.total] if vote_thresh is not None else None
     return m
 
 
-def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0):
+def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0, *, method="hard", sigma=0.5, min_score=0.001,
+                   vote_thresh=None, vote_score="id"):
     """The shot ensemble of utils.py:182-204: `cd` = detections_by_class(..., with_layout=True) of a sweep whose cached
     problems are laid out as c*shots + s (class c seen through its shot s alone: `cache.sweep(classes, shots="each")`
     on a k-shot cache, or a num_shot=1 model's cache of C*S one-shot sets). -> `merge_detections(cd, shots)` as dets[b][c], a
-    `MergedDetections` that `DetectionEvaluator.add_by_class` / `CocoEvaluator.add_by_class` take unchanged."""
+    `MergedDetections` that `DetectionEvaluator.add_by_class` / `CocoEvaluator.add_by_class` take unchanged. The soft-NMS and
+    voting keywords are `merge_detections`'; K shots vote K times for an object, which is what box voting averages."""
+    _soft_args("ensemble_shots", nms_thresh, method, sigma, min_score, vote_thresh, vote_score)
     shots = int(shots)
     if shots < 1 or cd.num_classes % shots:
         raise ValueError("ensemble_shots: %d sets per image are not a multiple of shots = %d" % (cd.num_classes, shots))
     C, B = cd.num_classes // shots, len(cd)
-    m = merge_detections(cd, shots, nms_thresh, nms_inclusive, max_dets, with_layout=True)
+    m = merge_detections(cd, shots, nms_thresh, nms_inclusive, max_dets, with_layout=True, method=method, sigma=sigma,
+                         min_score=min_score, vote_thresh=vote_thresh, vote_score=vote_score)
     out = MergedDetections([list(m[b * C:(b + 1) * C]) for b in range(B)])
-    out.packed, out.counts, out.offsets, out.layout_dev, out.num_classes = m.packed, m.counts, m.offsets, m.layout_dev, C
-    out.total, out.group, out.row = m.total, m.group, m.row
+    out._take_layout(m)
+    out.num_classes = C
     return out
 
 
@@ -335,6 +404,138 @@ def merge_numpy(lists_per_problem, groups, nms_thresh, nms_inclusive=False, max_
     counts = np.asarray([len(d) for d in out_d], np.int32)
     offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
     return dict(dets=out_d, group=out_g, row=out_r, counts=counts, offsets=offsets, margin=margin)
+
+
+def _iou32_rows(box, rest):
+    """iou(box, rest[j]) for every row j in float32, one IEEE operation per written operation (numpy's elementwise float32
+    operators round each result to float32): area = (x2 - x1 + 1) * (y2 - y1 + 1), w = max(min(x2) - max(x1) + 1, 0),
+    inter = w * h, iou = inter / ((area(a) + area(b)) - inter) -- the exact-division branch of csrc/nms.hip's iou_suppress"""
+    one, zero = np.float32(1.0), np.float32(0.0)
+    box = np.asarray(box, np.float32)
+    rest = np.asarray(rest, np.float32).reshape(-1, 4)
+    area = (box[2] - box[0] + one) * (box[3] - box[1] + one)
+    areas = (rest[:, 2] - rest[:, 0] + one) * (rest[:, 3] - rest[:, 1] + one)
+    w = np.maximum(np.minimum(box[2], rest[:, 2]) - np.maximum(box[0], rest[:, 0]) + one, zero)
+    h = np.maximum(np.minimum(box[3], rest[:, 3]) - np.maximum(box[1], rest[:, 1]) + one, zero)
+    inter = w * h
+    with np.errstate(divide="ignore", invalid="ignore"):
+        out = inter / ((area + areas) - inter)
+    assert out.dtype == np.float32
+    return out
+
+
+def _rel_gap(a, b):
+    """|a - b| relative to |b| (absolute where b is 0), in float64"""
+    a, b = float(a), float(b)
+    return abs(a - b) / abs(b) if b != 0.0 else abs(a - b)
+
+
+def merge_soft_numpy(lists_per_problem, groups, nms_thresh, nms_inclusive=False, max_dets=0, method="hard", sigma=0.5,
+                     min_score=0.001, vote_thresh=None, vote_score="id"):
+    """`merge_detections` with its soft-NMS / voting keywords restated in numpy (host), operation for operation as
+    include/dana_hip.h defines dana_detect_merge_soft: float32 for the IoU and the linear decay, Python floats (doubles) for
+    the Gaussian decay and the voting sums, explicit loops where an order is part of the definition. The parameters are
+    rounded to float32 first, as the C call receives them. `method="hard"` is `merge_numpy`'s chain with the float32 IoU the
+    device decides by (equal to merge_numpy wherever that one's margin is positive).
+    -> what `merge_numpy` returns, plus votes: list of int32 [K_l] (None with voting off), and margin: a dict of
+    pick: the smallest relative gap between the best and the second-best live working score over all picks (inf with fewer
+    than two live rows), drop: the smallest relative |t - min_score| over all removal decisions, vote: the smallest
+    |iou - vote_thresh| over all voter decisions -- how far the discrete outputs are from changing."""
+    _soft_args("merge_soft_numpy", nms_thresh, method, sigma, min_score, vote_thresh, vote_score)
+    groups = int(groups)
+    P = len(lists_per_problem)
+    if groups < 1 or P % groups:
+        raise ValueError("merge_soft_numpy: %d lists are not a multiple of groups = %d" % (P, groups))
+    nt = None if nms_thresh is None else np.float32(nms_thresh)
+    ms = np.float32(min_score)
+    dsigma = float(np.float32(sigma))
+    vt = None if vote_thresh is None else np.float32(vote_thresh)
+    one = np.float32(1.0)
+    margin = dict(pick=np.inf, drop=np.inf, vote=np.inf)
+    out_d, out_g, out_r, out_v = [], [], [], []
+    for l in range(P // groups):
+        parts = [np.asarray(lists_per_problem[l * groups + g], np.float32).reshape(-1, 5) for g in range(groups)]
+        cat = np.concatenate(parts, 0)
+        grp = np.concatenate([np.full(len(q), g, np.int32) for g, q in enumerate(parts)])
+        row = np.concatenate([np.arange(len(q), dtype=np.int32) for q in parts])
+        n = len(cat)
+        box, s = cat[:, :4], cat[:, 4]
+        limit = min(max_dets, n) if max_dets > 0 else n
+        sel, emit_t = [], []
+        if method == "hard":
+            order = np.argsort(-s.astype(np.float64), kind="stable")
+            if nt is None:
+                sel = list(order[:limit])
+            else:
+                dead = np.zeros(n, bool)
+                for pos in range(n):
+                    if len(sel) >= limit:
+                        break
+                    if dead[pos]:
+                        continue
+                    sel.append(order[pos])
+                    later = np.nonzero(~dead[pos + 1:])[0] + pos + 1
+                    if later.size:
+                        o = _iou32_rows(box[order[pos]], box[order[later]])
+                        dead[later[(o >= nt) if nms_inclusive else (o > nt)]] = True
+            emit_t = [s[j] for j in sel]
+        else:
+            t = s.copy()
+            live = np.ones(n, bool)
+            while live.any() and len(sel) < limit:
+                idx = np.nonzero(live)[0]
+                num = idx[~np.isnan(t[idx])]  # a NaN ranks behind every number
+                i = int(num[np.argmax(t[num])]) if num.size else int(idx[0])  # (argmax: the first, i.e. lowest, index of the maximum)
+                if num.size >= 2:
+                    top = np.sort(t[num].astype(np.float64))[-2:]
+                    margin["pick"] = min(margin["pick"], _rel_gap(top[0], top[1]))
+                sel.append(i)
+                emit_t.append(t[i])
+                live[i] = False
+                idx = np.nonzero(live)[0]
+                if not idx.size:
+                    break
+                o = _iou32_rows(box[i], box[idx])
+                if method == "linear":
+                    hit = (o >= nt) if nms_inclusive else (o > nt)
+                    t[idx[hit]] = t[idx[hit]] * (one - o[hit])
+                else:
+                    for j, oj in zip(idx, o):
+                        t[j] = np.float32(float(t[j]) * math.exp(-float(oj * oj) / dsigma))
+                gap = np.abs(t[idx].astype(np.float64) - float(ms)) / (abs(float(ms)) if ms != 0 else 1.0)
+                if not np.isnan(gap).all():
+                    margin["drop"] = min(margin["drop"], float(np.nanmin(gap)))
+                live[idx[t[idx] < ms]] = False
+        sel = np.asarray(sel, np.int64)
+        d = cat[sel].copy()
+        d[:, 4] = np.asarray(emit_t, np.float32)
+        votes = None
+        if vt is not None:
+            votes = np.zeros(len(sel), np.int32)
+            for k in range(len(sel)):
+                o = _iou32_rows(d[k, :4], box)
+                if n:
+                    margin["vote"] = min(margin["vote"], float(np.abs(o.astype(np.float64) - float(vt)).min()))
+                acc, wsum = [0.0, 0.0, 0.0, 0.0], 0.0
+                for j in np.nonzero(o >= vt)[0]:  # ascending concatenation index; the order is part of the definition
+                    sj = float(s[j])
+                    for c in range(4):
+                        acc[c] += sj * float(box[j, c])
+                    wsum += sj
+                    votes[k] += 1
+                if wsum > 0.0:
+                    d[k, :4] = [np.float32(a / wsum) for a in acc]
+                if vote_score == "avg":
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        d[k, 4] = np.float32(np.float64(wsum) / np.float64(votes[k]))
+        out_d.append(d)
+        out_g.append(grp[sel])
+        out_r.append(row[sel])
+        out_v.append(votes)
+    counts = np.asarray([len(d) for d in out_d], np.int32)
+    offsets = np.concatenate(([0], np.cumsum(counts))).astype(np.int32)
+    return dict(dets=out_d, group=out_g, row=out_r, counts=counts, offsets=offsets, margin=margin,
+                votes=None if vt is None else out_v)
 
 
 def gt_boxes_numpy(lists, im_scale, labels, score_thresh=0.5, max_boxes=50):

@@ -181,6 +181,33 @@ int dana_detect_merge(const float* dets_in, const int* counts_in, const int* off
                       int* group_out, int* row_out, int* counts_out, int* offsets_out, void* workspace,
                       size_t workspace_bytes, dana_stream_t stream);
 
+/* dana_detect_merge with Soft-NMS in place of the hard NMS and / or box voting after it. Neither is in the reference tree;
+ * both are restated from their papers -- Bodla et al., "Soft-NMS: Improving Object Detection With One Line of Code", ICCV
+ * 2017, and Gidaris & Komodakis, "Object detection via a multi-region & semantic segmentation-aware CNN model", ICCV 2015
+ * (box voting, scores kept: the "ID" scoring) -- and postprocess.merge_soft_numpy is the same definition in numpy. Inputs,
+ * concatenation, output layout and `capacity` as above; j below is a row's index in its list's concatenation, n its length.
+ * iou(a, b) = inter / ((area(a) + area(b)) - inter) in fp32 with the +1 widths, one IEEE operation per written operation.
+ * method 0 (hard): steps (2)-(4) of dana_detect_merge, bit for bit (do_nms is read by this method only).
+ * method 1 (linear) / 2 (gaussian): every row starts live with working score t_j = its score. While a row is live and fewer
+ *   than max_dets rows are out (max_dets <= 0: no limit): pick the live row i with the largest t (ties: the lowest j; a NaN
+ *   ranks behind every number), emit (box_i, t_i), retire i; for every live j with o = iou(box_i, box_j): linear
+ *   t_j = t_j * (1 - o) if o > nms_thresh (>= with nms_inclusive); gaussian t_j = (float)((double)t_j * exp(-(double)(o * o) /
+ *   (double)sigma)), nms_thresh unused; then every live j with t_j < min_score is retired without being emitted. Emitted
+ *   scores never increase, so the lists are in descending score order. One workgroup per list holds the list in LDS:
+ *   capacity <= 3072 (21 bytes per row in 64 KiB), checked here -- a larger frame is DANA_ERR_ARG, never a launch.
+ * vote_thresh >= 0 (negative: off; above 1: DANA_ERR_ARG): for every emitted row k, over ALL n rows j of the concatenation in
+ *   ascending j (suppressed rows and k itself included) with iou(box_k, box_j) >= vote_thresh: X_c += (double)s_j *
+ *   (double)box_j[c] for the four coordinates and W += (double)s_j, from 0.0, sequentially, with the ORIGINAL scores s_j. If
+ *   W > 0 the row's coordinates become (float)(X_c / W). vote_score 0 (id) leaves the score, 1 (avg) makes it
+ *   (float)(W / votes). votes_out[row] = the number of voters (written only when voting is on; may be null otherwise).
+ * group_out / row_out are the source of the emitted box as above. The workspace is dana_detect_merge's. */
+size_t dana_detect_merge_soft_workspace_bytes(int n_lists, int groups, int capacity);
+int dana_detect_merge_soft(const float* dets_in, const int* counts_in, const int* offsets_in, int n_lists, int groups,
+                           int capacity, int do_nms, float nms_thresh, int nms_inclusive, int max_dets, int method,
+                           float sigma, float min_score, float vote_thresh, int vote_score, float* dets_out, int* group_out,
+                           int* row_out, int* votes_out, int* counts_out, int* offsets_out, void* workspace,
+                           size_t workspace_bytes, dana_stream_t stream);
+
 /* Detection lists -> the ground-truth tensors of a train-mode forward (fs_loader.py:325; pseudo-labels are trained on,
  * utils.py:130-179): one list per image in the packed layout above (counts[B], offsets[B], device). Image b's first
  * max_boxes rows with score > score_thresh, in list order, become gt_boxes[b][i] = (x1, y1, x2, y2) * im_info[b][2] (back
