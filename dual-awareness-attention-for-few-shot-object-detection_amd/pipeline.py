@@ -212,6 +212,11 @@ class ImagePool:
     def row_boxes(self, row):
         return self._rows[row][2]
 
+    def frame_of(self, row):
+        """the index of the frame whose pixels `row` reads: a flipped twin has its twin's (and `meta[row, 2]` = 1 - its
+        twin's flipped bit; `meta[row, :2]` is the frame's h, w)"""
+        return self._rows[int(row)][0]
+
 
 class EpisodePlan:
     """One batch of episodes as the device reads it: `words` (int32) = `batch` query records, `n_supports` support
@@ -303,18 +308,8 @@ def _plan_query(pool, q, holder_hw, target_size):
                 out_w=out_w, clamp_x=clamp_x, clamp_y=clamp_y, pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=order)
 
 
-def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, support_size=320):
-    """Host only. queries: one dict per batch item with the loader's choices -- row, ratio (ratio_list_batch[index]),
-    pos_cls, and optionally order (the shuffled box order of fs_loader.py:183; default: as stored), need_crop with
-    crop_start (the y_s / x_s drawn at :186-255). supports: (row, box) per support slot, batch-major ([b][way * shot]
-    flattened), box = the support_db entry's unscaled (x1, y1, x2, y2). holder_hw: (H, W) of the holders' im_data.
-    -> EpisodePlan with everything that follows deterministically: scales, prepared sizes, copy windows, clamp limits, the
-    int16 support boxes and their resized sizes."""
-    queries, supports = list(queries), list(supports)
-    if queries and holder_hw is None:
-        raise ValueError("plan_episode: holder_hw is needed to plan queries")
-    qs = [_plan_query(pool, q, holder_hw, target_size) for q in queries]
-    ss = [_plan_support(pool, r, bx, target_size, support_size) for r, bx in supports]
+def _pack_plan(qs, ss):
+    """the host records of `_plan_query` / `_plan_support` -> the int32 words the kernels of csrc/episode.hip read"""
     n_rec = len(qs) * EP_QWORDS + len(ss) * EP_SWORDS
     words = np.zeros((n_rec + sum(len(q["order"]) for q in qs),), dtype=np.int32)
     f64 = words[:n_rec].view(np.float64)  # word 2k <-> double k
@@ -333,6 +328,22 @@ def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, su
         # cv2.resize(fx, fy) samples at 1 / fx, cv2.resize(dsize) at src / dst (csrc/pipeline.hip)
         f64[(o + S_INV) // 2], f64[(o + S_SX) // 2], f64[(o + S_SY) // 2] = 1.0 / s["im_scale"], s["cw"] / s["rw"], s["ch"] / s["rh"]
         words[o + S_X0:o + S_X0 + 8] = (s["x_min"], s["y_min"], s["cw"], s["ch"], s["rw"], s["rh"], s["oh"], s["ow"])
+    return words
+
+
+def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, support_size=320):
+    """Host only. queries: one dict per batch item with the loader's choices -- row, ratio (ratio_list_batch[index]),
+    pos_cls, and optionally order (the shuffled box order of fs_loader.py:183; default: as stored), need_crop with
+    crop_start (the y_s / x_s drawn at :186-255). supports: (row, box) per support slot, batch-major ([b][way * shot]
+    flattened), box = the support_db entry's unscaled (x1, y1, x2, y2). holder_hw: (H, W) of the holders' im_data.
+    -> EpisodePlan with everything that follows deterministically: scales, prepared sizes, copy windows, clamp limits, the
+    int16 support boxes and their resized sizes."""
+    queries, supports = list(queries), list(supports)
+    if queries and holder_hw is None:
+        raise ValueError("plan_episode: holder_hw is needed to plan queries")
+    qs = [_plan_query(pool, q, holder_hw, target_size) for q in queries]
+    ss = [_plan_support(pool, r, bx, target_size, support_size) for r, bx in supports]
+    words = _pack_plan(qs, ss)
     return EpisodePlan(words, qs, ss, None if holder_hw is None else (int(holder_hw[0]), int(holder_hw[1])))
 
 
@@ -442,3 +453,105 @@ class EpisodeAssembler:
         self._supports(d_plan, records, out)
         self._done(slot)
         return out
+
+
+# ---- views of pool frames: flip and multi-scale testing -------------------------------------------------------------------
+# Test-time augmentation is not in the reference tree. A view is a query record of the format above -- the frame at its own
+# scale, mirrored when the row is a flipped twin -- so `EpisodeAssembler.assemble` prepares the B * V view images with the
+# kernels that exist; `postprocess.ensemble_views` maps their detections back and merges them.
+
+class ViewSet:
+    """What `postprocess.fold_views` needs to know about the views of a `plan_views` plan: `n_images`, `views` (per image),
+    and `table`, host float32 [n_images * views][5] = (fw, fh, flip, area_lo, area_hi) per view in plan order -- the ORIGINAL
+    frame's width and height, whether the view was mirrored, and its box-area window in original-image pixels^2.
+    `scales` [n_images * views] are the views' im_scale, `rows` their pool rows."""
+
+    def __init__(self, n_images, views, table, scales, rows):
+        self.n_images, self.views = int(n_images), int(views)
+        self.table = np.ascontiguousarray(table, dtype=np.float32).reshape(self.n_images * self.views, 5)
+        self.scales, self.rows = np.asarray(scales, dtype=np.float64), np.asarray(rows, dtype=np.int64)
+        self._dev = {}
+
+    def table_dev(self, device):
+        """the table on `device`, uploaded once and cached"""
+        device = torch.device(device)
+        if device not in self._dev:
+            self._dev[device] = torch.from_numpy(self.table if self.table.size else np.zeros((1, 5), np.float32)).to(device)
+        return self._dev[device]
+
+
+def _view_rows(pool, rows, flip):
+    """-> per image (row, twin or None, h, w), checked"""
+    out = []
+    for entry in rows:
+        if flip:
+            if not isinstance(entry, (tuple, list)) or len(entry) != 2:
+                raise ValueError("plan_views: flip=True needs (row, twin_row) per image, got %r" % (entry,))
+            row, h, w = _pool_row(pool, entry[0])
+            twin, _, _ = _pool_row(pool, entry[1])
+            if pool.frame_of(twin) != pool.frame_of(row):
+                raise ValueError("plan_views: row %d is no twin of row %d: they read different frames" % (twin, row))
+            if int(pool.meta[twin, 2]) == int(pool.meta[row, 2]):
+                raise ValueError("plan_views: row %d is no twin of row %d: both have flipped = %d (ImagePool.add_flipped "
+                                 "makes the twin)" % (twin, row, int(pool.meta[row, 2])))
+        else:
+            if isinstance(entry, (tuple, list)):
+                raise ValueError("plan_views: (row, twin_row) entries need flip=True, got %r" % (entry,))
+            (row, h, w), twin = _pool_row(pool, entry), None
+        out.append((row, twin, h, w))
+    return out
+
+
+def _view_size(h, w, scale):
+    im_scale = float(scale) / float(min(h, w))  # blob.py:45, as _plan_query
+    return im_scale, cv_round(h * im_scale), cv_round(w * im_scale)
+
+
+def views_holder_hw(pool, rows, scales=(600,)):
+    """(H, W) of the smallest holder that takes every view of `plan_views(pool, rows, scales)`: the maximum prepared size"""
+    sizes = [_view_size(int(pool.meta[r, 0]), int(pool.meta[r, 1]), s)[1:]
+             for e in rows for r in [_pool_row(pool, e[0] if isinstance(e, (tuple, list)) else e)[0]] for s in scales]
+    return (max(s[0] for s in sizes), max(s[1] for s in sizes)) if sizes else (1, 1)
+
+
+def plan_views(pool, rows, scales=(600,), flip=False, area_ranges=None, holder_hw=None):
+    """Host only. The views of flip / multi-scale testing as one plan of query records. rows: one entry per image -- a pool
+    row, or with flip=True (row, twin_row), the twin made by `ImagePool.add_flipped`. Image i's V = len(scales) * F views
+    (F = 2 with flip, else 1) are records i * V + v, v = s * F + f: scale s, f = 0 the row as stored, f = 1 its twin. Every
+    view is the whole frame prepared so that its SHORTER side is scales[s] (Q_SCALE = scales[s] / min(h, w), as `_plan_query`
+    for that target_size), at the holder's top-left corner, with no crop, no clamp and no boxes. holder_hw defaults to
+    `views_holder_hw`: every view of a batch lies in a holder of the largest view's size.
+    area_ranges: None, or one (lo, hi) per scale: only boxes with lo <= area < hi in ORIGINAL-image pixels^2 are taken from
+    that scale's views (upscaled views answer for small objects, downscaled ones for large; Detectron's
+    BBOX_AUG.AREA_TH_LO / AREA_TH_HI, not in the reference). No default window is invented: None keeps everything.
+    -> (EpisodePlan for query-only holders of n_images * V rows, ViewSet)"""
+    scales = [float(_host_only("scales", s)) for s in scales]
+    if not scales or not all(s > 0 for s in scales):
+        raise ValueError("plan_views: scales must be positive, got %r" % (scales,))
+    if area_ranges is None:
+        area_ranges = [(-np.inf, np.inf)] * len(scales)
+    area_ranges = [(float(lo), float(hi)) for lo, hi in area_ranges]
+    if len(area_ranges) != len(scales):
+        raise ValueError("plan_views: %d area ranges for %d scales" % (len(area_ranges), len(scales)))
+    F = 2 if flip else 1
+    images = _view_rows(pool, list(rows), bool(flip))
+    if holder_hw is None:
+        holder_hw = views_holder_hw(pool, [im[0] for im in images], scales)
+    holder_hw = (int(holder_hw[0]), int(holder_hw[1]))
+    qs, table = [], []
+    for row, twin, h, w in images:
+        for s, (scale, (lo, hi)) in enumerate(zip(scales, area_ranges)):
+            im_scale, oh, ow = _view_size(h, w, scale)
+            if oh > holder_hw[0] or ow > holder_hw[1]:
+                raise ValueError("plan_episode: copy window %d x %d of row %d is larger than the holder (%d x %d)"
+                                 % (oh, ow, row, holder_hw[0], holder_hw[1]))
+            for f in range(F):
+                r = twin if f else row
+                qs.append(dict(row=r, im_scale=im_scale, oh=oh, ow=ow, y_s=0, x_s=0, copy_h=oh, copy_w=ow, out_h=oh, out_w=ow,
+                               clamp_x=-1, clamp_y=-1, pos_cls=0, order=np.zeros((0,), dtype=np.int32), view=s * F + f))
+                # a view is mirrored relative to the ORIGINAL image when its row's flipped bit says so
+                table.append((float(w), float(h), float(int(pool.meta[r, 2])), lo, hi))
+    plan = EpisodePlan(_pack_plan(qs, []), qs, [], holder_hw)
+    views = ViewSet(len(images), len(scales) * F, np.asarray(table, dtype=np.float32).reshape(-1, 5),
+                    [q["im_scale"] for q in qs], [q["row"] for q in qs])
+    return plan, views

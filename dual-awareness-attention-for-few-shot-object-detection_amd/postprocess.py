@@ -12,7 +12,12 @@ gt_boxes / num_boxes tensors of a train-mode forward (pseudo-labels are trained 
 device. `merge_numpy` is the merge restated in numpy float64 (host): the tests' yardstick, pinned to the reference's own
 chain by tests/golden/merge_dets.npz. `merge_detections(method="linear" | "gaussian", vote_thresh=...)` runs Soft-NMS and box
 voting in the same call (dana_detect_merge_soft; restated from their papers, not from the reference), and
-`merge_soft_numpy` is their host restatement, operation for operation."""
+`merge_soft_numpy` is their host restatement, operation for operation.
+
+`fold_views` / `ensemble_views` are the same merge for the other source of redundant lists, test-time augmentation: the
+lists of a sweep over the B * V views `pipeline.plan_views` planned (mirrored, several scales) are mapped back into the frame
+of their image and laid out list-major on the device (csrc/views.hip, one C call, nothing read back), then merged with
+groups = V. `fold_views_numpy` restates the fold in numpy float32. Neither is in the reference tree."""
 import ctypes
 import math
 
@@ -311,6 +316,108 @@ def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0,
     out._take_layout(m)
     out.num_classes = C
     return out
+
+
+# ---- view ensembles: flip and multi-scale testing -------------------------------------------------------------------------
+# Out of scope here: views times shots in one fold (fold the views, then merge the shots); views of an im_data tensor that
+# did not come from an ImagePool (a resize of a resized image is not the loader's image); vertical flips and rotations;
+# training-time augmentation; QueryBank views. The sibling detectors need nothing of their own: the fold sees only lists.
+
+class FoldedViews:
+    """`fold_views`' result, which `merge_detections(folded, folded.views, capacity=folded.capacity)` accepts: `packed`
+    [rows,5] and device int32 `counts` / `offsets` of the problems q = (i * C + c) * V + v, nothing of it on the host.
+    Rows of `packed` that no list's count covers are unwritten. `src_row` (device int32 per packed row) is a kept row's
+    index inside its input list; `capacity` the longest concatenation of an (image, class)'s V input lists, an upper bound
+    of the folded one because the fold only removes rows."""
+    layout_dev = None
+
+    def __init__(self, packed, counts, offsets, src_row, capacity, n_images, views, num_classes):
+        self.packed, self.counts, self.offsets, self.src_row = packed, counts, offsets, src_row
+        self.capacity, self.n_images, self.views, self.num_classes = capacity, n_images, views, num_classes
+
+
+def fold_views(cd, views):
+    """`cd` = detections_by_class(..., with_layout=True) of a class sweep over the n_images * V view images of
+    `pipeline.plan_views` (problem (i * V + v) * C + c), `views` its `ViewSet`. Every list is mapped into the frame of its
+    original image -- un-mirrored, rows outside the frame dropped, clipped to the frame (not to the padded holder), cut to
+    the view's area window -- and the layout transposed so that the V lists of one (image, class) are consecutive: the
+    rule of include/dana_hip.h (dana_detect_fold_views), restated by `fold_views_numpy`. One C call, nothing read back.
+    -> `FoldedViews`."""
+    V, B = int(views.views), int(views.n_images)
+    if len(cd) != B * V:
+        raise ValueError("fold_views: %d images in the detections, but %d images x %d views were planned" % (len(cd), B, V))
+    packed, P, hc, ho, p_counts, p_offsets, alive = _packed_layout(cd, "fold_views")
+    C = int(cd.num_classes)
+    if hc is None or C < 1 or P != B * V * C:
+        raise ValueError("fold_views: needs detections_by_class(..., with_layout=True) of %d x %d view images" % (B, V))
+    dev = packed.device
+    table = views.table_dev(dev)
+    out = torch.empty_like(packed)
+    ibuf = torch.empty((2 * P + packed.size(0),), dtype=torch.int32, device=dev)  # counts | offsets | src_row
+    counts, offsets, src_row = ibuf[:P], ibuf[P:2 * P], ibuf[2 * P:]
+    lib().call("dana_detect_fold_views", ops._p(packed), p_counts, p_offsets, B, V, C, ops._p(table), table.size(1), ops._p(out),
+               counts.data_ptr(), offsets.data_ptr(), src_row.data_ptr(), ops._stream())
+    del alive
+    capacity = int(hc.reshape(B, V, C).sum(1).max()) if P else 0
+    return FoldedViews(out, counts, offsets, src_row, capacity, B, V, C)
+
+
+def ensemble_views(cd, views, nms_thresh="cfg", nms_inclusive=False, max_dets=0, *, method="hard", sigma=0.5, min_score=0.001,
+                   vote_thresh=None, vote_score="id"):
+    """Flip / multi-scale testing merged on the device: `fold_views(cd, views)`, then `merge_detections` over the V views of
+    every (image, class) -> dets[i][c], a `MergedDetections` as `ensemble_shots` returns (`add_by_class`, `cap_per_image`,
+    `as_gt_boxes`, `render.prediction_sheet` take it unchanged). `group` is the view index v = s * F + f of a row and `row`
+    its index in the FOLDED list; `folded.src_row` (the `folded` attribute of the result) maps that to the row of `cd`'s
+    list. The keywords are `merge_detections`'. Under the soft methods the 3072-row limit of a concatenation applies to the
+    V views of a class together: with R rois per view, V * R <= 3072 is safe for any thresholds. Detect the views with
+    `detections_by_class(..., nms_thresh=None)` to let soft-NMS see unsuppressed lists."""
+    _soft_args("ensemble_views", nms_thresh, method, sigma, min_score, vote_thresh, vote_score)
+    folded = fold_views(cd, views)
+    B, C = folded.n_images, folded.num_classes
+    m = merge_detections(folded, folded.views, nms_thresh, nms_inclusive, max_dets, with_layout=True, capacity=folded.capacity,
+                         method=method, sigma=sigma, min_score=min_score, vote_thresh=vote_thresh, vote_score=vote_score)
+    out = MergedDetections([list(m[b * C:(b + 1) * C]) for b in range(B)])
+    out._take_layout(m)
+    out.num_classes = C
+    out.folded = folded
+    return out
+
+
+def fold_views_numpy(lists, table, V, C):
+    """`fold_views` restated in numpy float32 (host), operation for operation as include/dana_hip.h defines
+    dana_detect_fold_views. lists: P = B * V * C arrays [k,5] in problem order p = (i * V + v) * C + c; table [B * V][>=5]
+    = (fw, fh, flip, area_lo, area_hi) -> dict(dets: the P folded lists in list-major order q = (i * C + c) * V + v,
+    src_row: int32 [k'] per list, the kept rows' indices in the input list, counts int32 [P] in q order, source: int64 [P],
+    the input problem p of every q)."""
+    V, C = int(V), int(C)
+    table = np.asarray(table, np.float32)
+    table = table.reshape(-1, table.shape[-1] if table.ndim > 1 else 5)
+    P = len(lists)
+    if V < 1 or C < 1 or P % (V * C) or table.shape[0] * C != P or table.shape[1] < 5:
+        raise ValueError("fold_views_numpy: %d lists and %d table rows do not make images x %d views x %d lists" % (P, table.shape[0], V, C))
+    one, zero = np.float32(1.0), np.float32(0.0)
+    dets, rows, source = [None] * P, [None] * P, np.zeros(P, np.int64)
+    for p in range(P):
+        iv, c = divmod(p, C)
+        i, v = divmod(iv, V)
+        q = (i * C + c) * V + v
+        fw, fh, flip, lo, hi = table[iv, :5]
+        wm1, hm1 = fw - one, fh - one
+        d = np.array(lists[p], dtype=np.float32).reshape(-1, 5)
+        x1, y1, x2, y2 = d[:, 0], d[:, 1], d[:, 2], d[:, 3]
+        if flip != 0:
+            x1, x2 = wm1 - x2, wm1 - x1
+        with np.errstate(invalid="ignore"):
+            keep = (x1 <= wm1) & (y1 <= hm1) & (x2 >= zero) & (y2 >= zero)
+            clip = lambda a, m: (lambda b: np.where(b > m, m, b))(np.where(a < zero, zero, a))  # noqa: E731
+            x1, x2, y1, y2 = clip(x1, wm1), clip(x2, wm1), clip(y1, hm1), clip(y2, hm1)
+            area = (x2 - x1 + one) * (y2 - y1 + one)
+            keep &= (lo <= area) & (area < hi)
+        assert area.dtype == np.float32
+        dets[q] = np.stack((x1, y1, x2, y2, d[:, 4]), 1).astype(np.float32)[keep]
+        rows[q] = np.nonzero(keep)[0].astype(np.int32)
+        source[q] = p
+    return dict(dets=dets, src_row=rows, counts=np.asarray([len(d) for d in dets], np.int32), source=source)
 
 
 def cap_per_image(cd, max_per_image=100):

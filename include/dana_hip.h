@@ -208,6 +208,35 @@ int dana_detect_merge_soft(const float* dets_in, const int* counts_in, const int
                            int* row_out, int* votes_out, int* counts_out, int* offsets_out, void* workspace,
                            size_t workspace_bytes, dana_stream_t stream);
 
+/* View ensembles (test-time augmentation: an image seen mirrored and at several scales, each view detected on its own, the
+ * lists mapped back and merged). Not in the reference tree; the area window follows Detectron's BBOX_AUG.AREA_TH_LO /
+ * AREA_TH_HI, and postprocess.fold_views_numpy is the same definition in numpy. This call maps the lists of a class sweep
+ * over n_images * views view images into the frame of their original image and lays them out for dana_detect_merge /
+ * dana_detect_merge_soft with groups = views; neither of those changes. dets_in is the packed layout above, read on the
+ * DEVICE: problem p = (i * views + v) * lists_per_view + c (image i, view v, class slot c) has counts_in[p] rows from row
+ * offsets_in[p], already in original-image pixels (post-processing divided by the view's im_info[2]).
+ * view_table[(i * views + v) * view_stride + 0..4] = (fw, fh, flip, area_lo, area_hi), view_stride >= 5: the original
+ * frame's width and height as floats, flip 0 or 1, the area window (area_hi may be +inf, area_lo -inf).
+ * Per row, in fp32, one IEEE operation per written operation, with wm1 = fw - 1 and hm1 = fh - 1:
+ *   (1) if flip: (x1, x2) <- (wm1 - x2, wm1 - x1) -- the involution of imdb.append_flipped_images, written wm1 - x: ONE
+ *       rounding after wm1, not (fw - x) - 1;
+ *   (2) the row is kept only if it touches the frame: x1 <= wm1 && y1 <= hm1 && x2 >= 0 && y2 >= 0 (a NaN coordinate fails
+ *       its comparison and drops the row);
+ *   (3) clip: x <- min(max(x, 0), wm1), y <- min(max(y, 0), hm1), with max(x, 0) = (x < 0 ? 0 : x) and
+ *       min(x, m) = (x > m ? m : x);
+ *   (4) area = (x2 - x1 + 1) * (y2 - y1 + 1); kept only if area_lo <= area && area < area_hi;
+ *   (5) the score is copied unchanged.
+ * The kept rows of problem p are written in their input order (stable: still descending by score) to
+ * dets_out[offsets_in[p] + k], k < kept, and the layout is transposed to list-major: with q = (i * lists_per_view + c) *
+ * views + v, counts_out[q] = kept and offsets_out[q] = offsets_in[p], so the `views` lists of one (image, class) are
+ * consecutive problems. src_row_out[offsets_in[p] + k] = the row's index inside input list p (may be null). dets_out has the
+ * rows of dets_in and must not alias it (DANA_ERR_ARG); its rows beyond a list's kept count, and the rows no list owns, are
+ * left UNWRITTEN. No row moves between lists; no atomics and no ordering between workgroups: two runs give the same bytes.
+ * n_images * views * lists_per_view == 0 returns without a launch. */
+int dana_detect_fold_views(const float* dets_in, const int* counts_in, const int* offsets_in, int n_images, int views,
+                           int lists_per_view, const float* view_table, int view_stride, float* dets_out, int* counts_out,
+                           int* offsets_out, int* src_row_out, dana_stream_t stream);
+
 /* Detection lists -> the ground-truth tensors of a train-mode forward (fs_loader.py:325; pseudo-labels are trained on,
  * utils.py:130-179): one list per image in the packed layout above (counts[B], offsets[B], device). Image b's first
  * max_boxes rows with score > score_thresh, in list order, become gt_boxes[b][i] = (x1, y1, x2, y2) * im_info[b][2] (back
