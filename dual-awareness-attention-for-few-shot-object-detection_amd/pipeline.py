@@ -466,9 +466,11 @@ class ViewSet:
     frame's width and height, whether the view was mirrored, and its box-area window in original-image pixels^2.
     `scales` [n_images * views] are the views' im_scale, `rows` their pool rows."""
 
+    columns = 5  # floats per table row
+
     def __init__(self, n_images, views, table, scales, rows):
         self.n_images, self.views = int(n_images), int(views)
-        self.table = np.ascontiguousarray(table, dtype=np.float32).reshape(self.n_images * self.views, 5)
+        self.table = np.ascontiguousarray(table, dtype=np.float32).reshape(self.n_images * self.views, self.columns)
         self.scales, self.rows = np.asarray(scales, dtype=np.float64), np.asarray(rows, dtype=np.int64)
         self._dev = {}
 
@@ -476,7 +478,7 @@ class ViewSet:
         """the table on `device`, uploaded once and cached"""
         device = torch.device(device)
         if device not in self._dev:
-            self._dev[device] = torch.from_numpy(self.table if self.table.size else np.zeros((1, 5), np.float32)).to(device)
+            self._dev[device] = torch.from_numpy(self.table if self.table.size else np.zeros((1, self.columns), np.float32)).to(device)
         return self._dev[device]
 
 
@@ -555,3 +557,148 @@ def plan_views(pool, rows, scales=(600,), flip=False, area_ranges=None, holder_h
     views = ViewSet(len(images), len(scales) * F, np.asarray(table, dtype=np.float32).reshape(-1, 5),
                     [q["im_scale"] for q in qs], [q["row"] for q in qs])
     return plan, views
+
+
+# ---- tiles of pool frames: tiled inference --------------------------------------------------------------------------------
+# Every view above is the whole frame, so a small object in a large frame reaches the trunk as a cell or two. A tile is a
+# query record whose copy window (Q_YS, Q_XS, Q_COPY_H, Q_COPY_W) is a part of the frame prepared at a LARGER scale:
+# `episode_queries` samples the prepared frame at (x_s + x, y_s + y), so a tile image is bit-equal to that crop of the
+# prepared full frame and needs no kernel of its own. `postprocess.ensemble_views` maps the tiles' boxes back (clip to the
+# tile, seam rule, translate) and merges them with an optional full-frame view. Not in the reference tree.
+
+class TileSet(ViewSet):
+    """The `ViewSet` of a `plan_tiles` plan, which `postprocess.fold_tiles` / `ensemble_views` read. `table` is host float32
+    [n_images * views][13] per view in plan order, everything in ORIGINAL-image pixels:
+      0..4   fw, fh, flip, area_lo, area_hi   as a ViewSet's: the original frame, the row's flipped bit, the area window
+      5, 6   x_off, y_off                     float32(x_s / im_scale), float32(y_s / im_scale): divided in float64, rounded once
+      7, 8   tw, th                           float32(copy_w / im_scale), float32(copy_h / im_scale)
+      9..12  lim_x1, lim_y1, lim_x2, lim_y2   in tile coordinates: float32(margin / im_scale) and float32((copy - 1 - margin) /
+                                              im_scale) on an interior side, -inf / +inf on a side that is a side of the frame
+    For a mirrored view (flip = 1) the offsets are those of its window in the MIRRORED frame; the fold un-mirrors after
+    translating. The full-frame view has offsets 0, (tw, th) = (fw, fh) and infinite limits. `windows` is host int32
+    [n_images * views][4] = (y_s, x_s, copy_h, copy_w) in prepared pixels of the view."""
+    columns = 13
+
+    def __init__(self, n_images, views, table, scales, rows, windows):
+        super().__init__(n_images, views, table, scales, rows)
+        self.windows = np.ascontiguousarray(windows, dtype=np.int32).reshape(self.n_images * self.views, 4)
+
+
+def tile_windows(length, n, overlap=64, margin=4):
+    """The windows of `n` tiles along an axis of `length` prepared pixels -> (starts [n], size): for n = 1 the whole axis,
+    otherwise size = ceil((length + (n - 1) * overlap) / n) and start k = (k * (length - size)) // (n - 1). The first window
+    starts at 0, the last ends at `length`, neighbours overlap by at least `overlap`.
+    Coverage guarantee: every integer interval [a, b] of the axis with b - a <= overlap - 2 * margin lies in at least one
+    window [s, s + size) in which it keeps `margin` from every INTERIOR side (a side that is not an end of the axis):
+    a >= s + margin unless s = 0, and b <= s + size - 1 - margin unless s + size = length. (Take the first window whose far
+    side lets the interval pass: it failed the previous one by b >= e - margin, neighbours share at least `overlap` pixels,
+    so a >= b - (overlap - 2 * margin) >= e - overlap + margin >= s + margin.) ValueError for windows that cannot be:
+    size > length; length - size < n - 1 (a grid so fine that two windows would coincide); overlap - 2 * margin < 1."""
+    L, n, o, m = int(length), int(n), int(overlap), int(margin)
+    if n < 1 or o < 0 or m < 0:
+        raise ValueError("plan_tiles: need tiles >= 1, overlap >= 0, margin >= 0, got %d, %d, %d" % (n, o, m))
+    if n == 1:
+        return [0], L
+    if o - 2 * m < 1:
+        raise ValueError("plan_tiles: overlap %d - 2 * margin %d < 1: no box is safe from both of two neighbouring tiles' seams"
+                         % (o, m))
+    T = -(-(L + (n - 1) * o) // n)
+    if T > L:
+        raise ValueError("plan_tiles: %d tiles with overlap %d need windows of %d on an axis of %d prepared pixels" % (n, o, T, L))
+    if L - T < n - 1:
+        raise ValueError("plan_tiles: %d tiles of %d on an axis of %d prepared pixels would coincide (overlap %d)" % (n, T, L, o))
+    return [(k * (L - T)) // (n - 1) for k in range(n)], T
+
+
+def _tile_grid(grid):
+    ny, nx = (int(_host_only("grid", g)) for g in grid)
+    if ny < 1 or nx < 1:
+        raise ValueError("plan_tiles: grid must be (ny >= 1, nx >= 1), got %r" % (tuple(grid),))
+    return ny, nx
+
+
+def _tile_sizes(h, w, grid, scale, overlap, margin, full_frame):
+    """-> the (oh, ow) of every view of an h x w frame: the full frame first when there is one, then the tile size"""
+    _, oh, ow = _view_size(h, w, scale)
+    sizes = [(tile_windows(oh, grid[0], overlap, margin)[1], tile_windows(ow, grid[1], overlap, margin)[1])]
+    if full_frame is not None:
+        sizes.insert(0, _view_size(h, w, full_frame)[1:])
+    return sizes
+
+
+def tiles_holder_hw(pool, rows, grid, scale=600, overlap=64, margin=4, full_frame=600):
+    """(H, W) of the smallest holder that takes every view of `plan_tiles` with these arguments: the largest of the tiles
+    and the full-frame views"""
+    grid = _tile_grid(grid)
+    sizes = [s for e in rows for r in [_pool_row(pool, e[0] if isinstance(e, (tuple, list)) else e)[0]]
+             for s in _tile_sizes(int(pool.meta[r, 0]), int(pool.meta[r, 1]), grid, scale, overlap, margin, full_frame)]
+    return (max(s[0] for s in sizes), max(s[1] for s in sizes)) if sizes else (1, 1)
+
+
+def plan_tiles(pool, rows, grid, scale=600, overlap=64, margin=4, flip=False, full_frame=600, area_ranges=None, holder_hw=None):
+    """Host only. Tiled inference as one plan of query records. rows and flip as in `plan_views`. Every frame is prepared so
+    that its SHORTER side is `scale` -- the magnification of the whole frame: scale=1200 with a 2 x 2 grid gives tiles of
+    about 600 + overlap -- and cut into grid = (ny, nx) windows per `tile_windows`, `overlap` and `margin` in prepared pixels
+    of the tile views; with full_frame = a target size (None: no such view) the whole frame at that size comes first, as
+    `plan_views` would plan it. Image i's V = T * F views (T = ny * nx + 1 with the full frame, F = 2 with flip) are records
+    i * V + v, v = t * F + f: t = 0 the full frame when present, then the tiles row-major (ty * nx + tx); f = 1 the twin, whose
+    windows are the same numbers in the mirrored frame. A tile record copies its window of the prepared frame to the holder's
+    top-left corner, with no clamp and no boxes. The grid is the same for every image so that V is.
+    area_ranges: None or (full_range, tile_range), each (lo, hi) in ORIGINAL-image pixels^2, the table's area columns as in
+    `plan_views`: the full frame answers for large boxes, the tiles for small ones. No default window is invented.
+    holder_hw defaults to `tiles_holder_hw`. The coverage guarantee of `tile_windows` holds per axis, in prepared pixels: an
+    object no larger than overlap - 2 * margin is whole, and clear of the seams, in at least one tile; larger objects are the
+    full-frame view's. ValueError (naming the value) for the windows `tile_windows` refuses and for a view larger than the
+    holder. -> (EpisodePlan for query-only holders of n_images * V rows, TileSet)"""
+    ny, nx = grid = _tile_grid(grid)
+    scale = float(_host_only("scale", scale))
+    if not scale > 0 or (full_frame is not None and not float(_host_only("full_frame", full_frame)) > 0):
+        raise ValueError("plan_tiles: scale and full_frame must be positive, got %r and %r" % (scale, full_frame))
+    inf = (-np.inf, np.inf)
+    if area_ranges is None:
+        area_ranges = (inf, inf)
+    if len(area_ranges) != 2:
+        raise ValueError("plan_tiles: area_ranges is (full_range, tile_range), got %d ranges" % len(area_ranges))
+    full_range, tile_range = [(float(lo), float(hi)) for lo, hi in area_ranges]
+    F = 2 if flip else 1
+    images = _view_rows(pool, list(rows), bool(flip))
+    if holder_hw is None:
+        holder_hw = tiles_holder_hw(pool, [im[0] for im in images], grid, scale, overlap, margin, full_frame)
+    holder_hw = (int(holder_hw[0]), int(holder_hw[1]))
+    m = int(margin)
+    qs, table = [], []
+
+    def view(row, twin, h, w, im_scale, oh, ow, y_s, x_s, ch, cw, area, t, whole=False):
+        if ch > holder_hw[0] or cw > holder_hw[1]:
+            raise ValueError("plan_episode: copy window %d x %d of row %d is larger than the holder (%d x %d)"
+                             % (ch, cw, row, holder_hw[0], holder_hw[1]))
+        # an interior side keeps `margin` prepared pixels; a side of the frame has no seam
+        lim = (m / im_scale if x_s > 0 else -np.inf, m / im_scale if y_s > 0 else -np.inf,
+               (cw - 1 - m) / im_scale if x_s + cw < ow else np.inf, (ch - 1 - m) / im_scale if y_s + ch < oh else np.inf)
+        for f in range(F):
+            r = twin if f else row
+            qs.append(dict(row=r, im_scale=im_scale, oh=oh, ow=ow, y_s=y_s, x_s=x_s, copy_h=ch, copy_w=cw, out_h=ch, out_w=cw,
+                           clamp_x=-1, clamp_y=-1, pos_cls=0, order=np.zeros((0,), dtype=np.int32), view=t * F + f))
+            # (the whole frame in its own pixels, not its prepared size divided back)
+            size = (float(w), float(h)) if whole else (cw / im_scale, ch / im_scale)
+            table.append((float(w), float(h), float(int(pool.meta[r, 2]))) + area + (x_s / im_scale, y_s / im_scale) + size + lim)
+
+    for row, twin, h, w in images:
+        t = 0
+        if full_frame is not None:
+            im_scale, oh, ow = _view_size(h, w, full_frame)
+            view(row, twin, h, w, im_scale, oh, ow, 0, 0, oh, ow, full_range, t, whole=True)
+            t += 1
+        im_scale, oh, ow = _view_size(h, w, scale)
+        ys, th = tile_windows(oh, ny, overlap, margin)
+        xs, tw = tile_windows(ow, nx, overlap, margin)
+        for y_s in ys:
+            for x_s in xs:
+                view(row, twin, h, w, im_scale, oh, ow, y_s, x_s, th, tw, tile_range, t)
+                t += 1
+    plan = EpisodePlan(_pack_plan(qs, []), qs, [], holder_hw)
+    # (the tuples hold Python floats: the divisions above are float64 and the table rounds them once)
+    tiles = TileSet(len(images), (ny * nx + (full_frame is not None)) * F, np.asarray(table, dtype=np.float64).astype(np.float32)
+                    .reshape(-1, 13), [q["im_scale"] for q in qs], [q["row"] for q in qs],
+                    [(q["y_s"], q["x_s"], q["copy_h"], q["copy_w"]) for q in qs])
+    return plan, tiles

@@ -17,7 +17,12 @@ voting in the same call (dana_detect_merge_soft; restated from their papers, not
 `fold_views` / `ensemble_views` are the same merge for the other source of redundant lists, test-time augmentation: the
 lists of a sweep over the B * V views `pipeline.plan_views` planned (mirrored, several scales) are mapped back into the frame
 of their image and laid out list-major on the device (csrc/views.hip, one C call, nothing read back), then merged with
-groups = V. `fold_views_numpy` restates the fold in numpy float32. Neither is in the reference tree."""
+groups = V. `fold_views_numpy` restates the fold in numpy float32. Neither is in the reference tree.
+
+`fold_tiles` is that fold for tiled inference: the views of `pipeline.plan_tiles` are overlapping windows of the frame (beside
+an optional full-frame view), so a list is first tested against its tile, put through the seam rule, clipped to the tile and
+translated (dana_detect_fold_tiles, the same kernel body). `ensemble_views` takes a `TileSet` and folds with it;
+`fold_tiles_numpy` is the restatement."""
 import ctypes
 import math
 
@@ -336,6 +341,30 @@ class FoldedViews:
         self.capacity, self.n_images, self.views, self.num_classes = capacity, n_images, views, num_classes
 
 
+def _fold(who, entry, cd, views):
+    V, B = int(views.views), int(views.n_images)
+    if len(cd) != B * V:
+        raise ValueError("%s: %d images in the detections, but %d images x %d views were planned" % (who, len(cd), B, V))
+    packed, P, hc, ho, p_counts, p_offsets, alive = _packed_layout(cd, who)
+    C = int(cd.num_classes)
+    if hc is None or C < 1 or P != B * V * C:
+        raise ValueError("%s: needs detections_by_class(..., with_layout=True) of %d x %d view images" % (who, B, V))
+    dev = packed.device
+    table = views.table_dev(dev)
+    out = torch.empty_like(packed)
+    ibuf = torch.empty((2 * P + packed.size(0),), dtype=torch.int32, device=dev)  # counts | offsets | src_row
+    counts, offsets, src_row = ibuf[:P], ibuf[P:2 * P], ibuf[2 * P:]
+    lib().call(entry, ops._p(packed), p_counts, p_offsets, B, V, C, ops._p(table), table.size(1), ops._p(out),
+               counts.data_ptr(), offsets.data_ptr(), src_row.data_ptr(), ops._stream())
+    del alive
+    capacity = int(hc.reshape(B, V, C).sum(1).max()) if P else 0
+    return FoldedViews(out, counts, offsets, src_row, capacity, B, V, C)
+
+
+def _is_tiled(views):
+    return getattr(views, "columns", 5) >= 13
+
+
 def fold_views(cd, views):
     """`cd` = detections_by_class(..., with_layout=True) of a class sweep over the n_images * V view images of
     `pipeline.plan_views` (problem (i * V + v) * C + c), `views` its `ViewSet`. Every list is mapped into the frame of its
@@ -343,23 +372,27 @@ def fold_views(cd, views):
     the view's area window -- and the layout transposed so that the V lists of one (image, class) are consecutive: the
     rule of include/dana_hip.h (dana_detect_fold_views), restated by `fold_views_numpy`. One C call, nothing read back.
     -> `FoldedViews`."""
-    V, B = int(views.views), int(views.n_images)
-    if len(cd) != B * V:
-        raise ValueError("fold_views: %d images in the detections, but %d images x %d views were planned" % (len(cd), B, V))
-    packed, P, hc, ho, p_counts, p_offsets, alive = _packed_layout(cd, "fold_views")
-    C = int(cd.num_classes)
-    if hc is None or C < 1 or P != B * V * C:
-        raise ValueError("fold_views: needs detections_by_class(..., with_layout=True) of %d x %d view images" % (B, V))
-    dev = packed.device
-    table = views.table_dev(dev)
-    out = torch.empty_like(packed)
-    ibuf = torch.empty((2 * P + packed.size(0),), dtype=torch.int32, device=dev)  # counts | offsets | src_row
-    counts, offsets, src_row = ibuf[:P], ibuf[P:2 * P], ibuf[2 * P:]
-    lib().call("dana_detect_fold_views", ops._p(packed), p_counts, p_offsets, B, V, C, ops._p(table), table.size(1), ops._p(out),
-               counts.data_ptr(), offsets.data_ptr(), src_row.data_ptr(), ops._stream())
-    del alive
-    capacity = int(hc.reshape(B, V, C).sum(1).max()) if P else 0
-    return FoldedViews(out, counts, offsets, src_row, capacity, B, V, C)
+    if _is_tiled(views):
+        raise ValueError("fold_views: a TileSet's views are windows of the frame; fold them with fold_tiles")
+    return _fold("fold_views", "dana_detect_fold_views", cd, views)
+
+
+def fold_tiles(cd, tiles):
+    """`fold_views` for tiled inference: `cd` = detections_by_class(..., with_layout=True) of a class sweep over the
+    n_images * V view images of `pipeline.plan_tiles`, `tiles` its `TileSet`. A row is kept only if it touches its tile and
+    keeps the margin from every interior side of it (the seam rule, on the unclipped box: an object cut by a tile's side
+    comes back as a truncated box that NMS would not match with the whole box of the neighbouring tile); it is clipped to the
+    TILE (not the padded holder), translated into the frame and then folded as `fold_views` does -- un-mirrored, frame test,
+    clip, area window. The rule is include/dana_hip.h's (dana_detect_fold_tiles), restated by `fold_tiles_numpy`. The same
+    packing, capacity and one C call as `fold_views`, nothing read back -> `FoldedViews`.
+    Two limits. `capacity` is computed from the INPUT counts without a device read, and under the soft methods the 3072-row
+    limit of a concatenation applies to all V views of a class together: with many tiles, detect the views with a per-view
+    NMS or a score threshold, or merge with method="hard". And the coverage guarantee (`pipeline.tile_windows`) is about
+    boxes no larger than overlap - 2 * margin: larger objects are the full-frame view's."""
+    if not _is_tiled(tiles):
+        raise ValueError("fold_tiles: needs the TileSet of pipeline.plan_tiles (13 table columns), got %d columns"
+                         % getattr(tiles, "columns", 5))
+    return _fold("fold_tiles", "dana_detect_fold_tiles", cd, tiles)
 
 
 def ensemble_views(cd, views, nms_thresh="cfg", nms_inclusive=False, max_dets=0, *, method="hard", sigma=0.5, min_score=0.001,
@@ -370,9 +403,15 @@ def ensemble_views(cd, views, nms_thresh="cfg", nms_inclusive=False, max_dets=0,
     its index in the FOLDED list; `folded.src_row` (the `folded` attribute of the result) maps that to the row of `cd`'s
     list. The keywords are `merge_detections`'. Under the soft methods the 3072-row limit of a concatenation applies to the
     V views of a class together: with R rois per view, V * R <= 3072 is safe for any thresholds. Detect the views with
-    `detections_by_class(..., nms_thresh=None)` to let soft-NMS see unsuppressed lists."""
+    `detections_by_class(..., nms_thresh=None)` to let soft-NMS see unsuppressed lists.
+    `views` may be the `TileSet` of `pipeline.plan_tiles` (tiled inference): the lists are then folded with `fold_tiles`, and
+    `group` is the view index v = t * F + f (t = 0 the full frame when planned, then the tiles row-major). Its two limits: the
+    3072 rows are those of ALL V views of a class, counted on the INPUT lists without a device read -- with many tiles,
+    detect the views with a per-view NMS or a score threshold, or use method="hard"; and only boxes no larger than
+    overlap - 2 * margin are guaranteed a tile that holds them clear of its seams -- larger objects are the full-frame
+    view's."""
     _soft_args("ensemble_views", nms_thresh, method, sigma, min_score, vote_thresh, vote_score)
-    folded = fold_views(cd, views)
+    folded = fold_tiles(cd, views) if _is_tiled(views) else fold_views(cd, views)
     B, C = folded.n_images, folded.num_classes
     m = merge_detections(folded, folded.views, nms_thresh, nms_inclusive, max_dets, with_layout=True, capacity=folded.capacity,
                          method=method, sigma=sigma, min_score=min_score, vote_thresh=vote_thresh, vote_score=vote_score)
@@ -418,6 +457,43 @@ def fold_views_numpy(lists, table, V, C):
         rows[q] = np.nonzero(keep)[0].astype(np.int32)
         source[q] = p
     return dict(dets=dets, src_row=rows, counts=np.asarray([len(d) for d in dets], np.int32), source=source)
+
+
+def fold_tiles_numpy(lists, table, V, C):
+    """`fold_tiles` restated in numpy float32 (host), operation for operation as include/dana_hip.h defines
+    dana_detect_fold_tiles: lists and the result as `fold_views_numpy`'s, table [B * V][>=13] = (fw, fh, flip, area_lo, area_hi,
+    x_off, y_off, tw, th, lim_x1, lim_y1, lim_x2, lim_y2). Steps (a) - (d) -- tile test, seam rule on the unclipped box, clip to
+    the tile, translate -- then `fold_views_numpy` on the translated rows; a row stays if both keep it."""
+    V, C = int(V), int(C)
+    table = np.asarray(table, np.float32)
+    table = table.reshape(-1, table.shape[-1] if table.ndim > 1 else 13)
+    P = len(lists)
+    if V < 1 or C < 1 or P % (V * C) or table.shape[0] * C != P or table.shape[1] < 13:
+        raise ValueError("fold_tiles_numpy: %d lists and %d table rows of %d columns do not make images x %d views x %d lists"
+                         % (P, table.shape[0], table.shape[1], V, C))
+    one, zero = np.float32(1.0), np.float32(0.0)
+    moved, in_tile = [], []
+    for p in range(P):
+        x_off, y_off, tw, th, lx1, ly1, lx2, ly2 = table[p // C, 5:13]
+        twm1, thm1 = tw - one, th - one
+        d = np.array(lists[p], dtype=np.float32).reshape(-1, 5)
+        x1, y1, x2, y2 = d[:, 0], d[:, 1], d[:, 2], d[:, 3]
+        with np.errstate(invalid="ignore"):
+            keep = (x1 <= twm1) & (y1 <= thm1) & (x2 >= zero) & (y2 >= zero)
+            keep &= (x1 >= lx1) & (y1 >= ly1) & (x2 <= lx2) & (y2 <= ly2)
+            clip = lambda a, m: (lambda b: np.where(b > m, m, b))(np.where(a < zero, zero, a))  # noqa: E731
+            x1, x2, y1, y2 = clip(x1, twm1), clip(x2, twm1), clip(y1, thm1), clip(y2, thm1)
+            x1, x2, y1, y2 = x1 + x_off, x2 + x_off, y1 + y_off, y2 + y_off
+        assert x1.dtype == np.float32
+        moved.append(np.stack((x1, y1, x2, y2, d[:, 4]), 1).astype(np.float32))
+        in_tile.append(keep)
+    # steps (1) - (5) on every translated row; a row of the result is one that also passed (a) and (b)
+    r = fold_views_numpy(moved, table, V, C)
+    for q, p in enumerate(r["source"]):
+        sel = in_tile[p][r["src_row"][q]]
+        r["dets"][q], r["src_row"][q] = r["dets"][q][sel], r["src_row"][q][sel]
+    r["counts"] = np.asarray([len(d) for d in r["dets"]], np.int32)
+    return r
 
 
 def cap_per_image(cd, max_per_image=100):

@@ -237,6 +237,38 @@ int dana_detect_fold_views(const float* dets_in, const int* counts_in, const int
                            int lists_per_view, const float* view_table, int view_stride, float* dets_out, int* counts_out,
                            int* offsets_out, int* src_row_out, dana_stream_t stream);
 
+/* Tiled inference: a frame cut into overlapping tiles, each tile detected at the network's normal input size beside an
+ * optional full-frame view, the lists mapped back and merged. Not in the reference tree; postprocess.fold_tiles_numpy is the
+ * same definition in numpy and pipeline.plan_tiles makes the table. The call is dana_detect_fold_views for views that are
+ * WINDOWS of the frame: same arguments, same layout of dets_in / dets_out / counts / offsets / src_row_out, same guarantees
+ * (rows written in input order to the list's own rows, the rest UNWRITTEN, counts_out / offsets_out at the transposed index
+ * q = (i * lists_per_view + c) * views + v, no atomics, two runs give the same bytes, dets_out must not alias dets_in, a zero
+ * shape returns without a launch), and dana_detect_fold_views itself is unchanged. dets_in holds a tile's boxes in
+ * original-image pixels measured from the TILE's origin (post-processing divided by the view's im_info[2]).
+ * view_table[(i * views + v) * view_stride + 0..12], view_stride >= 13:
+ *    0..4   fw, fh, flip, area_lo, area_hi   as above: the ORIGINAL frame, 0 or 1, the area window;
+ *    5, 6   x_off, y_off                     the tile's origin in the frame -- for flip = 1 in the MIRRORED frame, where the
+ *                                            tile's window lies;
+ *    7, 8   tw, th                           the tile's width and height;
+ *    9..12  lim_x1, lim_y1, lim_x2, lim_y2   the seam limits in tile coordinates: margin and (size - 1 - margin) on a side
+ *                                            that lies inside the frame, -inf / +inf on a side that is a side of the frame.
+ * Per row, in fp32, one IEEE operation per written operation, with twm1 = tw - 1 and thm1 = th - 1; min and max are the
+ * selects of step (3) above and a NaN coordinate fails its comparison:
+ *   (a) the row is kept only if it touches the tile: x1 <= twm1 && y1 <= thm1 && x2 >= 0 && y2 >= 0;
+ *   (b) the seam rule, on the UNCLIPPED coordinates: kept only if x1 >= lim_x1 && y1 >= lim_y1 && x2 <= lim_x2 &&
+ *       y2 <= lim_y2. A box that runs off a frame-side edge of the tile stays and is clipped; a box within the margin of an
+ *       interior side -- most likely an object the tile's side cut, whose whole box the neighbouring tile has -- or one
+ *       running past it into the holder's padding goes;
+ *   (c) clip to the tile: x <- min(max(x, 0), twm1), y <- min(max(y, 0), thm1);
+ *   (d) translate: x <- x + x_off, y <- y + y_off;
+ *   (e) steps (1) - (5) of dana_detect_fold_views on the result: un-mirror, frame test, clip to the frame, area window,
+ *       score copied. The row is kept if (a), (b), (2) and (4) all hold.
+ * A whole-frame view is the row (.., 0, 0, fw, fh, -inf, -inf, +inf, +inf): it folds as dana_detect_fold_views does, except
+ * that a -0 coordinate comes back +0 from step (d). */
+int dana_detect_fold_tiles(const float* dets_in, const int* counts_in, const int* offsets_in, int n_images, int views,
+                           int lists_per_view, const float* view_table, int view_stride, float* dets_out, int* counts_out,
+                           int* offsets_out, int* src_row_out, dana_stream_t stream);
+
 /* Detection lists -> the ground-truth tensors of a train-mode forward (fs_loader.py:325; pseudo-labels are trained on,
  * utils.py:130-179): one list per image in the packed layout above (counts[B], offsets[B], device). Image b's first
  * max_boxes rows with score > score_thresh, in list order, become gt_boxes[b][i] = (x1, y1, x2, y2) * im_info[b][2] (back
