@@ -34,6 +34,24 @@ flags, one area range, no maxDets cut), `coco_numpy` is checked against the refe
   * objects are matched by index, not by annotation id: pycocotools' `dtm == 0` confusion over an annotation whose id is
     0 is not reproduced;
   * the rank is (class, score descending, image index, arrival): COCOeval's stable mergesort over the per-image lists.
+
+Proposal recall (`ProposalRecallEvaluator`, `eval_proposal_recall`, `proposal_recall_numpy`): the stage in front of both
+protocols -- py-faster-rcnn's `evaluate_recall`, which the reference still carries commented out (lib/datasets/
+imdb.py:137-225) -- on the `rois` an eval-mode forward returns: proposals and ground truth matched one to one, greedily
+(:193-210), the matched IoUs held against 0.50:0.05:0.95 (:214-221), averaged into AR (:223) per proposal budget
+(`limit`, :187-188) and object-size range (`area`, :150-174). One C call (csrc/recall.hip: one workgroup per (unit, limit,
+area range) for the matching, one thread per (limit, area range, pair) for the counts), float64 IoUs, integer counts.
+A proposal list is made for one image under one class, so it is measured twice: on the image's objects of that class
+(role 0) and, with others=True, on the image's other objects (role 1). ar[0] beside ar[1] is the selectivity the
+attention in front of the RPN is there to buy.
+
+Defined where the reference is not, or differs:
+  * when a list has fewer candidates than the image has objects in range, the objects left over count as missed
+    (IoU 0, no match): the reference's `assert (gt_ovr >= 0)` fires there;
+  * the area is (x2 - x1 + 1) * (y2 - y1 + 1) unless the caller gives one (the reference reads the roidb's `seg_areas`);
+  * crowd annotations are the caller's to leave out (:166-170 drops them through the roidb's overlaps).
+`proposal_recall_numpy` restates the matrix procedure in numpy float64 (host): the tests' yardstick, itself checked
+against hand-worked cases and an independent sorted sweep (tests/recall_cases.py).
 """
 import numpy as np
 import torch
@@ -888,3 +906,478 @@ def evaluate_coco_boxes(all_boxes, annotations, iou_thrs=None, rec_thrs=None, ar
         ev.add_packed(np.concatenate(rows, 0), np.concatenate(imgs), np.concatenate(clss), num_images=n_img)
     ev.num_images = max(ev.num_images, n_img)
     return ev.compute(codes=codes)
+
+
+# ==== proposal recall ========================================================================================================
+
+RECALL_AREA_NAMES = ("all", "small", "medium", "large", "96-128", "128-256", "256-512", "512-inf")  # imdb.py:150-160
+RECALL_AREA_RNG = np.asarray([[0 ** 2, 1e5 ** 2], [0 ** 2, 32 ** 2], [32 ** 2, 96 ** 2], [96 ** 2, 1e5 ** 2],
+                              [96 ** 2, 128 ** 2], [128 ** 2, 256 ** 2], [256 ** 2, 512 ** 2], [512 ** 2, 1e5 ** 2]], np.float64)
+RECALL_LIMITS = (10, 100, 300, 1000)
+RECALL_MAX_CANDIDATES = 65536  # rows of one proposal list (the matching kernel's bitmap of used candidates)
+
+
+def _recall_area(area):
+    """None -> the eight named ranges; a 1-d list of names / numbers -> those rows of RECALL_AREA_RNG; a 2-d array ->
+    [A,2] ranges as given. -> (names or None, float64 [A,2])"""
+    if area is None:
+        return RECALL_AREA_NAMES, RECALL_AREA_RNG.copy()
+    if isinstance(area, (str, int, np.integer)):
+        area = [area]
+    if not isinstance(area, np.ndarray) and len(area) and all(isinstance(x, (str, int, np.integer)) for x in area):
+        rows = []
+        for x in area:
+            if isinstance(x, str):
+                if x not in RECALL_AREA_NAMES:
+                    raise ValueError("unknown area range %r: one of %s" % (x, ", ".join(RECALL_AREA_NAMES)))
+                rows.append(RECALL_AREA_NAMES.index(x))
+            else:
+                if not 0 <= int(x) < len(RECALL_AREA_NAMES):
+                    raise ValueError("unknown area range %d: 0..%d" % (int(x), len(RECALL_AREA_NAMES) - 1))
+                rows.append(int(x))
+        return tuple(RECALL_AREA_NAMES[r] for r in rows), RECALL_AREA_RNG[rows].copy()
+    rng = np.ascontiguousarray(np.asarray(area, np.float64))
+    if rng.ndim != 2 or rng.shape[1] != 2:
+        raise ValueError("area ranges: names, numbers or an [A,2] array of (low, high)")
+    return None, rng
+
+
+def _recall_params(iou_thrs, limits, area):
+    """-> (iou_thrs float64 [T], limits int32 [L], area_rng float64 [A,2], area names or None), checked against what the
+    kernels take"""
+    thr = np.ascontiguousarray(np.asarray(COCO_THRESHOLDS if iou_thrs is None else iou_thrs, np.float64).reshape(-1))
+    lim = np.asarray(limits).reshape(-1)
+    names, rng = _recall_area(area)
+    if not (1 <= thr.size <= 16 and 1 <= lim.size <= 8 and 1 <= rng.shape[0] <= 8):
+        raise ValueError("proposal recall: 1..16 IoU thresholds, 1..8 limits, 1..8 area ranges (got %d, %d, %d)"
+                         % (thr.size, lim.size, rng.shape[0]))
+    if (np.abs(lim.astype(np.float64)) >= 2 ** 31).any() or (lim != np.round(lim)).any():
+        raise ValueError("proposal recall: limits are integers (<= 0: the whole list)")
+    return thr, np.ascontiguousarray(lim.astype(np.int32)), rng, names
+
+
+def _recall_tables(prob_img, prob_cls, counts, offsets, gt_img, gt_cls, n_cls, others=False):
+    """The host bookkeeping of proposal recall. Problems (image, class, count, first row) and ground-truth ids ->
+    dict(unit_tab int32 [U,9] = (box_off, box_count, gt0_begin, gt0_end, gt1_begin, gt1_end, pair_off, cls, role),
+    gt_order int32 [g] (the stable (image, class) order), n_pairs, pair_unit / pair_gt int64 [n_pairs]: the unit and the
+    ground-truth row of every pair). Units: the target unit of every problem in arrival order, then (others=True) the
+    other unit of every problem."""
+    K = int(n_cls)
+    p_img = np.asarray(prob_img, np.int64).reshape(-1)
+    p_cls = np.asarray(prob_cls, np.int64).reshape(-1)
+    cnt = np.asarray(counts, np.int64).reshape(-1)
+    P = cnt.size
+    off = np.asarray(offsets, np.int64).reshape(-1)[:P]
+    g_img = np.asarray(gt_img, np.int64).reshape(-1)
+    g_cls = np.asarray(gt_cls, np.int64).reshape(-1)
+    if K < 1 or p_img.size != P or p_cls.size != P or off.size != P or g_img.size != g_cls.size:
+        raise ValueError("proposal recall: %d problems need as many image ids, class ids and offsets; ground truth needs "
+                         "one image id and one class id per box" % P)
+    if P and ((p_img < 0).any() or (p_cls < 0).any() or (p_cls >= K).any() or (cnt < 0).any() or (off < 0).any()):
+        raise ValueError("proposal recall: problem ids outside [0, inf) x [0, %d), or a negative count / offset" % K)
+    if P and int(cnt.max()) > RECALL_MAX_CANDIDATES:
+        raise ValueError("proposal recall: a list of %d rows; at most %d candidates per list" % (int(cnt.max()),
+                                                                                                  RECALL_MAX_CANDIDATES))
+    if g_img.size and ((g_img < 0).any() or (g_cls < 0).any() or (g_cls >= K).any()):
+        raise ValueError("proposal recall: ground-truth ids outside [0, inf) x [0, %d)" % K)
+    gt_order = np.lexsort((g_cls, g_img))  # stable: by image, then class, then arrival
+    key = g_img[gt_order] * K + g_cls[gt_order]
+    b0 = np.searchsorted(key, p_img * K + p_cls, side="left")
+    e0 = np.searchsorted(key, p_img * K + p_cls, side="right")
+    ib = np.searchsorted(key, p_img * K, side="left")
+    ie = np.searchsorted(key, (p_img + 1) * K, side="left")
+    zero = np.zeros(P, np.int64)
+    tab = np.stack((off, cnt, b0, e0, zero, zero, zero, p_cls, zero), 1)
+    if others:
+        tab = np.concatenate((tab, np.stack((off, cnt, ib, b0, e0, ie, zero, p_cls, zero + 1), 1)), 0)
+    n_obj = (tab[:, 3] - tab[:, 2]) + (tab[:, 5] - tab[:, 4])
+    tab[:, 6] = np.cumsum(n_obj) - n_obj
+    n_pairs = int(n_obj.sum())
+    if n_pairs >= 2 ** 31 - 1 or tab.shape[0] >= 2 ** 31 - 1 or (P and int((off + cnt).max()) >= 2 ** 31 - 1):
+        raise ValueError("proposal recall: %d pairs / %d units overflow the int32 tables" % (n_pairs, tab.shape[0]))
+    pair_unit = np.repeat(np.arange(tab.shape[0], dtype=np.int64), n_obj)
+    within = np.arange(n_pairs, dtype=np.int64) - tab[pair_unit, 6]
+    n0 = (tab[:, 3] - tab[:, 2])[pair_unit]
+    pos = np.where(within < n0, tab[pair_unit, 2] + within, tab[pair_unit, 4] + within - n0)
+    return dict(unit_tab=np.ascontiguousarray(tab.astype(np.int32)), gt_order=gt_order.astype(np.int32), n_pairs=n_pairs,
+                pair_unit=pair_unit, pair_gt=gt_order[pos].astype(np.int64))
+
+
+def _recall_ratios(hits, npos):
+    """counts -> (recalls [2,T,L,A], ar [2,L,A]) in numpy float64: the classes are summed before the one division
+    (imdb.py:221), ar is the mean over the thresholds (:223); NaN where there are no objects"""
+    with np.errstate(divide="ignore", invalid="ignore"):
+        recalls = hits.sum(-1).astype(np.float64) / npos.sum(-1).astype(np.float64)[:, None, None, :]
+    return recalls, recalls.mean(1)
+
+
+def proposal_recall_numpy(boxes, prob_img, prob_cls, counts, offsets, gt_box, gt_img, gt_cls, n_cls, iou_thrs=None,
+                          limits=(0,), area_rng=None, gt_area=None, others=False):
+    """Proposal recall in numpy float64 (host), the tests' yardstick: imdb.py:137-225 per (unit, limit, area range), as
+    the matrix procedure -- the IoU matrix of candidates x objects; the column maxima; the best-covered object and the
+    candidate that covers it best (two argmax calls: the lowest object, then the lowest row among equals); record; take
+    the row and the column out. Taken entries are set to -inf, so that they lose against every IoU. boxes [n,4] with
+    problem p at rows offsets[p] : offsets[p] + counts[p]; area_rng as `_recall_area` takes it (None: the eight named
+    ranges). -> dict(unit_tab, gt_order, n_pairs, pair_unit, pair_gt, ov float64 [L,A,n_pairs], match int64
+    [L,A,n_pairs], hits int64 [2,T,L,A,K], npos int64 [2,A,K], recalls [2,T,L,A], ar [2,L,A])."""
+    thr, lim, rng, _ = _recall_params(iou_thrs, limits, area_rng)
+    K = int(n_cls)
+    T, L, A = thr.size, lim.size, rng.shape[0]
+    out = _recall_tables(prob_img, prob_cls, counts, offsets, gt_img, gt_cls, K, others)
+    tab, n_pairs, pair_gt = out["unit_tab"].astype(np.int64), out["n_pairs"], out["pair_gt"]
+    b64 = np.asarray(boxes, np.float32).reshape(-1, 4).astype(np.float64)
+    g64 = np.asarray(gt_box, np.float32).reshape(-1, 4).astype(np.float64)
+    if gt_area is None:
+        area = (g64[:, 2] - g64[:, 0] + 1.) * (g64[:, 3] - g64[:, 1] + 1.)
+    else:
+        area = np.asarray(gt_area, np.float64).reshape(-1)
+    if area.size != g64.shape[0] or g64.shape[0] != np.asarray(gt_img).size:
+        raise ValueError("proposal recall: %d ground-truth boxes need as many ids and areas" % g64.shape[0])
+    ov = np.full((L, A, n_pairs), -1.)
+    match = np.full((L, A, n_pairs), -1, np.int64)
+    for u in range(tab.shape[0]):
+        off, cnt, p0 = tab[u, 0], tab[u, 1], tab[u, 6]
+        rows = pair_gt[p0:p0 + (tab[u, 3] - tab[u, 2]) + (tab[u, 5] - tab[u, 4])]
+        if rows.size == 0:
+            continue
+        for li in range(L):
+            m = int(cnt if lim[li] <= 0 else min(lim[li], cnt))
+            full = _iou_matrix(b64[off:off + m], g64[rows]) if m else np.zeros((0, rows.size))
+            for a in range(A):
+                inside = np.nonzero((rng[a, 0] <= area[rows]) & (area[rows] <= rng[a, 1]))[0]
+                mat = full[:, inside].copy()
+                o = np.zeros(inside.size)
+                r = np.full(inside.size, -1, np.int64)
+                for _ in range(min(m, inside.size)):
+                    col_arg = mat.argmax(axis=0)
+                    col_max = mat.max(axis=0)
+                    j = int(col_max.argmax())
+                    i = int(col_arg[j])
+                    o[j], r[j] = mat[i, j], i
+                    mat[i, :] = -np.inf
+                    mat[:, j] = -np.inf
+                ov[li, a, p0 + inside] = o
+                match[li, a, p0 + inside] = r
+    role, k = tab[out["pair_unit"], 8], tab[out["pair_unit"], 7]
+    hits = np.zeros((2, T, L, A, K), np.int64)
+    npos = np.zeros((2, A, K), np.int64)
+    for a in range(A):
+        part = ov[0, a] != -1.
+        np.add.at(npos[:, a, :], (role[part], k[part]), 1)
+        for li in range(L):
+            for t in range(T):
+                hit = part & (ov[li, a] >= thr[t])
+                np.add.at(hits[:, t, li, a, :], (role[hit], k[hit]), 1)
+    recalls, ar = _recall_ratios(hits, npos)
+    out.update(ov=ov, match=match, hits=hits, npos=npos, recalls=recalls, ar=ar)
+    return out
+
+
+def eval_proposal_recall(boxes, unit_tab, gt_box, gt_area, gt_order, n_pairs, n_cls, iou_thr, limits, area_rng):
+    """One `dana_eval_proposal_recall` call on device tensors: boxes [n,4] float32, unit_tab int32 [U,9], gt_box [g,4]
+    float32, gt_area float64 [g] or None, gt_order int32 [g], iou_thr float64 [T], limits int32 [L], area_rng float64
+    [A,2]; n_pairs is the host's count. -> (ov float64 [L,A,n_pairs], match int32 [L,A,n_pairs], hits int64
+    [2,T,L,A,K], npos int64 [2,A,K]). No synchronisation, no device-to-host copy."""
+    boxes = ops._chk(boxes, "boxes")
+    dev = boxes.device
+    ops._chk(unit_tab, "unit_tab", torch.int32), ops._chk(gt_box, "gt_box"), ops._chk(gt_order, "gt_order", torch.int32)
+    ops._chk(iou_thr, "iou_thr", torch.float64), ops._chk(limits, "limits", torch.int32)
+    ops._chk(area_rng, "area_rng", torch.float64)
+    if gt_area is not None:
+        ops._chk(gt_area, "gt_area", torch.float64)
+    U, g = unit_tab.numel() // 9, gt_box.numel() // 4
+    T, L, A, K = iou_thr.numel(), limits.numel(), area_rng.numel() // 2, int(n_cls)
+    n_pairs = int(n_pairs)
+    if unit_tab.numel() != 9 * U or gt_order.numel() != g or (gt_area is not None and gt_area.numel() != g):
+        raise ValueError("eval_proposal_recall: unit_tab is [U,9]; gt_order and gt_area match the %d ground-truth boxes" % g)
+    ov = torch.empty((L, A, n_pairs), dtype=torch.float64, device=dev)
+    match = torch.empty((L, A, n_pairs), dtype=torch.int32, device=dev)
+    hits = torch.empty((2, T, L, A, K), dtype=torch.int64, device=dev)
+    npos = torch.empty((2, A, K), dtype=torch.int64, device=dev)
+    ws = ops._ws(lib().query("dana_eval_proposal_recall_workspace_bytes", boxes.size(0), U, n_pairs, T, L, A), dev)
+    lib().call("dana_eval_proposal_recall", ops._p(boxes), ops._p(unit_tab), U, ops._p(gt_box), ops._p(gt_area),
+               ops._p(gt_order), g, n_pairs, K, ops._p(iou_thr), T, ops._p(limits), L, ops._p(area_rng), A, ops._p(ov),
+               ops._p(match), ops._p(hits), ops._p(npos), ops._p(ws), ws.numel(), ops._stream())
+    return ov, match, hits, npos
+
+
+class ProposalRecallResult:
+    """Device tensors of one proposal-recall `compute()`. Role 0 is the target units (the objects of the class the list
+    was proposed for), role 1 the other units (the image's other objects under the same list).
+      hits int64 [2,T,L,A,K], npos int64 [2,A,K]: the raw counts (K: the class the proposals were made for);
+      recalls [2,T,L,A]: the classes summed before the division; ar [2,L,A]: its mean over the thresholds (imdb.py:223);
+      per_class_recalls [2,T,L,A,K], per_class_ar [2,L,A,K]; all float64, NaN where npos == 0.
+    From `compute()` also ov float64 / match int32 [L,A,n_pairs] and the host pair tables: pair_gt[n_pairs] is the
+    ground-truth row (in the order it was added) and pair_unit[n_pairs] the row of unit_tab of every pair.
+    `params` = (iou_thrs, limits, area_rng, area names or None) as host arrays."""
+
+    def __init__(self, hits, npos, params, ov=None, match=None, tables=None):
+        self.hits, self.npos, self.params = hits, npos, params
+        self.iou_thrs, self.limits, self.area_rng, self.area_names = params
+        self.ov, self.match = ov, match
+        tables = tables or {}
+        self.unit_tab, self.pair_unit, self.pair_gt = (tables.get(k) for k in ("unit_tab", "pair_unit", "pair_gt"))
+        h, n = hits.to(torch.float64), npos.to(torch.float64)
+        self.recalls = h.sum(-1) / n.sum(-1)[:, None, None, :]
+        self.ar = self.recalls.mean(1)
+        self.per_class_recalls = h / n[:, None, None, :, :]
+        self.per_class_ar = self.per_class_recalls.mean(1)
+
+    @classmethod
+    def from_counts(cls, hits, npos, params):
+        """the result of pooled counts: a caller that all-reduces (sums) `hits` and `npos` across ranks gets the pooled
+        recalls from here. `params` as `ProposalRecallEvaluator.params` / a result's `.params`."""
+        T, L, A = len(params[0]), len(params[1]), len(params[2])
+        if hits.dim() != 5 or npos.dim() != 3 or tuple(hits.shape[:4]) != (2, T, L, A) or \
+                tuple(npos.shape) != (2, A, hits.size(4)):
+            raise ValueError("from_counts: hits [2,%d,%d,%d,K] and npos [2,%d,K] expected, got %s and %s"
+                             % (T, L, A, A, tuple(hits.shape), tuple(npos.shape)))
+        return cls(hits, npos, params)
+
+    def _index(self, limit, area):
+        lim = [int(x) for x in self.limits]
+        if int(limit) not in lim:
+            raise ValueError("limit %r is not one of %s" % (limit, lim))
+        if isinstance(area, str):
+            if self.area_names is None or area not in self.area_names:
+                raise ValueError("area range %r is not one of %s" % (area, self.area_names))
+            area = self.area_names.index(area)
+        if not 0 <= int(area) < len(self.area_rng):
+            raise ValueError("area range %r outside 0..%d" % (area, len(self.area_rng) - 1))
+        return lim.index(int(limit)), int(area)
+
+    def gt_overlaps(self, limit, area=0):
+        """-> [n_pairs] float64 view: the matched IoU of every pair under this limit (its value) and area range (its name
+        or its index): -1 outside the range, 0 when the candidates ran out. `pair_gt` / `pair_unit` name the pairs."""
+        if self.ov is None:
+            raise ValueError("gt_overlaps needs a result of compute(), not of from_counts()")
+        li, a = self._index(limit, area)
+        return self.ov[li, a]
+
+    def matched_rows(self, limit, area=0):
+        """-> [n_pairs] int32 view: the row, within its list, of the proposal matched to every pair (-1: none)"""
+        if self.match is None:
+            raise ValueError("matched_rows needs a result of compute(), not of from_counts()")
+        li, a = self._index(limit, area)
+        return self.match[li, a]
+
+    def selectivity(self):
+        """-> [L,A] float64: ar[0] / ar[1], the recall the list gives its own class over the recall it gives the image's
+        other objects. NaN without `others` (no other unit has an object)."""
+        return self.ar[0] / self.ar[1]
+
+
+def _box_rows(x):
+    """rows of an [*,4] array or tensor, read from its shape"""
+    n = int(np.prod(np.shape(x)))
+    if n % 4:
+        raise ValueError("boxes are [*,4] rows (x1, y1, x2, y2); got shape %s" % (tuple(np.shape(x)),))
+    return n // 4
+
+
+class ProposalRecallEvaluator:
+    """Proposal recall living on `device`: py-faster-rcnn's `evaluate_recall` (imdb.py:137-225) per proposal list, fed
+    from the `rois` an eval-mode forward returns. A list is made for one image under one class (a class sweep makes C per
+    image); it is measured on the image's objects of that class (the target unit) and, with others=True, also on the
+    image's other objects (the other unit): ar[0] beside ar[1] is the RPN's selectivity. A list added twice (shot views of
+    one class) is two trials; ground truth of a class for which no list of its image was added does not count. Classes
+    are 0..num_classes-1, images the caller's indices; all ids are host integers, boxes may live on the device, no method
+    reads from the device."""
+
+    def __init__(self, num_classes, device="cuda", iou_thresholds=COCO_THRESHOLDS, limits=RECALL_LIMITS, area_ranges=None,
+                 others=False):
+        self.num_classes = int(num_classes)
+        if self.num_classes < 1:
+            raise ValueError("ProposalRecallEvaluator: num_classes >= 1")
+        self.params = _recall_params(iou_thresholds, limits, area_ranges)
+        self.others = bool(others)
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("ProposalRecallEvaluator lives on a CUDA (HIP) device: this build has no CPU path")
+        self._params_dev = None  # uploaded by the first compute()
+        self.reset()
+
+    def reset(self):
+        self.num_rows = 0
+        self._cap = 0
+        self._box = None
+        self._prob = []  # (image ids, class ids, counts, first rows) per add, host int64
+        self._gt = []    # (boxes [k,4] float32 on the device, area [k] float64 on the device or None, image ids, labels)
+
+    _dev = _DetectionStore._dev
+
+    def _reserve(self, rows):
+        need = self.num_rows + rows
+        if need <= self._cap:
+            return
+        cap = max(need, 2 * self._cap, 1024)
+        box = torch.empty((cap, 4), dtype=torch.float32, device=self.device)
+        if self.num_rows:
+            box[:self.num_rows].copy_(self._box[:self.num_rows])
+        self._box, self._cap = box, cap
+
+    # -- ground truth
+    def _add_gt(self, who, boxes, img, labels, area):
+        k = _box_rows(boxes)  # (every check comes before the first byte moves to the device)
+        if img is None or labels is None:
+            raise ValueError("%s: image indices and labels are host integers (nothing is read back)" % who)
+        if img.size != k or labels.size != k:
+            raise ValueError("%s: %d boxes, %d image ids, %d labels" % (who, k, img.size, labels.size))
+        if k and ((img < 0).any() or (labels < 0).any() or (labels >= self.num_classes).any()):
+            raise ValueError("%s: ids outside [0, inf) x [0, %d)" % (who, self.num_classes))
+        if area is not None:
+            if int(np.prod(np.shape(area))) != k:
+                raise ValueError("%s: %d boxes, %d areas" % (who, k, int(np.prod(np.shape(area)))))
+            area = self._dev(area, torch.float64).reshape(-1)
+        boxes = self._dev(boxes, torch.float32).reshape(-1, 4)
+        self._gt.append((boxes, area, img.astype(np.int64), labels.astype(np.int64)))
+
+    def add_ground_truth(self, image_index, boxes, labels, area=None):
+        """the objects of one image: boxes [k,4] (x1,y1,x2,y2) in original-image pixels, labels [k] host class indices,
+        area [k] (default (x2 - x1 + 1) * (y2 - y1 + 1); a dataset's `seg_areas` go here)"""
+        labels = _host_ints(labels)
+        img = None if labels is None else np.full(labels.size, int(image_index), np.int32)
+        self._add_gt("add_ground_truth", boxes, img, labels, area)
+
+    def add_ground_truth_packed(self, boxes, img_ids, labels, area=None):
+        """the objects of many images at once, with per-row host image ids"""
+        self._add_gt("add_ground_truth_packed", boxes, _host_ints(img_ids), _host_ints(labels), area)
+
+    # -- proposals
+    def add_proposals(self, boxes_packed, counts, offsets, image_indices, class_indices):
+        """The primitive: P proposal lists, list p the rows offsets[p] : offsets[p] + counts[p] of boxes_packed [*,4]
+        (x1,y1,x2,y2 in original-image pixels, best first), made for image image_indices[p] under class class_indices[p]
+        (host integers; an int applies to all). offsets=None: the lists follow each other. The rows are appended to the
+        evaluator's device buffer; nothing is read back."""
+        counts = _host_ints(counts)
+        if counts is None:
+            raise ValueError("add_proposals: counts are host integers")
+        P = counts.size
+        if offsets is None:
+            offsets = np.concatenate(([0], np.cumsum(counts[:-1], dtype=np.int64))) if P else counts
+        offsets = _host_ints(offsets)
+        img, cls = _host_ints(image_indices), _host_ints(class_indices)
+        if offsets is None or img is None or cls is None:
+            raise ValueError("add_proposals: offsets, image and class indices are host integers (nothing is read back)")
+        img = np.repeat(img, P) if img.size == 1 and P != 1 else img
+        cls = np.repeat(cls, P) if cls.size == 1 and P != 1 else cls
+        offsets = offsets[:P].astype(np.int64)
+        if offsets.size != P or img.size != P or cls.size != P or (counts < 0).any() or (offsets < 0).any():
+            raise ValueError("add_proposals: %d lists need as many counts, offsets, image and class indices" % P)
+        if P and ((img < 0).any() or (cls < 0).any() or (cls >= self.num_classes).any()):
+            raise ValueError("add_proposals: ids outside [0, inf) x [0, %d)" % self.num_classes)
+        if P and int(counts.max()) > RECALL_MAX_CANDIDATES:
+            raise ValueError("add_proposals: a list of %d rows; at most %d candidates per list"
+                             % (int(counts.max()), RECALL_MAX_CANDIDATES))
+        cnt = counts.astype(np.int64)
+        if P and int((offsets + cnt).max()) > _box_rows(boxes_packed):
+            raise ValueError("add_proposals: offsets + counts run past the %d packed rows" % _box_rows(boxes_packed))
+        src = self._dev(boxes_packed, torch.float32).reshape(-1, 4)
+        rows = int(cnt.sum())
+        dst = self.num_rows + np.cumsum(cnt) - cnt
+        self._prob.append((img.astype(np.int64), cls.astype(np.int64), cnt, dst))
+        if rows == 0:
+            return
+        self._reserve(rows)
+        a = self.num_rows
+        live = cnt > 0
+        first = offsets[live]
+        if (first[1:] == first[:-1] + cnt[live][:-1]).all():  # one run of rows
+            self._box[a:a + rows].copy_(src[int(first[0]):int(first[0]) + rows])
+        else:
+            within = np.arange(rows, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)
+            idx = ops._h2d_int32((np.repeat(offsets, cnt) + within).astype(np.int32), self.device)
+            self._box[a:a + rows].copy_(src.index_select(0, idx))
+        self.num_rows += rows
+
+    def add_rois(self, rois, im_info, image_indices, class_indices, counts=None):
+        """The `rois` [P,R,5] of an eval-mode forward (column 0 the problem, columns 1..4 the box in network-input pixels)
+        with the forward's im_info [B,3]: the boxes are divided by the image's scale im_info[.., 2] -- one fp32 division,
+        as inference.py:125 does for the detections. P == B: image_indices [B], class_indices [B] or an int. A class sweep
+        (P == B * C, problem p = b * C + c uses im_info[b]): `add_rois(rois, im_info, image_indices, sweep.classes)` with
+        the B image indices and the C classes. counts=None: all R rows count -- the proposal layer pads a short list with
+        zero rows, which then stand as one-pixel boxes at the origin (they are last in the list and overlap next to
+        nothing, but they do fill a budget); a caller that knows the real lengths passes them as `counts` [P]."""
+        if not isinstance(rois, torch.Tensor) or rois.dim() != 3 or rois.size(2) != 5:
+            raise ValueError("add_rois: rois are the [P,R,5] tensor of an eval-mode forward")
+        P, R = int(rois.size(0)), int(rois.size(1))
+        img, cls = _host_ints(image_indices), _host_ints(class_indices)
+        if img is None or cls is None:
+            raise ValueError("add_rois: image and class indices are host integers (nothing is read back)")
+        if not isinstance(im_info, torch.Tensor):
+            im_info = torch.from_numpy(np.ascontiguousarray(np.asarray(im_info, np.float32)))
+        im_info = im_info.reshape(-1, 3)
+        B = int(im_info.size(0))
+        if B < 1 or P % B:
+            raise ValueError("add_rois: %d problems over %d rows of im_info" % (P, B))
+        C = P // B
+        if img.size == P and cls.size == P:
+            p_img, p_cls = img, cls
+        elif img.size == B and cls.size == C:
+            p_img, p_cls = np.repeat(img, C), np.tile(cls, B)
+        elif img.size == B and cls.size == 1:
+            p_img, p_cls = np.repeat(img, C), np.repeat(cls, P)
+        else:
+            raise ValueError("add_rois: %d problems = %d images x %d classes; got %d image and %d class indices"
+                             % (P, B, C, img.size, cls.size))
+        scale = im_info[:, 2].to(device=self.device, dtype=torch.float32).repeat_interleave(C)
+        boxes = (rois.to(self.device)[:, :, 1:5] / scale.view(P, 1, 1)).reshape(-1, 4)
+        if counts is None:
+            cnt = np.full(P, R, np.int32)
+        else:
+            cnt = _host_ints(counts)
+            if cnt is None or cnt.size != P or (cnt < 0).any() or (cnt > R).any():
+                raise ValueError("add_rois: counts are %d host integers in 0..%d" % (P, R))
+        self.add_proposals(boxes, cnt, np.arange(P, dtype=np.int64) * R, p_img, p_cls)
+
+    def proposals(self):
+        """-> (boxes [n,4] device view of the rows added so far, image ids, class ids, counts, first rows: host int64 [P])"""
+        box = self._box[:self.num_rows] if self.num_rows else torch.empty((0, 4), dtype=torch.float32, device=self.device)
+        return (box,) + self._problems()
+
+    # -- the host tables and the call
+    def _problems(self):
+        if not self._prob:
+            e = np.zeros(0, np.int64)
+            return e, e, e, e
+        return tuple(np.concatenate([p[i] for p in self._prob]) for i in range(4))
+
+    def _ground_truth(self):
+        """-> (boxes [g,4] device, area [g] float64 device or None, image ids, labels): area is None when no add gave one"""
+        if not self._gt:
+            e = np.zeros(0, np.int64)
+            return torch.empty((0, 4), dtype=torch.float32, device=self.device), None, e, e
+        box = torch.cat([g[0] for g in self._gt], 0).contiguous()
+        area = None
+        if any(g[1] is not None for g in self._gt):
+            parts = []
+            for b, ar, _, _ in self._gt:
+                if ar is None:
+                    b64 = b.to(torch.float64)
+                    ar = (b64[:, 2] - b64[:, 0] + 1.) * (b64[:, 3] - b64[:, 1] + 1.)
+                parts.append(ar)
+            area = torch.cat(parts, 0).contiguous()
+        return box, area, np.concatenate([g[2] for g in self._gt]), np.concatenate([g[3] for g in self._gt])
+
+    def tables(self):
+        """the host bookkeeping `compute()` uploads (see `_recall_tables`)"""
+        p_img, p_cls, cnt, off = self._problems()
+        _, _, g_img, g_cls = self._ground_truth()
+        return _recall_tables(p_img, p_cls, cnt, off, g_img, g_cls, self.num_classes, self.others)
+
+    def compute(self):
+        """-> ProposalRecallResult (device tensors; one upload of the unit table and the ground-truth order, one C call,
+        nothing synchronised or read back)"""
+        gbox, garea, g_img, g_cls = self._ground_truth()
+        p_img, p_cls, cnt, off = self._problems()
+        tb = _recall_tables(p_img, p_cls, cnt, off, g_img, g_cls, self.num_classes, self.others)
+        U, g = tb["unit_tab"].shape[0], tb["gt_order"].size
+        small = ops._h2d_int32(np.concatenate((tb["unit_tab"].reshape(-1), tb["gt_order"], np.zeros(1, np.int32))),
+                               self.device)
+        boxes = self.proposals()[0]
+        if self._params_dev is None:
+            self._params_dev = tuple(torch.from_numpy(p).to(self.device) for p in self.params[:3])
+        thr, lim, rng = self._params_dev
+        ov, match, hits, npos = eval_proposal_recall(boxes, small[:9 * U].view(U, 9), gbox, garea, small[9 * U:9 * U + g],
+                                                     tb["n_pairs"], self.num_classes, thr, lim, rng)
+        return ProposalRecallResult(hits, npos, self.params, ov, match, tb)

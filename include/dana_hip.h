@@ -1007,6 +1007,45 @@ int dana_eval_coco(const float* det, const int* det_img, const int* det_cls, lon
                    int* segpos, void* codes, int* npig, void* precision, void* recall, void* scores, void* workspace,
                    size_t workspace_bytes, dana_stream_t stream);
 
+/* ---- proposal recall: lib/datasets/imdb.py:137-225 (`evaluate_recall`, which the reference carries commented out) ---------
+ * Proposals and ground truth matched one to one, greedily; the matched IoUs held against n_thr thresholds; counted per
+ * proposal budget (`limits`) and object-size range (`area_rng`). Float64, unfused.
+ *
+ * Units (built by the host, dana_amd/evaluate.py): a problem is one proposal list -- box_count rows (x1, y1, x2, y2) of
+ * `boxes` from row box_off on, best first -- made for image i under class c. Its TARGET unit (role 0) holds the ground truth
+ * of image i with class c, its OTHER unit (role 1) the ground truth of image i with any other class. gt_order[g] is the
+ * ground truth sorted stably by (image, class), so a unit's objects are at most two position ranges of gt_order. A pair is
+ * one (unit, object); pairs are numbered unit by unit in position order from the unit's pair_off.
+ *   unit_tab[n_units][9] = (box_off, box_count, gt0_begin, gt0_end, gt1_begin, gt1_end, pair_off, cls, role), device memory.
+ *
+ * Matching, for every unit, limit l and area range a: the candidates are the unit's first m rows (m = box_count when
+ * limits[l] <= 0, else min(limits[l], box_count); at most 65 536 are considered), the objects its boxes with
+ * area_rng[a][0] <= area <= area_rng[a][1] (both ends inclusive, :173-174), area = gt_area[g] when given, else
+ * (x2 - x1 + 1) * (y2 - y1 + 1). Until no object is left: among the remaining (candidate, object) entries the largest IoU
+ * (the `+ 1.` convention) -- among equal IoUs the lowest object position, then the lowest candidate row, as :196-204's two
+ * argmax calls give -- is recorded, ov[pair] = IoU and match[pair] = candidate row, and both leave. An IoU of 0 is still
+ * a match. When the candidates run out the remaining objects get ov = 0, match = -1 (the reference's assert fires there).
+ * An object outside the area range gets ov = -1, match = -1 and takes no part. The kernel stays inside its buffers
+ * whatever the coordinates are; results are defined for finite coordinates.
+ *   ov [n_limits][n_area][n_pairs] (C `double`), match [n_limits][n_area][n_pairs].
+ *
+ * Counts (:220-221 before the division): npos[role][a][k] = pairs of class k with ov != -1; hits[role][t][l][a][k] = those
+ * with ov >= iou_thr[t]. k is the unit's cls: for role 1 the class the proposals were made for.
+ *   hits [2][n_thr][n_limits][n_area][n_cls], npos [2][n_area][n_cls], both C `long long`, zeroed by the call.
+ *
+ * n_thr 1..16, n_limits 1..8, n_area 1..8 (the reference names eight ranges); iou_thr, limits and area_rng[n_area][2] in
+ * device memory; boxes and gt_box 16-byte aligned (read as float4). The objects of a unit are bounded by the workspace
+ * only. Doubles and long longs are passed as void*. n_units == 0 or n_pairs == 0 zeroes the counts and returns. Integer
+ * counts, fixed positions: two calls give the same bytes. No synchronisation, no device-to-host copy.
+ * dana_eval_proposal_recall_workspace_bytes is 0 for a shape the call refuses. */
+size_t dana_eval_proposal_recall_workspace_bytes(long n_boxes, long n_units, long n_pairs, int n_thr, int n_limits,
+                                                 int n_area);
+int dana_eval_proposal_recall(const float* boxes, const int* unit_tab, long n_units, const float* gt_box,
+                              const void* gt_area /* double[g] or null */, const int* gt_order, long g, long n_pairs,
+                              int n_cls, const void* iou_thr, int n_thr, const int* limits, int n_limits,
+                              const void* area_rng, int n_area, void* ov, int* match, void* hits, void* npos,
+                              void* workspace, size_t workspace_bytes, dana_stream_t stream);
+
 /* ---- attention maps: README.md "Attention Visualization" (images/attention_visualization.jpg) ------------------------------
  * The reference shows where a query region looks in a support image; the weights are the tensors its forward builds and
  * drops: support_adaptive_attention_weight at the RPN level (lib/model/framework/dana.py:142-146) and at the RoI level
