@@ -1046,6 +1046,59 @@ int dana_eval_proposal_recall(const float* boxes, const int* unit_tab, long n_un
                               const void* area_rng, int n_area, void* ov, int* match, void* hits, void* npos,
                               void* workspace, size_t workspace_bytes, dana_stream_t stream);
 
+/* ---- error diagnosis: TIDE (Bolya et al., "TIDE: A General Toolbox for Identifying Object Detection Errors", ECCV 2020) ------
+ * Why the AP is not higher: every false positive and every undetected object of dana_eval_ap's marking gets one of six
+ * error types, and each type gets the AP that repairing it alone would give. Restated from the paper (the reference tree
+ * has nothing of the kind); the choices the paper leaves open are the ones written here. Inputs as for dana_eval_ap.
+ * thresholds: two C `double` in device memory, (t_f, t_b), the foreground and background IoU thresholds with
+ * 0 <= t_b < t_f (the caller's to keep: the values are not read on the host). IoU is voc_eval's: float64, `+ 1.`, unfused.
+ *
+ * Step 1 is dana_eval_ap at the one threshold t_f -- the call is made inside -- so order[n], cls_offsets[n_cls + 1],
+ * tpfp[n] (1 = TP, 2 = FP, 0 = matched a difficult box), npos[n_cls] and ap[n_cls] are the evaluator's, bit for bit.
+ *
+ * Step 2, a type for every FP. Only the COUNTED objects of the detection's image are looked at: ids in range and not
+ * difficult (a difficult object is never a ref). For a detection of class c, (ov_same, j_same) are the largest IoU and the
+ * lowest object index among equal maxima over the counted objects of class c, (ov_other, j_other) the same over the counted
+ * objects of every other class; a side without objects has IoU -inf and no index. The first rule that holds decides:
+ *   Dupe: ov_same > t_f (strictly, as voc_eval has it: step 1 gave the object to a higher-ranked detection), ref = j_same
+ *   Loc:  t_b <= ov_same <= t_f, ref = j_same (Loc is asked before Cls)
+ *   Cls:  ov_other > t_f, ref = j_other
+ *   Both: t_b <= ov_other <= t_f, ref = j_other
+ *   Bkg:  otherwise, ref = -1
+ *   det_type[n] bytes by rank: 0 = no part (tpfp 0, or ids out of range), 1 = TP (ref = its object), 2 = Cls, 3 = Loc,
+ *     4 = Both, 5 = Dupe, 6 = Bkg; det_ref[n] by rank: the caller's ground-truth row, or -1;
+ *   gt_state[g] bytes by the caller's row: 0 = not counted, 1 = detected in step 1, 2 = undetected but a Loc or Cls
+ *     detection refers to it (covered), 3 = Miss;
+ *   counts[n_cls][7] (C `long long`): TP, Cls, Loc, Both, Dupe, Bkg per detection class, Miss per object class;
+ *   confusion[n_cls + 1][n_cls + 1] (C `long long`), [object class][detection class]: a TP at [c][c], a Cls at [class of
+ *     its ref][c], Loc / Both / Dupe / Bkg at [n_cls][c], an object in state 2 or 3 at [c][n_cls].
+ *
+ * Step 3, ap_fixed[8][n_cls] (C `double`): the AP with one error type repaired, in the order Cls, Loc, Both, Dupe, Bkg,
+ * Miss, FP, FN; each oracle alone on step 1's marking, then the evaluator's curve rule (the same metric; NaN where the
+ * oracle's npos is 0). Under the area metric the terms are those of dana_eval_ap, added in double-double and rounded
+ * once: a repaired AP is the correctly rounded sum of its terms and does not depend on the order they are added in
+ * (`ap` keeps the evaluator's bits, so an oracle that changes nothing can differ from it in the last bit).
+ *   Both, Dupe, Bkg: the detections of that type are removed. FP: every tpfp 2 is removed.
+ *   Loc: a Loc detection becomes a TP when its ref is undetected (state 2) and it is the highest-ranked Loc detection with
+ *     that ref; every other Loc detection is removed.
+ *   Cls: a Cls detection becomes a TP of its ref's class, with its own score, when its ref is undetected and it wins the
+ *     ref: the highest score among all Cls detections with that ref whatever their class, equal scores to the lower
+ *     detection row; every other Cls detection is removed. The rows are ranked again by (class, score descending,
+ *     arrival); npos is unchanged.
+ *   Miss: npos[c] loses the class's state-3 objects. FN: npos[c] becomes the class's TP count.
+ * Every finite ap_fixed[o][c] >= ap[c].
+ *
+ * Bytes, doubles and long longs are passed as void*. The claims on an object are 64-bit integer atomic minima, the counts
+ * integer atomic adds, the float64 sums run in a fixed order: two calls give the same bits. No synchronisation, no
+ * device-to-host copy. (n_cls + 1)^2 * 7 < 2^31. dana_diagnose_errors_workspace_bytes is 0 for a shape the call refuses. */
+size_t dana_diagnose_errors_workspace_bytes(long n, long g, int n_img, int n_cls);
+int dana_diagnose_errors(const float* det, const int* det_img, const int* det_cls, long n, const float* gt_box,
+                         const int* gt_img, const int* gt_cls, const unsigned char* gt_difficult, long g, int n_img,
+                         int n_cls, const void* thresholds, int use_07_metric, int* order, int* cls_offsets, void* tpfp,
+                         int* npos, void* ap, void* det_type, int* det_ref, void* gt_state, void* counts,
+                         void* confusion, void* ap_fixed, void* workspace, size_t workspace_bytes,
+                         dana_stream_t stream);
+
 /* ---- attention maps: README.md "Attention Visualization" (images/attention_visualization.jpg) ------------------------------
  * The reference shows where a query region looks in a support image; the weights are the tensors its forward builds and
  * drops: support_adaptive_attention_weight at the RPN level (lib/model/framework/dana.py:142-146) and at the RoI level
