@@ -14,19 +14,27 @@
 // The pool: one byte buffer of packed uint8 RGB frames; offsets[row] (bytes), meta[row] = (h, w, flipped, box_off, box_cnt).
 // The plan: int32 words. Query record (EP_QWORDS, at q_off + b * EP_QWORDS), support record (EP_SWORDS, at
 // s_off + n * EP_SWORDS); doubles sit on even words. The box orders of the queries follow the records.
+//
+// Training-time augmentation (not in the reference tree): the *_aug entry points launch the same three bodies with AUG set.
+// They read a third plan section, one augmentation record (EP_AWORDS) per query and per support: a 3x4 colour map applied
+// to each source tap before the mean is subtracted, and for queries the visibility threshold of the box filter. The plain
+// entry points instantiate the bodies without it (the new kernel arguments come last and are not read): the same
+// arithmetic, the same bits.
 #include "common.h"
 #include "../../include/dana_hip.h"
 
 namespace {
 
-enum { EP_QWORDS = 16, EP_SWORDS = 16, EP_META = 5 };
+enum { EP_QWORDS = 16, EP_SWORDS = 16, EP_AWORDS = 16, EP_META = 5 };
 // query record
 enum { Q_ROW = 0, Q_NORDER = 1, Q_SCALE = 2, Q_INV = 4, Q_YS = 6, Q_XS = 7, Q_COPY_H = 8, Q_COPY_W = 9, Q_CLAMP_X = 10,
        Q_CLAMP_Y = 11, Q_CLS = 12, Q_ORDER_OFF = 13, Q_OH = 14, Q_OW = 15 };
 // support record (words 14, 15 of both: the prepared size oh, ow; the host's limits come from it, no kernel reads it)
 enum { S_ROW = 0, S_INV = 2, S_SX = 4, S_SY = 6, S_X0 = 8, S_Y0 = 9, S_CW = 10, S_CH = 11, S_RW = 12, S_RH = 13,
        S_OH = 14, S_OW = 15 };
-
+// augmentation record: float M[3][4] (rows R, G, B of the distorted pixel, columns r, g, b of the source and the offset),
+// float min_visible, flags
+enum { A_M = 0, A_MIN_VISIBLE = 12, A_FLAGS = 13, A_HAS_COLOR = 1, A_HAS_VISIBLE = 2 };
 
 __device__ __forceinline__ double plan_double(const int* rec, int word) {
   return *reinterpret_cast<const double*>(rec + word);
@@ -50,24 +58,51 @@ __device__ __forceinline__ bool source_of(const unsigned char* pool, const long 
   return true;
 }
 
+// the colour map of one augmentation record; `on` is false where the record asks for none
+struct Colour {
+  bool on;
+  float m[12];
+};
+__device__ __forceinline__ Colour colour_of(const int* arec) {
+  Colour col;
+  col.on = (arec[A_FLAGS] & A_HAS_COLOR) != 0;
+#pragma unroll
+  for (int k = 0; k < 12; ++k) col.m[k] = col.on ? __int_as_float(arec[A_M + k]) : 0.f;
+  return col;
+}
+
+// what the source pixel px (RGB) counts as in input channel ci: the byte itself, or row ci of the colour map at it, clamped
+// to the range of a byte (so the map cannot move behind the resample). float32, in this order, uncontracted.
+template <bool AUG>
+__device__ __forceinline__ float source_value(const unsigned char* px, int ci, const Colour& col) {
+  if (!AUG || !col.on) return (float)px[ci];
+  const float* k = col.m + ci * 4;
+  const float d = ((k[0] * (float)px[0] + k[1] * (float)px[1]) + k[2] * (float)px[2]) + k[3];
+  return fminf(fmaxf(d, 0.f), 255.f);
+}
+
 // prep_image_kernel's value of channel c (BGR) at the prepared pixel whose taps are (tx, ty)
-__device__ __forceinline__ float prep_value(const Source& s, const DanaTap& tx, const DanaTap& ty, int c, float mean) {
+template <bool AUG>
+__device__ __forceinline__ float prep_value(const Source& s, const DanaTap& tx, const DanaTap& ty, int c, float mean,
+                                            const Colour& col) {
   const int x0 = s.flipped ? s.w - 1 - tx.s0 : tx.s0, x1 = s.flipped ? s.w - 1 - tx.s1 : tx.s1;
   const unsigned char* r0 = s.im + (long)ty.s0 * s.w * 3;
   const unsigned char* r1 = s.im + (long)ty.s1 * s.w * 3;
   const int ci = 2 - c;  // output channel c (BGR) reads input channel 2 - c (RGB)
-  const float t00 = (float)r0[x0 * 3 + ci] - mean, t01 = (float)r0[x1 * 3 + ci] - mean;
-  const float t10 = (float)r1[x0 * 3 + ci] - mean, t11 = (float)r1[x1 * 3 + ci] - mean;
+  const float t00 = source_value<AUG>(r0 + x0 * 3, ci, col) - mean, t01 = source_value<AUG>(r0 + x1 * 3, ci, col) - mean;
+  const float t10 = source_value<AUG>(r1 + x0 * 3, ci, col) - mean, t11 = source_value<AUG>(r1 + x1 * 3, ci, col) - mean;
   const float h0 = t00 * tx.a0 + t01 * tx.a1;
   const float h1 = t10 * tx.a0 + t11 * tx.a1;
   return h0 * ty.a0 + h1 * ty.a1;
 }
 
+// plan: the query records; aug (AUG only): the queries' augmentation records
+template <bool AUG>
 __global__ void __launch_bounds__(256)
 episode_queries_kernel(const unsigned char* __restrict__ pool, const long long* __restrict__ offsets,
                        const int* __restrict__ meta, int n_rows, long pool_bytes, const int* __restrict__ plan, int B,
                        float m0, float m1, float m2, float* __restrict__ im_data, int H, int W,
-                       float* __restrict__ im_info) {
+                       float* __restrict__ im_info, const int* __restrict__ aug) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long plane = (long)H * W;
   if (i < B) {  // (H, W, im_scale): EpisodeHolders.put_query's row
@@ -87,18 +122,24 @@ episode_queries_kernel(const unsigned char* __restrict__ pool, const long long* 
     const double inv = plan_double(rec, Q_INV);
     const DanaTap tx = dana_linear_tap(rec[Q_XS] + x, inv, s.w), ty = dana_linear_tap(rec[Q_YS] + y, inv, s.h);
     const float mean[3] = {m0, m1, m2};
+    Colour col;
+    col.on = false;
+    if (AUG) col = colour_of(aug + (long)b * EP_AWORDS);
 #pragma unroll
-    for (int c = 0; c < 3; ++c) v[c] = prep_value(s, tx, ty, c, mean[c]);
+    for (int c = 0; c < 3; ++c) v[c] = prep_value<AUG>(s, tx, ty, c, mean[c], col);
   }
   float* o = im_data + (long)b * 3 * plane + p;
 #pragma unroll
   for (int c = 0; c < 3; ++c) o[(long)c * plane] = v[c];
 }
 
+// plan: the support records; aug (AUG only): the supports' augmentation records
+template <bool AUG>
 __global__ void __launch_bounds__(256)
 episode_supports_kernel(const unsigned char* __restrict__ pool, const long long* __restrict__ offsets,
                         const int* __restrict__ meta, int n_rows, long pool_bytes, const int* __restrict__ plan, int N,
-                        float m0, float m1, float m2, int target, float* __restrict__ out) {
+                        float m0, float m1, float m2, int target, float* __restrict__ out,
+                        const int* __restrict__ aug) {
   const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
   const long plane = (long)target * target;
   if (i >= (long)N * plane) return;
@@ -118,10 +159,13 @@ episode_supports_kernel(const unsigned char* __restrict__ pool, const long long*
     const DanaTap px0 = dana_linear_tap(x0 + tx.s0, inv, s.w), px1 = dana_linear_tap(x0 + tx.s1, inv, s.w);
     const DanaTap py0 = dana_linear_tap(y0 + ty.s0, inv, s.h), py1 = dana_linear_tap(y0 + ty.s1, inv, s.h);
     const float mean[3] = {m0, m1, m2};
+    Colour col;
+    col.on = false;
+    if (AUG) col = colour_of(aug + (long)n * EP_AWORDS);  // at each of the (up to) sixteen source taps below
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
-      const float h0 = prep_value(s, px0, py0, c, mean[c]) * tx.a0 + prep_value(s, px1, py0, c, mean[c]) * tx.a1;
-      const float h1 = prep_value(s, px0, py1, c, mean[c]) * tx.a0 + prep_value(s, px1, py1, c, mean[c]) * tx.a1;
+      const float h0 = prep_value<AUG>(s, px0, py0, c, mean[c], col) * tx.a0 + prep_value<AUG>(s, px1, py0, c, mean[c], col) * tx.a1;
+      const float h1 = prep_value<AUG>(s, px0, py1, c, mean[c], col) * tx.a0 + prep_value<AUG>(s, px1, py1, c, mean[c], col) * tx.a1;
       v[c] = h0 * ty.a0 + h1 * ty.a1;
     }
   }
@@ -130,12 +174,14 @@ episode_supports_kernel(const unsigned char* __restrict__ pool, const long long*
   for (int c = 0; c < 3; ++c) o[(long)c * plane] = v[c];
 }
 
-// one wavefront per image: 64 boxes of the plan's order per pass, kept boxes compacted in order with a ballot
+// one wavefront per image: 64 boxes of the plan's order per pass, kept boxes compacted in order with a ballot.
+// AUG: a record with A_HAS_VISIBLE also drops a box of which the shift and the clamp leave less than min_visible of its area
+template <bool AUG>
 __global__ void __launch_bounds__(64)
 episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const int* __restrict__ meta, int n_rows,
                      const int* __restrict__ plan, int plan_words, int q_off, int max_num_box,
                      float* __restrict__ gt_boxes, long long* __restrict__ num_boxes, float* __restrict__ all_boxes,
-                     long long* __restrict__ all_num_boxes) {
+                     long long* __restrict__ all_num_boxes, int a_off) {
   const int b = blockIdx.x, lane = threadIdx.x;
   const int* rec = plan + q_off + (long)b * EP_QWORDS;
   const int row = rec[Q_ROW];
@@ -152,6 +198,13 @@ episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const 
   const float xs = (float)rec[Q_XS], ys = (float)rec[Q_YS];
   const int clamp_x = rec[Q_CLAMP_X], clamp_y = rec[Q_CLAMP_Y];
   const float cls = (float)rec[Q_CLS];
+  bool visible_rule = false;
+  float min_visible = 0.f;
+  if (AUG) {
+    const int* arec = plan + a_off + (long)b * EP_AWORDS;
+    visible_rule = (arec[A_FLAGS] & A_HAS_VISIBLE) != 0;
+    min_visible = __int_as_float(arec[A_MIN_VISIBLE]);
+  }
   float* fs_out = gt_boxes + (long)b * max_num_box * 5;
   float* all_out = all_boxes + (long)b * max_num_box * 5;
   const unsigned long long below = (1ull << lane) - 1ull;
@@ -161,6 +214,7 @@ episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const 
     const int idx = k < n_order ? plan[order_off + k] : -1;
     bool keep = false, pos = false;
     float v[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float u[4] = {0.f, 0.f, 0.f, 0.f};  // the shifted row before the clamp
     if (idx >= 0 && idx < box_cnt) {
       const float* src = boxes + (box_off + idx) * 5;
 #pragma unroll
@@ -168,12 +222,17 @@ episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const 
         // minibatch.py:53: the product in double, rounded into the float32 array
         float t = (float)((double)src[j] * scale);
         t = t - ((j & 1) ? ys : xs);  // fs_loader.py:215-216, 251-252
+        u[j] = t;
         const int lim = (j & 1) ? clamp_y : clamp_x;
         if (lim >= 0) t = fminf(fmaxf(t, 0.f), (float)lim);  // :219-220, :254-255, :281
         v[j] = t;
       }
       v[4] = src[4];
       keep = !(v[0] == v[2] || v[1] == v[3]);  // :294, :306
+      if (AUG && visible_rule) {
+        const float full = (u[2] - u[0]) * (u[3] - u[1]), seen = (v[2] - v[0]) * (v[3] - v[1]);
+        keep = keep && seen >= min_visible * full;
+      }
       pos = keep && v[4] == cls;               // :288
     }
     const unsigned long long m_all = __ballot(keep), m_fs = __ballot(pos);
@@ -200,6 +259,11 @@ episode_boxes_kernel(const float* __restrict__ boxes, long n_boxes_total, const 
   }
 }
 
+// `count` augmentation records at a_off: on an even word like the other sections, and inside the plan
+bool aug_fits(int a_off, long count, int plan_words) {
+  return a_off >= 0 && a_off % 2 == 0 && (long)a_off + count * EP_AWORDS <= plan_words;
+}
+
 }  // namespace
 
 extern "C" {
@@ -215,10 +279,31 @@ int dana_episode_queries(const unsigned char* pool, long pool_bytes, const long 
                  "dana_episode_queries: null pointer");
   const long blocks = ((long)batch * height * width + 255) / 256;
   DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_queries: too many pixels for one launch");
-  episode_queries_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+  episode_queries_kernel<false><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
       pool, offsets, meta, n_rows, pool_bytes, plan + q_off, batch, pixel_means_bgr[0], pixel_means_bgr[1],
-      pixel_means_bgr[2], im_data, height, width, im_info);
+      pixel_means_bgr[2], im_data, height, width, im_info, nullptr);
   DANA_CHECK_LAUNCH("dana_episode_queries");
+  return DANA_OK;
+}
+
+int dana_episode_queries_aug(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                             int n_rows, const int* plan, int plan_words, int q_off, int a_off, int batch,
+                             const float* pixel_means_bgr, float* im_data, int height, int width, float* im_info,
+                             dana_stream_t stream) {
+  DANA_CHECK_ARG(batch > 0 && height > 0 && width > 0 && n_rows > 0 && pool_bytes > 0,
+                 "dana_episode_queries_aug: bad shape");
+  DANA_CHECK_ARG(q_off >= 0 && q_off % 2 == 0 && (long)q_off + (long)batch * EP_QWORDS <= plan_words,
+                 "dana_episode_queries_aug: the query records do not fit the plan");
+  DANA_CHECK_ARG(aug_fits(a_off, batch, plan_words),
+                 "dana_episode_queries_aug: the augmentation records do not fit the plan");
+  DANA_CHECK_ARG(pool && offsets && meta && plan && pixel_means_bgr && im_data && im_info,
+                 "dana_episode_queries_aug: null pointer");
+  const long blocks = ((long)batch * height * width + 255) / 256;
+  DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_queries_aug: too many pixels for one launch");
+  episode_queries_kernel<true><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+      pool, offsets, meta, n_rows, pool_bytes, plan + q_off, batch, pixel_means_bgr[0], pixel_means_bgr[1],
+      pixel_means_bgr[2], im_data, height, width, im_info, plan + a_off);
+  DANA_CHECK_LAUNCH("dana_episode_queries_aug");
   return DANA_OK;
 }
 
@@ -231,10 +316,29 @@ int dana_episode_supports(const unsigned char* pool, long pool_bytes, const long
   DANA_CHECK_ARG(pool && offsets && meta && plan && pixel_means_bgr && out_chw, "dana_episode_supports: null pointer");
   const long blocks = ((long)n_supports * target * target + 255) / 256;
   DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_supports: too many pixels for one launch");
-  episode_supports_kernel<<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+  episode_supports_kernel<false><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
       pool, offsets, meta, n_rows, pool_bytes, plan + s_off, n_supports, pixel_means_bgr[0], pixel_means_bgr[1],
-      pixel_means_bgr[2], target, out_chw);
+      pixel_means_bgr[2], target, out_chw, nullptr);
   DANA_CHECK_LAUNCH("dana_episode_supports");
+  return DANA_OK;
+}
+
+int dana_episode_supports_aug(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                              int n_rows, const int* plan, int plan_words, int s_off, int a_off, int n_supports,
+                              const float* pixel_means_bgr, int target, float* out_chw, dana_stream_t stream) {
+  DANA_CHECK_ARG(n_supports > 0 && target > 0 && n_rows > 0 && pool_bytes > 0, "dana_episode_supports_aug: bad shape");
+  DANA_CHECK_ARG(s_off >= 0 && s_off % 2 == 0 && (long)s_off + (long)n_supports * EP_SWORDS <= plan_words,
+                 "dana_episode_supports_aug: the support records do not fit the plan");
+  DANA_CHECK_ARG(aug_fits(a_off, n_supports, plan_words),
+                 "dana_episode_supports_aug: the augmentation records do not fit the plan");
+  DANA_CHECK_ARG(pool && offsets && meta && plan && pixel_means_bgr && out_chw,
+                 "dana_episode_supports_aug: null pointer");
+  const long blocks = ((long)n_supports * target * target + 255) / 256;
+  DANA_CHECK_ARG(blocks <= 0x7fffffffL, "dana_episode_supports_aug: too many pixels for one launch");
+  episode_supports_kernel<true><<<(int)blocks, 256, 0, (hipStream_t)stream>>>(
+      pool, offsets, meta, n_rows, pool_bytes, plan + s_off, n_supports, pixel_means_bgr[0], pixel_means_bgr[1],
+      pixel_means_bgr[2], target, out_chw, plan + a_off);
+  DANA_CHECK_LAUNCH("dana_episode_supports_aug");
   return DANA_OK;
 }
 
@@ -247,10 +351,29 @@ int dana_episode_boxes(const float* boxes, long n_boxes_total, const int* meta, 
   DANA_CHECK_ARG(meta && plan && gt_boxes && num_boxes && all_cls_gt_boxes && all_cls_num_boxes &&
                      (boxes || n_boxes_total == 0),
                  "dana_episode_boxes: null pointer");
-  episode_boxes_kernel<<<batch, 64, 0, (hipStream_t)stream>>>(boxes, n_boxes_total, meta, n_rows, plan, plan_words, q_off,
-                                                              max_num_box, gt_boxes, num_boxes, all_cls_gt_boxes,
-                                                              all_cls_num_boxes);
+  episode_boxes_kernel<false><<<batch, 64, 0, (hipStream_t)stream>>>(boxes, n_boxes_total, meta, n_rows, plan, plan_words,
+                                                                     q_off, max_num_box, gt_boxes, num_boxes,
+                                                                     all_cls_gt_boxes, all_cls_num_boxes, 0);
   DANA_CHECK_LAUNCH("dana_episode_boxes");
+  return DANA_OK;
+}
+
+int dana_episode_boxes_aug(const float* boxes, long n_boxes_total, const int* meta, int n_rows, const int* plan,
+                           int plan_words, int q_off, int a_off, int batch, int max_num_box, float* gt_boxes,
+                           long long* num_boxes, float* all_cls_gt_boxes, long long* all_cls_num_boxes,
+                           dana_stream_t stream) {
+  DANA_CHECK_ARG(batch > 0 && max_num_box > 0 && n_rows > 0 && n_boxes_total >= 0, "dana_episode_boxes_aug: bad shape");
+  DANA_CHECK_ARG(q_off >= 0 && q_off % 2 == 0 && (long)q_off + (long)batch * EP_QWORDS <= plan_words,
+                 "dana_episode_boxes_aug: the query records do not fit the plan");
+  DANA_CHECK_ARG(aug_fits(a_off, batch, plan_words),
+                 "dana_episode_boxes_aug: the augmentation records do not fit the plan");
+  DANA_CHECK_ARG(meta && plan && gt_boxes && num_boxes && all_cls_gt_boxes && all_cls_num_boxes &&
+                     (boxes || n_boxes_total == 0),
+                 "dana_episode_boxes_aug: null pointer");
+  episode_boxes_kernel<true><<<batch, 64, 0, (hipStream_t)stream>>>(boxes, n_boxes_total, meta, n_rows, plan, plan_words,
+                                                                    q_off, max_num_box, gt_boxes, num_boxes,
+                                                                    all_cls_gt_boxes, all_cls_num_boxes, a_off);
+  DANA_CHECK_LAUNCH("dana_episode_boxes_aug");
   return DANA_OK;
 }
 

@@ -7,6 +7,8 @@ Mirrors what the reference's loaders do per image on the CPU with cv2 / numpy:
   * `EpisodeHolders`     train.py:61-66,125-129 (persistent device holders the model is fed from)
   * `ImagePool`, `plan_episode`, `EpisodeAssembler`   fs_loader.py:81-325 for a whole batch: resident frames, one plan
                          made on the host, three launches (csrc/episode.hip), the same bits as the functions above
+  * `color_matrix`, `draw_color_matrix`, the query keys target_size / crop / min_visible / color   training-time
+                         augmentation, chosen per record on the host and evaluated by those launches (not in the reference)
 Raw uint8 RGB frames are uploaded once; everything else happens in HBM through libdana_hip.so. The data-dependent
 host decisions (which crop window, which supports: np.random / random in fs_loader.py) stay on the host, as they
 are in the reference."""
@@ -127,6 +129,11 @@ EP_QWORDS, EP_SWORDS = 16, 16
 (Q_ROW, Q_NORDER, Q_SCALE, Q_INV, Q_YS, Q_XS, Q_COPY_H, Q_COPY_W, Q_CLAMP_X, Q_CLAMP_Y, Q_CLS,
  Q_ORDER_OFF, Q_OH, Q_OW) = 0, 1, 2, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15
 S_ROW, S_INV, S_SX, S_SY, S_X0, S_Y0, S_CW, S_CH, S_RW, S_RH, S_OH, S_OW = 0, 2, 4, 6, 8, 9, 10, 11, 12, 13, 14, 15
+# augmentation record (the plan's third section, present only when something asks for it): float32 M[3][4], float32
+# min_visible, flags
+EP_AWORDS = 16
+A_M, A_MIN_VISIBLE, A_FLAGS = 0, 12, 13
+A_HAS_COLOR, A_HAS_VISIBLE = 1, 2
 
 
 class ImagePool:
@@ -220,17 +227,21 @@ class ImagePool:
 
 class EpisodePlan:
     """One batch of episodes as the device reads it: `words` (int32) = `batch` query records, `n_supports` support
-    records, the queries' box orders. `queries` / `supports` are the same records as dicts, for the host."""
+    records, the queries' box orders. `queries` / `supports` are the same records as dicts, for the host.
+    `augmented`: the words end with a third section at `a_off` (an even word), one augmentation record per query, then one
+    per support; `EpisodeAssembler` then runs the augmented launches. a_off is None for a plan that asks for none."""
 
-    def __init__(self, words, queries, supports, holder_hw):
+    def __init__(self, words, queries, supports, holder_hw, a_off=None):
         self.words, self.queries, self.supports, self.holder_hw = words, queries, supports, holder_hw
         self.batch, self.n_supports = len(queries), len(supports)
         self.q_off, self.s_off = 0, len(queries) * EP_QWORDS
+        self.augmented, self.a_off = a_off is not None, a_off
 
     def boxes_numpy(self, pool, max_num_box):
         """`episode_boxes_numpy` per query -> (gt_boxes [B][max][5], num_boxes [B], all_cls_gt_boxes, all_cls_num_boxes)"""
         per = [episode_boxes_numpy(pool.row_boxes(q["row"]), q["order"], q["im_scale"], q["x_s"], q["y_s"], q["clamp_x"],
-                                   q["clamp_y"], q["pos_cls"], max_num_box) for q in self.queries]
+                                   q["clamp_y"], q["pos_cls"], max_num_box, min_visible=q.get("min_visible") or 0.0)
+               for q in self.queries]
         return (np.stack([p[0] for p in per]), np.array([p[1] for p in per], dtype=np.int64),
                 np.stack([p[2] for p in per]), np.array([p[3] for p in per], dtype=np.int64))
 
@@ -249,6 +260,80 @@ def _pool_row(pool, row):
         raise IndexError("plan_episode: pool row %d outside [0, %d)" % (row, len(pool)))
     h, w = int(pool.meta[row, 0]), int(pool.meta[row, 1])
     return row, h, w
+
+
+def color_matrix(brightness=0.0, contrast=1.0, saturation=1.0, hue=0.0, pivot=128.0):
+    """The colour distortions of a training loader as ONE affine map of an RGB pixel -> float32 [3][4], rows R, G, B of the
+    distorted pixel, columns r, g, b of the source, the offset in column 3. Applied in this order: brightness (v + b),
+    contrast about a fixed pivot (c * (v - pivot) + pivot), saturation (s * v + (1 - s) * luma(v), luma weights 0.299 /
+    0.587 / 0.114), hue (a rotation by `hue` degrees of the I, Q plane of YIQ). Composed in float64 and rounded once; a
+    component at its neutral value contributes nothing, so `color_matrix()` is the identity exactly. Not in the reference."""
+    m = np.eye(4, dtype=np.float64)
+    luma = np.array([0.299, 0.587, 0.114], dtype=np.float64)
+    step = np.eye(4, dtype=np.float64)
+    if brightness != 0.0:
+        step[:3, 3] = float(brightness)
+        m = step @ m
+    if contrast != 1.0:
+        step = np.eye(4, dtype=np.float64)
+        step[:3, :3] *= float(contrast)
+        step[:3, 3] = (1.0 - float(contrast)) * float(pivot)
+        m = step @ m
+    if saturation != 1.0:
+        step = np.eye(4, dtype=np.float64)
+        step[:3, :3] = float(saturation) * np.eye(3) + (1.0 - float(saturation)) * np.tile(luma, (3, 1))
+        m = step @ m
+    if hue != 0.0:
+        to_yiq = np.array([luma, [0.595716, -0.274453, -0.321263], [0.211456, -0.522591, 0.311135]], dtype=np.float64)
+        a = np.deg2rad(float(hue))
+        rot = np.array([[1.0, 0.0, 0.0], [0.0, np.cos(a), -np.sin(a)], [0.0, np.sin(a), np.cos(a)]], dtype=np.float64)
+        step = np.eye(4, dtype=np.float64)
+        step[:3, :3] = np.linalg.solve(to_yiq, rot @ to_yiq)
+        m = step @ m
+    return np.ascontiguousarray(m[:3], dtype=np.float32)
+
+
+def draw_color_params(rng, brightness=32, contrast=(0.5, 1.5), saturation=(0.5, 1.5), hue=18, p=0.5):
+    """One draw of the four components from a `numpy.random.Generator`, on the host: brightness uniform in [-b, b],
+    contrast and saturation uniform in their (lo, hi), hue uniform in [-hue, hue] degrees, each applied with probability p
+    and neutral otherwise. Eight numbers are drawn whatever the outcome, so the stream after a draw does not depend on it.
+    -> the keyword arguments of `color_matrix`"""
+    gate = rng.random(4) < float(p)
+    u = rng.random(4)
+    return dict(brightness=float((2.0 * u[0] - 1.0) * brightness) if gate[0] else 0.0,
+                contrast=float(contrast[0] + u[1] * (contrast[1] - contrast[0])) if gate[1] else 1.0,
+                saturation=float(saturation[0] + u[2] * (saturation[1] - saturation[0])) if gate[2] else 1.0,
+                hue=float((2.0 * u[3] - 1.0) * hue) if gate[3] else 0.0)
+
+
+def draw_color_matrix(rng, brightness=32, contrast=(0.5, 1.5), saturation=(0.5, 1.5), hue=18, p=0.5):
+    """`color_matrix` of one `draw_color_params` draw: deterministic under the generator's seed"""
+    return color_matrix(**draw_color_params(rng, brightness, contrast, saturation, hue, p))
+
+
+def apply_color_numpy(im_rgb_u8, m):
+    """The colour map as the kernels of csrc/episode.hip evaluate it at a source tap, for a whole frame, in numpy: float32,
+    ((M[j][0]*r + M[j][1]*g) + M[j][2]*b) + M[j][3], clamped to [0, 255] -> float32 [h][w][3] RGB. The distorted image is
+    never rounded to uint8: that rounding is defined away."""
+    im = np.asarray(im_rgb_u8).astype(np.float32)
+    m = np.asarray(m, dtype=np.float32).reshape(3, 4)
+    r, g, b = im[..., 0], im[..., 1], im[..., 2]
+    d = np.stack([((m[j, 0] * r + m[j, 1] * g) + m[j, 2] * b) + m[j, 3] for j in range(3)], axis=-1)
+    return np.minimum(np.maximum(d, np.float32(0)), np.float32(255)).astype(np.float32)
+
+
+def _color(name, m):
+    """a caller's colour map, checked -> float32 [3][4] (None stays None: no map)"""
+    if m is None:
+        return None
+    m = np.asarray(_host_only(name, m))
+    if m.shape != (3, 4):
+        raise ValueError("plan_episode: %s must be a [3][4] matrix, got shape %s" % (name, tuple(m.shape)))
+    with np.errstate(over="ignore"):
+        m = np.ascontiguousarray(m, dtype=np.float32)
+    if not np.isfinite(m).all():
+        raise ValueError("plan_episode: %s is not finite" % name)
+    return m
 
 
 def _plan_support(pool, row, box, target_size, support_size):
@@ -275,11 +360,44 @@ def _plan_support(pool, row, box, target_size, support_size):
                 cw=cw, ch=ch)
 
 
+QUERY_KEYS = ("row", "ratio", "pos_cls", "order", "need_crop", "crop_start", "target_size", "crop", "min_visible", "color")
+AUGMENT_KEYS = ("min_visible", "color")  # a query that carries one of these (not None) makes the plan an augmented one
+
+
 def _plan_query(pool, q, holder_hw, target_size):
+    for key in q:
+        if key not in QUERY_KEYS:
+            raise ValueError("plan_episode: unknown key %r in a query (known: %s)" % (key, ", ".join(QUERY_KEYS)))
     row, h, w = _pool_row(pool, q["row"])
-    ratio = float(_host_only("ratio", q["ratio"]))
+    if q.get("target_size") is not None:  # this query's own scale: multi-scale training (cfg.TRAIN.SCALES)
+        target_size = float(_host_only("target_size", q["target_size"]))
+        if not target_size > 0:
+            raise ValueError("plan_episode: target_size of row %d must be positive, got %r" % (row, target_size))
     im_scale = float(target_size) / float(min(h, w))
     oh, ow = cv_round(h * im_scale), cv_round(w * im_scale)
+    color = _color("color", q.get("color"))
+    min_visible = q.get("min_visible")
+    if min_visible is not None:
+        min_visible = float(_host_only("min_visible", min_visible))
+        if not 0.0 <= min_visible <= 1.0:
+            raise ValueError("plan_episode: min_visible of row %d must lie in [0, 1], got %r" % (row, min_visible))
+    if q.get("crop") is not None:
+        # a free window of the prepared image in place of the ratio crop, with the loader's own convention for a crop
+        # (fs_loader.py:215-220, 251-255): shift by the start, clamp to [0, size - 1]. No ratio padding follows.
+        if q.get("need_crop", False) or q.get("crop_start") is not None:
+            raise ValueError("plan_episode: row %d gives both crop and need_crop / crop_start" % row)
+        win = np.asarray(_host_only("crop", q["crop"])).reshape(-1)
+        if win.size != 4:
+            raise ValueError("plan_episode: crop must be (y, x, h, w), got %r" % (q["crop"],))
+        y_s, x_s, ch, cw = [int(v) for v in win]
+        if y_s < 0 or x_s < 0 or ch < 1 or cw < 1 or y_s + ch > oh or x_s + cw > ow:
+            raise ValueError("plan_episode: crop window (y %d, x %d, %d x %d) leaves the prepared image (%d x %d) of row %d"
+                             % (y_s, x_s, ch, cw, oh, ow, row))
+        return dict(row=row, im_scale=im_scale, oh=oh, ow=ow, y_s=y_s, x_s=x_s, copy_h=min(ch, int(holder_hw[0])),
+                    copy_w=min(cw, int(holder_hw[1])), out_h=ch, out_w=cw, clamp_x=cw - 1, clamp_y=ch - 1,
+                    pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=_box_order(pool, row, q), color=color,
+                    min_visible=min_visible)
+    ratio = float(_host_only("ratio", q["ratio"]))
     data_h, data_w, y_s, x_s, clamp_x, clamp_y = oh, ow, 0, 0, -1, -1
     if q.get("need_crop", False):
         start = int(_host_only("crop_start", q.get("crop_start", 0)))
@@ -299,19 +417,43 @@ def _plan_query(pool, q, holder_hw, target_size):
     if copy_h > holder_hw[0] or copy_w > holder_hw[1]:
         raise ValueError("plan_episode: copy window %d x %d of row %d is larger than the holder (%d x %d)"
                          % (copy_h, copy_w, row, holder_hw[0], holder_hw[1]))
+    order = _box_order(pool, row, q)
+    return dict(row=row, im_scale=im_scale, oh=oh, ow=ow, y_s=y_s, x_s=x_s, copy_h=copy_h, copy_w=copy_w, out_h=out_h,
+                out_w=out_w, clamp_x=clamp_x, clamp_y=clamp_y, pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=order,
+                color=color, min_visible=min_visible)
+
+
+def _box_order(pool, row, q):
     n_box = int(pool.meta[row, 4])
     order = q.get("order")
     order = np.arange(n_box, dtype=np.int32) if order is None else np.asarray(_host_only("order", order)).astype(np.int32).reshape(-1)
     if len(order) and (order.min() < 0 or order.max() >= n_box):
         raise ValueError("plan_episode: box order of row %d names a box outside [0, %d)" % (row, n_box))
-    return dict(row=row, im_scale=im_scale, oh=oh, ow=ow, y_s=y_s, x_s=x_s, copy_h=copy_h, copy_w=copy_w, out_h=out_h,
-                out_w=out_w, clamp_x=clamp_x, clamp_y=clamp_y, pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=order)
+    return order
 
 
-def _pack_plan(qs, ss):
-    """the host records of `_plan_query` / `_plan_support` -> the int32 words the kernels of csrc/episode.hip read"""
+def _aug_offset(qs, ss):
+    """the word at which the augmentation section starts: behind the box orders, on an even word"""
+    n = len(qs) * EP_QWORDS + len(ss) * EP_SWORDS + sum(len(q["order"]) for q in qs)
+    return n + (n & 1)
+
+
+def _pack_plan(qs, ss, augmented=False):
+    """the host records of `_plan_query` / `_plan_support` -> the int32 words the kernels of csrc/episode.hip read.
+    augmented: the words go on to `_aug_offset(qs, ss)` and carry one augmentation record per query, then one per support
+    (a record without a colour map holds the identity and no A_HAS_COLOR; min_visible > 0 sets A_HAS_VISIBLE)"""
     n_rec = len(qs) * EP_QWORDS + len(ss) * EP_SWORDS
-    words = np.zeros((n_rec + sum(len(q["order"]) for q in qs),), dtype=np.int32)
+    n_words = n_rec + sum(len(q["order"]) for q in qs)
+    a_off = _aug_offset(qs, ss)
+    words = np.zeros((a_off + (len(qs) + len(ss)) * EP_AWORDS if augmented else n_words,), dtype=np.int32)
+    if augmented:
+        f32 = words.view(np.float32)
+        for k, rec in enumerate(list(qs) + list(ss)):
+            o = a_off + k * EP_AWORDS
+            color, f = rec.get("color"), rec.get("min_visible") or 0.0
+            f32[o + A_M:o + A_M + 12] = (np.eye(3, 4, dtype=np.float32) if color is None else color).reshape(-1)
+            f32[o + A_MIN_VISIBLE] = f
+            words[o + A_FLAGS] = (A_HAS_COLOR if color is not None else 0) | (A_HAS_VISIBLE if f > 0 else 0)
     f64 = words[:n_rec].view(np.float64)  # word 2k <-> double k
     at = n_rec
     for b, q in enumerate(qs):
@@ -337,29 +479,54 @@ def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, su
     crop_start (the y_s / x_s drawn at :186-255). supports: (row, box) per support slot, batch-major ([b][way * shot]
     flattened), box = the support_db entry's unscaled (x1, y1, x2, y2). holder_hw: (H, W) of the holders' im_data.
     -> EpisodePlan with everything that follows deterministically: scales, prepared sizes, copy windows, clamp limits, the
-    int16 support boxes and their resized sizes."""
+    int16 support boxes and their resized sizes.
+    Training-time augmentation (not in the reference; the draws stay on the host, e.g. `draw_color_matrix`), per record:
+      q["target_size"]  this query's own scale in place of `target_size` (multi-scale training)
+      q["crop"]         (y, x, h, w) in prepared pixels: a free window in place of need_crop / crop_start; boxes are shifted
+                        by its start and clamped to [0, w - 1] x [0, h - 1]; no ratio padding (`ratio` is not read)
+      q["min_visible"]  f in [0, 1]: a box stays only if the shift and the clamp leave at least f of its area (0: no rule)
+      q["color"]        a float [3][4] map of the source's RGB (`color_matrix`), applied to every source tap
+      supports          (row, box, color) in place of (row, box)
+    A plan in which a query carries min_visible or color, or a support a color, is `augmented`: its words end with the
+    augmentation section and `EpisodeAssembler` runs the augmented launches. Any other plan has the words it always had.
+    A key that is none of `QUERY_KEYS` is refused."""
     queries, supports = list(queries), list(supports)
     if queries and holder_hw is None:
         raise ValueError("plan_episode: holder_hw is needed to plan queries")
     qs = [_plan_query(pool, q, holder_hw, target_size) for q in queries]
-    ss = [_plan_support(pool, r, bx, target_size, support_size) for r, bx in supports]
-    words = _pack_plan(qs, ss)
-    return EpisodePlan(words, qs, ss, None if holder_hw is None else (int(holder_hw[0]), int(holder_hw[1])))
+    ss = []
+    for sup in supports:
+        if len(sup) not in (2, 3):
+            raise ValueError("plan_episode: a support is (row, box) or (row, box, color), got %d entries" % len(sup))
+        s = _plan_support(pool, sup[0], sup[1], target_size, support_size)
+        s["color"] = _color("color", sup[2]) if len(sup) == 3 else None
+        ss.append(s)
+    augmented = any(q.get(k) is not None for q in queries for k in AUGMENT_KEYS) or any(s["color"] is not None for s in ss)
+    words = _pack_plan(qs, ss, augmented)
+    return EpisodePlan(words, qs, ss, None if holder_hw is None else (int(holder_hw[0]), int(holder_hw[1])),
+                       _aug_offset(qs, ss) if augmented else None)
 
 
-def episode_boxes_numpy(boxes, order, im_scale, x_s, y_s, clamp_x, clamp_y, pos_cls, max_num_box):
+def episode_boxes_numpy(boxes, order, im_scale, x_s, y_s, clamp_x, clamp_y, pos_cls, max_num_box, min_visible=0.0):
     """minibatch.py:52-54 + fs_loader.py:183-315 for one image, in numpy. boxes: float32 [n][5] unscaled; clamp_x / clamp_y:
-    upper clamp limit of that axis, < 0 for none -> (fs_gt_boxes [max][5], num_boxes, all-class gt_boxes [max][5], its count)"""
+    upper clamp limit of that axis, < 0 for none -> (fs_gt_boxes [max][5], num_boxes, all-class gt_boxes [max][5], its count).
+    min_visible = f > 0 (not in the reference): with u the shifted row before the clamp and v after it, a box is also dropped
+    unless (v2 - v0) * (v3 - v1) >= f * ((u2 - u0) * (u3 - u1)), all in float32."""
     src = np.asarray(boxes, dtype=np.float32).reshape(-1, 5)[np.asarray(order, dtype=np.int64).reshape(-1)]
     gt = np.empty((src.shape[0], 5), dtype=np.float32)
     gt[:, 0:4] = src[:, 0:4].astype(np.float64) * float(im_scale)  # the product in double, rounded by the assignment
     gt[:, 4] = src[:, 4]
     gt[:, 0:4:2] -= np.float32(x_s)  # :215-216, :251-252
     gt[:, 1:4:2] -= np.float32(y_s)
+    u = gt[:, 0:4].copy()
     if clamp_x >= 0:
         gt[:, 0:4:2] = np.clip(gt[:, 0:4:2], np.float32(0), np.float32(clamp_x))  # :219-220, :254-255, :281
     if clamp_y >= 0:
         gt[:, 1:4:2] = np.clip(gt[:, 1:4:2], np.float32(0), np.float32(clamp_y))
+    if min_visible > 0:  # in front of both compactions, beside the degenerate-box filter below
+        full = (u[:, 2] - u[:, 0]) * (u[:, 3] - u[:, 1])
+        seen = (gt[:, 2] - gt[:, 0]) * (gt[:, 3] - gt[:, 1])
+        gt = gt[seen >= np.float32(min_visible) * full]
     fs = gt[gt[:, 4] == pos_cls].copy()  # :286-291
     fs[:, 4] = 1.0
     out = []
@@ -414,6 +581,11 @@ class EpisodeAssembler:
 
     def _supports(self, d_plan, plan, out):
         p = self.pool
+        if plan.augmented:  # the supports' augmentation records follow the queries'
+            lib().call("dana_episode_supports_aug", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p),
+                       _p(d_plan), int(plan.words.size), plan.s_off, plan.a_off + plan.batch * EP_AWORDS, plan.n_supports,
+                       self._means_p, self.support_size, _p(out), _stream())
+            return
         lib().call("dana_episode_supports", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p), _p(d_plan),
                    int(plan.words.size), plan.s_off, plan.n_supports, self._means_p, self.support_size, _p(out), _stream())
 
@@ -428,13 +600,23 @@ class EpisodeAssembler:
                              "(%d, %d, %s)" % (plan.batch, plan.n_supports, plan.holder_hw, B, n_sup, (H, W)))
         d_plan, slot = self._upload(plan)
         n_words, stream = int(plan.words.size), _stream()
-        lib().call("dana_episode_queries", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p), _p(d_plan),
-                   n_words, plan.q_off, B, self._means_p, _p(h.im_data), H, W, _p(h.im_info), stream)
+        if plan.augmented:
+            lib().call("dana_episode_queries_aug", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p),
+                       _p(d_plan), n_words, plan.q_off, plan.a_off, B, self._means_p, _p(h.im_data), H, W, _p(h.im_info),
+                       stream)
+        else:
+            lib().call("dana_episode_queries", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p), _p(d_plan),
+                       n_words, plan.q_off, B, self._means_p, _p(h.im_data), H, W, _p(h.im_info), stream)
         if n_sup:
             self._supports(d_plan, plan, h.support_ims)
-        lib().call("dana_episode_boxes", _p(p.d_boxes), len(p.boxes), _p(p.d_meta), len(p), _p(d_plan), n_words, plan.q_off, B,
-                   h.gt_boxes.size(1), _p(h.gt_boxes), _p(h.num_boxes), _p(self.all_cls_gt_boxes),
-                   _p(self.all_cls_num_boxes), stream)
+        if plan.augmented:
+            lib().call("dana_episode_boxes_aug", _p(p.d_boxes), len(p.boxes), _p(p.d_meta), len(p), _p(d_plan), n_words,
+                       plan.q_off, plan.a_off, B, h.gt_boxes.size(1), _p(h.gt_boxes), _p(h.num_boxes),
+                       _p(self.all_cls_gt_boxes), _p(self.all_cls_num_boxes), stream)
+        else:
+            lib().call("dana_episode_boxes", _p(p.d_boxes), len(p.boxes), _p(p.d_meta), len(p), _p(d_plan), n_words,
+                       plan.q_off, B, h.gt_boxes.size(1), _p(h.gt_boxes), _p(h.num_boxes), _p(self.all_cls_gt_boxes),
+                       _p(self.all_cls_num_boxes), stream)
         self._done(slot)
         return h.tensors() + (self.all_cls_gt_boxes,)
 
@@ -514,6 +696,26 @@ def views_holder_hw(pool, rows, scales=(600,)):
     sizes = [_view_size(int(pool.meta[r, 0]), int(pool.meta[r, 1]), s)[1:]
              for e in rows for r in [_pool_row(pool, e[0] if isinstance(e, (tuple, list)) else e)[0]] for s in scales]
     return (max(s[0] for s in sizes), max(s[1] for s in sizes)) if sizes else (1, 1)
+
+
+def scales_holder_hw(pool, rows, scales=(600,), ratios=None):
+    """(H, W) of the smallest holder that takes every copy window `plan_episode` can make for these rows when a query draws
+    its `target_size` from `scales` (multi-scale training). ratios: None, or one ratio per row (ratio_list_batch). Without
+    ratios the bound is the maximum prepared size; with them it is `pad_plan`'s copy window of the uncropped image, which a
+    ratio crop or a `crop` window only makes smaller."""
+    rows = list(rows)
+    ratios = [None] * len(rows) if ratios is None else [float(r) for r in ratios]
+    if len(ratios) != len(rows):
+        raise ValueError("scales_holder_hw: %d ratios for %d rows" % (len(ratios), len(rows)))
+    H, W = 1, 1
+    for entry, ratio in zip(rows, ratios):
+        _, h, w = _pool_row(pool, entry)
+        for s in scales:
+            _, oh, ow = _view_size(h, w, s)
+            if ratio is not None:
+                oh, ow = pad_plan(oh, ow, ratio)[2:]
+            H, W = max(H, oh), max(W, ow)
+    return H, W
 
 
 def plan_views(pool, rows, scales=(600,), flip=False, area_ranges=None, holder_hw=None):

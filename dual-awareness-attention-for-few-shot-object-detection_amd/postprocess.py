@@ -326,7 +326,7 @@ def ensemble_shots(cd, shots, nms_thresh="cfg", nms_inclusive=False, max_dets=0,
 # ---- view ensembles: flip and multi-scale testing -------------------------------------------------------------------------
 # Out of scope here: views times shots in one fold (fold the views, then merge the shots); views of an im_data tensor that
 # did not come from an ImagePool (a resize of a resized image is not the loader's image); vertical flips and rotations;
-# training-time augmentation; QueryBank views. The sibling detectors need nothing of their own: the fold sees only lists.
+# QueryBank views (training-time augmentation is `pipeline.plan_episode`'s, not a view's). The sibling detectors need nothing of their own: the fold sees only lists.
 
 class FoldedViews:
     """`fold_views`' result, which `merge_detections(folded, folded.views, capacity=folded.capacity)` accepts: `packed`

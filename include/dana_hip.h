@@ -862,6 +862,37 @@ int dana_episode_boxes(const float* boxes, long n_boxes_total, const int* meta, 
                        int plan_words, int q_off, int batch, int max_num_box, float* gt_boxes, long long* num_boxes,
                        float* all_cls_gt_boxes, long long* all_cls_num_boxes, dana_stream_t stream);
 
+/* Training-time augmentation of such a batch. NOT IN THE REFERENCE: its loader has the flipped twin and the aspect-ratio
+ * crop (fs_loader.py:186-255) and nothing else, so these three extend those lines and have no counterpart to be checked
+ * against; with records that ask for nothing they give the bits of the three entry points above.
+ * The plan carries a third section of 16-word augmentation records (pipeline.plan_episode writes it when a query or a
+ * support asks for augmentation): float M[3][4] in words 0..11, float min_visible in word 12, flags in word 13 (1: the
+ * record has a colour map, 2: it has a visibility threshold). a_off is the word offset of the FIRST record the call reads
+ * -- the queries' records come first in the section, the supports' follow them -- and must be even and inside plan_words.
+ * Colour: every source tap (r, g, b) of a record with flag 1 counts as
+ *   d_j = clamp(((M[j][0]*r + M[j][1]*g) + M[j][2]*b) + M[j][3], 0, 255), j in R, G, B   (float32, in this order, unfused)
+ * before the mean is subtracted and before any interpolation: the image that was distorted and then prepared, except
+ * that the distorted image is never rounded to uint8. */
+
+/* dana_episode_queries (blob.py:35-52 + fs_loader.py:186-280) with the colour map of record b at its four source taps */
+int dana_episode_queries_aug(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                             int n_rows, const int* plan, int plan_words, int q_off, int a_off, int batch,
+                             const float* pixel_means_bgr, float* im_data, int height, int width, float* im_info,
+                             dana_stream_t stream);
+/* dana_episode_supports (fs_loader.py:113-139) with the colour map of record n at the (up to) sixteen source taps of its
+ * two composed resamples */
+int dana_episode_supports_aug(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                              int n_rows, const int* plan, int plan_words, int s_off, int a_off, int n_supports,
+                              const float* pixel_means_bgr, int target, float* out_chw, dana_stream_t stream);
+/* dana_episode_boxes (fs_loader.py:183-315) with one more reason to drop a box, in front of both compactions beside the
+ * degenerate-box filter of :294,306: for a record with flag 2, u = the shifted row before the clamp, v = after it,
+ * full = (u2 - u0) * (u3 - u1), seen = (v2 - v0) * (v3 - v1) in float32, and the box stays only if
+ * seen >= min_visible * full */
+int dana_episode_boxes_aug(const float* boxes, long n_boxes_total, const int* meta, int n_rows, const int* plan,
+                           int plan_words, int q_off, int a_off, int batch, int max_num_box, float* gt_boxes,
+                           long long* num_boxes, float* all_cls_gt_boxes, long long* all_cls_num_boxes,
+                           dana_stream_t stream);
+
 /* ---- counter-based device RNG for the training target layers (opt-in) ---------------------------
  * Philox-4x32-10 keyed by (seed, offset, image): the draws of anchor_target_layer.py:137-156 and
  * proposal_target_layer_cascade.py:143-175 without reading the fg / bg counts back to the host. */
