@@ -9,6 +9,8 @@ Mirrors what the reference's loaders do per image on the CPU with cv2 / numpy:
                          made on the host, three launches (csrc/episode.hip), the same bits as the functions above
   * `color_matrix`, `draw_color_matrix`, the query keys target_size / crop / min_visible / color   training-time
                          augmentation, chosen per record on the host and evaluated by those launches (not in the reference)
+  * `mosaic_query`, `paste_part`, `draw_mosaic`, `draw_paste`, the query keys parts / at   composed queries: mosaic,
+                         copy-paste and random erasing as ordered parts painted into one holder image (not in the reference)
 Raw uint8 RGB frames are uploaded once; everything else happens in HBM through libdana_hip.so. The data-dependent
 host decisions (which crop window, which supports: np.random / random in fs_loader.py) stay on the host, as they
 are in the reference."""
@@ -134,6 +136,13 @@ S_ROW, S_INV, S_SX, S_SY, S_X0, S_Y0, S_CW, S_CH, S_RW, S_RH, S_OH, S_OW = 0, 2,
 EP_AWORDS = 16
 A_M, A_MIN_VISIBLE, A_FLAGS = 0, 12, 13
 A_HAS_COLOR, A_HAS_VISIBLE = 1, 2
+# composed section (the plan's last, present only when a query is composed): one header per query, then one table of
+# `max_parts` part records per query. A part record starts like a query record and goes on with the destination, the word
+# offset of its box order, its flags (A_HAS_COLOR) and float32 M[3][4]; words 28, 29 hold the prepared size for the host.
+EP_CWORDS, EP_PWORDS, EP_MAX_PARTS = 8, 32, 16
+C_NPARTS, C_CLS, C_MIN_VISIBLE, C_FLAGS = 0, 1, 2, 3
+(P_ROW, P_NORDER, P_SCALE, P_INV, P_YS, P_XS, P_H, P_W, P_CLAMP_X, P_CLAMP_Y, P_DY, P_DX, P_ORDER_OFF, P_FLAGS, P_M, P_OH,
+ P_OW) = 0, 1, 2, 4, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 28, 29
 
 
 class ImagePool:
@@ -229,17 +238,26 @@ class EpisodePlan:
     """One batch of episodes as the device reads it: `words` (int32) = `batch` query records, `n_supports` support
     records, the queries' box orders. `queries` / `supports` are the same records as dicts, for the host.
     `augmented`: the words end with a third section at `a_off` (an even word), one augmentation record per query, then one
-    per support; `EpisodeAssembler` then runs the augmented launches. a_off is None for a plan that asks for none."""
+    per support; `EpisodeAssembler` then runs the augmented launches. a_off is None for a plan that asks for none.
+    `composed`: a query carries `parts`; the words end with the composed section at `c_off` (an even word): `batch` headers,
+    then `batch` tables of `max_parts` part records, then the parts' box orders. `EpisodeAssembler` then runs the composed
+    query and box launches for the whole batch (a query that is not composed is one part at (0, 0) in that section, built
+    from its own record), and the section in front of it is what the plan would have without composed queries; in a
+    composed plan `augmented` says only whether a support carries a colour map. c_off is None for any other plan."""
 
-    def __init__(self, words, queries, supports, holder_hw, a_off=None):
+    def __init__(self, words, queries, supports, holder_hw, a_off=None, c_off=None, max_parts=0):
         self.words, self.queries, self.supports, self.holder_hw = words, queries, supports, holder_hw
         self.batch, self.n_supports = len(queries), len(supports)
         self.q_off, self.s_off = 0, len(queries) * EP_QWORDS
         self.augmented, self.a_off = a_off is not None, a_off
+        self.composed, self.c_off, self.max_parts = c_off is not None, c_off, int(max_parts)
 
     def boxes_numpy(self, pool, max_num_box):
-        """`episode_boxes_numpy` per query -> (gt_boxes [B][max][5], num_boxes [B], all_cls_gt_boxes, all_cls_num_boxes)"""
-        per = [episode_boxes_numpy(pool.row_boxes(q["row"]), q["order"], q["im_scale"], q["x_s"], q["y_s"], q["clamp_x"],
+        """`episode_boxes_numpy` per query (`composed_boxes_numpy` for a composed one) -> (gt_boxes [B][max][5],
+        num_boxes [B], all_cls_gt_boxes, all_cls_num_boxes)"""
+        per = [composed_boxes_numpy([dict(p, boxes=None if p["row"] < 0 else pool.row_boxes(p["row"])) for p in q["parts"]],
+                                    q["pos_cls"], max_num_box, min_visible=q.get("min_visible") or 0.0) if "parts" in q else
+               episode_boxes_numpy(pool.row_boxes(q["row"]), q["order"], q["im_scale"], q["x_s"], q["y_s"], q["clamp_x"],
                                    q["clamp_y"], q["pos_cls"], max_num_box, min_visible=q.get("min_visible") or 0.0)
                for q in self.queries]
         return (np.stack([p[0] for p in per]), np.array([p[1] for p in per], dtype=np.int64),
@@ -311,6 +329,94 @@ def draw_color_matrix(rng, brightness=32, contrast=(0.5, 1.5), saturation=(0.5, 
     return color_matrix(**draw_color_params(rng, brightness, contrast, saturation, hue, p))
 
 
+def _prepared_hw(pool, row, target_size):
+    row, h, w = _pool_row(pool, row)
+    im_scale = float(target_size) / float(min(h, w))
+    return row, im_scale, cv_round(h * im_scale), cv_round(w * im_scale)
+
+
+def mosaic_query(pool, rows, center, holder_hw, target_size=600, pos_cls=1, min_visible=0.5, colors=None, starts=None):
+    """The composed query of a four-image mosaic, host only. rows: the pool rows of the top-left, top-right, bottom-left
+    and bottom-right quadrant; center = (cy, cx) with 0 < cy < H, 0 < cx < W: the quadrants are [0, cy) / [cy, H) by
+    [0, cx) / [cx, W) and tile the holder exactly. target_size: one scale or one per row. Each part is a window of its
+    prepared image as large as its quadrant; starts: its (y, x) per part (None: the corner of the image that touches the
+    centre, i.e. the top-left part ends with its image's last row and column). An image whose prepared size does not cover
+    its quadrant is refused. colors: one map (or None) per part. -> dict(parts=[4 parts], pos_cls, min_visible) for
+    `plan_episode`. Set min_visible: without it a box the window cuts down to a sliver stays."""
+    H, W = int(holder_hw[0]), int(holder_hw[1])
+    cy, cx = int(center[0]), int(center[1])
+    if len(rows) != 4:
+        raise ValueError("mosaic_query: needs four rows, got %d" % len(rows))
+    if not (0 < cy < H and 0 < cx < W):
+        raise ValueError("mosaic_query: centre (%d, %d) leaves no room for four quadrants in %d x %d" % (cy, cx, H, W))
+    sizes = list(target_size) if np.ndim(target_size) else [target_size] * 4
+    quads = [(0, 0, cy, cx), (0, cx, cy, W - cx), (cy, 0, H - cy, cx), (cy, cx, H - cy, W - cx)]
+    parts = []
+    for k, (dy, dx, qh, qw) in enumerate(quads):
+        row, _, oh, ow = _prepared_hw(pool, rows[k], sizes[k])
+        if qh > oh or qw > ow:
+            raise ValueError("mosaic_query: row %d prepared to %d x %d does not cover its %d x %d quadrant" % (row, oh, ow, qh, qw))
+        start = None if starts is None else starts[k]
+        y, x = ((oh - qh) * (k < 2), (ow - qw) * (k % 2 == 0)) if start is None else (int(start[0]), int(start[1]))
+        part = dict(row=row, crop=(y, x, qh, qw), at=(dy, dx), target_size=sizes[k])
+        if colors is not None and colors[k] is not None:
+            part["color"] = colors[k]
+        parts.append(part)
+    return dict(parts=parts, pos_cls=pos_cls, min_visible=min_visible)
+
+
+def draw_mosaic(rng, pool, rows, holder_hw, target_size=600, center=(0.25, 0.75), **kw):
+    """One mosaic from a `numpy.random.Generator`, on the host: the centre uniform in `center` (fractions of H and of W),
+    each part's window uniform over the positions its prepared image allows. Ten numbers are drawn whatever the outcome.
+    -> `mosaic_query(...)`, or None where a row's prepared image does not cover its quadrant"""
+    u = rng.random(10)
+    H, W = int(holder_hw[0]), int(holder_hw[1])
+    cy = min(max(int(H * (center[0] + u[0] * (center[1] - center[0]))), 1), H - 1)
+    cx = min(max(int(W * (center[0] + u[1] * (center[1] - center[0]))), 1), W - 1)
+    sizes = list(target_size) if np.ndim(target_size) else [target_size] * 4
+    quads = [(cy, cx), (cy, W - cx), (H - cy, cx), (H - cy, W - cx)]
+    starts = []
+    for k, (qh, qw) in enumerate(quads):
+        _, _, oh, ow = _prepared_hw(pool, rows[k], sizes[k])
+        if qh > oh or qw > ow:
+            return None
+        starts.append((min(int(u[2 + 2 * k] * (oh - qh + 1)), oh - qh), min(int(u[3 + 2 * k] * (ow - qw + 1)), ow - qw)))
+    return mosaic_query(pool, rows, (cy, cx), holder_hw, target_size=sizes, starts=starts, **kw)
+
+
+def paste_part(pool, row, box_index, at, target_size=600, margin=0, color=None):
+    """The part that pastes ONE stored box of `row`, host only: the window of the prepared image around box `box_index`
+    (its scaled corners rounded outwards, `margin` prepared pixels more on every side, cut at the image), painted at
+    at = (dy, dx), carrying only that box (order = [box_index]). -> a part dict for q["parts"]"""
+    row, im_scale, oh, ow = _prepared_hw(pool, row, target_size)
+    boxes = pool.row_boxes(row)
+    k = int(box_index)
+    if not 0 <= k < len(boxes):
+        raise ValueError("paste_part: row %d has no box %d" % (row, k))
+    x1, y1, x2, y2 = [float(v) * im_scale for v in boxes[k, :4]]
+    m = int(margin)
+    x0, y0 = max(int(np.floor(x1)) - m, 0), max(int(np.floor(y1)) - m, 0)
+    xe, ye = min(int(np.ceil(x2)) + m, ow - 1), min(int(np.ceil(y2)) + m, oh - 1)
+    if xe < x0 or ye < y0:
+        raise ValueError("paste_part: box %d of row %d lies outside its image" % (k, row))
+    part = dict(row=row, crop=(y0, x0, ye - y0 + 1, xe - x0 + 1), at=(int(at[0]), int(at[1])), target_size=target_size, order=[k])
+    if color is not None:
+        part["color"] = color
+    return part
+
+
+def draw_paste(rng, pool, row, box_index, holder_hw, target_size=600, margin=0, color=None):
+    """`paste_part` at a destination drawn uniformly over the positions at which the window stays inside the holder. Two
+    numbers are drawn whatever the outcome. -> the part, or None where the window is larger than the holder"""
+    u = rng.random(2)
+    part = paste_part(pool, row, box_index, (0, 0), target_size, margin, color)
+    room_y, room_x = int(holder_hw[0]) - part["crop"][2], int(holder_hw[1]) - part["crop"][3]
+    if room_y < 0 or room_x < 0:
+        return None
+    part["at"] = (min(int(u[0] * (room_y + 1)), room_y), min(int(u[1] * (room_x + 1)), room_x))
+    return part
+
+
 def apply_color_numpy(im_rgb_u8, m):
     """The colour map as the kernels of csrc/episode.hip evaluate it at a source tap, for a whole frame, in numpy: float32,
     ((M[j][0]*r + M[j][1]*g) + M[j][2]*b) + M[j][3], clamped to [0, 255] -> float32 [h][w][3] RGB. The distorted image is
@@ -360,14 +466,80 @@ def _plan_support(pool, row, box, target_size, support_size):
                 cw=cw, ch=ch)
 
 
-QUERY_KEYS = ("row", "ratio", "pos_cls", "order", "need_crop", "crop_start", "target_size", "crop", "min_visible", "color")
+QUERY_KEYS = ("row", "ratio", "pos_cls", "order", "need_crop", "crop_start", "target_size", "crop", "min_visible", "color",
+              "at", "parts")
 AUGMENT_KEYS = ("min_visible", "color")  # a query that carries one of these (not None) makes the plan an augmented one
+COMPOSE_KEYS = ("at", "parts")  # a query that carries one of these (not None) is composed, and so is the plan
+PART_KEYS = ("row", "crop", "at", "target_size", "color", "order", "erase")
+
+
+def _rect(name, v, n):
+    v = np.asarray(_host_only(name, v)).reshape(-1)
+    if v.size != n:
+        raise ValueError("plan_episode: %s must have %d entries, got %r" % (name, n, v.tolist()))
+    return [int(x) for x in v]
+
+
+def _plan_part(pool, part, k, holder_hw, target_size):
+    """one part of a composed query -> its host record: the record of a `crop` query plus the destination (dy, dx) and the
+    painted size (h, w); an erase part has row -1, no boxes and no source"""
+    H, W = int(holder_hw[0]), int(holder_hw[1])
+    for key in part:
+        if key not in PART_KEYS:
+            raise ValueError("plan_episode: unknown key %r in part %d (known: %s)" % (key, k, ", ".join(PART_KEYS)))
+    if part.get("erase") is not None:
+        if any(part.get(key) is not None for key in PART_KEYS if key != "erase"):
+            raise ValueError("plan_episode: part %d gives erase together with %s" %
+                             (k, ", ".join(key for key in PART_KEYS if key != "erase" and part.get(key) is not None)))
+        dy, dx, h, w = _rect("erase", part["erase"], 4)
+        rec = dict(row=-1, im_scale=1.0, oh=h, ow=w, y_s=0, x_s=0, order=np.zeros((0,), dtype=np.int32), color=None, erase=True)
+    else:
+        if part.get("row") is None or part.get("crop") is None or part.get("at") is None:
+            raise ValueError("plan_episode: part %d needs row, crop and at (or erase)" % k)
+        dy, dx = _rect("at", part["at"], 2)
+        r = _plan_query(pool, dict(row=part["row"], crop=part["crop"], pos_cls=0, target_size=part.get("target_size"),
+                                   color=part.get("color"), order=part.get("order")), (1 << 30, 1 << 30), target_size)
+        h, w = r["out_h"], r["out_w"]
+        rec = dict({key: r[key] for key in ("row", "im_scale", "oh", "ow", "y_s", "x_s", "order", "color")}, erase=False)
+    if h < 1 or w < 1 or dy < 0 or dx < 0 or dy + h > H or dx + w > W:
+        raise ValueError("plan_episode: part %d's destination (y %d, x %d, %d x %d) leaves the holder (%d x %d)"
+                         % (k, dy, dx, h, w, H, W))
+    return dict(rec, h=h, w=w, clamp_x=w - 1, clamp_y=h - 1, dy=dy, dx=dx)
+
+
+def _plan_composed(pool, q, holder_hw, target_size):
+    """a query with `at` (itself the only part) or `parts` -> its host record: part 0's numbers where a query record has
+    them (what im_info reads), an empty box order of its own, and `parts`"""
+    for key in ("ratio", "need_crop", "crop_start"):
+        if q.get(key) is not None and q.get(key) is not False:
+            raise ValueError("plan_episode: a composed query places windows (crop, at); it cannot carry %s" % key)
+    if q.get("parts") is not None:
+        for key in PART_KEYS:
+            if q.get(key) is not None:
+                raise ValueError("plan_episode: a query with parts cannot carry %s of its own; it belongs to a part" % key)
+        parts = list(_host_only("parts", q["parts"]))
+    else:
+        parts = [{key: q[key] for key in PART_KEYS if q.get(key) is not None}]
+    if not 1 <= len(parts) <= EP_MAX_PARTS:
+        raise ValueError("plan_episode: a composed query has 1 to %d parts, got %d" % (EP_MAX_PARTS, len(parts)))
+    recs = [_plan_part(pool, part, k, holder_hw, target_size) for k, part in enumerate(parts)]
+    min_visible = q.get("min_visible")
+    if min_visible is not None:
+        min_visible = float(_host_only("min_visible", min_visible))
+        if not 0.0 <= min_visible <= 1.0:
+            raise ValueError("plan_episode: min_visible of a composed query must lie in [0, 1], got %r" % min_visible)
+    head = {key: recs[0][key] for key in ("row", "im_scale", "oh", "ow", "y_s", "x_s", "clamp_x", "clamp_y")}
+    head.update(copy_h=recs[0]["h"], copy_w=recs[0]["w"], out_h=recs[0]["h"], out_w=recs[0]["w"])
+    return dict(head, pos_cls=int(_host_only("pos_cls", q["pos_cls"])), order=np.zeros((0,), dtype=np.int32), color=None,
+                min_visible=min_visible, parts=recs)
 
 
 def _plan_query(pool, q, holder_hw, target_size):
     for key in q:
         if key not in QUERY_KEYS:
             raise ValueError("plan_episode: unknown key %r in a query (known: %s)" % (key, ", ".join(QUERY_KEYS)))
+    if q.get("at") is not None or q.get("parts") is not None:  # COMPOSE_KEYS
+        return _plan_composed(pool, q, holder_hw, target_size)
     row, h, w = _pool_row(pool, q["row"])
     if q.get("target_size") is not None:  # this query's own scale: multi-scale training (cfg.TRAIN.SCALES)
         target_size = float(_host_only("target_size", q["target_size"]))
@@ -473,6 +645,43 @@ def _pack_plan(qs, ss, augmented=False):
     return words
 
 
+def _pack_composed(words, qs):
+    """the words of `_pack_plan` + the composed section behind them, on an even word -> (words, c_off, max_parts).
+    Headers, then one table of max_parts part records per query (unused records stay zero), then the parts' box orders.
+    A query without `parts` becomes one part at (0, 0) made of its own record, its box order left where it is."""
+    B = len(qs)
+    max_parts = max(len(q.get("parts", (None,))) for q in qs)
+    c_off = int(words.size) + (int(words.size) & 1)
+    p_off = c_off + B * EP_CWORDS
+    o_off = p_off + B * max_parts * EP_PWORDS
+    out = np.zeros((o_off + sum(len(p["order"]) for q in qs for p in q.get("parts", ())),), dtype=np.int32)
+    out[:words.size] = words
+    f32, f64 = out.view(np.float32), out[:o_off].view(np.float64)
+    at = o_off
+    for b, q in enumerate(qs):
+        o = c_off + b * EP_CWORDS
+        f = q.get("min_visible") or 0.0
+        parts = q.get("parts")
+        if parts is None:  # its 16-word record says where its order is
+            parts = [dict(q, h=q["copy_h"], w=q["copy_w"], dy=0, dx=0, order_off=int(words[b * EP_QWORDS + Q_ORDER_OFF]))]
+        out[o + C_NPARTS], out[o + C_CLS], out[o + C_FLAGS] = len(parts), q["pos_cls"], (A_HAS_VISIBLE if f > 0 else 0)
+        f32[o + C_MIN_VISIBLE] = f
+        for k, p in enumerate(parts):
+            o = p_off + (b * max_parts + k) * EP_PWORDS
+            order_off = p.get("order_off")
+            if order_off is None:
+                order_off = at
+                out[at:at + len(p["order"])] = p["order"]
+                at += len(p["order"])
+            out[o + P_ROW], out[o + P_NORDER] = p["row"], len(p["order"])
+            f64[(o + P_SCALE) // 2], f64[(o + P_INV) // 2] = p["im_scale"], 1.0 / p["im_scale"]
+            out[o + P_YS:o + P_YS + 10] = (p["y_s"], p["x_s"], p["h"], p["w"], p["clamp_x"], p["clamp_y"], p["dy"], p["dx"],
+                                           order_off, A_HAS_COLOR if p.get("color") is not None else 0)
+            f32[o + P_M:o + P_M + 12] = (np.eye(3, 4, dtype=np.float32) if p.get("color") is None else p["color"]).reshape(-1)
+            out[o + P_OH], out[o + P_OW] = p["oh"], p["ow"]
+    return out, c_off, max_parts
+
+
 def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, support_size=320):
     """Host only. queries: one dict per batch item with the loader's choices -- row, ratio (ratio_list_batch[index]),
     pos_cls, and optionally order (the shuffled box order of fs_loader.py:183; default: as stored), need_crop with
@@ -489,7 +698,22 @@ def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, su
       supports          (row, box, color) in place of (row, box)
     A plan in which a query carries min_visible or color, or a support a color, is `augmented`: its words end with the
     augmentation section and `EpisodeAssembler` runs the augmented launches. Any other plan has the words it always had.
-    A key that is none of `QUERY_KEYS` is refused."""
+    Composed queries (not in the reference; `mosaic_query`, `paste_part`, `draw_mosaic`, `draw_paste` build them): an ordered
+    list of 1 to 16 parts painted into the holder, later parts over earlier ones, their boxes gathered in that order.
+      q["parts"]        [dict(row, crop, at, target_size?, color?, order?) | dict(erase=(dy, dx, h, w))]: a part is the
+                        window `crop` of its row's prepared image, painted with its top-left corner at at = (dy, dx); the
+                        destination rectangle must lie inside the holder. An erase part paints 0 (the mean pixel) and
+                        has no boxes. The query itself carries pos_cls and min_visible and nothing of a part
+      q["at"]           without parts: the query (row, crop, at, ...) is itself the only part
+      boxes             a part's boxes are shifted and clamped to its window as for q["crop"], then moved by (dx, dy); with
+                        min_visible = f > 0 a box stays only if (seen - hidden) >= f * full, hidden = the sum over the
+                        LATER parts of the area of the box their rectangles cover (`composed_boxes_numpy`). An area two
+                        later parts share counts twice. f = 0 applies no rule at all -- a box that later parts cover
+                        entirely stays -- so composed queries should set min_visible.
+    A composed query takes no ratio / need_crop / crop_start. One composed query makes the plan `composed`: its words end
+    with the composed section and `EpisodeAssembler` runs the composed launches; the other queries of the batch come out
+    with the bits they have in a plan without it. im_info carries part 0's im_scale (1 for an erase part).
+    A key that is none of `QUERY_KEYS` (`PART_KEYS` in a part) is refused."""
     queries, supports = list(queries), list(supports)
     if queries and holder_hw is None:
         raise ValueError("plan_episode: holder_hw is needed to plan queries")
@@ -501,10 +725,16 @@ def plan_episode(pool, queries, supports=(), holder_hw=None, target_size=600, su
         s = _plan_support(pool, sup[0], sup[1], target_size, support_size)
         s["color"] = _color("color", sup[2]) if len(sup) == 3 else None
         ss.append(s)
-    augmented = any(q.get(k) is not None for q in queries for k in AUGMENT_KEYS) or any(s["color"] is not None for s in ss)
+    composed = any("parts" in q for q in qs)
+    # (in a composed plan the queries' colour maps and thresholds travel in the composed section)
+    augmented = (not composed and any(q.get(k) is not None for q in queries for k in AUGMENT_KEYS)) or \
+        any(s["color"] is not None for s in ss)
     words = _pack_plan(qs, ss, augmented)
+    c_off, max_parts = None, 0
+    if composed:
+        words, c_off, max_parts = _pack_composed(words, qs)
     return EpisodePlan(words, qs, ss, None if holder_hw is None else (int(holder_hw[0]), int(holder_hw[1])),
-                       _aug_offset(qs, ss) if augmented else None)
+                       _aug_offset(qs, ss) if augmented else None, c_off, max_parts)
 
 
 def episode_boxes_numpy(boxes, order, im_scale, x_s, y_s, clamp_x, clamp_y, pos_cls, max_num_box, min_visible=0.0):
@@ -532,6 +762,62 @@ def episode_boxes_numpy(boxes, order, im_scale, x_s, y_s, clamp_x, clamp_y, pos_
     out = []
     for g in (fs, gt):  # :294-315
         g = g[~((g[:, 0] == g[:, 2]) | (g[:, 1] == g[:, 3]))]
+        n = min(g.shape[0], max_num_box)
+        pad = np.zeros((max_num_box, 5), dtype=np.float32)
+        pad[:n] = g[:n]
+        out += [pad, n]
+    return tuple(out)
+
+
+def composed_boxes_numpy(parts, pos_cls, max_num_box, min_visible=0.0):
+    """The box rule of a composed query (csrc/episode.hip: episode_boxes_composed_kernel) in numpy, every step one float32
+    operation. parts: in painting order, dicts with boxes (float32 [n][5] unscaled; None for an erase part), order, im_scale,
+    x_s, y_s (the window's start), h, w (its size), dy, dx (its destination) and optionally clamp_x, clamp_y (default
+    w - 1, h - 1; < 0 for none). Per part, in its order: u = the double product rounded to float32, minus the window start;
+    v = u clamped to the window; the output row t = v + (dx, dy, dx, dy). hidden = 0, then for each LATER part r in order
+    hidden += max(min(t2, dx_r + w_r - 1) - max(t0, dx_r), 0) * max(min(t3, dy_r + h_r - 1) - max(t1, dy_r), 0): where
+    later parts overlap each other the area counts twice (conservative, and the same in any restatement). A row stays
+    unless v0 == v2 or v1 == v3 (on v: the translation could merge distinct values) and, with min_visible = f > 0, unless
+    (seen - hidden) < f * full, seen and full as in `episode_boxes_numpy`. f = 0 applies no rule: a covered box stays.
+    -> (fs_gt_boxes [max][5], num_boxes, all-class gt_boxes [max][5], its count), both lists in walk order"""
+    f32 = np.float32
+    rects = [(f32(p["dx"]), f32(p["dy"]), f32(p["dx"] + p["w"] - 1), f32(p["dy"] + p["h"] - 1)) for p in parts]
+    kept = [np.zeros((0, 5), dtype=np.float32)]
+    for k, p in enumerate(parts):
+        order = np.asarray(p.get("order", ()), dtype=np.int64).reshape(-1)
+        if p.get("boxes") is None or not len(order):
+            continue
+        src = np.asarray(p["boxes"], dtype=np.float32).reshape(-1, 5)[order]
+        u = np.empty((src.shape[0], 4), dtype=np.float32)
+        u[:] = src[:, 0:4].astype(np.float64) * float(p["im_scale"])  # the product in double, rounded by the assignment
+        u[:, 0::2] -= f32(p["x_s"])
+        u[:, 1::2] -= f32(p["y_s"])
+        v = u.copy()
+        clamp_x, clamp_y = p.get("clamp_x", p["w"] - 1), p.get("clamp_y", p["h"] - 1)
+        if clamp_x >= 0:
+            v[:, 0::2] = np.clip(v[:, 0::2], f32(0), f32(clamp_x))
+        if clamp_y >= 0:
+            v[:, 1::2] = np.clip(v[:, 1::2], f32(0), f32(clamp_y))
+        t = np.empty((src.shape[0], 5), dtype=np.float32)
+        t[:, 0:4:2] = v[:, 0::2] + f32(p["dx"])
+        t[:, 1:4:2] = v[:, 1::2] + f32(p["dy"])
+        t[:, 4] = src[:, 4]
+        keep = ~((v[:, 0] == v[:, 2]) | (v[:, 1] == v[:, 3]))
+        if min_visible > 0:
+            hidden = np.zeros((src.shape[0],), dtype=np.float32)
+            for x1, y1, x2, y2 in rects[k + 1:]:
+                ox = np.maximum(np.minimum(t[:, 2], x2) - np.maximum(t[:, 0], x1), f32(0))
+                oy = np.maximum(np.minimum(t[:, 3], y2) - np.maximum(t[:, 1], y1), f32(0))
+                hidden = hidden + ox * oy
+            full = (u[:, 2] - u[:, 0]) * (u[:, 3] - u[:, 1])
+            seen = (v[:, 2] - v[:, 0]) * (v[:, 3] - v[:, 1])
+            keep &= (seen - hidden) >= f32(min_visible) * full
+        kept.append(t[keep])
+    gt = np.concatenate(kept, axis=0)
+    fs = gt[gt[:, 4] == pos_cls].copy()
+    fs[:, 4] = 1.0
+    out = []
+    for g in (fs, gt):
         n = min(g.shape[0], max_num_box)
         pad = np.zeros((max_num_box, 5), dtype=np.float32)
         pad[:n] = g[:n]
@@ -600,6 +886,17 @@ class EpisodeAssembler:
                              "(%d, %d, %s)" % (plan.batch, plan.n_supports, plan.holder_hw, B, n_sup, (H, W)))
         d_plan, slot = self._upload(plan)
         n_words, stream = int(plan.words.size), _stream()
+        if plan.composed:  # still three launches; the supports' is the one it always was
+            lib().call("dana_episode_queries_composed", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p),
+                       _p(d_plan), n_words, plan.c_off, plan.max_parts, B, self._means_p, _p(h.im_data), H, W,
+                       _p(h.im_info), stream)
+            if n_sup:
+                self._supports(d_plan, plan, h.support_ims)
+            lib().call("dana_episode_boxes_composed", _p(p.d_boxes), len(p.boxes), _p(p.d_meta), len(p), _p(d_plan), n_words,
+                       plan.c_off, plan.max_parts, B, h.gt_boxes.size(1), _p(h.gt_boxes), _p(h.num_boxes),
+                       _p(self.all_cls_gt_boxes), _p(self.all_cls_num_boxes), stream)
+            self._done(slot)
+            return h.tensors() + (self.all_cls_gt_boxes,)
         if plan.augmented:
             lib().call("dana_episode_queries_aug", _p(p.data), p.data.numel(), _p(p.d_offsets), _p(p.d_meta), len(p),
                        _p(d_plan), n_words, plan.q_off, plan.a_off, B, self._means_p, _p(h.im_data), H, W, _p(h.im_info),

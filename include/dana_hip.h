@@ -893,6 +893,37 @@ int dana_episode_boxes_aug(const float* boxes, long n_boxes_total, const int* me
                            long long* num_boxes, float* all_cls_gt_boxes, long long* all_cls_num_boxes,
                            dana_stream_t stream);
 
+/* Composed queries: mosaic, copy-paste, random erasing. NOT IN THE REFERENCE (its loader, fs_loader.py:81-325, reads one
+ * image per query), so the rule is this project's own; a query of one part at (0, 0) gives the bits of the entry points
+ * above. A composed query is an ordered list of 1..16 parts painted into one holder image, later parts over earlier ones.
+ * The plan carries one more section at c_off (an even word, written by pipeline.plan_episode when a query asks for it):
+ *   `batch` headers of 8 words: part count, positive class, float min_visible, flags (2: a visibility threshold)
+ *   `batch` tables of max_parts part records of 32 words each (query b's table starts at record b * max_parts):
+ *     words 0..11 as a query record (row, order length, double im_scale, double 1 / im_scale, y_s, x_s, h, w, clamp_x,
+ *     clamp_y), 12..13 the destination (dy, dx), 14 the word offset of the part's box order, 15 flags (1: a colour map),
+ *     16..27 float M[3][4]. A part whose row is outside the pool (an erase part has row -1) paints zeros, has no boxes and
+ *     occludes like any other.
+ * max_parts is the largest part count of the batch and must lie in 1..16; a header's own count is limited to it. Both
+ * entry points refuse a section that does not fit plan_words, an odd c_off and a max_parts outside 1..16. */
+
+/* dana_episode_queries_aug (blob.py:35-52 + fs_loader.py:186-280) per part: holder pixel (y, x) belongs to the LAST part
+ * whose rectangle [dy, dy + h) x [dx, dx + w) contains it and holds that part's value at prepared pixel (y_s + y - dy,
+ * x_s + x - dx), the same expressions with that part's colour map; 0 under no part. im_info [batch][3] = (height, width,
+ * im_scale of part 0) */
+int dana_episode_queries_composed(const unsigned char* pool, long pool_bytes, const long long* offsets, const int* meta,
+                                  int n_rows, const int* plan, int plan_words, int c_off, int max_parts, int batch,
+                                  const float* pixel_means_bgr, float* im_data, int height, int width, float* im_info,
+                                  dana_stream_t stream);
+/* dana_episode_boxes_aug (minibatch.py:52-54 + fs_loader.py:183-315) over the parts in order: u, v of a box as there, the
+ * output row t = v + (dx, dy, dx, dy); hidden = the sum over the later parts r, in order, of ox * oy with ox = max(min(t2,
+ * dx_r + w_r - 1) - max(t0, dx_r), 0) and oy alike (float32; an area two later parts share counts twice). A box stays if
+ * v is not degenerate and, under a threshold, (seen - hidden) >= min_visible * full. Both lists are compacted in walk
+ * order across the parts and cut at max_num_box. */
+int dana_episode_boxes_composed(const float* boxes, long n_boxes_total, const int* meta, int n_rows, const int* plan,
+                                int plan_words, int c_off, int max_parts, int batch, int max_num_box, float* gt_boxes,
+                                long long* num_boxes, float* all_cls_gt_boxes, long long* all_cls_num_boxes,
+                                dana_stream_t stream);
+
 /* ---- counter-based device RNG for the training target layers (opt-in) ---------------------------
  * Philox-4x32-10 keyed by (seed, offset, image): the draws of anchor_target_layer.py:137-156 and
  * proposal_target_layer_cascade.py:143-175 without reading the fg / bg counts back to the host. */
