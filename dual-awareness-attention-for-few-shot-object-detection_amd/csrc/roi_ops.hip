@@ -18,11 +18,15 @@
 // reference's C++ and like oracle/dana_oracle.c: parity is bit-exact.
 #include "common.h"
 #include "../../include/dana_hip.h"
+#include "../../include/dana_hip_debug.h"
 #include <float.h>
 #include <stdlib.h>
 #include <atomic>
 
 namespace {
+
+// the form of the most recent dana_roi_align_backward (dana_debug_last_roi_align_backward_form; host state only)
+std::atomic<int> g_last_roi_align_bwd(0);
 
 struct AxisSample {  // one bilinear sample position along one axis
   int lo, hi;
@@ -586,6 +590,7 @@ int dana_roi_align_backward(const float* grad_out, const float* rois, float* gra
     roi_align_bwd_gather_nhwc<<<batch * ty * tx, 256, 0, s>>>(grad_out, rois, grad_in, num_rois, channels, height, width,
                                                               pooled_h, pooled_w, spatial_scale, sampling_ratio, ty, tx);
     DANA_CHECK_LAUNCH("dana_roi_align_backward(gather)");
+    g_last_roi_align_bwd.store(DANA_ROI_ALIGN_BWD_GATHER, std::memory_order_relaxed);
     return DANA_OK;
   }
   size_t bytes = (size_t)batch * channels * height * width * sizeof(float);
@@ -596,16 +601,22 @@ int dana_roi_align_backward(const float* grad_out, const float* rois, float* gra
       return DANA_ERR_HIP;
     }
   }
-  if (num_rois == 0) return DANA_OK;
+  if (num_rois == 0) {
+    g_last_roi_align_bwd.store(DANA_ROI_ALIGN_BWD_MEMSET, std::memory_order_relaxed);
+    return DANA_OK;
+  }
   DANA_CHECK_ARG(grad_out && rois, "dana_roi_align_backward: null pointer");
   long total = (long)num_rois * channels * pooled_h * pooled_w;
-  if (layout == DANA_LAYOUT_NCHW)
+  int form = DANA_ROI_ALIGN_BWD_SCATTER_NHWC;
+  if (layout == DANA_LAYOUT_NCHW) {
+    form = DANA_ROI_ALIGN_BWD_SCATTER_NCHW;
     roi_align_bwd<false><<<stream_grid(total, 256), 256, 0, s>>>(grad_out, rois, grad_in, total, channels, height,
                                                                  width, pooled_h, pooled_w, spatial_scale,
                                                                  sampling_ratio);
-  else if (channels % 4 == 0 && height <= RB_MAX && width <= RB_MAX && pooled_h * pooled_w <= 65535 &&
+  } else if (channels % 4 == 0 && height <= RB_MAX && width <= RB_MAX && pooled_h * pooled_w <= 65535 &&
            ((uintptr_t)grad_out & 15) == 0) {
     dim3 grid(num_rois, pooled_h * pooled_w);
+    form = DANA_ROI_ALIGN_BWD_BINS;
     roi_align_bwd_nhwc_bins<<<grid, 256, 0, s>>>(grad_out, rois, grad_in, channels, height, width, pooled_h, pooled_w,
                                                  spatial_scale, sampling_ratio);
   } else
@@ -613,8 +624,11 @@ int dana_roi_align_backward(const float* grad_out, const float* rois, float* gra
                                                                 width, pooled_h, pooled_w, spatial_scale,
                                                                 sampling_ratio);
   DANA_CHECK_LAUNCH("dana_roi_align_backward");
+  g_last_roi_align_bwd.store(form, std::memory_order_relaxed);
   return DANA_OK;
 }
+
+int dana_debug_last_roi_align_backward_form(void) { return g_last_roi_align_bwd.load(std::memory_order_relaxed); }
 
 int dana_roi_pool_forward(const float* input, const float* rois, float* output, int* argmax, int batch,
                           int channels, int height, int width, int num_rois, float spatial_scale, int pooled_h,

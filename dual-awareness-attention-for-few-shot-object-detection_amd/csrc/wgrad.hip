@@ -13,10 +13,12 @@
 //
 // Replaces what autograd + cuDNN do for nn.Conv2d / nn.Linear weights in the reference's train step
 // (train.py:141-143: loss.backward()); BN is frozen (dana.py:362-385) so dY arrives already scaled.
+#include <atomic>
 #include <cstdlib>
 
 #include "common.h"
 #include "../../include/dana_hip.h"
+#include "../../include/dana_hip_debug.h"
 
 namespace {
 
@@ -229,6 +231,12 @@ __global__ void __launch_bounds__(256, 2) wgrad_f32_128_kernel(WgradParams p) {
 // stage dY, waves 2-3 the implicit-im2col X slab. Channel c of the tile lives in LDS row (c & 3) * 32 + (c >> 2):
 // consecutive lanes write consecutive rows (no 8-way bank conflict), and the epilogue undoes the permutation.
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
+// One level of the three-way split: x to the NEAREST bf16 (ties away from zero; one add more than truncation), as fp32 bits.
+// x - hi is exact and at most 2^-8 of x's binade, the second level leaves at most seven significant bits for lo, and the
+// three dropped products (mid * lo twice, lo * lo) stay at about 2^-24 of |a b|: at one fp32 rounding even where an output is
+// a single product (M = 1). With truncation they reached 2^-20 (tests/test_gpu_wgrad_forms.py measured 4.5e-07 there).
+// Inf stays Inf (the residual is NaN: it propagates); a NaN stays one unless its top mantissa bits are all ones.
+__device__ __forceinline__ unsigned wsplit_hi(float x) { return (__float_as_uint(x) + 0x8000u) & 0xffff0000u; }
 constexpr int WSLD = 12;  // dwords per LDS row of one plane
 constexpr int WSK = 16;   // pixels per step
 
@@ -309,9 +317,9 @@ __global__ void __launch_bounds__(256, 2) wgrad_split_128_kernel(WgradParams p) 
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float x = e == 0 ? r[i].x : e == 1 ? r[i].y : e == 2 ? r[i].z : r[i].w;
-        hb[i] = __float_as_uint(x) & 0xffff0000u;
+        hb[i] = wsplit_hi(x);
         const float r1 = x - __uint_as_float(hb[i]);  // exact
-        mb[i] = __float_as_uint(r1) & 0xffff0000u;
+        mb[i] = wsplit_hi(r1);
         lb[i] = __float_as_uint(r1 - __uint_as_float(mb[i]));  // exact; <= 8 significant bits
       }
       uint2 h, m, l;
@@ -476,9 +484,9 @@ __global__ void __launch_bounds__(256, 2) wgrad_split_128p_kernel(WgradParams p)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const float x = e == 0 ? r[i].x : e == 1 ? r[i].y : e == 2 ? r[i].z : r[i].w;
-        hb[i] = __float_as_uint(x) & 0xffff0000u;
+        hb[i] = wsplit_hi(x);
         const float t1 = x - __uint_as_float(hb[i]);
-        mb[i] = __float_as_uint(t1) & 0xffff0000u;
+        mb[i] = wsplit_hi(t1);
         lb[i] = __float_as_uint(t1 - __uint_as_float(mb[i]));
       }
       uint2 h, m, l;
@@ -567,16 +575,16 @@ __global__ void __launch_bounds__(256, 2) wgrad_split_128p_kernel(WgradParams p)
           constexpr int i0 = (r & 1) * 2, i1 = i0 + 1;
           auto el = [&](int i) { return e == 0 ? cv[i].x : e == 1 ? cv[i].y : e == 2 ? cv[i].z : cv[i].w; };
           if constexpr (r < 2) {
-            hb[e][i0] = __float_as_uint(el(i0)) & 0xffff0000u;
-            hb[e][i1] = __float_as_uint(el(i1)) & 0xffff0000u;
+            hb[e][i0] = wsplit_hi(el(i0));
+            hb[e][i1] = wsplit_hi(el(i1));
             asm volatile("" : "+v"(hb[e][i0]), "+v"(hb[e][i1]));
           } else if constexpr (r < 4) {
             t1[e][i0] = el(i0) - __uint_as_float(hb[e][i0]);
             t1[e][i1] = el(i1) - __uint_as_float(hb[e][i1]);
             asm volatile("" : "+v"(t1[e][i0]), "+v"(t1[e][i1]));
           } else if constexpr (r < 6) {
-            mb[e][i0] = __float_as_uint(t1[e][i0]) & 0xffff0000u;
-            mb[e][i1] = __float_as_uint(t1[e][i1]) & 0xffff0000u;
+            mb[e][i0] = wsplit_hi(t1[e][i0]);
+            mb[e][i1] = wsplit_hi(t1[e][i1]);
             asm volatile("" : "+v"(mb[e][i0]), "+v"(mb[e][i1]));
           } else if constexpr (r < 8) {
             lb[e][i0] = __float_as_uint(t1[e][i0] - __uint_as_float(mb[e][i0]));
@@ -737,6 +745,13 @@ downsample_gather_kernel(const float* __restrict__ x, float4* __restrict__ compa
   compact[i] = *(const float4*)(x + ((b * IH + (long)oh * stride) * IW + (long)ow * stride) * ldx + c * 4);
 }
 
+// debug (include/dana_hip_debug.h): dana_debug_force_wgrad's (tile | slices << 8), 0 = the cost model's choice, and the
+// record of the most recent launch (dana_debug_last_wgrad_form). Host state only, relaxed atomics like igemm.hip's.
+std::atomic<int> g_wgrad_force(0);
+std::atomic<int> g_wgrad_last(0);
+
+int wgrad_chunk(int M, int S) { return ((M + S - 1) / S + 31) / 32 * 32; }
+
 // tile edge (64 or 128) and pixel split of one weight-gradient launch
 struct WgradShape {
   int tile, tn, tk, S;
@@ -745,9 +760,14 @@ WgradShape wgrad_shape(int N, int K, int M, int planes = 1) {
   // Pick (tile, S) by a small cost model: `rounds` of workgroups over the chip's slots (2 per CU for the 128x128
   // tile, 4 for 64x64), each doing chunk/32 slabs, plus the HBM round trip of the S partial tiles. The 128x128
   // tile sustains ~0.75 of the per-CU MFMA peak (one LDS read per MFMA), the 64x64 tile ~0.5 (two).
+  // A forced tile (64 / 128) restricts the outer loop to it, a forced slice count replaces the inner one: every caller
+  // (launches and workspace sizes) comes through here, so all of them follow the forced choice.
+  const int force = g_wgrad_force.load(std::memory_order_relaxed);
+  const int f_tile = force & 255, f_slices = force >> 8;
   WgradShape best = {64, 1, 1, 1};
   double best_t = 1e30;
   for (int tile = 64; tile <= 128; tile += 64) {
+    if (f_tile && tile != f_tile) continue;
     const int tn = (N + tile - 1) / tile, tk = (K + tile - 1) / tile;
     const long tiles = (long)tn * tk * planes;
     const int slots = tile == 128 ? 512 : 1024;
@@ -756,9 +776,19 @@ WgradShape wgrad_shape(int N, int K, int M, int planes = 1) {
     const bool split = tile == 128 && dana_get_mfma_mode() != 0;
     const double cu_flops = split ? 419.4e12 / 256.0 * 0.5 : 157.3e12 / 256.0 * (tile == 128 ? 0.75 : 0.5);
     const double wg_flops = cu_flops / (tile == 128 ? 2 : 4);
-    const int maxS = (M + 255) / 256 < 64 ? (M + 255) / 256 : 64;
-    for (int S = 1; S <= (maxS < 1 ? 1 : maxS); ++S) {
-      const int chunk = ((M + S - 1) / S + 31) / 32 * 32;
+    int minS = 1, maxS = (M + 255) / 256 < 64 ? (M + 255) / 256 : 64;
+    if (maxS < 1) maxS = 1;
+    if (f_slices) {
+      // no empty slice (at least 32 pixels each but the last, the last not empty) and a grid the launch can take
+      int S = f_slices;
+      S = S < (M + 31) / 32 ? S : (M + 31) / 32;
+      S = (long)planes * S <= 65535 ? S : 65535 / planes;
+      S = S < 1 ? 1 : S;
+      while (S > 1 && (long)(S - 1) * wgrad_chunk(M, S) >= M) --S;
+      minS = maxS = S;
+    }
+    for (int S = minS; S <= maxS; ++S) {
+      const int chunk = wgrad_chunk(M, S);
       const long rounds = (tiles * S + slots - 1) / slots;
       const double t_mma = (double)rounds * (chunk / 32) * (2.0 * tile * tile * 32) / wg_flops + rounds * 2e-6;
       const double t_part = 2.0 * S * (double)N * K * planes * 4.0 / 4e12;
@@ -772,9 +802,14 @@ WgradShape wgrad_shape(int N, int K, int M, int planes = 1) {
   return best;
 }
 
-// 128 x 128 tile: bf16x6 split kernel unless dana_set_mfma_mode(0)
-void launch_wgrad_128(const WgradParams& p, dim3 grid, hipStream_t s) {
-  if (dana_get_mfma_mode() != 0) {
+// The compute kernel of one launch: the 64 x 64 tile is always the f32-MFMA kernel; the 128 x 128 tile is the bf16x6 split
+// kernel unless dana_set_mfma_mode(0). Records the launch for dana_debug_last_wgrad_form.
+void launch_wgrad(const WgradShape& ws, const WgradParams& p, dim3 grid, hipStream_t s) {
+  int kernel;
+  if (ws.tile != 128) {
+    kernel = DANA_WGRAD_KERNEL_F32_64;
+    wgrad_f32_kernel<<<grid, 256, 0, s>>>(p);
+  } else if (dana_get_mfma_mode() != 0) {
     constexpr int lds = 2 * 2 * 3 * 128 * WSLD * (int)sizeof(unsigned);
     static DeviceOnce attr;
     attr.once([&] { return hipFuncSetAttribute((const void*)wgrad_split_128_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
@@ -783,13 +818,18 @@ void launch_wgrad_128(const WgradParams& p, dim3 grid, hipStream_t s) {
     if (p.KH * p.KW == 1 && p.stride == 1 && p.pad == 0) {
       static DeviceOnce attr_p;
       attr_p.once([&] { return hipFuncSetAttribute((const void*)wgrad_split_128p_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds); });
+      kernel = DANA_WGRAD_KERNEL_SPLIT_128P;
       wgrad_split_128p_kernel<<<grid, 256, lds, s>>>(p);
     } else {
+      kernel = DANA_WGRAD_KERNEL_SPLIT_128;
       wgrad_split_128_kernel<<<grid, 256, lds, s>>>(p);
     }
   } else {
+    kernel = DANA_WGRAD_KERNEL_F32_128;
     wgrad_f32_128_kernel<<<grid, 256, 0, s>>>(p);
   }
+  const unsigned planes = grid.z / (unsigned)p.nsplit;
+  g_wgrad_last.store(kernel | p.nsplit << 4 | (int)(planes < 65535u ? planes : 65535u) << 12, std::memory_order_relaxed);
 }
 
 }  // namespace
@@ -829,7 +869,7 @@ int dana_wgrad_tn_batched(const float* dY, const float* X, float* out, int plane
   p.y_bytes = (unsigned)yb;
   const WgradShape ws = wgrad_shape(N, K, M, planes);
   const int S = ws.S;
-  p.m_chunk = ((M + S - 1) / S + 31) / 32 * 32;
+  p.m_chunk = wgrad_chunk(M, S);
   p.nsplit = S;
   const size_t need = dana_wgrad_tn_batched_workspace(planes, M, N, K);
   if (need && (!workspace || workspace_bytes < need)) {
@@ -840,10 +880,7 @@ int dana_wgrad_tn_batched(const float* dY, const float* X, float* out, int plane
   DANA_CHECK_ARG((long)planes * S <= 65535, "dana_wgrad_tn_batched: too many slices");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(ws.tn, ws.tk, planes * S);
-  if (ws.tile == 128)
-    launch_wgrad_128(p, grid, s);
-  else
-    wgrad_f32_kernel<<<grid, 256, 0, s>>>(p);
+  launch_wgrad(ws, p, grid, s);
   DANA_CHECK_LAUNCH("dana_wgrad_tn_batched");
   if (S > 1) {
     const long n4 = (long)N * K / 4;
@@ -855,6 +892,15 @@ int dana_wgrad_tn_batched(const float* dY, const float* X, float* out, int plane
 }
 
 extern "C" {
+
+int dana_debug_force_wgrad(int tile, int slices) {
+  DANA_CHECK_ARG((tile == 0 || tile == 64 || tile == 128) && slices >= 0 && slices <= 64,
+                 "dana_debug_force_wgrad: tile 0 (cost model), 64 or 128; slices 0 (cost model) or 1..64");
+  g_wgrad_force.store(tile | slices << 8, std::memory_order_relaxed);
+  return DANA_OK;
+}
+
+int dana_debug_last_wgrad_form(void) { return g_wgrad_last.load(std::memory_order_relaxed); }
 
 /* out[z][n][k] (+)= sum_m y[z][m][n] * x[z][m][k] for n < n_valid: a batch of "TN" GEMMs (the adjoints of torch.bmm
  * w.r.t. its right operand, dana.py:140-150 / 270-283, one plane per image). N rows are computed (y may carry zero
@@ -901,7 +947,7 @@ int dana_gemm_tn_batched(const float* y, const float* x, float* out, int planes,
   p.y_bytes = (unsigned)yb;
   const WgradShape ws = wgrad_shape(n, k, m, planes);
   const int S = ws.S;
-  p.m_chunk = ((m + S - 1) / S + 31) / 32 * 32;
+  p.m_chunk = wgrad_chunk(m, S);
   p.nsplit = S;
   const size_t need = (size_t)planes * S * n * k * sizeof(float);
   if (!workspace || workspace_bytes < need) {
@@ -912,10 +958,7 @@ int dana_gemm_tn_batched(const float* y, const float* x, float* out, int planes,
   DANA_CHECK_ARG((long)planes * S <= 65535, "dana_gemm_tn_batched: too many slices");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(ws.tn, ws.tk, planes * S);
-  if (ws.tile == 128)
-    launch_wgrad_128(p, grid, s);
-  else
-    wgrad_f32_kernel<<<grid, 256, 0, s>>>(p);
+  launch_wgrad(ws, p, grid, s);
   DANA_CHECK_LAUNCH("dana_gemm_tn_batched");
   const long n4 = (long)n * k / 4, n4v = (long)n_valid * k / 4;
   dim3 rgrid(dana_ceil_div(n4v, 64), planes);
@@ -967,13 +1010,14 @@ int dana_conv2d_wgrad_nhwc(const float* grad_out, const float* input, float* gra
   DANA_CHECK_ARG(p.ldx % 4 == 0 && p.ldy % 4 == 0 && ((uintptr_t)grad_out & 15) == 0 && ((uintptr_t)input & 15) == 0 &&
                      ((uintptr_t)grad_weight & 15) == 0,
                  "dana_conv2d_wgrad_nhwc: strides / pointers must be 16-byte aligned");
+  DANA_CHECK_ARG(p.ldx >= cin && p.ldy >= cout, "dana_conv2d_wgrad_nhwc: in_pix_stride < cin or grad_pix_stride < cout");
   const long xb = (long)batch * in_h * in_w * p.ldx * 4, yb = (long)p.M * p.ldy * 4;
   DANA_CHECK_ARG(xb < (long)OOB && yb < (long)OOB, "dana_conv2d_wgrad_nhwc: operand span >= 2 GiB; split the batch");
   p.x_bytes = (unsigned)xb;
   p.y_bytes = (unsigned)yb;
   const WgradShape ws = wgrad_shape(cout, p.K, p.M);
   const int tn = ws.tn, tk = ws.tk, S = ws.S;
-  p.m_chunk = ((p.M + S - 1) / S + 31) / 32 * 32;
+  p.m_chunk = wgrad_chunk(p.M, S);
   p.nsplit = S;
   const size_t need = (size_t)S * cout * p.K * sizeof(float);
   if (!workspace || workspace_bytes < need) {
@@ -983,10 +1027,7 @@ int dana_conv2d_wgrad_nhwc(const float* grad_out, const float* input, float* gra
   p.partial = (float*)workspace;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid(tn, tk, S);
-  if (ws.tile == 128)
-    launch_wgrad_128(p, grid, s);
-  else
-    wgrad_f32_kernel<<<grid, 256, 0, s>>>(p);
+  launch_wgrad(ws, p, grid, s);
   DANA_CHECK_LAUNCH("dana_conv2d_wgrad_nhwc");
   const long n4 = (long)cout * p.K / 4;
   wgrad_reduce_kernel<<<dana_ceil_div(n4, 64), 256, 0, s>>>((const float4*)workspace, (float4*)grad_weight, row_scale,

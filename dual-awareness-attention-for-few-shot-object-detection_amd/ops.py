@@ -1039,6 +1039,45 @@ def igemm_forms(tile=0, dma=-1, pp=-1, epilogue=0):
         set_epilogue_mode(prev_epi)
 
 
+WgradForm = collections.namedtuple("WgradForm", "kernel slices planes")
+_WGRAD_KERNELS = {0: None, 1: "f32_64", 2: "f32_128", 3: "split_128", 4: "split_128p"}
+_ROI_ALIGN_BWD_FORMS = {0: None, 1: "gather", 2: "bins", 3: "scatter_nhwc", 4: "scatter_nchw", 5: "memset"}
+
+
+def force_wgrad(tile=0, slices=0):
+    """debug (include/dana_hip_debug.h: dana_debug_force_wgrad): the weight-gradient launches' tile (0 = the cost model, 64,
+    128) and pixel slices (0 = the cost model, 1..64; clamped per launch so that no slice is empty). The workspace sizes
+    follow it."""
+    lib().call("dana_debug_force_wgrad", int(tile), int(slices))
+
+
+def decode_wgrad_form(code):
+    """the int of dana_debug_last_wgrad_form (bit layout: include/dana_hip_debug.h) -> WgradForm"""
+    return WgradForm(_WGRAD_KERNELS[code & 15], code >> 4 & 127, code >> 12 & 65535)
+
+
+def last_wgrad_form():
+    """debug: kernel, slice count S and planes of the most recent weight-gradient launch of this process (kernel None: none
+    yet)"""
+    return decode_wgrad_form(lib().query("dana_debug_last_wgrad_form"))
+
+
+@contextlib.contextmanager
+def wgrad_forms(tile=0, slices=0):
+    """debug: force_wgrad(tile, slices) inside the block, the cost model's own choice (0, 0) behind it"""
+    try:
+        force_wgrad(tile, slices)
+        yield
+    finally:
+        force_wgrad(0, 0)
+
+
+def last_roi_align_backward_form():
+    """debug (dana_debug_last_roi_align_backward_form): "gather", "bins", "scatter_nhwc", "scatter_nchw", "memset" (no rois)
+    or None (no call yet)"""
+    return _ROI_ALIGN_BWD_FORMS[lib().query("dana_debug_last_roi_align_backward_form")]
+
+
 SPLIT_K = True  # split-K for tile-starved GEMMs (few tiles, long K); tools flip it for A/Bs
 
 

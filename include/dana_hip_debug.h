@@ -46,6 +46,34 @@ int dana_debug_get_pp_stages(void);
 #define DANA_IGEMM_FAMILY_SPLIT_128 3
 #define DANA_IGEMM_FAMILY_DMA 4
 int dana_debug_last_igemm_form(void);
+/* Tile and pixel split of the weight-gradient launches (csrc/wgrad.hip: dana_conv2d_wgrad_nhwc, dana_gemm_tn_batched and the
+ * Winograd-domain weight gradient), which a cost model picks otherwise. tile: 0 = the cost model (default), 64 = the 64x64
+ * tile (always wgrad_f32_kernel), 128 = the 128x128 tile (the bf16x6 split kernels, or wgrad_f32_128_kernel under
+ * dana_set_mfma_mode(0), as without the switch). slices: 0 = the cost model, 1..64 = that many pixel slices S, clamped on
+ * the host to ceil(M / 32), to the largest count that leaves no slice empty and to planes * S <= 65535 -- a forced value
+ * never gives a launch the cost model could not give for some shape. Any other argument is refused and changes nothing.
+ * The workspace-size functions follow the forced choice: size the workspace and launch under the same setting. */
+int dana_debug_force_wgrad(int tile, int slices);
+/* The most recent weight-gradient launch of this process (stored when the launch is issued; 0 = none yet):
+ *   bits  0..3  compute kernel (DANA_WGRAD_KERNEL_*: wgrad_f32_kernel, wgrad_f32_128_kernel, wgrad_split_128_kernel,
+ *               wgrad_split_128p_kernel)
+ *   bits  4..10 S, the pixel slices (with S == 1 the Winograd-domain launch writes its result itself; every other launch
+ *               goes through wgrad_reduce_kernel)
+ *   bits 12..27 planes of a batched launch, capped at 65535 */
+#define DANA_WGRAD_KERNEL_F32_64 1
+#define DANA_WGRAD_KERNEL_F32_128 2
+#define DANA_WGRAD_KERNEL_SPLIT_128 3
+#define DANA_WGRAD_KERNEL_SPLIT_128P 4
+int dana_debug_last_wgrad_form(void);
+/* Which form the most recent dana_roi_align_backward of this process took (csrc/roi_ops.hip; 0 = none yet): 1 = the NHWC
+ * gather (pooled size <= 8, channels % 4 == 0), 2 = the NHWC per-bin kernel (maps of at most 128 x 128), 3 = the NHWC atomic
+ * scatter, 4 = the NCHW atomic scatter, 5 = the zero fill alone (no rois). */
+#define DANA_ROI_ALIGN_BWD_GATHER 1
+#define DANA_ROI_ALIGN_BWD_BINS 2
+#define DANA_ROI_ALIGN_BWD_SCATTER_NHWC 3
+#define DANA_ROI_ALIGN_BWD_SCATTER_NCHW 4
+#define DANA_ROI_ALIGN_BWD_MEMSET 5
+int dana_debug_last_roi_align_backward_form(void);
 /* While `buffer` is non-null every split-kernel block writes eight 64-bit words {shader-clock at start, at the first
  * K-step, after the K loop, at the end, HW_ID, 100 MHz wall clock at the end, wall clock at the start, 0} at
  * buffer[(z * grid + block) * 8]. The pointer is read when a launch is ISSUED, so two launches issued with two buffers can

@@ -38,7 +38,8 @@ def test_library_exports_every_declared_symbol():
     dbg = _lib.parse_header(_lib.DEBUG_HEADER)
     assert {"dana_set_epilogue_mode", "dana_set_sort_mode", "dana_set_igemm_trace", "dana_debug_force_tile",
             "dana_debug_stream_create_cumask", "dana_debug_set_dma_kernel", "dana_debug_get_dma_kernel",
-            "dana_debug_set_pp_stages", "dana_debug_get_pp_stages", "dana_debug_last_igemm_form"} <= set(dbg)
+            "dana_debug_set_pp_stages", "dana_debug_get_pp_stages", "dana_debug_last_igemm_form", "dana_debug_force_wgrad",
+            "dana_debug_last_wgrad_form", "dana_debug_last_roi_align_backward_form"} <= set(dbg)
     assert not set(dbg) & set(protos)
     for name in dbg:
         assert hasattr(cdll, name), "libdana_hip.so does not export %s" % name
@@ -205,6 +206,79 @@ def test_contraction_form_selectors_roundtrip_errors_and_environment():
     assert _selectors_in_a_child(DANA_DMA_KERNEL="2", DANA_PP_STAGES="13")[:2] == (2, 13)
     dm, pp, err = _selectors_in_a_child(DANA_PP_STAGES="5")
     assert (dm, pp) == (-1, -1) and "DANA_PP_STAGES=5 is not one of the accepted values; ignored" in err
+
+
+def test_wgrad_selector_refusals_and_decoding():
+    """dana_debug_force_wgrad (host-side state only): tile 0 / 64 / 128 and slices 0..64, anything else is an argument error
+    that changes nothing (seen through the workspace size, which follows the forced slice count); the launch records decode"""
+    L = _lib.lib()
+    size = lambda: L.query("dana_conv2d_wgrad_workspace_bytes", 1, 19, 23, 64, 64, 3, 3, 1, 1)  # noqa: E731  (M = 437, K = 576)
+    unit = 64 * 576 * 4
+    try:
+        ops.force_wgrad(0, 0)
+        s0 = size()
+        assert s0 % unit == 0 and 1 <= s0 // unit <= 2  # the cost model: at most ceil(M / 256) slices
+        ops.force_wgrad(64, 5)
+        assert size() == 5 * unit
+        for tile, slices in ((32, 0), (1, 1), (256, 0), (-64, 0), (129, 2), (64, -1), (128, 65), (0, 1000)):
+            with pytest.raises(_lib.DanaError, match="dana_debug_force_wgrad"):
+                L.call("dana_debug_force_wgrad", tile, slices)
+            assert size() == 5 * unit, (tile, slices)
+        with ops.wgrad_forms(tile=128, slices=2):
+            assert size() == 2 * unit
+        assert size() == s0  # the context manager leaves (0, 0) behind
+    finally:
+        ops.force_wgrad(0, 0)
+    assert ops.decode_wgrad_form(0) == ops.WgradForm(None, 0, 0)
+    assert ops.decode_wgrad_form(4 | 5 << 4 | 36 << 12) == ops.WgradForm("split_128p", 5, 36)
+    assert ops.decode_wgrad_form(1 | 64 << 4 | 65535 << 12) == ops.WgradForm("f32_64", 64, 65535)
+    assert [ops.decode_wgrad_form(k).kernel for k in (2, 3)] == ["f32_128", "split_128"]
+    assert ops.last_roi_align_backward_form() in (None, "gather", "bins", "scatter_nhwc", "scatter_nchw", "memset")
+
+
+def test_wgrad_workspace_sizes_follow_a_forced_slice_count():
+    """the override sits in wgrad_shape(), so dana_conv2d_wgrad_workspace_bytes / dana_gemm_tn_batched_workspace_bytes (and
+    through the latter's internal twin the Winograd-domain weight gradient) size for the forced S, clamped to ceil(M / 32),
+    to a last slice that is not empty and to planes * S <= 65535; a forced tile alone leaves the cost model's S"""
+    L = _lib.lib()
+    conv = lambda b, h, w: L.query("dana_conv2d_wgrad_workspace_bytes", b, h, w, 64, 64, 3, 3, 1, 1) // (64 * 576 * 4)  # noqa: E731
+    tn = lambda planes, m: L.query("dana_gemm_tn_batched_workspace_bytes", planes, m, 8, 64) // (planes * 8 * 64 * 4)  # noqa: E731
+    wino = lambda: L.query("dana_conv3x3_wgrad_winograd4_workspace_bytes", 2, 17, 20, 64, 8)  # noqa: E731  (50 tiles of 4x4)
+    try:
+        ops.force_wgrad(0, 0)
+        assert conv(1, 19, 23) in (1, 2) and tn(3, 49) == 1
+        w0 = wino()
+        for tile in (64, 128):
+            ops.force_wgrad(tile, 1)
+            assert (conv(1, 19, 23), tn(3, 49), tn(3, 1)) == (1, 1, 1)
+            w1 = wino()
+            ops.force_wgrad(tile, 2)
+            assert (conv(1, 19, 23), tn(3, 49), tn(3, 33), tn(3, 32), tn(3, 1)) == (2, 2, 2, 1, 1)
+            assert wino() == w1 + 36 * 2 * 8 * 64 * 4  # S = 1 needs no partial tiles, S = 2 two per plane
+            ops.force_wgrad(tile, 5)
+            assert (conv(1, 19, 23), conv(1, 5, 7), conv(1, 1, 1), tn(3, 49), tn(30000, 437)) == (5, 2, 1, 2, 2)
+            ops.force_wgrad(tile, 64)
+            assert (conv(1, 19, 23), conv(1, 15, 20)) == (14, 10)  # ceil(437 / 32), ceil(300 / 32)
+            # M = 300 in 9 slices: chunks of 64 pixels, of which only five are not empty (6, 7 and 8 slices likewise) -> 5
+            ops.force_wgrad(tile, 9)
+            assert conv(1, 15, 20) == 5
+            ops.force_wgrad(tile, 0)
+            assert (conv(1, 19, 23), tn(3, 49)) in ((1, 1), (2, 1)) and wino() in (w0, w1)
+    finally:
+        ops.force_wgrad(0, 0)
+
+
+def test_wgrad_refuses_pixel_strides_below_the_channel_count():
+    """dana_conv2d_wgrad_nhwc: in_pix_stride < cin or grad_pix_stride < cout is an argument error before the workspace is
+    looked at and before any launch (dana_gemm_tn_batched checks ldy >= n / ldx >= k the same way)"""
+    L = _lib.lib()
+    for in_stride, grad_stride in ((60, 0), (0, 4), (60, 4)):
+        with pytest.raises(_lib.DanaError, match="in_pix_stride < cin or grad_pix_stride < cout"):
+            L.call("dana_conv2d_wgrad_nhwc", 16, 16, 16, 1, 5, 7, 64, 8, 1, 1, 1, 0, in_stride, grad_stride, None, 0, None, 0, None)
+    with pytest.raises(_lib.DanaError, match="workspace"):  # strides at the channel counts pass the check
+        L.call("dana_conv2d_wgrad_nhwc", 16, 16, 16, 1, 5, 7, 64, 8, 1, 1, 1, 0, 64, 8, None, 0, None, 0, None)
+    with pytest.raises(_lib.DanaError, match="16-byte aligned"):
+        L.call("dana_gemm_tn_batched", 16, 16, 16, 1, 5, 8, 64, 4, 64, 0, 0, 0, 8, 0, None, 0, None)
 
 
 def test_ops_refuse_cpu_tensors():
